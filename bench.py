@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Acquisition throughput benchmark (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload b1c|b2a|joint]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload b1c|b2a|joint] [--dump-outputs DIR] [--full]
 
 A *step* is one complete acquisition pass of the hot path over one synthetic IF
 block: forward transforms of every Doppler bin, the PRN x Doppler parallel
@@ -23,6 +23,16 @@ step ends with one RCCL all-reduce(SUM) per signal of the three per-PRN result v
 (3 x 63 f64), the only exchange the path has.  Total work is fixed, so scaling is "strong".
 
 Prints ONE JSON line on rank 0.
+
+A plain run sets up, warms up, times the K steps and prints the headline (`value`, `ms_per_step`, the roofline of the timed
+pair).  ``--full`` adds the legs that take runs of their own, none of them part of `value`: the CPU baselines, tracking
+(`tracking`, `tracking_full`), fp32 storage (`strict_f32`) and the shader-clock probe, the other search modes (`serving` /
+`default` / `minimal`), the B2a workload beside B1C (`b2a`) and the cold starts (`cold`); the ``--no-*`` options skip single
+legs of a full run.
+
+``--dump-outputs DIR`` writes the acqResults of the last timed step, per signal, as float64 arrays:
+DIR/<signal>_carrFreq.npy, DIR/<signal>_codePhase.npy, DIR/<signal>_peakMetric.npy (<signal> = b1c / b2a).  The inputs
+are seeded: the same arguments give the same IF blocks in every run, so two builds can be compared output for output.
 """
 from __future__ import annotations
 
@@ -435,6 +445,15 @@ def kernel_label(tm):
                                                   tm.get("plan_l1", 0), tm.get("plan_l2", 0), "; " + ", ".join(extra) if extra else "")
 
 
+def dump_outputs(path, sigs, res_all):
+    """--dump-outputs: what a caller of the timed path receives (acqResults: carrFreq, codePhase, peakMetric, one entry per PRN),
+    from the last timed step, per signal, as float64 .npy files."""
+    os.makedirs(path, exist_ok=True)
+    for g, r in zip(sigs, res_all):
+        for field, a in zip(("carrFreq", "codePhase", "peakMetric"), r):
+            np.save(os.path.join(path, f"{g['name']}_{field}.npy"), np.ascontiguousarray(a, dtype=np.float64))
+
+
 def b2a_leg(local_rank, steps=5):
     """Extra key `b2a` (BASELINE.json configs[1], never `value`): the B2a full acquisition -- 63 PRNs x 26 Doppler bins, 1 ms code,
     99.375 MS/s -- timed like the headline (block resident in HBM, code spectra cached, `steps` complete bds_acq_run calls)."""
@@ -607,9 +626,16 @@ def main():
                     help="inter-pass buffer budget of the search the headline runs with (include/bds_mi355x.h, bds_acq_set_pair_budget_gb): "
                          "serving = 'auto', as many PRNs' Doppler rows per launch pair as 60 %% of the free HBM hold (allocated before the timed "
                          "region); default = the library's own default (40 GiB: 8 PRNs per pair at cfg3); minimal = 0 (one PRN per pair, 5 GB). "
-                         "The other two are timed beside the headline (keys `serving` / `default` / `minimal`)")
+                         "With --full the other two are timed beside the headline (keys `serving` / `default` / `minimal`)")
     ap.add_argument("--lean", action="store_true", help="same as --mode minimal")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the extra legs (CPU baselines, tracking, fp32 storage, shader clock, other modes, B2a beside B1C, cold starts); "
+                         "a plain run times the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the acqResults of the last timed step as DIR/<signal>_{carrFreq,codePhase,peakMetric}.npy (float64)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if args.lean:
         args.mode = "minimal"
 
@@ -665,8 +691,8 @@ def main():
         g["ctx"] = bds_amd.get_context(local_rank) if k == 0 else bds_amd.native.Context(local_rank)
         # The headline is what a plain bds_acquire caller gets: the LIBRARY DEFAULT (round 6; rounds 1-5 put the opt-in serving mode
         # here).  The serving mode (include/bds_mi355x.h, bds_acq_set_pair_budget_gb / BDS_ACQ_PAIR_GB=auto -- as many PRNs' Doppler rows
-        # per launch pair as 60 % of the free HBM hold) and the minimal footprint (one PRN per pair) are timed beside it (keys `serving`,
-        # `minimal`); a first call in a fresh process is the `cold` key.
+        # per launch pair as 60 % of the free HBM hold) and the minimal footprint (one PRN per pair) are timed beside it with --full (keys
+        # `serving`, `minimal`); a first call in a fresh process is the `cold` key.
         if args.mode != "default":
             g["ctx"].acq_set_pair_budget({"serving": "auto", "minimal": 0}[args.mode])
         if g["shard"]:
@@ -804,7 +830,7 @@ def main():
                                    "default": "library default (inter-pass buffer budget 40 GiB): %d launch pairs of %.0f (PRN, bin) cells on average" % (int(tm["n_pairs"]), tm["cells_per_pair"]),
                                    "serving": "serving (bds_acq_set_pair_budget_gb(auto) = BDS_ACQ_PAIR_GB=auto): %d launch pairs of %.0f (PRN, bin) cells on average, "
                                               "inter-pass buffer allocated in the warm-up call (a first call in a fresh process: cold.b1c_serving); the library default "
-                                              "(40 GiB) and the minimal footprint are timed beside it (keys `default`, `minimal`)" % (int(tm["n_pairs"]), tm["cells_per_pair"])}[args.mode],
+                                              "(40 GiB) and the minimal footprint are timed beside it with --full (keys `default`, `minimal`)" % (int(tm["n_pairs"]), tm["cells_per_pair"])}[args.mode],
                    "fft_len": tm["fft_len"], "components": ncomp,
                    "parallelism": f"(signal, PRN) job shard x{world}, LPT by cost; one all-reduce(SUM) of 3 x 63 f64 per signal",
                    "jobs": sum(len(set(int(p) for p in g["s"].acqSatelliteList)) for g in sigs),
@@ -837,23 +863,27 @@ def main():
             g["ctx"].close()
     bds_amd.release_context(local_rank)
     if rank == 0:
-        if world == 1 and not args.no_cpu_baseline:
-            out["cpu_baseline"] = cpu_baseline(s, x, names[0])
-        else:
-            out["cpu_baseline"] = None
-        out["tracking"] = tracking_leg(names[0], local_rank, s) if world == 1 and not args.no_tracking else None
-        out["tracking_full"] = (tracking_full_leg(local_rank, s) if world == 1 and names[0] == "b1c" and not args.no_tracking
-                                and not args.no_tracking_full else None)
         import hashlib
 
         # acqResults of the last step, per signal, as a digest: sharded / joint runs must reproduce the single-device bits
         out["config"]["results_sha256"] = {g["name"]: hashlib.sha256(np.ascontiguousarray(np.stack(r), dtype=np.float64).tobytes()).hexdigest()
                                            for g, r in zip(sigs, res_all)}
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, sigs, res_all)
+        # the extra legs take runs of their own: --full only (a plain run reports the headline alone)
+        full = args.full
+        if world == 1 and full and not args.no_cpu_baseline:
+            out["cpu_baseline"] = cpu_baseline(s, x, names[0])
+        else:
+            out["cpu_baseline"] = None
+        out["tracking"] = tracking_leg(names[0], local_rank, s) if world == 1 and full and not args.no_tracking else None
+        out["tracking_full"] = (tracking_full_leg(local_rank, s) if world == 1 and full and names[0] == "b1c" and not args.no_tracking
+                                and not args.no_tracking_full else None)
         out["strict_f32"] = (strict_f32_leg(local_rank, s, x, float(n_circ) * p_total * n_bins, ncomp, n_circ)
-                             if world == 1 and len(sigs) == 1 and not args.no_fast_path else None)
+                             if world == 1 and full and len(sigs) == 1 and not args.no_fast_path else None)
         if out["strict_f32"]:
             out["roofline"]["frac_strict_f32"] = out["strict_f32"]["frac"]
-        if valu is not None and world == 1 and len(sigs) == 1 and not args.no_fast_path:
+        if valu is not None and world == 1 and full and len(sigs) == 1 and not args.no_fast_path:
             ck = clock_leg(local_rank, s, x)
             if ck["shader_clock_GHz"]:
                 valu["shader_clock_GHz"] = ck["shader_clock_GHz"]
@@ -863,18 +893,18 @@ def main():
                 valu["frac_of_issue_bound_at_shader_clock"] = (valu["bound_ms_at_shader_clock"] * ck["cells_per_pair"] / cells_per_pair / ck["pair_ms"]
                                                                if ck["pair_ms"] and cells_per_pair else None)
                 valu["shader_clock_probe_pair"] = {"pair_ms": ck["pair_ms"], "cells_per_pair": ck["cells_per_pair"], "mode": "library default"}
-        if world == 1 and len(sigs) == 1 and args.prns == 63 and not args.no_cold:
+        if world == 1 and full and len(sigs) == 1 and args.prns == 63 and not args.no_cold:
             out["cold"] = {names[0]: cold_leg(local_rank, s, x)}
             if names == ["b1c"]:
                 out["cold"]["b1c_serving"] = cold_leg(local_rank, s, x, budget="auto")
             if names == ["b1c"] and not args.no_b2a:
                 s2, x2, _, _ = build_workload("b2a")
                 out["cold"]["b2a"] = cold_leg(local_rank, s2, x2)
-        if world == 1 and names == ["b1c"] and args.prns == 63 and not args.no_fast_path:
+        if world == 1 and full and names == ["b1c"] and args.prns == 63 and not args.no_fast_path:
             for m, b in (("serving", "auto"), ("default", None), ("minimal", 0)):
                 if m != args.mode:
                     out[m] = other_mode_leg(local_rank, s, x, b)
-        out["b2a"] = b2a_leg(local_rank) if world == 1 and names == ["b1c"] and not args.no_b2a and args.prns == 63 else None
+        out["b2a"] = b2a_leg(local_rank) if world == 1 and full and names == ["b1c"] and not args.no_b2a and args.prns == 63 else None
         if len(sigs) > 1:
             out["config"]["satellites_detected_per_signal"] = {g["name"]: sorted(int(p) for p in np.nonzero(r[0])[0] + 1)
                                                                 for g, r in zip(sigs, res_all)}

@@ -41,12 +41,37 @@ def check_line(d, n_gpus, prns=63):
 
 
 def test_bench_line_single():
-    d = run_bench(["--workload", "b2a"] + FAST)
+    d = run_bench(["--workload", "b2a", "--full"] + FAST)
     check_line(d, 1)
     assert d["config"]["jobs_rank0"] == {"b2a": 63}
     cold = d["cold"]["b2a"]  # SURVEY 8d "also report cold": fresh context, load + prepare + first run
     assert cold["cold_total_ms"] > cold["warm_run_ms"] > 0 and cold["load_ms"] > 0 and cold["prepare_ms"] > 0
     assert abs(cold["cold_total_ms"] - (cold["load_ms"] + cold["prepare_ms"] + cold["first_run_ms"])) < 1e-6
+
+
+def test_bench_plain_run_and_dumped_outputs(tmp_path):
+    """A plain run (no --full) times the headline only: the extra legs stay off and their keys empty.  --dump-outputs writes
+    the last timed step's acqResults as float64 arrays: the bits results_sha256 digests, the same in a second run."""
+    import hashlib
+
+    import numpy as np
+
+    d = run_bench(["--workload", "b2a", "--steps", "2", "--warmup", "1", "--dump-outputs", str(tmp_path / "a")])
+    check_line(d, 1)
+    assert d["steps"] == 2 and d["ms_per_step"] > 0
+    assert d["cpu_baseline"] is None and d["tracking"] is None and d["strict_f32"] is None and d["b2a"] is None
+    for k in ("cold", "serving", "minimal"):
+        assert k not in d, k
+    got = {}
+    for run in ("a", "b"):
+        if run == "b":
+            run_bench(["--workload", "b2a", "--steps", "1", "--warmup", "0", "--dump-outputs", str(tmp_path / "b")])
+        got[run] = [np.load(tmp_path / run / f"b2a_{f}.npy") for f in ("carrFreq", "codePhase", "peakMetric")]
+        assert all(a.dtype == np.float64 and a.shape == (63,) for a in got[run])
+    assert hashlib.sha256(np.stack(got["a"]).tobytes()).hexdigest() == d["config"]["results_sha256"]["b2a"]
+    for a, b in zip(got["a"], got["b"]):
+        np.testing.assert_array_equal(a, b)
+    assert sorted(int(p) for p in np.nonzero(got["a"][0])[0] + 1) == d["config"]["satellites_detected"]
 
 
 def test_bench_two_ranks_self_spawn():
@@ -71,8 +96,8 @@ def test_joint_workload_at_full_size_is_bit_equal_to_the_single_signal_runs():
     """BASELINE.json configs[4]: B1C + B2a jointly, 63 PRNs each = 126 (signal, PRN) jobs, on the HIP path at full size:
     one rank, and two ranks (LPT shards, one exchange per signal) sharing the one GPU of the box over gloo.  acqResults of
     each signal must be the bits of that signal's own single-device run (zero-filled shards summed: x + 0)."""
-    b1c = run_bench(["--workload", "b1c"] + FAST)
-    # (the default B1C run also times cfg2 -- extra key `b2a` -- and labels its kernels from the plan)
+    b1c = run_bench(["--workload", "b1c", "--full"] + FAST)
+    # (the full B1C run also times cfg2 -- extra key `b2a` -- and labels its kernels from the plan)
     assert b1c["b2a"]["ms_per_step"] > 0 and b1c["b2a"]["satellites_detected"] == b1c["b2a"]["satellites_injected"]
     assert "k_cols_small_f<80>" in b1c["b2a"]["kernel"] and "k_pfa_cols<636>" in b1c["roofline"]["kernel"]
     for k in ("frac_strict_f32", "frac_at_stored_bytes", "traffic_source"):

@@ -11,8 +11,8 @@ cp gpurun_out/r04_coissue.txt profiles/r04_coissue.txt
 cp gpurun_out/r04_sieve_error.txt profiles/r04_sieve_error.txt
 cp gpurun_out/r04_plan_729.txt profiles/r04_plan_729.txt
 grep -o "Power (W): [0-9.]*\|sclk clock level: [0-9S]: ([0-9]*Mhz)" gpurun_out/r04_power_samples.txt | paste - - > profiles/r04_power_samples.txt
-tail -1 gpurun_out/bench_b1c.json > profiles/r04_bench_b1c.json
-tail -1 gpurun_out/bench_b2a.json > profiles/r04_bench_b2a.json
+tail -1 "${BENCH_OUT:-bench_out}/bench_b1c.json" > profiles/r04_bench_b1c.json
+tail -1 "${BENCH_OUT:-bench_out}/bench_b2a.json" > profiles/r04_bench_b2a.json
 cp gpurun_out/bench_under_rocprof_b1c.json profiles/r04_bench_b1c_under_rocprof.json 2>/dev/null
 python tools/make_traffic.py gpurun_out/pmc_summary_default.txt b1c 201 profiles/r04_b1c_pmc.txt k_cols_wave_f "round 4" > /dev/null
 python tools/make_valu.py gpurun_out/pmc_summary_default.txt profiles/r04_isa_mix.json b1c 201 "round 4" > /dev/null

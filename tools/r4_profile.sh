@@ -4,6 +4,7 @@
 # bench line.  Everything lands under gpurun_out/; tools/r4_collect.sh copies the summaries into profiles/ afterwards.
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 mkdir -p gpurun_out
+export BENCH_OUT="${BENCH_OUT:-bench_out}"; mkdir -p "$BENCH_OUT"  # the full bench lines (bench.py --full) are written here
 bash tools/pmc_run.sh > gpurun_out/pmc_run.log 2>&1; tail -2 gpurun_out/pmc_run.log
 cp gpurun_out/pmc_summary.txt gpurun_out/pmc_summary_default.txt
 bash tools/profile_run.sh > gpurun_out/profile_run.log 2>&1; tail -3 gpurun_out/profile_run.log
@@ -20,5 +21,5 @@ for l in sys.stdin:
         j=json.loads(l); r=j['roofline']; print('plan $pl (run-time-plan kernels): pair', round(r['pair_ms'],3), 'ms per 201 cells, fft_len', j['config']['fft_len'], 'detected', j['config']['satellites_detected'])"
 done > gpurun_out/r04_plan_729.txt 2>&1; cat gpurun_out/r04_plan_729.txt
 bash tools/exp/r4_power.sh > gpurun_out/r04_power.txt 2>&1; grep -o "Power (W): [0-9.]*\|sclk clock level: [0-9S]: ([0-9]*Mhz)" gpurun_out/r04_power_samples.txt | paste - - | sort | uniq -c | sort -rn | head -5
-timeout 1200 python bench.py > gpurun_out/bench_b1c.json 2> gpurun_out/bench_b1c.err; echo "bench b1c rc=$?"
-timeout 600 python bench.py --workload b2a > gpurun_out/bench_b2a.json 2> gpurun_out/bench_b2a.err; echo "bench b2a rc=$?"
+timeout 1200 python bench.py --full > "$BENCH_OUT/bench_b1c.json" 2> "$BENCH_OUT/bench_b1c.err"; echo "bench b1c rc=$?"
+timeout 600 python bench.py --full --workload b2a > "$BENCH_OUT/bench_b2a.json" 2> "$BENCH_OUT/bench_b2a.err"; echo "bench b2a rc=$?"
