@@ -185,7 +185,7 @@ struct AcqState {
     std::map<int, PrnResult> last;
     // (PRN, bin) cells per launch pair; 0 = all Doppler bins of the PRN that fit the work-buffer budget.
     // Measured on the B1C plan (us/cell): 1 -> 41, 4 -> 25, 16 -> 21 without the row-pass cell loop;
-    // with it 16 -> 17.5, 48 -> 16.5, 201 -> 15.9 (tools/exp/exp_gchunk.sh)
+    // with it 16 -> 17.5, 48 -> 16.5, 201 -> 15.9 (HISTORY.md 1.4)
     int group_env = 0;
     int group = 16;
     bool half = false;         // spectra + inter-pass buffer stored as fp16 complex (specialised plans only)
@@ -359,10 +359,7 @@ static int set_lds_limits(bds_ctx *ctx) {
 // forward passes on the specialised stages (plans with pl.fast)
 template <int S, class Loader>
 static void launch_cols_fwd_t(bds_ctx *ctx, hipStream_t s_, const Plan2D &pl, Loader ld, int nb, float2 *Bw) {
-#ifndef BDS_FWD_T
-#define BDS_FWD_T 4
-#endif
-    constexpr int T = BDS_FWD_T;
+    constexpr int T = 4;
     const size_t lds = sizeof(float2) * (T * tspan<S>() + lds_span(twiddle_entries<S>()));
     want_lds(ctx, k_cols_fwd_t<S, T, Loader>, lds);
     hipLaunchKernelGGL((k_cols_fwd_t<S, T, Loader>), dim3((pl.L2 + T - 1) / T, nb), dim3(cols_threads<S, T>()), lds, s_,
@@ -465,14 +462,14 @@ struct SieveOut {
 template <int S, int NC, class ST>
 static void launch_rows_f(bds_ctx *ctx, hipStream_t sr, const Plan2D &pl, const void *Xs, int G, int bin0, const void *Cs,
                           void *Bw, float out_scale, const CellList &cl, bool ilv) {
-    const size_t lds = sizeof(float2) * (tspan<S>() + f32_tw_span<S, kF32TabRows>());
+    const size_t lds = sizeof(float2) * (tspan<S>() + f32_tw_span<S, false>());
     want_lds(ctx, k_rows_inv_f<S, NC, ST>, lds);
     // balanced chunks of at most tune.gchunk cells
     int nch = (G + ctx->tune.gchunk - 1) / ctx->tune.gchunk;
     int gc = (G + nch - 1) / nch;
     if (cl.bin) gc = cl.gc, nch = (G + cl.gc - 1) / cl.gc;  // a workgroup stays inside one PRN's cells
     const int nvb = pl.L1 * nch;  // L1 % 8 == 0 on every specialised plan: virtual workgroup vb sits on XCD vb % 8
-    const RowsFArgs A{(const float2 *)(kF32TabRows ? pl.d_ftab2 : pl.d_tw2), pl.twl, Xs, pl.L, pl.L1, G, bin0, Cs, Bw, out_scale, gc, nch, cl.bin, cl.cs, nvb, ctx->tune.clockprobe ? pl.d_clk : nullptr, ilv ? 1 : 0};
+    const RowsFArgs A{pl.d_tw2, pl.twl, Xs, pl.L, pl.L1, G, bin0, Cs, Bw, out_scale, gc, nch, cl.bin, cl.cs, nvb, ctx->tune.clockprobe ? pl.d_clk : nullptr, ilv ? 1 : 0};
     const int grid = ctx->tune.rows_grid > 0 ? std::min(nvb, (ctx->tune.rows_grid + 7) / 8 * 8) : nvb;
     if constexpr (S == 4096 && std::is_same<ST, __half2>::value) {
         if (ctx->tune.wrows != 0 || pl.small) {  // wave-private row pass (bds_acq_wrows.h): per-lane twiddle constants, 4 barriers per cell
@@ -1568,17 +1565,6 @@ extern "C" int bds_acq_run(bds_ctx *ctx, const bds_settings *s_in, const int32_t
         if (int rc2 = bds_acq_prepare(ctx, s_in)) return rc2;
     }
 }
-
-#ifdef BDS_EXP_PHASES
-// timing build only: the phase-clock sums of the wave-private search kernels (bds_acq_f32.h), read and cleared
-extern "C" __attribute__((visibility("default"))) int bds_debug_phases(unsigned long long *out, int n) {
-    unsigned long long h[128] = {};
-    if (hipMemcpyFromSymbol(h, HIP_SYMBOL(g_phase), sizeof(h)) != hipSuccess) return -1;
-    for (int i = 0; i < n && i < 128; ++i) out[i] = h[i];
-    unsigned long long z[128] = {};
-    return hipMemcpyToSymbol(HIP_SYMBOL(g_phase), z, sizeof(z)) == hipSuccess ? 0 : -1;
-}
-#endif
 
 extern "C" int bds_resample_plan(const bds_settings *s, double *new_fs, double *new_if, double *wp) {
     if (!s) return BDS_ERR_ARG;

@@ -19,73 +19,17 @@
 
 #include "bds_acq_fast.h"
 
-// Timing experiments (tools/exp/exp_parts.sh; results are INVALID with any of these defined):
-//   BDS_EXP_NOBARRIER  __syncthreads() of the two search kernels compiled out
-//   BDS_EXP_ROWS_NOSTORE / BDS_EXP_COLS_NOLOAD  no inter-pass buffer traffic
-//   BDS_EXP_ROWS_OCC   launch bound (waves per SIMD) of the row pass
-#ifdef BDS_EXP_NOBARRIER
-#define BDS_SYNC() __builtin_amdgcn_s_waitcnt(0)
-#else
-#define BDS_SYNC() __syncthreads()
-#endif
-// Row pass at 2 waves per SIMD: it needs ~216 VGPRs (two packed code-spectrum rows, the inter-pass twiddles and a
-// radix-16 butterfly with its twiddles live at once); squeezed into the 168 of a third wave it spills ~48 of them
-// to scratch inside the cell loop, which doubles the kernel's HBM reads (measured 2.4 ms vs 2.0 ms per 201 cells).
-#ifndef BDS_EXP_ROWS_OCC
-#define BDS_EXP_ROWS_OCC 2
-#endif
-
-// BDS_EXP_PHASES (tools/exp/phases.sh; a timing build, never the product): the wave-private search kernels stamp the shader clock
-// (s_memtime) at their phase boundaries, with explicit waits so that memory / LDS / barrier waits are told apart from issue
-// time, and add the intervals to g_phase[]; read and cleared by bds_debug_phases().
-#ifdef BDS_EXP_PHASES
-__device__ unsigned long long g_phase[128];
-#define PH_DECL(n)                       \
-    unsigned long long ph_acc[n] = {};   \
-    unsigned long long ph_t = __builtin_readcyclecounter()
-#define PH_MARK(i)                                                   \
-    do {                                                             \
-        __builtin_amdgcn_sched_barrier(0);                           \
-        const unsigned long long t_ = __builtin_readcyclecounter();  \
-        ph_acc[i] += t_ - ph_t;                                      \
-        ph_t = t_;                                                   \
-        __builtin_amdgcn_sched_barrier(0);                           \
-    } while (0)
-#define PH_WAIT_VM() asm volatile("s_waitcnt vmcnt(0)" ::: "memory")
-#define PH_WAIT_LGKM() asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory")
-#define PH_FLUSH(base, n)                                                            \
-    do {                                                                             \
-        if ((threadIdx.x & 63) == 0 && (blockIdx.x & 127) == 5) { /* sampled: same-line atomics run at ~10 M/s */ \
-            for (int i_ = 0; i_ < (n); ++i_) atomicAdd(&g_phase[(base) + i_], ph_acc[i_]); \
-            atomicAdd(&g_phase[(base) + (n)], 1ull);                                 \
-        }                                                                            \
-    } while (0)
-#else
-#define PH_DECL(n)
-#define PH_MARK(i)
-#define PH_WAIT_VM()
-#define PH_WAIT_LGKM()
-#define PH_FLUSH(base, n)
-#endif
-
 namespace bds {
 
 // Per-stage [q][k] twiddle tables in LDS for the inverse fp32 transforms (bds_fft_t.h tstage TAB) instead of the W_S
 // table + products: -44 vector instructions per radix-16 butterfly and twiddled stage for 8-35 KB of LDS and 11 more
 // LDS reads.  Measured on cfg3: column pass 2.32 vs 2.38 ms, row pass 2.12 vs 2.10 ms (its LDS pipe is as busy as its
 // vector unit) -- so the column pass takes the tables and the row pass keeps the products.
-#ifndef BDS_F32_TAB_COLS
-#define BDS_F32_TAB_COLS 1
-#endif
-#ifndef BDS_F32_TAB_ROWS
-#define BDS_F32_TAB_ROWS 0
-#endif
-static constexpr bool kF32TabRows = BDS_F32_TAB_ROWS != 0;
-// column pass: only the 768-point plan (cfg3) -- the 256-point kernel, whose twiddled stage is also its register-heavy
+// Column pass: only the 768-point plan (cfg3) -- the 256-point kernel, whose twiddled stage is also its register-heavy
 // last stage, spills 25 VGPRs with the tables and runs 2x slower (cfg2: 2.95 vs 1.43 ms)
 template <int S>
 __host__ __device__ constexpr bool f32_tab_cols() {
-    return BDS_F32_TAB_COLS != 0 && S == 768;
+    return S == 768;
 }
 // float2 entries of the twiddle area behind the data in LDS
 template <int S, bool TAB>
@@ -142,13 +86,9 @@ struct RowsFArgs {
 struct ClockProbe {
     unsigned long long *acc;
     long long c0 = 0, r0 = 0;
-#ifdef BDS_EXP_NOCLOCK
-    __device__ __forceinline__ ClockProbe(unsigned long long *, unsigned) : acc(nullptr) {}
-#else
     __device__ __forceinline__ ClockProbe(unsigned long long *p, unsigned mask) : acc((p && (blockIdx.x & mask) == 0) ? p : nullptr) {
         if (acc) c0 = clock64(), r0 = wall_clock64();
     }
-#endif
     __device__ __forceinline__ void finish(int tid) const {
         if (acc) {
             const long long c1 = clock64(), r1 = wall_clock64();
@@ -172,10 +112,7 @@ __device__ __forceinline__ void rows_inv_f_body(const RowsFArgs &A, int vb, int 
     extern __shared__ __attribute__((aligned(16))) float2 ldsf[];  // tspan<S>() data + twiddle table
     __shared__ float2 s_a[MBL], s_b[RL];
     float2 *tw_lds = ldsf + tspan<S>();
-    if constexpr (kF32TabRows)
-        load_stage_tables<S, NT>(tw_lds, A.tw, tid);
-    else
-        load_twiddles<S, NT>(tw_lds, A.tw, tid);
+    load_twiddles<S, NT>(tw_lds, A.tw, tid);
     const long L = A.L;
     const int xcd = vb & 7, m = vb >> 3;
     const int GC = A.GC, NCH = A.NCH;
@@ -258,9 +195,6 @@ __device__ __forceinline__ void rows_inv_f_body(const RowsFArgs &A, int vb, int 
             };
             auto out = [&](int i, int q, int, int e, float2 v) {
                 const float2 t = cmul(v, wo[i][q]);
-#ifdef BDS_EXP_ROWS_NOSTORE
-                if (t.x == 1.2345f)
-#endif
                 if constexpr (HS)
                     *reinterpret_cast<uint32_t *>(dst + e) = f2_to_h2(t);
                 else
@@ -271,8 +205,8 @@ __device__ __forceinline__ void rows_inv_f_body(const RowsFArgs &A, int vb, int 
             auto next = [&]() {
                 if (comp == NCOMP - 1 && g + 1 < g1) fetch_x(g + 1);
             };
-            TPlan<S>::template run_hook<1, NT, +1, kF32TabRows>(ldsf, (const float2 *)tw_lds, tid, src, out, next);
-            if (comp + 1 < NCOMP || g + 1 < g1) BDS_SYNC();  // last-stage reads precede the next first-stage writes
+            TPlan<S>::template run_hook<1, NT, +1>(ldsf, (const float2 *)tw_lds, tid, src, out, next);
+            if (comp + 1 < NCOMP || g + 1 < g1) __syncthreads();  // last-stage reads precede the next first-stage writes
         }
     }
 }
@@ -357,11 +291,7 @@ __device__ __forceinline__ void cols_inv_max_f_body(const ColsFArgs &A, int tb, 
         for (int i = 0; i < NI; ++i) {
             const int it = tid + i * NT;
             const int r = it / QG, cq = (it % QG) * 4;
-#ifdef BDS_EXP_COLS_NOLOAD
-            if (full_tile && A.w0 == 1.2345f) {
-#else
             if (full_tile) {
-#endif
                 if constexpr (HS)
                     pre[i] = *reinterpret_cast<const uint4 *>(src + (long)r * L2 + c0 + cq);
                 else
@@ -387,7 +317,7 @@ __device__ __forceinline__ void cols_inv_max_f_body(const ColsFArgs &A, int tb, 
                 for (int k = 0; k < 4; ++k) ldsf[(cq + k) * SP + pr] = pre[i].v[k];
             }
         }
-        BDS_SYNC();
+        __syncthreads();
         if (comp + 1 < NCOMP) fetch(comp + 1);  // in flight during the transform
         const float w = comp == 0 ? A.w0 : A.w1;
         // Output q of the last stage covers rows q*NSL .. q*NSL+NSL-1: a whole q beyond the searched lags
@@ -400,7 +330,7 @@ __device__ __forceinline__ void cols_inv_max_f_body(const ColsFArgs &A, int tb, 
             }
         };
         TPlan<S>::template run<T, NT, +1, f32_tab_cols<S>()>(ldsf, (const float2 *)tw_lds, tid, LdsIO{}, out);
-        if (comp + 1 < NCOMP) BDS_SYNC();  // last-stage reads done before the tile is overwritten
+        if (comp + 1 < NCOMP) __syncthreads();  // last-stage reads done before the tile is overwritten
     }
     // lag of output (i, q): (bb + q NSL) L2 + c0 + j with b = tid + i NT, j = b / NSL, bb = b % NSL
     auto lag_of = [&](int i, int q) {
@@ -441,7 +371,6 @@ __device__ __forceinline__ void cols_inv_max_f_body(const ColsFArgs &A, int tb, 
         return;
     }
     const float thr = Mt * A.keep;
-#ifndef BDS_NO_SLOWPATH
     if (mx >= thr) {  // rare: this thread holds the maximum or a value within the sieve tolerance of it
 #pragma unroll
         for (int i = 0; i < MBL; ++i) {
@@ -469,24 +398,25 @@ __device__ __forceinline__ void cols_inv_max_f_body(const ColsFArgs &A, int tb, 
             }
         }
     }
-#endif
 }
 
+// Row pass at 2 waves per SIMD: it needs ~216 VGPRs (two packed code-spectrum rows, the inter-pass twiddles and a
+// radix-16 butterfly with its twiddles live at once); squeezed into the 168 of a third wave it spills ~48 of them
+// to scratch inside the cell loop, which doubles the kernel's HBM reads (measured 2.4 ms vs 2.0 ms per 201 cells).
+constexpr int kRowsFOcc = 2;
+
 template <int S, int NCOMP, class ST>
-__global__ __launch_bounds__(rows_threads<S>(), BDS_EXP_ROWS_OCC) void k_rows_inv_f(RowsFArgs A) {
+__global__ __launch_bounds__(rows_threads<S>(), kRowsFOcc) void k_rows_inv_f(RowsFArgs A) {
     // (a grid smaller than nvb makes the workgroups persistent: with the column pass of the previous group on a
     //  second stream they then share every CU with it instead of queueing in front of it)
     for (int vb = (int)blockIdx.x; vb < A.nvb; vb += (int)gridDim.x) {
         rows_inv_f_body<S, NCOMP, ST>(A, vb, (int)threadIdx.x);
-        if (vb + (int)gridDim.x < A.nvb) BDS_SYNC();  // the next item rewrites the LDS tables
+        if (vb + (int)gridDim.x < A.nvb) __syncthreads();  // the next item rewrites the LDS tables
     }
 }
 
-#ifndef BDS_COLS_MINW
-#define BDS_COLS_MINW 4
-#endif
 template <int S, int T, int NCOMP, bool MASKED, class ST>
-__global__ __launch_bounds__((cols_threads<S, T>()), BDS_COLS_MINW) void k_cols_inv_max_f(ColsFArgs A) {
+__global__ __launch_bounds__((cols_threads<S, T>()), 4) void k_cols_inv_max_f(ColsFArgs A) {
     cols_inv_max_f_body<S, T, NCOMP, MASKED, ST>(A, (int)blockIdx.x, (int)gridDim.x, (int)blockIdx.y, (int)threadIdx.x);
 }
 

@@ -31,12 +31,6 @@
 
 #include "bds_acq_wcols.h"  // Extra, wc_pack, wave_max_f32; bds_fft_pk.h, bds_lds.h
 
-#ifdef PFA_EXP_R_NOBAR
-#define PFA_RSYNC() __builtin_amdgcn_s_waitcnt(0)
-#else
-#define PFA_RSYNC() __syncthreads()
-#endif
-
 namespace bds {
 namespace pfa {
 
@@ -202,13 +196,8 @@ __global__ __launch_bounds__(kRowsThreads, 2) void k_pfa_rows(RowsArgs A) {
         //  five vector instructions per load: 8 % of the cell loop)
         const int xoff = ((k1s * K2 + k2s) * (2 * K3) + o3 + jj) * 4;  // < 2^25 bytes
         uint32_t xn[25];
-#ifdef PFA_EXP_R_NOLOAD
-#pragma unroll
-        for (int q = 0; q < 25; ++q) xn[q] = 0x3c003800u + q + cell + (uint32_t)xoff;
-#else
 #pragma unroll
         for (int q = 0; q < 25; ++q) xn[q] = __builtin_amdgcn_raw_buffer_load_b32(xs_rsrc, xoff, 500 * q, 0);
-#endif
         int bin_next = A.bin[min(cell + 1, c1 - 1)];
         uint32_t outp[NC][25];
 #pragma unroll
@@ -216,8 +205,7 @@ __global__ __launch_bounds__(kRowsThreads, 2) void k_pfa_rows(RowsArgs A) {
             v2f x[25];
             // X conj(C): (xr, -xi).(cr', ci') and (xi, xr).(cr', ci') with C' = conj(C) stored.  The three-operand v_dot2_f32_f16 with an inline
             // zero addend, five products per asm block with the dot -> VALU hazard closed by hand (s_nop 2), as bds_acq_wrows.h: the
-            // builtin compiles to the accumulating v_dot2c behind a v_mov 0 per result (50 moves per cell).  -DPFA_ROWS_DOT2_BUILTIN: the builtin.
-#ifndef PFA_ROWS_DOT2_BUILTIN
+            // builtin compiles to the accumulating v_dot2c behind a v_mov 0 per result (50 moves per cell).
 #pragma unroll
             for (int q = 0; q < 25; q += 5) {
                 uint32_t xs[5], xc[5];
@@ -238,19 +226,9 @@ __global__ __launch_bounds__(kRowsThreads, 2) void k_pfa_rows(RowsArgs A) {
 #pragma unroll
                 for (int i = 0; i < 5; ++i) x[q + i] = (v2f){re[i], im[i]};
             }
-#else
-#pragma unroll
-            for (int q = 0; q < 25; ++q) {
-                const uint32_t xs = __builtin_amdgcn_alignbit(xn[q], xn[q], 16), xc = xn[q] ^ 0x80000000u;
-                typedef _Float16 h2 __attribute__((ext_vector_type(2)));
-                const h2 hc = __builtin_bit_cast(h2, cv[c][q]);
-                x[q] = (v2f){__builtin_amdgcn_fdot2(__builtin_bit_cast(h2, xc), hc, 0.f, false),
-                             __builtin_amdgcn_fdot2(__builtin_bit_cast(h2, xs), hc, 0.f, false)};
-            }
-#endif
             // stage 1: 25 points over q (k3 = j + 125 q) -> p, twiddle W3125^(j p), a[j][p] at 25 j + p
             pk_radix25(x);
-            if (c > 0) PFA_RSYNC();  // the previous component's stage-3 reads of the region are done
+            if (c > 0) __syncthreads();  // the previous component's stage-3 reads of the region are done
             if (live) {
 #pragma unroll
                 for (int sl = 0; sl < 25; ++sl) {
@@ -261,7 +239,7 @@ __global__ __launch_bounds__(kRowsThreads, 2) void k_pfa_rows(RowsArgs A) {
                     region[25 * j + p] = to_f2(v);
                 }
             }
-            PFA_RSYNC();
+            __syncthreads();
             // stage 2: thread (i, pg): for c5 = 0..4: 5 points over r of a[i + 25 r][5 pg + c5] -> u, twiddle W125^(i u), in place
             if (live) {
 #pragma unroll
@@ -277,7 +255,7 @@ __global__ __launch_bounds__(kRowsThreads, 2) void k_pfa_rows(RowsArgs A) {
                     }
                 }
             }
-            PFA_RSYNC();
+            __syncthreads();
             // stage 3: thread t' = p + 25 u: 25 points over i of b[p][i][u] at 25 (i + 25 u) + p -> t'': X[t' + 125 t'']
             lds_read25<25 * 8>(x, region_b + (unsigned)(625 * (jj / 25) + jj % 25) * 8u);  // b[p][i][u] at 25 (i + 25 u) + p, i = 0..24
             pk_radix25(x);
@@ -288,20 +266,13 @@ __global__ __launch_bounds__(kRowsThreads, 2) void k_pfa_rows(RowsArgs A) {
                 outp[c][tq] = __builtin_bit_cast(uint32_t, __builtin_convertvector(x[sl], h2));  // v_cvt_pk_f16_f32: round to nearest even
             }
         }
-        // the two rows of the pair meet: after the swap half 0 holds (row 0, row 1) of t'' = e, half 1 of t'' = e + 1
-        // (descriptor at the piece of lag 0: a lag's offset is tile * 82 944 + (lag in the tile) * 16 bytes)
-        const __amdgpu_buffer_rsrc_t dst_rsrc = __builtin_amdgcn_make_buffer_rsrc((void *)(A.Bw + (size_t)cell * kCellElems + bw_piece(mp, k2, 0)), 0,
-                                                                                   (unsigned)((kCellElems - bw_piece(mp, k2, 0)) * 4), 0x00020000);
         asm volatile("" : "+v"(bin_next));  // (the bin's wait stands here: every load long back, no store in flight yet)
         bin_cur = __builtin_amdgcn_readfirstlane(bin_next);
+        // (descriptor at the piece of lag 0: a lag's offset is tile * 82 944 + (lag in the tile) * 16 bytes)
         typedef int v4i __attribute__((ext_vector_type(4)));
-#ifdef PFA_EXP_R_SAMECELL  // (timing experiment: every cell's stores into the first cell's 16 MB -- the Infinity Cache takes them)
-        const unsigned long long dst_base = (unsigned long long)(A.Bw + bw_piece(mp, k2, 0));
-#else
         const unsigned long long dst_base = (unsigned long long)(A.Bw + (size_t)cell * kCellElems + bw_piece(mp, k2, 0));
-#endif
         const v4i dst_words = {(int)(unsigned)dst_base, (int)((unsigned)(dst_base >> 32) & 0xffffu), (int)(unsigned)((kCellElems - bw_piece(mp, k2, 0)) * 4), 0x00020000};
-        (void)dst_rsrc;
+        // the two rows of the pair meet: after the swap half 0 holds (row 0, row 1) of t'' = e, half 1 of t'' = e + 1
 #pragma unroll
         for (int e = 0; e < 25; e += 2) {
             uint32_t P[2], Q[2];
@@ -316,12 +287,6 @@ __global__ __launch_bounds__(kRowsThreads, 2) void k_pfa_rows(RowsArgs A) {
             if (live && tq < 25) {  // lag t3 = j + 125 tq
                 typedef uint32_t u4 __attribute__((ext_vector_type(4)));
                 const int t3s = j + 125 * tq;
-#ifdef PFA_EXP_R_NOSTORE
-                asm volatile("" ::"v"(P[0]), "v"(Q[0]), "v"(P[1]), "v"(Q[1]), "v"(t3s));
-#else
-#ifdef PFA_ROWS_STORE_BUILTIN
-                __builtin_amdgcn_raw_buffer_store_b128((u4){P[0], Q[0], P[1], Q[1]}, dst_rsrc, (int)(bw_piece(0, 0, t3s) * 4), 0, 0);
-#else
                 // Issued by hand: loads and stores share the vmcnt counter and return out of order relative to each other, so with stores
                 // the compiler knows of in flight its first wait for a load of the NEXT cell becomes vmcnt(0) -- the whole latency of this
                 // cell's 13 stores in front of every cell (the row pass with its stores compiled out ran 17 % faster).  Stores it does not
@@ -329,11 +294,9 @@ __global__ __launch_bounds__(kRowsThreads, 2) void k_pfa_rows(RowsArgs A) {
                 // Nothing in this kernel reads the buffer; the end of the kernel makes the stores visible.
                 asm volatile("buffer_store_dwordx4 %0, %1, %2, 0 offen\n s_nop 0" ::"v"((u4){P[0], Q[0], P[1], Q[1]}), "v"((int)(bw_piece(0, 0, t3s) * 4)), "s"(dst_words)
                              : "memory");
-#endif
-#endif
             }
         }
-        PFA_RSYNC();  // region free for the next cell
+        __syncthreads();  // region free for the next cell
     }
 }
 
@@ -362,11 +325,6 @@ inline void make_coef_frags(uint16_t *out /* kCoefBytes / 2 halves */) {
                     out[((((size_t)nb * 4 + ins) * 2 + 1) * 64 + lane) * 8 + e] = lo;
                 }
 }
-
-#ifndef PFA_COLS_BOUND_PARTS
-#define PFA_COLS_BOUND_PARTS 1
-#endif
-constexpr int kBoundParts = PFA_COLS_BOUND_PARTS;  // coefficient parts of the column pass's bound pass (1: hi only; 2: as the values' pass)
 
 struct ColsArgs {
     const uint32_t *Bw;           // inter-pass buffer of the launch's cells
@@ -448,19 +406,11 @@ __global__ __launch_bounds__(kColsThreads, 2) void k_pfa_cols(ColsArgs A) {
 #pragma unroll
             for (int ins = 0; ins < 4; ++ins) {
                 const int mg = 4 * ins + ks;
-                uint4 l0 = make_uint4(0, 0, 0, 0), l1 = l0;
                 const size_t off = bw_piece(0, 4 * quad + r, t3);
-#ifdef PFA_EXP_C_NOLOAD
-                l0 = make_uint4(0x3c003800u + lane, 0x38003c00u + cl + blk, 0x3c003400u + quad, 0x34003c00u + ins), l1 = l0;
-                if (false) {
-#else
-                {
-#endif
                 // (rows past the 54th -- k1 >= 54: the K padding of the last matrix instruction -- read row pair 26 again: their coefficients are
                 //  zeros and the buffer holds finite values, and a load under a lane condition costs a branch and a full vmcnt(0) wait per quad)
-                l0 = *reinterpret_cast<const uint4 *>(base + (size_t)min(2 * mg, MP - 1) * K2 * (kTileLags * 4) + off);
-                l1 = *reinterpret_cast<const uint4 *>(base + (size_t)min(2 * mg + 1, MP - 1) * K2 * (kTileLags * 4) + off);
-                }
+                const uint4 l0 = *reinterpret_cast<const uint4 *>(base + (size_t)min(2 * mg, MP - 1) * K2 * (kTileLags * 4) + off);
+                const uint4 l1 = *reinterpret_cast<const uint4 *>(base + (size_t)min(2 * mg + 1, MP - 1) * K2 * (kTileLags * 4) + off);
                 fa[0][quad][ins] = make_uint4(l0.x, l0.y, l1.x, l1.y);
                 fa[1][quad][ins] = make_uint4(l0.z, l0.w, l1.z, l1.w);
             }
@@ -478,10 +428,6 @@ __global__ __launch_bounds__(kColsThreads, 2) void k_pfa_cols(ColsArgs A) {
             for (int c = 0; c < NC; ++c) {
 #pragma unroll
                 for (int quad = 0; quad < 3; ++quad) acc2[c][quad] = (f4){0.f, 0.f, 0.f, 0.f};
-#ifdef PFA_EXP_C_NOMFMA  // (timing experiments, tools/exp/r6_pfa_parts.sh: results INVALID)
-#pragma unroll
-                for (int quad = 0; quad < 3; ++quad) acc2[c][quad] = (f4){__uint_as_float(fa[c][quad][0].x), __uint_as_float(fb[1][0].y), __uint_as_float(fa[c][quad][2].z), __uint_as_float(fb[3][1].w)};
-#else
 #pragma unroll
                 for (int ins = 0; ins < 4; ++ins)
 #pragma unroll
@@ -490,18 +436,12 @@ __global__ __launch_bounds__(kColsThreads, 2) void k_pfa_cols(ColsArgs A) {
                         for (int quad = 0; quad < 3; ++quad)
                             acc2[c][quad] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(h8, fa[c][quad][ins]), __builtin_bit_cast(h8, fb[ins][part]),
                                                                                    acc2[c][quad], 0, 0, 0);
-#endif
             }
         };
         auto epilogue = [&](const f4 (&acc2)[NC][3], float (&m2)[2][6]) {
 #pragma unroll
             for (int c = 0; c < NC; ++c) {
                 const f4(&acc)[3] = acc2[c];
-#ifdef PFA_EXP_C_NOEPI
-#pragma unroll
-                for (int t = 0; t < 6; ++t) m2[c][t] = acc[t >> 1][t & 1] + acc[t >> 1][2 + (t & 1)];
-                continue;
-#endif
                 // lane (G = lane >> 4, o = lane & 15): acc[quad][rr] = row 4 G + rr <-> (t3 = t0 + G, k2 = 4 quad + rr) of output 16 nb + o
                 float v[12], P[7], Q[7];
 #pragma unroll
@@ -536,7 +476,8 @@ __global__ __launch_bounds__(kColsThreads, 2) void k_pfa_cols(ColsArgs A) {
             epilogue(acc2, m2);
         };
         const int t3o = t0 + (lane >> 4);  // the lag t3 of this lane's outputs
-        constexpr int kParts1 = DBG ? 2 : kBoundParts;  // (the debug instantiation reports this pass's values: both parts)
+        // coefficient parts of the bound pass: hi only (the debug instantiation reports this pass's values: both parts)
+        constexpr int kParts1 = DBG ? 2 : 1;
         float best = 0.f, ssum = 0.f;
         // The bound pass, software-pipelined: the matrix instructions of output block nb + 1 are in flight while the vector pipe works on
         // block nb's accumulators (two waves per SIMD that started together stay in step -- both in their matrix phase, then both in
@@ -594,12 +535,7 @@ __global__ __launch_bounds__(kColsThreads, 2) void k_pfa_cols(ColsArgs A) {
         const float ub = wave_max_f32(sqrtf(best) + dlt);
         const float bw = ub * ub * wsum2 * 1.00001f;
         const float curv = __uint_as_float(cur), lim = fminf(curv, lbv * A.keep);
-#if defined(PFA_EXP_C_NOEXACT) || defined(PFA_EXP_C_NOMFMA) || defined(PFA_EXP_C_NOEPI) || defined(PFA_EXP_C_NOLOAD) || defined(PFA_EXP_R_NOLOAD) || defined(PFA_EXP_R_NOSTORE)
-        if (bw < 0.f)  // (timing experiments on invalid data: the bound pass alone)
-#else
-        if (!(bw < lim * lim))  // (wave-uniform; also taken while the bounds are unset or not finite)
-#endif
-        {
+        if (!(bw < lim * lim)) {  // (wave-uniform; also taken while the bounds are unset or not finite)
             if (A.stats && lane == 0) atomicAdd(A.stats + 1, 1ull);
             // -- only the output blocks in which some lane's bound reaches the limit (the same expression per lane and block as the wave's test
             // above: the block that failed it is among them); every output of the other blocks is below the cell's maximum so far and

@@ -35,21 +35,6 @@
 #include "bds_fft_pk.h"
 #include "bds_lds.h"
 
-// Timing experiments (tools/exp/exp_wparts.sh; results are INVALID with any of these defined):
-//   BDS_EXP_WC_NOTAIL  nothing after the wave maximum (no bounds, no list, no atomics)
-//   BDS_EXP_WC_NOLOAD  the inter-pass buffer is not read
-//   BDS_EXP_WC_NOBAR   workgroup barriers compiled out
-#ifdef BDS_EXP_WC_NOBAR
-#define BDS_WSYNC() __builtin_amdgcn_s_waitcnt(0)
-#else
-#define BDS_WSYNC() __syncthreads()
-#endif
-
-// cache policy of the column pass's tile-row loads (aux of the buffer load: 0 default, 2 = nt; round 5, tools/exp/r5_nt.sh)
-#ifndef BDS_COLS_AUX
-#define BDS_COLS_AUX 0
-#endif
-
 namespace bds {
 
 template <int DIR>
@@ -104,11 +89,7 @@ struct WCols {
     static constexpr size_t kLdsBytes = sizeof(float2) * NW * RS;
     // waves per SIMD the register budget is set for (measured unconstrained need: 80 / 123 / 174 / 215 VGPRs; the
     // LDS regions allow 9 / 4 / 3 / 2 workgroups per CU, so neither resource is wasted on the other's account)
-#ifdef BDS_WCOLS_OCC
-    static constexpr int kOcc = BDS_WCOLS_OCC;
-#else
     static constexpr int kOcc = R1 == 4 ? 5 : R1 == 8 ? 4 : R1 == 12 ? 3 : 2;
-#endif
 };
 
 struct WColsArgs {
@@ -160,7 +141,6 @@ __global__ __launch_bounds__(WCols<S>::NT, WCols<S>::kOcc) void k_cols_wave_f(WC
     const int L2 = A.L2;
     const long L = A.L;
     const ClockProbe clkp(A.clk ? A.clk + 2 : nullptr, 255);
-    PH_DECL(24);
 
     // ---- the item of this workgroup ----------------------------------------------------------------------
     // One tile per workgroup, workgroups started by the hardware in list order.  Workgroup id % 8 = XCD; XCD x keeps the
@@ -187,10 +167,6 @@ __global__ __launch_bounds__(WCols<S>::NT, WCols<S>::kOcc) void k_cols_wave_f(WC
         g = g >= A.G ? g - A.G : g;
         c0 = (xcd * TX + tg * 4 + t4) * W::T;
     }
-#ifdef BDS_EXP_PHASES
-    asm volatile("" : "+s"(g), "+s"(c0));
-#endif
-    PH_MARK(16);  // kernel arguments read, item decoded
 
     // ---- rows of both components: in flight before anything else ---------------------------------------------
     // phase A: butterfly b of column pair cp takes rows b + 64 q
@@ -205,28 +181,14 @@ __global__ __launch_bounds__(WCols<S>::NT, WCols<S>::kOcc) void k_cols_wave_f(WC
                                : (const char *)A.Bw + (((long)g * NCOMP + comp) * L + c0) * (long)sizeof(ST);
         const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc((void *)base, 0, 0x7fffffff, 0x00020000);
         const int rowstep = 64 * L2 * (int)sizeof(ST) * (ILV ? 2 : 1);
+        // (default cache policy: nt tile-row loads measured 1.63 vs 1.46 ms for the column pass, profiles/r05_nt_ab.txt)
 #pragma unroll
         for (int q = 0; q < R1; ++q) {
-#ifdef BDS_EXP_WC_NOLOAD
-            if (A.w0 != 1.2345f) {
-                pre[q] = Raw{};
-                continue;
-            }
-#endif
             if constexpr (ILV) {
-#ifdef BDS_COLS_DMA
-                // experiment: the tile rows by LDS DMA -- buffer_load_dwordx4 ... lds, lane i's 16 bytes at
-                // [q][i] of the wave's own region (free until phase A writes: one tile per workgroup) -- read back below
-                typedef __attribute__((address_space(3))) void *lds_vp;
-                const unsigned off = __builtin_amdgcn_readfirstlane(lds_offset(reinterpret_cast<C *>(ldsf) + wave * RS) + q * 1024u);
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (lds_vp)(uintptr_t)off, 16, voff, q * rowstep, 0, BDS_COLS_AUX);
-                pre[q] = make_uint4(0, 0, 0, 0);
-#else
-                const auto v = __builtin_amdgcn_raw_buffer_load_b128(rsrc, voff, q * rowstep, BDS_COLS_AUX);
+                const auto v = __builtin_amdgcn_raw_buffer_load_b128(rsrc, voff, q * rowstep, 0);
                 pre[q] = make_uint4(v[0], v[1], v[2], v[3]);  // (column 2 cp: data, pilot; column 2 cp + 1: data, pilot)
-#endif
             } else if constexpr (HS) {
-                const auto v = __builtin_amdgcn_raw_buffer_load_b64(rsrc, voff, q * rowstep, BDS_COLS_AUX);
+                const auto v = __builtin_amdgcn_raw_buffer_load_b64(rsrc, voff, q * rowstep, 0);
                 pre[q] = make_uint2(v[0], v[1]);
             } else {
                 const auto v = __builtin_amdgcn_raw_buffer_load_b128(rsrc, voff, q * rowstep, 0);
@@ -235,8 +197,8 @@ __global__ __launch_bounds__(WCols<S>::NT, WCols<S>::kOcc) void k_cols_wave_f(WC
         }
     };
     // Order of the requests (round 4): a load instruction costs this wave 120 - 290 cycles of issue time while the other
-    // workgroups of the CU keep the vector-memory unit busy (tools/phases.py: 8.3 k of a wave's 24 k cycles went into requesting
-    // 45 loads before anything was computed).  So only what phase A of component 0 needs is requested up front -- the rows
+    // workgroups of the CU keep the vector-memory unit busy (the phase-clock profile, HISTORY.md 1.4: 8.3 k of a wave's 24 k cycles
+    // went into requesting 45 loads before anything was computed).  So only what phase A of component 0 needs is requested up front -- the rows
     // and ONE twiddle w_S^b, the others being its powers (ten complex products; their rounding, a few 1e-7, is far inside
     // the sieve's tolerance) -- and the rest (component 1's rows unless interleaved, the phase-B constants, the running bounds)
     // goes out behind phase A's arithmetic, where its latency is covered by phase B of component 0.
@@ -250,7 +212,6 @@ __global__ __launch_bounds__(WCols<S>::NT, WCols<S>::kOcc) void k_cols_wave_f(WC
         cx_set(twB1, u.x, u.y);
     }
     fetch(pre0, 0);
-    PH_MARK(17);  // rows of component 0 requested
     const int cell = A.cell0 + g;
     float *const lbp = A.lb + cell / A.lb_div;
     {
@@ -258,7 +219,6 @@ __global__ __launch_bounds__(WCols<S>::NT, WCols<S>::kOcc) void k_cols_wave_f(WC
 #pragma unroll
         for (int p = 2; p < R1; ++p) twA[p] = (p & 1) ? cx_mul(twA[p - 1], w) : cx_mul(twA[p / 2], twA[p / 2]);
     }
-    PH_MARK(19);  // phase-A constants formed
     C *const ldsc = reinterpret_cast<C *>(ldsf);
     C *wrA[4];  // + m MS, by the swizzle (m & 7) >> 1 of row m
 #pragma unroll
@@ -331,18 +291,6 @@ __global__ __launch_bounds__(WCols<S>::NT, WCols<S>::kOcc) void k_cols_wave_f(WC
     float bmax = 0.f;         // maximum of |y_d|^2 (+ |y_p|^2) over the wave's outputs
     float lbv = 0.f;
     unsigned cur = 0;
-    PH_MARK(15);  // set-up: kernel arguments, item, loads issued
-    PH_WAIT_VM();
-#ifdef BDS_COLS_DMA
-    if constexpr (ILV) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        const uint4 *stage = reinterpret_cast<const uint4 *>(reinterpret_cast<C *>(ldsf) + wave * RS) + lane;
-#pragma unroll
-        for (int q = 0; q < R1; ++q) pre0[q] = stage[64 * q];
-        __syncthreads();  // every wave has its rows in registers before phase A writes into the regions
-    }
-#endif
-    PH_MARK(0);  // rows of both components + per-lane constants have arrived
 #pragma unroll
     for (int comp = 0; comp < NCOMP; ++comp) {
         {
@@ -373,19 +321,14 @@ __global__ __launch_bounds__(WCols<S>::NT, WCols<S>::kOcc) void k_cols_wave_f(WC
                     phaseA(pre1, z, 1);
                 }
             }
-            PH_MARK(1 + 6 * comp);  // phase A arithmetic
-            if (comp > 0) BDS_WSYNC();  // every wave is through with its region (last reads of the previous component)
-            PH_MARK(2 + 6 * comp);  // (barrier before the writes)
+            if (comp > 0) __syncthreads();  // every wave is through with its region (last reads of the previous component)
 #pragma unroll
             for (int c = 0; c < 2; ++c) {
 #pragma unroll
                 for (int p = 0; p < R1; ++p) wrA[((c * R1 + p) & 7) >> 1][(c * R1 + p) * MS] = z[c][p];
             }
-            PH_WAIT_LGKM();
-            PH_MARK(3 + 6 * comp);  // phase A writes issued and landed
         }
-        BDS_WSYNC();
-        PH_MARK(4 + 6 * comp);  // barrier
+        __syncthreads();
         // ---- phase B, one slot (= 8 of the wave's rows m) at a time so that only 16-32 points are live:
         //   st2(s): radix 8 over bh, back in place;  st3(s): twiddle, radix 8 over bl, magnitudes.
         // Row m is read and written by the 8 lanes of one ml only, all in this wave, and LDS traffic of a wave is in
@@ -430,7 +373,6 @@ __global__ __launch_bounds__(WCols<S>::NT, WCols<S>::kOcc) void k_cols_wave_f(WC
             if constexpr (s + 1 < SL) st2(std::integral_constant<int, s + 1>{});
             st3(sc);
         });
-        PH_MARK(5 + 6 * comp);  // phase B
     }
     // ---- maximum of the wave's two columns, candidates ------------------------------------------
     // Cauchy-Schwarz: (w_d |y_d| + w_p |y_p|)^2 <= (w_d^2 + w_p^2) (|y_d|^2 + |y_p|^2).  If even that bound, over all of the
@@ -440,11 +382,7 @@ __global__ __launch_bounds__(WCols<S>::NT, WCols<S>::kOcc) void k_cols_wave_f(WC
     const float wsum2 = NCOMP > 1 ? A.w0 * A.w0 + A.w1 * A.w1 : A.w0 * A.w0;
     const float bw = wave_max_f32(bmax) * wsum2 * 1.00001f;
     const float curv = __uint_as_float(cur), lim = fminf(curv, lbv * A.keep);
-#ifdef BDS_EXP_WC_NOTAIL
-    if (bw == 1.2345f) {
-#else
     if (!(bw < lim * lim)) {  // (wave-uniform; also taken while the bounds are unset or not finite)
-#endif
         // exact values; lags outside the searched ranges hold -1 (searched values are >= 0)
         float mag[SL][NV];
         float mx = -1.f;
@@ -520,8 +458,6 @@ __global__ __launch_bounds__(WCols<S>::NT, WCols<S>::kOcc) void k_cols_wave_f(WC
         }
         }
     }
-    PH_MARK(13);  // tail
-    PH_FLUSH(0, 24);
     clkp.finish(tid);
 }
 

@@ -43,21 +43,11 @@ constexpr int kWRowsRegion = 1024;  // elements of a wave's region (4 q' x 256)
 // cycles).  Stride 20 with every octet of e'' shifted by one slot more (mod 4) is clean both ways, and both sides still
 // address it as one per-lane base + a compile-time offset.
 constexpr int kWRowsXS = 20;
-// cache policy of the row pass's streams (round 5, tools/exp/r5_nt.sh, profiles/r05_nt_ab.txt; per 201 cells, alternating on one
-// box): non-temporal STORES of the inter-pass buffer pair 3.175 vs 3.189 ms (kept: rows 1.685 vs 1.703, columns 1.451 vs 1.470);
+// cache policy of the row pass's streams: non-temporal on its stores only (round 5, profiles/r05_nt_ab.txt; per 201 cells, alternating
+// on one box): non-temporal STORES of the inter-pass buffer pair 3.175 vs 3.189 ms (kept: rows 1.685 vs 1.703, columns 1.451 vs 1.470);
 // non-temporal loads of the signal-spectrum rows 3.40 vs 3.19 (rows 1.93 vs 1.70: dropped), of the code-spectrum rows as well
 // 3.43; the column pass's tile-row loads with aux = 2 (nt) 3.34 (columns 1.63 vs 1.47: the 128-byte lines adjacent tiles share
 // are evicted between them)
-#ifndef BDS_ROWS_NT_X
-#define BDS_ROWS_NT_X 0
-#endif
-#ifndef BDS_ROWS_NT_C
-#define BDS_ROWS_NT_C 0
-#endif
-#ifndef BDS_ROWS_NT_ST
-#define BDS_ROWS_NT_ST 1
-#endif
-constexpr bool kRowsNtX = BDS_ROWS_NT_X != 0, kRowsNtC = BDS_ROWS_NT_C != 0, kRowsNtSt = BDS_ROWS_NT_ST != 0;
 constexpr size_t kWRowsLdsBytes = sizeof(float2) * (4 * kWRowsRegion + 256 * kWRowsXS + 4);
 
 // PK: the butterflies and twiddle products on packed fp32 pairs (bds_fft_pk.h: half the vector issue slots for the same pipe time)
@@ -76,7 +66,6 @@ __global__ __launch_bounds__(256, 2) void k_rows_wave_f(RowsFArgs A) {
     const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const long L = A.L;
     const ClockProbe clkp(A.clk, 63);
-    PH_DECL(17);
     auto wave_sync = [] {  // LDS traffic of one wave is in order; this only stops the compiler from moving it
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
@@ -110,21 +99,18 @@ __global__ __launch_bounds__(256, 2) void k_rows_wave_f(RowsFArgs A) {
         // (stored in the order this kernel multiplies them, wrows_perm() of bds_acq_fast.h: element xoff + 256 bh of the row
         //  sits at [16 tid + bh] -- four 16-byte loads per lane, 4 KB contiguous per wave)
         uint32_t xn[16];
-        auto fetch16 = [&](const ST *row, uint32_t(&d)[16], auto nt_c) {
-            constexpr bool NT = decltype(nt_c)::value;
+        auto fetch16 = [&](const ST *row, uint32_t(&d)[16]) {
             typedef uint32_t u4v __attribute__((ext_vector_type(4)));
             const u4v *p = reinterpret_cast<const u4v *>(row + 16 * tid);
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
-                // NT: read-once streams (the signal spectra: 2.5 GB per Doppler grid, nothing of it survives in L2 / MALL until
-                // the next PRN's launch) are requested non-temporal -- BDS_ROWS_NT_X, measured in tools/exp/r5_nt.sh
-                const u4v v = NT ? __builtin_nontemporal_load(p + k) : p[k];
+                const u4v v = p[k];
                 d[4 * k] = v.x, d[4 * k + 1] = v.y, d[4 * k + 2] = v.z, d[4 * k + 3] = v.w;
             }
         };
         auto fetch_x = [&](int g) {
             const int bin = A.cell_bin ? A.cell_bin[g] : A.bin0 + g;
-            fetch16((const ST *)A.Xs + (long)bin * L + (long)k1 * S, xn, std::integral_constant<bool, kRowsNtX>{});
+            fetch16((const ST *)A.Xs + (long)bin * L + (long)k1 * S, xn);
         };
         // The inter-pass twiddle W_L^(k1 e) of output e = tid + 256 p' factors into a per-thread part
         //   wi = W_L^(k1 tid) x storage scale x w16^(u v) (u = tid & 15, v = tid >> 4: undoes the rotated read of phase 1b)
@@ -160,9 +146,8 @@ __global__ __launch_bounds__(256, 2) void k_rows_wave_f(RowsFArgs A) {
         uint32_t cv[NCOMP][16];
 #pragma unroll
         for (int comp = 0; comp < NCOMP; ++comp) {
-            fetch16(Cs + (long)comp * L + (long)k1 * S, cv[comp], std::integral_constant<bool, kRowsNtC>{});
+            fetch16(Cs + (long)comp * L + (long)k1 * S, cv[comp]);
         }
-        PH_MARK(16);  // workgroup prologue: twiddles, code rows issued
         for (int g = g0; g < g1; ++g) {
             uint32_t r0[ILV_OK ? 16 : 1];  // packed outputs of component 0, held for the interleaved store
 #pragma unroll
@@ -171,11 +156,11 @@ __global__ __launch_bounds__(256, 2) void k_rows_wave_f(RowsFArgs A) {
                 // butterfly layer that produces / consumes it -- the four outputs of a layer-2 group are written while the next
                 // group is computed, reads are issued in the order the layer-1 groups need them -- instead of 16 writes and 16
                 // reads back to back: a burst from all four waves queues on the LDS store path at ~40 cycles per write against
-                // ~20 spread out, tools/phases.py.)
+                // ~20 spread out, HISTORY.md 1.4.)
                 C y[16], a[4][4], o[4];
-#ifndef BDS_ROWS_DOT2_BUILTIN  // (-DBDS_ROWS_DOT2_BUILTIN: the compiler builtin instead; rows 1.82 vs 1.78 ms per 201 cells)
                 // The products with the three-operand v_dot2_f32_f16 (addend 0 inline) in inline assembly: the builtin compiles to
-                // the accumulating v_dot2c_f32_f16 behind a v_mov 0 per result (64 moves per cell).  The compiler does not know
+                // the accumulating v_dot2c_f32_f16 behind a v_mov 0 per result (64 moves per cell; rows 1.82 ms per 201 cells with
+                // the builtin against 1.78).  The compiler does not know
                 // these are dot instructions, so the hazard it would pad -- 3 wait states between a dot's write and another
                 // vector instruction's read -- is closed by hand: four products per block, s_nop 2 at its end.
 #pragma unroll
@@ -198,13 +183,6 @@ __global__ __launch_bounds__(256, 2) void k_rows_wave_f(RowsFArgs A) {
 #pragma unroll
                     for (int i = 0; i < 4; ++i) cx_set(y[q + i], re[i], im[i]);
                 }
-#else
-#pragma unroll
-                for (int q = 0; q < 16; ++q) {  // ((xi, xr) is re-formed per component: one v_alignbit against 16 registers held across both)
-                    const float2 t = cmul_h(xn[q], __builtin_amdgcn_alignbit(xn[q], xn[q], 16), cv[comp][q]);
-                    cx_set(y[q], t.x, t.y);
-                }
-#endif
                 // the last component's products are the last readers of xn: the next cell's row is fetched into the same
                 // registers while the transform and the stores run
                 if (comp == NCOMP - 1 && g + 1 < g1) fetch_x(g + 1);
@@ -231,49 +209,35 @@ __global__ __launch_bounds__(256, 2) void k_rows_wave_f(RowsFArgs A) {
                 }
                 wave_sync();
                 __builtin_amdgcn_sched_barrier(0);
-                PH_MARK(8 * comp + 0);  // products, phase 1a, exchange issued
 #pragma unroll
                 for (int n2 = 0; n2 < 4; ++n2) cx_bfly16_l1<true>(y, twB, n2, a[n2]);  // twiddle w256^(bl u) on the inputs (up to the factor w256^(u u))
-                PH_MARK(8 * comp + 2);  // phase 1b layer 1 (waits for its inputs group by group)
-                if (comp > 0 || g > g0) BDS_SYNC();  // every thread is through with the exchange buffer (previous transform)
-                PH_MARK(8 * comp + 3);  // barrier
+                if (comp > 0 || g > g0) __syncthreads();  // every thread is through with the exchange buffer (previous transform)
                 BDS_WR_L2(0, wrx, 16 * XS, 2);
                 BDS_WR_L2(1, wrx, 16 * XS, 2);
                 BDS_WR_L2(2, wrx, 16 * XS, 2);
                 BDS_WR_L2(3, wrx, 16 * XS, 2);
 #undef BDS_WR_L2
-                PH_MARK(8 * comp + 4);  // phase 1b layer 2 + exchange writes
-                BDS_SYNC();
-                PH_MARK(8 * comp + 5);  // barrier
+                __syncthreads();
                 // ---- phase 2: twiddle (wi folded in), radix 16 over q', uniform factor, store
                 lds_read16(y, rd2a);  // bds_lds.h: sixteen ds_read_b64 (the compiler's ds_read2_b64 pairs take twice the LDS cycles)
                 __builtin_amdgcn_sched_barrier(0);
-                PH_MARK(8 * comp + 6);  // exchange reads issued
 #pragma unroll
                 for (int n2 = 0; n2 < 4; ++n2) cx_bfly16_l1<true, true>(y, twC, n2, a[n2]);
                 auto emit = [&](int p, C yv) {
                     const float2 t = cx_f2(cx_mul_uniform(yv, sbx[p], sby[p]));
                     const uint32_t h = f2_to_h2(t);
-#ifdef BDS_EXP_ROWS_NOSTORE
-                    if (t.x == 1.2345f)
-#endif
-                    {
-                        if constexpr (ILV) {
-                            if (comp == 0) {
-                                r0[ILV_OK ? p : 0] = h;
-                            } else {
-                                typedef uint32_t u2v __attribute__((ext_vector_type(2)));
-                                u2v *dst2 = (u2v *)A.Bw + (long)g * L + (long)k1 * S + tid + 256 * p;
-                                const u2v val = {r0[ILV_OK ? p : 0], h};
-                                if constexpr (kRowsNtSt)
-                                    __builtin_nontemporal_store(val, dst2);
-                                else
-                                    *dst2 = val;
-                            }
+                    if constexpr (ILV) {
+                        if (comp == 0) {
+                            r0[ILV_OK ? p : 0] = h;
                         } else {
-                            ST *dst = (ST *)A.Bw + ((long)g * NCOMP + comp) * L + (long)k1 * S + tid;
-                            *reinterpret_cast<uint32_t *>(dst + 256 * p) = h;
+                            typedef uint32_t u2v __attribute__((ext_vector_type(2)));
+                            u2v *dst2 = (u2v *)A.Bw + (long)g * L + (long)k1 * S + tid + 256 * p;
+                            const u2v val = {r0[ILV_OK ? p : 0], h};
+                            __builtin_nontemporal_store(val, dst2);
                         }
+                    } else {
+                        ST *dst = (ST *)A.Bw + ((long)g * NCOMP + comp) * L + (long)k1 * S + tid;
+                        *reinterpret_cast<uint32_t *>(dst + 256 * p) = h;
                     }
                 };
 #define BDS_ST_L2(K1)                                     \
@@ -284,12 +248,10 @@ __global__ __launch_bounds__(256, 2) void k_rows_wave_f(RowsFArgs A) {
                 BDS_ST_L2(2);
                 BDS_ST_L2(3);
 #undef BDS_ST_L2
-                PH_MARK(8 * comp + 7);  // phase 2 arithmetic, stores issued
             }
         }
-        if (vb + (int)gridDim.x < A.nvb) BDS_SYNC();
+        if (vb + (int)gridDim.x < A.nvb) __syncthreads();
     }
-    PH_FLUSH(32, 17);
     clkp.finish(tid);
 }
 

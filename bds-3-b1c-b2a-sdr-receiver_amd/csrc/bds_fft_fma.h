@@ -82,14 +82,6 @@ __device__ __forceinline__ void bfly16_l2(const float2 (&a)[4][4], float2 (&u)[4
 // v <- DFT16(tw .* v) (TW: tw[1 .. 15] are applied to the inputs, tw[0] is taken as 1 unless TW0) or DFT16(v); DIR as Butterfly<16, DIR>
 template <int DIR, bool TW, bool TW0 = false>
 __device__ __forceinline__ void bfly16_fma(float2 *v, const float2 *tw) {
-#ifdef BDS_EXP_PLAIN_BFLY  // timing experiment: the same transform with separate twiddle products and Butterfly<16, DIR>
-    if constexpr (TW) {
-#pragma unroll
-        for (int i = TW0 ? 0 : 1; i < 16; ++i) v[i] = cmul(v[i], tw[i]);
-    }
-    Butterfly<16, DIR>::run(v);
-    return;
-#endif
     float2 a[4][4];
 #pragma unroll
     for (int n2 = 0; n2 < 4; ++n2) bfly16_l1<DIR, TW, TW0>(v, tw, n2, a[n2]);
@@ -137,14 +129,6 @@ __device__ __forceinline__ void bfly8_l2(const float2 (&a0)[4], const float2 (&a
 // v <- DFT8(tw .* v) (TW: tw[1 .. 7] on the inputs) or DFT8(v): 72 instructions against 28 + 56, 52 against 56
 template <int DIR, bool TW>
 __device__ __forceinline__ void bfly8_fma(float2 *v, const float2 *tw) {
-#ifdef BDS_EXP_PLAIN_BFLY
-    if constexpr (TW) {
-#pragma unroll
-        for (int i = 1; i < 8; ++i) v[i] = cmul(v[i], tw[i]);
-    }
-    Butterfly<8, DIR>::run(v);
-    return;
-#endif
     float2 a0[4], a1[4];
     bfly8_l1<DIR, TW>(v, tw, 0, a0);
     bfly8_l1<DIR, TW>(v, tw, 1, a1);

@@ -15,12 +15,6 @@
 #include "bds_fft.h"
 #include "bds_fft_fma.h"
 
-#ifdef BDS_EXP_NOBARRIER
-#define BDS_TSYNC() __builtin_amdgcn_s_waitcnt(0)
-#else
-#define BDS_TSYNC() __syncthreads()
-#endif
-
 namespace bds {
 
 template <int S>
@@ -57,11 +51,7 @@ __device__ __forceinline__ void tstage(C *__restrict__ buf, const C *__restrict_
     constexpr bool SRC_LDS = std::is_same<Src, LdsIO>::value;
     constexpr bool DST_LDS = std::is_same<Dst, LdsIO>::value;
     constexpr bool HALF = std::is_same<C, h2>::value;
-#ifdef BDS_EXP_PLAIN_TSTAGE
-    constexpr bool kFma = false;
-#else
     constexpr bool kFma = std::is_same<C, float2>::value && (R == 16 || R == 8);
-#endif
     static_assert(NB % 16 == 0, "S/R must be a multiple of 16");
     static_assert(NS == 1 || NS % 16 == 0, "later stages need NS % 16 == 0");
     static_assert(NS > 1 || R == 16, "the first stage must be radix 16");
@@ -91,7 +81,7 @@ __device__ __forceinline__ void tstage(C *__restrict__ buf, const C *__restrict_
             }
         }
     }
-    if constexpr (SRC_LDS && DST_LDS) BDS_TSYNC();  // every read of this stage precedes its writes
+    if constexpr (SRC_LDS && DST_LDS) __syncthreads();  // every read of this stage precedes its writes
 #pragma unroll
     for (int i = 0; i < MB; ++i) {
         const int b = tid + i * NT;
@@ -176,7 +166,7 @@ __device__ __forceinline__ void tstage(C *__restrict__ buf, const C *__restrict_
             }
         }
     }
-    if constexpr (DST_LDS) BDS_TSYNC();
+    if constexpr (DST_LDS) __syncthreads();
 }
 
 // All stages of a plan; the first stage takes Src, the last one Dst, everything between is LDS.

@@ -281,16 +281,7 @@ __device__ __forceinline__ void correlate_slice(const int8_t *__restrict__ data,
 //            LDS; the segment totals are scanned in f64 over the workgroup (segment bases)
 //   phase 2  the index steps of the six (E/P/L x {code, BOC(6,1)}) sequences are spread over the
 //            threads; each finds its k_u, reads S(k_u) = base + local prefix and adds its term in f64
-#ifndef BDS_TRK_CAP1
-#define BDS_TRK_CAP1 256
-#endif
-#ifndef BDS_TRK_CAP6
-#define BDS_TRK_CAP6 1280
-#endif
-#ifndef BDS_TRK_MINW
-#define BDS_TRK_MINW 1
-#endif
-static constexpr int kCap1 = BDS_TRK_CAP1, kCap6 = BDS_TRK_CAP6;  // code / BOC(6,1) table entries of a wave's pass staged in LDS
+static constexpr int kCap1 = 256, kCap6 = 1280;  // code / BOC(6,1) table entries of a wave's pass staged in LDS
 template <int R6>
 __device__ __forceinline__ double code_arg(const ColonVec &v, int k) {
     double t = colon_at(v, k);  // element k of the reference's colon vector (-ffp-contract=off: one rounding per operation)
@@ -725,7 +716,7 @@ __device__ __forceinline__ void apply_update(const TrkParams &p, ChanState &s, c
 // floor of a small dependent launch).  State and partial sums ping-pong between two buffers; workgroup 0 of the channel
 // writes the results of the previous epoch and the state the current one starts from.
 template <int MODE, int SEG, bool CPLX, int PREC>
-__global__ __launch_bounds__(kTrkThreads, BDS_TRK_MINW) void k_trk_correlate(const int8_t *__restrict__ data,
+__global__ __launch_bounds__(kTrkThreads, 1) void k_trk_correlate(const int8_t *__restrict__ data,
                                                               const int8_t *__restrict__ prim, TrkParams p,
                                                               const ChanState *__restrict__ st_in, ChanState *__restrict__ st_out,
                                                               const double *__restrict__ part_prev, double *__restrict__ part,

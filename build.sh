@@ -23,7 +23,7 @@ elif [ "${BDS_SAN:-0}" = 1 ]; then
 fi
 # Two libraries from one set of objects: the RELEASE library reads the documented environment knobs (csrc/bds_api.hip,
 # include/bds_mi355x.h); libbds_mi355x_hooks.so (-DBDS_TEST_HOOKS: only bds_api.hip and bds_multi.hip differ) also reads the
-# tuning / test switches and is what tests/ and tools/exp/ load (tests/conftest.py).  BDS_TEST_HOOKS=0 skips it.
+# tuning / test switches and is what tests/ load (tests/conftest.py).  BDS_TEST_HOOKS=0 skips it.
 # Debug / sanitizer builds carry the hooks themselves.  (This has to stand BEFORE FLAGS is formed: for most of round 5 it stood after,
 # so the debug library had no hooks and tools/run_debug.sh stopped at the suite's "needs the test-hooks build" assertion.)
 HOOKS="${BDS_TEST_HOOKS:-1}"

@@ -129,7 +129,7 @@ def test_cfg4_whole_horizon_against_the_c_oracle(ctx, tmp_path, mode, fs, epochs
     itself (a code phase 1e-6 chip apart flips ~20 samples per epoch).  DESIGN.md section 2: any two float64 implementations that
     differ in a sin or a summation order do this to each other, MATLAB and NumPy included: the correlator sums of the HIP path are
     1e-13 of |P| from the oracle's, which moves codeFreq by an ulp now and then and remCodePhase with it by an ulp of the code length
-    (1.8e-12 chip; tools/exp/r5_cfg4_flip.py).  Measured (profiles/r05_cfg4_full_vs_c_oracle.txt): with the default correlator
+    (1.8e-12 chip).  Measured (profiles/r05_cfg4_full_vs_c_oracle.txt, which also traces one such separation): with the default correlator
     (BDS_TRK_PREC=4) 11 of 12 channels inside 8d over all 3 600 epochs, one separates at epoch 1 530 on a single BOC(6,1) sample;
     with BDS_TRK_PREC=5 (4e-10 from the oracle) six separate between epochs 1 531 and 3 517.
     Asserted: few such separations, each starting from a single-sample-sized discrepancy, the floor after them bounded (I/Q 1e-2 of

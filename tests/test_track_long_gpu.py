@@ -12,7 +12,7 @@ epoch 142 / 1 588) or even an accurate f64 phasor recurrence (d ~ 1e-11: epoch 3
 reference by that noise.  The default correlator (TrkParams::prec 4) reproduces trigarg(k) bit for bit (k ./ fs by an exactly
 rounded reciprocal division, csrc/bds_strict_math.h), takes a library-free f64 sin / cos of it per sample and keeps the prefix
 sums in f64: correlator sums 1e-13 of |P| from the oracle, d a few ulps of the code length (~1e-12 chip) or exactly 0, no flip on
-either fixture (profiles/r05_trk_prec_first.txt, r05_trk_prec_strict.txt, tools/exp/r5_trk_prec.py).  prec 5 -- one sin / cos per
+either fixture (profiles/r05_trk_prec_first.txt, r05_trk_prec_strict.txt).  prec 5 -- one sin / cos per
 lane and 16 samples, the other 15 by angle addition with a first-order correction, 12 % faster -- gives the same on these fixtures
 and was the default until the whole of cfg4 at full rate was run against the oracle (tests/test_cfg4_gpu.py, profiles/
 r05_cfg4_full_vs_c_oracle.txt: 43 200 epoch-channels of 1e6 samples; prec 4 is 1e-13 from the oracle and loses ONE channel to a flip,

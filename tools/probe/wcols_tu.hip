@@ -1,5 +1,5 @@
 // One instantiation of the wave-private column pass on its own: fast turn-around for register / ISA checks
-//   tools/wcols_res.sh [-DBDS_WCOLS_OCC=2 ...]
+//   tools/wcols_res.sh [-DWC_S=1024 ...]
 #include "bds_acq_wcols.h"
 #ifndef WC_S
 #define WC_S 768
