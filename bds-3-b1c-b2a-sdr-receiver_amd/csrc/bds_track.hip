@@ -1555,4 +1555,48 @@ extern "C" int bds_track_correlate(bds_ctx *ctx, const bds_settings *s, const in
     return BDS_OK;
 }
 
+// Test aid (bds_track_colon): element k[i] of the colon vector a[i] : d[i] : b[i] exactly as the correlators form it
+__global__ void k_colon_eval(const double *__restrict__ a, const double *__restrict__ d, const double *__restrict__ b,
+                             const int *__restrict__ k, int n, double *__restrict__ val, double *__restrict__ cend,
+                             int *__restrict__ nint) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const ColonVec v = colon_vec(a[i], d[i], b[i]);
+    val[i] = colon_at(v, k[i]);
+    cend[i] = v.c;
+    nint[i] = v.n;
+}
+
+extern "C" int bds_track_colon(bds_ctx *ctx, int n, const double *a, const double *d, const double *b, const int32_t *k,
+                               double *value, double *c_end, int32_t *n_intervals) {
+    if (!ctx || !a || !d || !b || !k || !value || !c_end || !n_intervals || n < 1) return BDS_ERR_ARG;
+    BDS_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t nd = sizeof(double) * (size_t)n, ni = sizeof(int) * (size_t)n;
+    double *d_in = nullptr, *d_out = nullptr;  // a, d, b | value, c
+    int *d_k = nullptr, *d_n = nullptr;
+    struct Scope {  // released on every exit path
+        void **p[4];
+        ~Scope() {
+            for (void **q : p)
+                if (*q) (void)hipFree(*q);
+        }
+    } scope{{(void **)&d_in, (void **)&d_out, (void **)&d_k, (void **)&d_n}};
+    BDS_HIP(ctx, hipMalloc((void **)&d_in, 3 * nd));
+    BDS_HIP(ctx, hipMalloc((void **)&d_out, 2 * nd));
+    BDS_HIP(ctx, hipMalloc((void **)&d_k, ni));
+    BDS_HIP(ctx, hipMalloc((void **)&d_n, ni));
+    BDS_HIP(ctx, hipMemcpyAsync(d_in, a, nd, hipMemcpyHostToDevice, st(ctx)));
+    BDS_HIP(ctx, hipMemcpyAsync(d_in + n, d, nd, hipMemcpyHostToDevice, st(ctx)));
+    BDS_HIP(ctx, hipMemcpyAsync(d_in + 2 * (size_t)n, b, nd, hipMemcpyHostToDevice, st(ctx)));
+    BDS_HIP(ctx, hipMemcpyAsync(d_k, k, ni, hipMemcpyHostToDevice, st(ctx)));
+    hipLaunchKernelGGL(k_colon_eval, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st(ctx), (const double *)d_in,
+                       (const double *)(d_in + n), (const double *)(d_in + 2 * (size_t)n), (const int *)d_k, n, d_out, d_out + n, d_n);
+    BDS_HIP(ctx, hipGetLastError());
+    BDS_HIP(ctx, hipMemcpyAsync(value, d_out, nd, hipMemcpyDeviceToHost, st(ctx)));
+    BDS_HIP(ctx, hipMemcpyAsync(c_end, d_out + n, nd, hipMemcpyDeviceToHost, st(ctx)));
+    BDS_HIP(ctx, hipMemcpyAsync(n_intervals, d_n, ni, hipMemcpyDeviceToHost, st(ctx)));
+    BDS_HIP(ctx, hipStreamSynchronize(st(ctx)));
+    return BDS_OK;
+}
+
 BDS_DEBUG_TU_READER(bds_debug_failures_track)

@@ -84,7 +84,7 @@ class AcqJob(C.Structure):
 EXPORTS = [
     "bds_create", "bds_destroy", "bds_reload_tuning", "bds_last_error", "bds_device_name", "bds_abi_check", "bds_build_flags", "bds_gen_code", "bds_acquire",
     "bds_acq_load", "bds_acq_prepare", "bds_acq_run", "bds_acq_set_pair_budget_gb", "bds_resample_plan", "bds_fir1_bandpass", "bds_frame_sync", "bds_sync_pattern", "bds_unpack_cplx", "bds_unpack_cplx_file", "bds_acq_grid", "bds_acq_peaks", "bds_acq_candidates", "bds_acq_coherent_sums", "bds_get_timing",
-    "bds_track", "bds_track_mem", "bds_track_loaded_bytes", "bds_track_correlate", "bds_calc_loop_coef", "bds_calc_loop_coef_carr",
+    "bds_track", "bds_track_mem", "bds_track_loaded_bytes", "bds_track_correlate", "bds_track_colon", "bds_calc_loop_coef", "bds_calc_loop_coef_carr",
     "bds_calc_weighing_factor", "bds_pre_run", "bds_pre_run_device", "bds_acquire_track",
     "bds_multi_create", "bds_multi_destroy", "bds_multi_last_error", "bds_multi_size", "bds_multi_ctx",
     "bds_multi_rccl_ranks", "bds_acquire_multi", "bds_shard_jobs", "bds_acq_job_cost",
@@ -152,6 +152,7 @@ def lib():
     L.bds_track_mem.argtypes = [vp, SP, i8p, sz, i32, C.POINTER(Channel), C.POINTER(TrackOut)]
     L.bds_track_correlate.restype = i32
     L.bds_track_correlate.argtypes = [vp, SP, i8p, sz, i32, _IP, _DP, _DP]
+    L.bds_track_colon.restype, L.bds_track_colon.argtypes = i32, [vp, i32, _DP, _DP, _DP, _IP, _DP, _DP, _IP]
     L.bds_calc_loop_coef.restype = None
     L.bds_calc_loop_coef.argtypes = [C.c_double, C.c_double, C.c_double, _DP, _DP]
     L.bds_calc_loop_coef_carr.restype, L.bds_calc_loop_coef_carr.argtypes = None, [SP, _DP, _DP, _DP]
@@ -590,6 +591,17 @@ class Context:
                                                   prn.ctypes.data_as(_IP), st.ctypes.data_as(_DP),
                                                   sums.ctypes.data_as(_DP)))
         return sums
+
+    def track_colon(self, a, d, b, k):
+        """Test aid: element k[i] of the colon vector a[i]:d[i]:b[i] as the tracking kernels form it, evaluated on the device.
+        Returns (value, c_end, n_intervals)."""
+        k = np.ascontiguousarray(k, dtype=np.int32)
+        a, d, b = (np.ascontiguousarray(np.broadcast_to(np.asarray(v, dtype=np.float64), k.shape)) for v in (a, d, b))
+        val, c_end, n_int = np.empty(k.size), np.empty(k.size), np.empty(k.size, dtype=np.int32)
+        self._check(self._lib.bds_track_colon(self._h, k.size, a.ctypes.data_as(_DP), d.ctypes.data_as(_DP), b.ctypes.data_as(_DP),
+                                              k.ctypes.data_as(_IP), val.ctypes.data_as(_DP), c_end.ctypes.data_as(_DP),
+                                              n_int.ctypes.data_as(_IP)))
+        return val, c_end, n_int
 
 
 def calc_loop_coef(lbw, zeta, k):

@@ -313,6 +313,14 @@ BDS_API long long bds_track_loaded_bytes(bds_ctx *ctx);
 BDS_API int bds_track_correlate(bds_ctx *ctx, const bds_settings *s, const int8_t *file_bytes,
                                 size_t n_bytes, int n_ch, const int32_t *prn,
                                 const double *state6, double *sums18);
+/* Test aid, never needed by a host application: element k[i] (0-based) of the MATLAB colon vector a[i] : d[i] : b[i]
+ * (non-integer operands, d > 0) exactly as the tracking kernels form their replica index vectors tcode -- first half
+ * a + k d, second half from the right-hand end point, mid-point of an even interval count -- evaluated on the device, one
+ * thread per entry.  value[i]: the element; c_end[i]: the right-hand end point (a + n d, snapped to b within
+ * 2 eps max(|a|,|b|)); n_intervals[i]: n (the vector has n + 1 elements).  The tests hold them bit for bit against the
+ * oracle's restatement of MathWorks' colonop. */
+BDS_API int bds_track_colon(bds_ctx *ctx, int n, const double *a, const double *d, const double *b, const int32_t *k,
+                            double *value, double *c_end, int32_t *n_intervals);
 
 /* ---- helpers replacing small host functions on the path ------------------------ */
 /* Common/calcLoopCoef.m:41-45 */

@@ -152,6 +152,13 @@ def trk_epoch(raw8, blk, iq, rem_code, step, spc_el, scale, rem_carr, carr_freq,
         L.bds_oracle_trk_epoch.restype = ctypes.c_int
         L._trk_ready = True
     raw8 = np.ascontiguousarray(raw8, dtype=np.int8)
+    # the look-ups [c(end) c c(1)](ceil(tcode) + 1) must stay inside the padded arrays, as in MATLAB ("index exceeds the number of array
+    # elements" / "index must be a positive integer"): the C loop does not check (tcode ascends: its ends are the extremes)
+    first, last = (rem_code - spc_el) * scale, (((blk - 1) * step + rem_code) + spc_el) * scale
+    for arr, mul in ((dcode, 1.0), (pcode, 1.0), (p6code, 6.0)):
+        if arr is not None and (np.ceil(first * mul) + 1 < 1 or np.ceil(last * mul) + 1 > len(arr)):
+            raise IndexError(f"replica index ceil(tcode * {mul:g}) + 1 runs from {int(np.ceil(first * mul)) + 1} to {int(np.ceil(last * mul)) + 1}: "
+                             f"outside the padded code array of {len(arr)} elements (earlyLateSpc {spc_el} too wide for it)")
     sums = np.zeros(18)
     t_p = ctypes.c_double()
     t_e = ctypes.c_double()

@@ -80,11 +80,13 @@ def resample_b1c(iq=False):
     return s, x, sats
 
 
-def track_case(signal, mode, n_epochs, seed=21, iq=False, fs=None, IF=None):
+def track_case(signal, mode, n_epochs, seed=21, iq=False, fs=None, IF=None, zero_doppler=False, spacing=None):
     """Synthetic record + channels for the tracking tests at a reduced sampling rate.
 
     Returns (settings, file_bytes int8, channels) with channels filled the way preRun
-    would from a perfect acquisition (codePhase = first sample of a code period)."""
+    would from a perfect acquisition (codePhase = first sample of a code period).
+    zero_doppler: the satellites have no Doppler, so every channel starts with acquiredFreq = IF and codeFreq = codeFreqBasis;
+    spacing: dllCorrelatorSpacing instead of the receiver's default."""
     from types import SimpleNamespace
 
     if signal == "B2A":
@@ -98,6 +100,10 @@ def track_case(signal, mode, n_epochs, seed=21, iq=False, fs=None, IF=None):
                                       pilotTRKflag=flag, CNoInterval=10, FEBW=10e6, fileType=2 if iq else 1)
         sat_list = [synth.Sat(3, 230.0, 40000.3, 1.0, 48.0), synth.Sat(12, -410.0, 99000.8, 2.0, 45.0),
                     synth.Sat(27, 1800.0, 7000.5, 0.2, 46.0)]
+    if zero_doppler:
+        sat_list = [synth.Sat(sat.prn, 0.0, sat.delay, sat.phase, sat.cn0_dbhz) for sat in sat_list]
+    if spacing is not None:
+        s = s.copy(dllCorrelatorSpacing=spacing)
     spc = spc_of(s)
     # a complex record correlates under B2a/tracking.m's exp(+j th) when conjugated, under the B1C
     # trackers' exp(-j th) when not (synth.make_if)
@@ -110,3 +116,28 @@ def track_case(signal, mode, n_epochs, seed=21, iq=False, fs=None, IF=None):
         chans.append(SimpleNamespace(PRN=sat.prn, acquiredFreq=float(cf), codePhase=float(int(np.ceil(sat.delay)) + 1),
                                      codeFreq=float(code_freq), status="T"))
     return s, x, chans
+
+
+def assert_closed_loop_parity(ref, got, mode):
+    """Closed-loop tracking results against the oracle's, SURVEY.md section 8d: I/Q <= 1e-4 of |P|, carrFreq <= 1e-3 Hz,
+    codeFreq <= 1e-6 Hz, absoluteSample exact (tests/test_track_gpu.py test_closed_loop_tracking and the cases that share it)."""
+    for r, g in zip(ref, got):
+        assert g.status == r.status == "T" and g.PRN == r.PRN
+        np.testing.assert_array_equal(g.absoluteSample, r.absoluteSample)
+        p = np.hypot(r.I_P, r.Q_P).max()
+        for f in ("I_E", "I_P", "I_L", "Q_E", "Q_P", "Q_L", "Pilot_I_P", "Pilot_Q_P"):
+            np.testing.assert_allclose(getattr(g, f), getattr(r, f), rtol=0, atol=1e-4 * p, err_msg=f)
+        if mode == "WB":
+            for f in ("Pilot_I_E", "Pilot_I_L", "Pilot_Q_E", "Pilot_Q_L"):
+                np.testing.assert_allclose(getattr(g, f), getattr(r, f), rtol=0, atol=1e-4 * p, err_msg=f)
+        np.testing.assert_allclose(g.carrFreq, r.carrFreq, rtol=0, atol=1e-3)
+        np.testing.assert_allclose(g.codeFreq, r.codeFreq, rtol=0, atol=1e-6)
+        np.testing.assert_allclose(g.remCodePhase, r.remCodePhase, rtol=0, atol=1e-7)
+        np.testing.assert_allclose(g.remCarrPhase, r.remCarrPhase, rtol=0, atol=1e-6)
+        for f, tol in (("dllDiscr", 1e-6), ("dllDiscrFilt", 1e-6), ("pllDiscr", 1e-6), ("pllDiscrFilt", 1e-3)):
+            np.testing.assert_allclose(getattr(g, f), getattr(r, f), rtol=0, atol=tol, err_msg=f)
+        cn = "B2a_CNo" if mode == "B2A" else "B1C_CNo"
+        for f in ("DataCNo", "PilotCNo", cn):
+            np.testing.assert_allclose(getattr(g, f), getattr(r, f), rtol=0, atol=1e-3, err_msg=f)
+        for f in ("DataPLD", "PilotPLD"):
+            np.testing.assert_allclose(getattr(g, f), getattr(r, f), rtol=0, atol=1e-5, err_msg=f)

@@ -183,4 +183,5 @@ def test_cfg4_whole_horizon_against_the_c_oracle(ctx, tmp_path, mode, fs, epochs
     print(f"whole horizon ({mode}_tracking), {len(ref)} channels x {EPOCHS} epochs x {fs / 1e6:g} MS/s vs the oracle: absoluteSample exact on all {total} epoch-channels; "
           f"{total - n_bad} inside SURVEY 8d (worst there: I/Q {quiet['iq']:.2e} of |P|, carrFreq {quiet['carr']:.2e} Hz, codeFreq {quiet['code']:.2e} Hz); "
           f"{n_eps} separation(s) after a ceil() flip, {n_bad} epoch-channels after them")
-    assert n_eps <= 8 and n_bad <= 0.25 * total
+    # (measured after the colon-vector change, profiles/r07_whole_horizon.txt: WB 1 separation, 4.8 % of the epoch-channels after it; NB none)
+    assert n_eps <= 2 and n_bad <= 0.06 * total

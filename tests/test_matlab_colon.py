@@ -1,6 +1,8 @@
 """MATLAB's colon operator as the oracle restates it (oracle/matlab.py m_colon, after MathWorks' published colonop.m): hand-worked
 cases, and the C oracle's per-sample form (oracle/c/trk_oracle.c colon_at) against it on the reference's tcode vectors
-(B2a/tracking.m:260-286, B1C/WB_tracking.m:289-317)."""
+(B2a/tracking.m:260-286, B1C/WB_tracking.m:289-317).  Also the CPU guards of tests/colon_states.py, the table of open-loop states
+tests/test_track_colon_gpu.py runs the device correlators on: every state must be one on which the colon vector and a + k d really
+part, or the GPU module would prove nothing."""
 import ctypes
 
 import numpy as np
@@ -8,6 +10,8 @@ import pytest
 
 from oracle import cfast
 from oracle.matlab import m_colon, m_colon_parts
+
+import colon_states as cs
 
 
 def test_known_matlab_elements():
@@ -68,19 +72,90 @@ def test_c_per_sample_form_is_the_vector(scale, spc, code_len):
         step = code_freq / fs
         rem = rng.uniform(0, step) if trial else 0.0
         blk = int(np.ceil((code_len - rem) / step))
-        counts = (ctypes.c_long * 6)()
-        mu = ctypes.c_double()
-        assert L.bds_oracle_trk_colon_diff(blk, rem, step, spc, scale, counts, ctypes.byref(mu)) == 0
-        kk = np.arange(blk, dtype=np.float64)
-        for r, off in enumerate((-spc, 0.0, spc)):
-            t = m_colon((rem + off) * scale, step * scale, (((blk - 1) * step + rem) + off) * scale)
-            assert len(t) == blk
-            plain = (rem + off) * scale + kk * (step * scale)
-            assert np.all(np.diff(t) > 0)
-            assert counts[r] == int(np.count_nonzero(np.ceil(t) != np.ceil(plain)))
-            assert counts[3 + r] == int(np.count_nonzero(np.ceil(t * 6) != np.ceil(plain * 6)))
-            # the first half IS a + k d; the second half is within a few ulp of it
-            h = (blk - 1) // 2
-            np.testing.assert_array_equal(t[:h], plain[:h])
-            assert np.max(np.abs(t - plain)) <= 4 * np.spacing(t[-1])
-        assert 0 <= mu.value <= 4
+        _c_form_is_the_vector(L, blk, rem, step, spc, scale)
+
+
+def _c_form_is_the_vector(L, blk, rem, step, spc, scale):
+    counts = (ctypes.c_long * 6)()
+    mu = ctypes.c_double()
+    assert L.bds_oracle_trk_colon_diff(blk, rem, step, spc, scale, counts, ctypes.byref(mu)) == 0
+    kk = np.arange(blk, dtype=np.float64)
+    for r, off in enumerate((-spc, 0.0, spc)):
+        t = m_colon((rem + off) * scale, step * scale, (((blk - 1) * step + rem) + off) * scale)
+        assert len(t) == blk
+        plain = (rem + off) * scale + kk * (step * scale)
+        assert np.all(np.diff(t) > 0)
+        assert counts[r] == int(np.count_nonzero(np.ceil(t) != np.ceil(plain)))
+        assert counts[3 + r] == int(np.count_nonzero(np.ceil(t * 6) != np.ceil(plain * 6)))
+        # the first half IS a + k d; the second half is within a few ulp of it
+        h = (blk - 1) // 2
+        np.testing.assert_array_equal(t[:h], plain[:h])
+        assert np.max(np.abs(t - plain)) <= 4 * np.spacing(t[-1])
+    assert 0 <= mu.value <= 4
+    return [int(c) for c in counts]
+
+
+_IDS = [s.name for s in cs.STATES]
+
+
+@pytest.mark.parametrize("st", cs.STATES, ids=_IDS)
+def test_colon_states_are_adversarial(st):
+    """every state of the table the GPU module runs: (1) >= 100 samples whose index differs between the colon vector and a + k d, in
+    an index the state's mode reads (C oracle's counter); (2) the NumPy oracle's vector and the C oracle's per-sample form agree on
+    the state; (3) on the record the GPU test uses, the C oracle's sums in the two forms differ by >= 1e-3 of |P| in a sum the mode
+    reports -- 1000 x the open-loop tolerance.  All oracle against oracle."""
+    read = cs.counts_read(st)
+    counts = _c_form_is_the_vector(cs._trk_lib(), cs.blk_of(st), st.rem, cs.step_of(st), st.spacing, 1.0 if st.signal == "B2A" else 2.0)
+    assert counts == cs.colon_counts(st)
+    x, chans = cs.record_of(st)
+    colon, plain = cs.oracle_sums(st, x, chans), cs.oracle_sums(st, x, chans, plain=True)
+    n = cs.n_sums(st)
+    gap = np.abs(colon[:, :n] - plain[:, :n]).max(axis=1) / np.hypot(colon[:, 2], colon[:, 3])
+    assert np.array_equal(cs.oracle_sums(st, x, chans), colon)  # the plain form was switched off again
+    if st.counted:
+        assert max(read) >= 100, read
+        assert gap.min() >= 1e-3, gap  # every channel of the record
+    else:
+        assert 0 < max(read) < 100 and gap.max() > 0
+    # a real correlation peak: the prompt sum stands well above the early / late ones' difference from it
+    assert np.all(np.hypot(colon[:, 2], colon[:, 3]) > 50 * np.sqrt(cs.blk_of(st)))
+    if "-h-" in st.name:
+        assert cs.junction_place(st)[3], "the block length does not put the junction where the name says"
+
+
+def test_colon_state_table_covers_what_it_claims():
+    c = [s for s in cs.STATES if s.counted]
+    assert {(s.signal, s.mode) for s in c} == {("B2A", "B2A"), ("B1C", "NB"), ("B1C", "WB")}
+    for mode in ("B2A", "NB", "WB"):
+        assert {s.iq for s in c if s.mode == mode} == {False, True}
+    diff = {s.name: cs.colon_counts(s) for s in c}
+    assert any(v[1] >= 100 and v[0] == 0 and v[2] == 0 for v in diff.values())  # the prompt replica alone
+    assert any(min(v[:3]) >= 100 for v in diff.values())  # early and late as well
+    assert any(max(v[:3]) == 0 and v[4] >= 100 for s, v in zip(c, diff.values()) if s.mode == "WB")  # the BOC(6,1) index alone
+    assert any(v[0] >= 100 and v[3] >= 100 and v[5] >= 100 for s, v in zip(c, diff.values()) if s.mode == "WB")  # wide-band early / late
+    assert {(cs.blk_of(s) - 1) % 2 for s in c} == {0, 1}
+    assert any(s.fs == 99.375e6 and s.signal == "B2A" for s in c) and any(s.fs == 99.375e6 and s.signal == "B1C" for s in c)
+    places = {cs.junction_place(s)[:3] for s in c if "-h-" in s.name}
+    assert places == {(w, e, p) for w in ("chunk", "pass", "seg") for e in ("first", "last") for p in ("even", "odd")}
+    assert any(cs.blk_of(s) % 16 not in (0, 1, 15) and cs.blk_of(s) < 0.5 * cs.nominal_blk(s) for s in c)  # ends inside a segment
+
+
+@pytest.mark.parametrize("st", cs.QUIET, ids=[s.name for s in cs.QUIET])
+def test_the_guard_rejects_a_state_off_the_lattice(st):
+    """the same rates with a code phase off the boundary lattice: no differing sample, identical sums -- such a row in the table would
+    fail test_colon_states_are_adversarial"""
+    assert cs.colon_counts(st) == [0] * 6
+    x, chans = cs.record_of(st)
+    np.testing.assert_array_equal(cs.oracle_sums(st, x, chans), cs.oracle_sums(st, x, chans, plain=True))
+
+
+def test_oracle_refuses_a_spacing_whose_indices_leave_the_code_arrays():
+    """wide-band mode with a quarter-chip spacing: ceil(tcode * 6) + 1 of the early replica starts at -2 and that of the late one ends
+    past [p(end) p p(1)] -- MATLAB stops with an index error there (WB_tracking.m:298,324); the C sample loop would read outside its
+    arrays, so its front raises first"""
+    st = cs.STATES[0]._replace(spacing=0.25)
+    assert st.mode == "WB"
+    x, chans = cs.record_of(st)
+    with pytest.raises(IndexError, match="outside the padded code array"):
+        cs.oracle_sums(st, x, chans)
+    cs.oracle_sums(st._replace(spacing=1.0 / 12.5), x, chans)  # inside 1 / 12 chip: fine

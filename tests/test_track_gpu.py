@@ -10,7 +10,7 @@ import pytest
 import bds_amd
 from oracle import tracking as otrk
 
-from helpers import track_case
+from helpers import assert_closed_loop_parity, track_case
 
 pytestmark = pytest.mark.gpu
 
@@ -40,26 +40,7 @@ def test_closed_loop_tracking(ctx, signal, mode, n_epochs, iq):
     s, x, chans = track_case(signal, mode, n_epochs, iq=iq)
     ref, _ = otrk.tracking(otrk.RawFile(x), chans, s, mode=mode)
     got, _ = bds_amd.tracking(x, chans, s, mode=mode)
-    for r, g in zip(ref, got):
-        assert g.status == r.status == "T" and g.PRN == r.PRN
-        np.testing.assert_array_equal(g.absoluteSample, r.absoluteSample)
-        p = np.hypot(r.I_P, r.Q_P).max()
-        for f in ("I_E", "I_P", "I_L", "Q_E", "Q_P", "Q_L", "Pilot_I_P", "Pilot_Q_P"):
-            np.testing.assert_allclose(getattr(g, f), getattr(r, f), rtol=0, atol=1e-4 * p, err_msg=f)
-        if mode == "WB":
-            for f in ("Pilot_I_E", "Pilot_I_L", "Pilot_Q_E", "Pilot_Q_L"):
-                np.testing.assert_allclose(getattr(g, f), getattr(r, f), rtol=0, atol=1e-4 * p, err_msg=f)
-        np.testing.assert_allclose(g.carrFreq, r.carrFreq, rtol=0, atol=1e-3)
-        np.testing.assert_allclose(g.codeFreq, r.codeFreq, rtol=0, atol=1e-6)
-        np.testing.assert_allclose(g.remCodePhase, r.remCodePhase, rtol=0, atol=1e-7)
-        np.testing.assert_allclose(g.remCarrPhase, r.remCarrPhase, rtol=0, atol=1e-6)
-        for f, tol in (("dllDiscr", 1e-6), ("dllDiscrFilt", 1e-6), ("pllDiscr", 1e-6), ("pllDiscrFilt", 1e-3)):
-            np.testing.assert_allclose(getattr(g, f), getattr(r, f), rtol=0, atol=tol, err_msg=f)
-        cn = "B2a_CNo" if mode == "B2A" else "B1C_CNo"
-        for f in ("DataCNo", "PilotCNo", cn):
-            np.testing.assert_allclose(getattr(g, f), getattr(r, f), rtol=0, atol=1e-3, err_msg=f)
-        for f in ("DataPLD", "PilotPLD"):
-            np.testing.assert_allclose(getattr(g, f), getattr(r, f), rtol=0, atol=1e-5, err_msg=f)
+    assert_closed_loop_parity(ref, got, mode)
 
 
 def test_short_file_returns_partial_results(ctx):

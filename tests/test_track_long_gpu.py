@@ -138,4 +138,4 @@ def test_b2a_tracking_at_the_references_defaults_whole_horizon(ctx):
     print(f"B2a tracking at the reference's defaults, 12 channels x {n_ep} epochs x 99.375 MS/s vs the oracle: absoluteSample exact on all {total} "
           f"epoch-channels; {total - n_bad} inside SURVEY 8d (worst there: I/Q {quiet[0]:.2e} of |P|, carrFreq {quiet[1]:.2e} Hz, codeFreq {quiet[2]:.2e} Hz); "
           f"{n_sep} channel(s) separate after a ceil() flip")
-    assert n_sep <= 6
+    assert n_sep <= 2 and n_bad <= 0.06 * total  # (measured, profiles/r07_whole_horizon.txt: no separation)

@@ -11,6 +11,11 @@ record and reports
       (I/Q 1e-4 of |P|, carrFreq 1e-3 Hz, codeFreq 1e-6 Hz), and the floor after it.
 
     python tools/colon_effect.py [--epochs 3600] [--mode WB|NB] > profiles/r06_colon_effect.txt
+
+--states prints instead the table of DESIGN.md section 2: the open-loop states of tests/colon_states.py (inputs on which the two forms DO
+part), per state the samples whose index differs and what that does to the oracle's correlator sums.
+
+    python tools/colon_effect.py --states > profiles/r07_colon_states.txt
 """
 import argparse
 import ctypes
@@ -28,12 +33,34 @@ import bench  # noqa: E402
 from oracle import cfast  # noqa: E402
 
 
+def states_table():
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import colon_states as cs
+
+    print("| state | fs (MS/s) | mode | spacing | rem | codeFreq / nominal - 1 | blk | differing samples, ceil(tcode) E / P / L | ceil(tcode*6) E / P / L | "
+          "oracle sums, colon vs a + k d (of \\|P\\|, two channels) |")
+    print("|---|---|---|---|---|---|---|---|---|---|")
+    for st in cs.STATES + cs.QUIET:
+        c = cs.colon_counts(st)
+        x, chans = cs.record_of(st)
+        a, b = cs.oracle_sums(st, x, chans), cs.oracle_sums(st, x, chans, plain=True)
+        n = cs.n_sums(st)
+        gap = np.abs(a[:, :n] - b[:, :n]).max(axis=1) / np.hypot(a[:, 2], a[:, 3])
+        six = f"{c[3]} / {c[4]} / {c[5]}" if st.mode == "WB" else "–"
+        cf = (st.code_freq or cs.nominal_code_freq(st.signal)) / cs.nominal_code_freq(st.signal) - 1
+        print(f"| {st.name} | {st.fs / 1e6:g} | {st.mode}{' I/Q' if st.iq else ''} | {st.spacing:.4g} | {st.rem:.4g} | {cf:+.2e} | {cs.blk_of(st)} | "
+              f"{c[0]} / {c[1]} / {c[2]} | {six} | {gap[0]:.1e}, {gap[1]:.1e} |")
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--states", action="store_true", help="table of the adversarial open-loop states of tests/colon_states.py (seconds)")
     ap.add_argument("--epochs", type=int, default=3600)
     ap.add_argument("--mode", default="WB", help="WB | NB (cfg4 record) | B2A (the reference's B2a defaults: 12 channels x 49 000 one-ms epochs)")
     a = ap.parse_args()
     cfast.build()
+    if a.states:
+        return states_table()
     L = cfast.lib()
     L.bds_oracle_trk_colon_diff.argtypes = [ctypes.c_long] + [ctypes.c_double] * 4 + [ctypes.POINTER(ctypes.c_long), ctypes.POINTER(ctypes.c_double)]
     L.bds_oracle_trk_colon_diff.restype = ctypes.c_int
