@@ -34,6 +34,7 @@
 #include "bds_acq_refine.h"
 #include "bds_acq_wrows.h"
 #include "bds_acq_pfa.h"
+#include "bds_acq_pfa32.h"
 #include "bds_internal.h"
 
 namespace bds {
@@ -193,8 +194,9 @@ struct AcqState {
     double sum_sq_ext = 0;     // sum x^2 over it: X_rms^2 (Parseval)
     long sums_N = 0, sums_next = 0;  // sizes the two sums above were computed for
     float sX = 1.f, sC = 1.f, sB = 1.f;  // power-of-two storage scales
-    // N-point plan (bds_acq_pfa.h, round 6): the cached code spectra are in its layout (53 x 12 x 3125, CRT order), the search runs its pair
-    bool cs_pfa = false;
+    // N-point plan (bds_acq_pfa.h: 1, bds_acq_pfa32.h: 2; 0: none): the cached code spectra are in its layout (CRT order), the search
+    // runs its pair
+    int cs_pfa = 0;
     uint4 *d_pfa_coef = nullptr;  // B fragments of the 53-point stage (pfa::make_coef_frags)
     long sigpower_X = 0;       // X the cached B1C normaliser was computed for (0: none; reset by bds_acq_load)
     double sigpower = 0;       // sqrt(var(sig(1:X)) * X), B1C/acquisition.m:150
@@ -780,17 +782,36 @@ extern "C" int bds_acq_load(bds_ctx *ctx, const bds_settings *s_in, const int8_t
     return BDS_OK;
 }
 
-// Does the N-point pair (bds_acq_pfa.h) apply to a run with these settings?  B1C with both components on N = 53 x 12 x 3125 samples
-// (99.375 MS/s, acqCohT = 10), fp16 storage, no resampling, and whole spectrum bins per Doppler step: acqStep N / fs an integer
+// Does an N-point pair apply to a run with these settings, and which?  B1C with both components on N = 53 x 12 x 3125 samples
+// (99.375 MS/s, acqCohT = 10: bds_acq_pfa.h) or N = 53 x 32 x 625 (53 MS/s, the reference's initSettings.m: bds_acq_pfa32.h), fp16
+// storage, no resampling, and whole spectrum bins per Doppler step: acqStep N / fs an integer
 // (B1C/acquisition.m:194-198: frqBins(b) = IF - band + acqStep (b - 1), so fft(carr_b x)[k] = fft(carr_1 x)[k - (b - 1) acqStep N / fs]).
 // Everything else -- and every fallback of a run (fp32 storage, run-time-plan kernels) -- takes the L-point pair.
-static int pfa_shift(const bds_ctx *ctx, const AcqState &a, const bds_settings &s) {
-    if (!ctx->tune.pfa || !a.half || a.no_fast_search || a.signal != BDS_SIGNAL_B1C || a.ncomp != 2 || a.N != pfa::NP || a.rs.on) return 0;
+struct PfaPick {
+    int kind = 0;   // 0: the L-point pair, 1: bds_acq_pfa.h, 2: bds_acq_pfa32.h
+    int shift = 0;  // spectrum bins per Doppler step
+};
+static PfaPick pfa_pick(const bds_ctx *ctx, const AcqState &a, const bds_settings &s) {
+    static const struct {
+        long N;
+        int kind;
+    } admitted[] = {{pfa::NP, 1}, {pfa32::NP, 2}};
+    PfaPick pk;
+    if (!ctx->tune.pfa || !a.half || a.no_fast_search || a.signal != BDS_SIGNAL_B1C || a.ncomp != 2 || a.rs.on) return pk;
+    int kind = 0;
+    for (const auto &ad : admitted)
+        if (a.N == ad.N) kind = ad.kind;
+    if (!kind) return pk;
     const double sh = s.acqStep * (double)a.N / s.samplingFreq;
     const long D = (long)m_round(s.acqSearchBand * 2 / s.acqStep) + 1;
-    if (!(sh >= 1.0) || sh != std::floor(sh) || sh * (double)D >= (double)a.N) return 0;
-    return (int)sh;
+    if (!(sh >= 1.0) || sh != std::floor(sh) || sh * (double)D >= (double)a.N) return pk;
+    pk.kind = kind, pk.shift = (int)sh;
+    return pk;
 }
+// sizes of the selected pair
+static long pfa_np(int kind) { return kind == 2 ? pfa32::NP : pfa::NP; }
+static int pfa_k3(int kind) { return kind == 2 ? pfa32::K3 : pfa::K3; }
+static int pfa_rows(int kind) { return kind == 2 ? pfa32::K1 * pfa32::K2 : pfa::K1 * pfa::K2; }
 
 extern "C" int bds_acq_prepare(bds_ctx *ctx, const bds_settings *s_in) {
     if (!ctx || !s_in) return BDS_ERR_ARG;
@@ -806,7 +827,7 @@ extern "C" int bds_acq_prepare(bds_ctx *ctx, const bds_settings *s_in) {
     pick_group(a, *s);
     if ((rc = ensure(ctx, &a.d_Bw, &a.bw_cap, bw_batches(a, ctx->tune) * (size_t)pl.L))) return rc;
     {   // layout of the cached code spectra: the N-point plan's or the L-point plan's; a change drops the cache
-        const bool want = pfa_shift(ctx, a, *s) > 0;
+        const int want = pfa_pick(ctx, a, *s).kind;
         if (want != a.cs_pfa) a.cs_slot.clear();
         a.cs_pfa = want;
         if (a.half) a.sC = (float)std::exp2(std::floor(std::log2(32768.0 * (double)(want ? a.N : pl.L) / (double)a.X)));
@@ -845,8 +866,11 @@ extern "C" int bds_acq_prepare(bds_ctx *ctx, const bds_settings *s_in) {
         // half storage: the same byte buffer holds 4-byte elements, so offsets count in those
         float2 *cs_dst = a.half ? (float2 *)((__half2 *)a.d_Cs + (size_t)slot * a.ncomp * pl.L)
                                 : a.d_Cs + (size_t)slot * a.ncomp * pl.L;
-        if (a.cs_pfa) {  // conj(fft(code)) / N in the CRT layout, [slot][component][53][12][3125] (the slots keep the L-point stride)
-            pfa::forward(st(ctx), ld, a.ncomp, a.d_Bw, (uint32_t *)cs_dst, pfa::NP, 1, (float)((double)a.sC / (double)a.N), 0);
+        if (a.cs_pfa) {  // conj(fft(code)) / N in the CRT layout, [slot][component][53][K2][K3] (the slots keep the L-point stride)
+            if (a.cs_pfa == 2)
+                pfa32::forward(st(ctx), ld, a.ncomp, a.d_Bw, (uint32_t *)cs_dst, pfa32::NP, 1, (float)((double)a.sC / (double)a.N), 0);
+            else
+                pfa::forward(st(ctx), ld, a.ncomp, a.d_Bw, (uint32_t *)cs_dst, pfa::NP, 1, (float)((double)a.sC / (double)a.N), 0);
             BDS_HIP(ctx, hipGetLastError());
         } else if ((rc = forward(ctx, a, ld, a.ncomp, cs_dst, pl.L, 1, (float)((double)a.sC / (double)pl.L))))
             return rc;
@@ -991,7 +1015,8 @@ struct AcqRun {
     double f0 = 0, kDelta = 0;
     float w0 = 1.f, w1 = 1.f;
     bool fsearch = false, wcols = false, multiprn = false, overlap = false;
-    int pfa = 0;               // > 0: the N-point pair runs (bds_acq_pfa.h); the value = spectrum bins per Doppler step
+    int pfa = 0;               // > 0: an N-point pair runs; the value = spectrum bins per Doppler step
+    int pfa_kind = 0;          // which: 1 bds_acq_pfa.h, 2 bds_acq_pfa32.h
     size_t cell_elems = 0;     // fp16-complex-sized elements of one cell in the inter-pass buffer (both components)
     bool dev_refined = false;  // the refinement ran as the device chain
     size_t elem = 8;  // bytes of one stored complex value
@@ -1050,11 +1075,14 @@ int AcqRun::setup() {
     ncomp = a.ncomp;
     pick_group(a, *s);
     G = a.group;
-    pfa = a.cs_pfa ? pfa_shift(ctx, a, *s) : 0;  // (bds_acq_prepare laid the code spectra out for it with these very settings)
+    if (a.cs_pfa) {  // (bds_acq_prepare laid the code spectra out for it with these very settings)
+        const PfaPick pk = pfa_pick(ctx, a, *s);
+        if (pk.kind == a.cs_pfa) pfa = pk.shift, pfa_kind = pk.kind;
+    }
     if (a.cs_pfa && !pfa) return fail(ctx, BDS_ERR_HIP, "internal: code spectra in the N-point layout for a run that cannot use them");
     if ((rc = ensure(ctx, &a.d_Bw, &a.bw_cap, bw_batches(a, ctx->tune) * (size_t)pl.L))) return rc;
     // (N-point pair: ONE signal spectrum, every row stored twice -- 2 N fp16 complex = N float2-sized elements)
-    if ((rc = ensure(ctx, &a.d_Xs, &a.xs_cap, pfa ? (size_t)pfa::NP : (size_t)D * pl.L))) return rc;
+    if ((rc = ensure(ctx, &a.d_Xs, &a.xs_cap, pfa ? (size_t)pfa_np(pfa_kind) : (size_t)D * pl.L))) return rc;
 
     BDS_HIP(ctx, evp.make(&ev0));
     BDS_HIP(ctx, evp.make(&ev1));
@@ -1076,7 +1104,7 @@ int AcqRun::setup() {
         // inter-pass values: rms = X_rms * C_rms / L * sqrt(L2) (Parseval); allow 64 x rms
         // (N-point pair: transform length N, rows of 3125 points; its row pass has no output scale -- sB rides on the stored signal
         //  spectrum, whose rms stays ~0.2 whatever the block: forward_all)
-        const double b_rms = pfa ? std::sqrt(a.sum_sq_ext) * std::sqrt((double)a.X) / (double)a.N * std::sqrt((double)pfa::K3)
+        const double b_rms = pfa ? std::sqrt(a.sum_sq_ext) * std::sqrt((double)a.X) / (double)a.N * std::sqrt((double)pfa_k3(pfa_kind))
                                  : std::sqrt(a.sum_sq_ext) * std::sqrt((double)a.X) / (double)pl.L * std::sqrt((double)pl.L2);
         a.sB = (float)std::exp2(std::floor(std::log2(32768.0 / (64.0 * std::max(1e-30, b_rms) * a.sX * a.sC))));
     }
@@ -1135,7 +1163,7 @@ int AcqRun::setup() {
         so.recs = a.d_recs;
     }
     elem = a.half ? 4 : 8;
-    cell_elems = pfa ? pfa::kCellElems : (size_t)ncomp * pl.L;  // stored complex values of one cell in the inter-pass buffer
+    cell_elems = pfa ? (pfa_kind == 2 ? pfa32::kCellElems : pfa::kCellElems) : (size_t)ncomp * pl.L;  // stored complex values of one cell in the inter-pass buffer
     // One launch pair carries the whole Doppler rows of SEVERAL PRNs through a cell list: the grids fill the chip, a row workgroup
     // walks all the bins of one PRN (its code rows and twiddles set up once per D cells), the row workgroups of different PRNs
     // read the same spectrum rows at about the same time, and a call is a few long launches instead of many short ones.
@@ -1206,7 +1234,10 @@ int AcqRun::forward_all() {
     Plan2D &pl = a.plan;
     if (pfa) {  // ONE transform: the spectrum of bin 0; bin b is its rotation by b * pfa bins (bds_acq_pfa.h)
         SignalLoader ld{a.sview(), a.N, a.n_ext, f0, s->acqStep, 1.0 / a.fs, 0};
-        pfa::forward(stream(), ld, 1, a.d_Bw, (uint32_t *)a.d_Xs, 0, 0, a.sX * a.sB, 1);
+        if (pfa_kind == 2)
+            pfa32::forward(stream(), ld, 1, a.d_Bw, (uint32_t *)a.d_Xs, 0, 0, a.sX * a.sB, 1);
+        else
+            pfa::forward(stream(), ld, 1, a.d_Bw, (uint32_t *)a.d_Xs, 0, 0, a.sX * a.sB, 1);
         BDS_HIP(ctx, hipGetLastError());
         BDS_HIP(ctx, hipEventRecord(ev1, stream()));
         return BDS_OK;
@@ -1278,6 +1309,20 @@ void AcqRun::launch_list(int ncells, Rec *recs, const CellList &cl, int cell0, h
     so1.mid = mid;
     if (mid) mids = true;
     const int hi1 = cl.rng ? -1 : (int)a.N - 1, lo2 = cl.rng ? 0 : 1, hi2 = cl.rng ? -1 : 0;
+    if (pfa_kind == 2) {  // the N-point pair of bds_acq_pfa32.h: the same cell list and sieve outputs, its own grids
+        const int gc = std::max(1, cl.gc), chunks = (ncells + gc - 1) / gc;
+        want_lds(ctx, pfa32::k_pfa32_cols, pfa32::kColsLds);
+        pfa::RowsArgs ra{(const uint32_t *)a.d_Xs, (const uint32_t *)a.d_Cs, (uint32_t *)a.d_Bw, cl.bin, cl.cs, ncells, gc, pfa};
+        hipLaunchKernelGGL(pfa32::k_pfa32_rows, dim3((unsigned)(pfa32::kRowsWgs * chunks)), dim3(pfa32::kRowsThreads), pfa32::kRowsLds, s_main, ra);
+        if (mid) (void)hipEventRecord(mid, s_main);
+        const int qch = ctx->tune.pfa_qchunk > 0 ? ctx->tune.pfa_qchunk : 1;
+        const long items = (long)((pfa32::kTiles + qch - 1) / qch) * qch * ncells;
+        const unsigned cgrid = (unsigned)std::min<long>(items, ctx->tune.pfa_cgrid > 0 ? ctx->tune.pfa_cgrid : std::max<long>(512, std::min<long>(8192, items / 24)));
+        pfa::ColsArgs ca{(const uint32_t *)a.d_Bw, a.d_pfa_coef, ncells, w0, w1, so1.cellmax, so1.lb, so1.lb_div, so1.extra, so1.extra_count,
+                         so1.extra_cap, cell0, so1.keep, qch, nullptr, nullptr, -1, -1};
+        hipLaunchKernelGGL(pfa32::k_pfa32_cols, dim3(cgrid), dim3(pfa32::kColsThreads), pfa32::kColsLds, s_main, ca);
+        return;
+    }
     if (pfa) {  // the N-point pair (bds_acq_pfa.h): every lag of the N is searched, the cells come as a list
         const int gc = std::max(1, cl.gc), chunks = (ncells + gc - 1) / gc;
         const size_t rows_lds = 2 * 3136 * sizeof(float2);
@@ -1366,7 +1411,7 @@ int AcqRun::search() {
                     const int gc_ = D / dv;  // dv chunks per PRN and row
                     if (gc_ < 32 && dv > 1) break;
                     cl.gc = gc_;
-                    if ((long)(pfa ? pfa::MP * pfa::K2 : pl.L1) * np_ * dv >= want_wgs) break;
+                    if ((long)(pfa_kind == 2 ? pfa32::kRowsWgs : pfa ? pfa::MP * pfa::K2 : pl.L1) * np_ * dv >= want_wgs) break;
                 }
             }
             // (a call is a handful of pairs: all of them are timed, the last, shorter one included -- cell_pair_ms and
@@ -1451,14 +1496,14 @@ int AcqRun::finish() {
     t.cell_pair_ms = nsamp ? acc / nsamp : (n_pairs_total ? t.search_ms / (double)n_pairs_total : 0);
     t.cells_per_pair = samp_cells > 0 && nsamp ? samp_cells / nsamp : (double)cells_per_pair;
     t.n_pairs = n_pairs_total;
-    t.fft_len = pfa ? pfa::NP : pl.L;
+    t.fft_len = pfa ? pfa_np(pfa_kind) : pl.L;
     t.n_circ = a.N;
     t.n_bins = D;
     t.n_prn = P;
     t.n_comp = ncomp;
     t.half_storage = a.half ? 1 : 0;  // 0 fp32; 1 fp16 storage (fp32 arithmetic either way)
-    t.plan_l1 = pfa ? pfa::K1 * pfa::K2 : pl.L1;
-    t.plan_l2 = pfa ? pfa::K3 : pl.L2;
+    t.plan_l1 = pfa ? pfa_rows(pfa_kind) : pl.L1;
+    t.plan_l2 = pfa ? pfa_k3(pfa_kind) : pl.L2;
     t.refine_path = dev_refined ? 1 : 0;
     {
         const bool wrows_on = fsearch && a.half && pl.L2 == 4096 && (tune.wrows != 0 || pl.small);

@@ -141,8 +141,8 @@ typedef struct bds_timing {
     double shader_clock_GHz; /* engine clock the search kernels ran at (sampled workgroups time themselves with the shader
                                 clock against the reference clock); 0 unless BDS_ACQ_CLOCKPROBE=1              */
     int32_t plan_l1, plan_l2; /* two-pass factorisation of fft_len: column length x row length                          */
-    int32_t rows_kernel;    /* row pass of the search: 0 run-time plan (k_rows_inv), 1 k_rows_inv_f, 2 k_rows_wave_f, 3 k_pfa_rows (N-point pair) */
-    int32_t cols_kernel;    /* column pass: 0 run-time plan (k_cols_inv_max), 1 tile kernel k_cols_inv_max_f, 2 k_cols_wave_f, 3 k_cols_small_f, 4 k_pfa_cols */
+    int32_t rows_kernel;    /* row pass of the search: 0 run-time plan (k_rows_inv), 1 k_rows_inv_f, 2 k_rows_wave_f, 3 N-point pair: k_pfa_rows (fft_len 1 987 500 = 53 x 12 x 3125, B1C at 99.375 MS/s) or k_pfa32_rows (fft_len 1 060 000 = 53 x 32 x 625, B1C at 53 MS/s) */
+    int32_t cols_kernel;    /* column pass: 0 run-time plan (k_cols_inv_max), 1 tile kernel k_cols_inv_max_f, 2 k_cols_wave_f, 3 k_cols_small_f, 4 k_pfa_cols / k_pfa32_cols */
     int32_t kernel_flags;   /* bit 0: components interleaved in the inter-pass buffer; bit 1: packed-fp32 butterflies     */
     int32_t refine_path;     /* 1: candidates -> f64 sums -> peak / second peak / fine search as one device chain with a single download (csrc/bds_acq_refine.h); 0: through the host */
 } bds_timing;
@@ -223,7 +223,9 @@ BDS_API int bds_acq_run(bds_ctx *ctx, const bds_settings *s, const int32_t *prn_
  *    40        12 - 13 PRNs per pair        132.1 - 133.0         (the DEFAULT)
  *    80        21 PRNs per pair             132.8
  *   < 0       60 % of the device memory that is free: 32 + 31 PRNs, 100 GiB    132.2   (the SERVING mode; bench.py key `serving`)
- * With the L-point pair of rounds 3-5 (5 GB per PRN; every configuration the N-point pair does not cover) more PRNs per pair also
+ * B1C at 53 MS/s with the settings of the reference's B1C/initSettings.m (N = 1 060 000 = 53 x 32 x 625) runs on the N-point pair of
+ * csrc/bds_acq_pfa32.h: 1.76 GB per PRN of 201 bins.
+ * With the L-point pair of rounds 3-5 (5 GB per PRN; every configuration the two N-point pairs do not cover) more PRNs per pair also
  * shared the 2.5 GB of signal-spectrum rows in L2: 196.7 / 191.6 - 192.1 (8 PRNs) / 189.3 - 189.8 / 186.8 - 187.1 ms.
  * The price is the footprint, and time when it changes hands: a fresh allocation is free (a first call costs the same in every
  * mode), but the driver clears freed device memory at ~33 GB/s and whoever allocates next waits -- up to ~4.8 s after a 150-GiB
