@@ -29,6 +29,7 @@
 #include <set>
 #include <tuple>
 
+#include "bds_acq_sieve.h"
 #include "bds_acq_scols.h"
 #include "bds_acq_wcols.h"
 #include "bds_acq_refine.h"
@@ -143,7 +144,7 @@ struct AcqState {
     std::vector<int> mcells_bin;
     std::vector<long> ref_tabs_cs;   // what d_ref_tabs holds (refinement chain: code-spectrum offset and PRN of every searched PRN)
     std::vector<int> ref_tabs_prn;
-    Extra *d_extra = nullptr;        // overflow list of the column pass (bds_acq_f32.h)
+    Extra *d_extra = nullptr;        // overflow list of the column pass (bds_acq_sieve.h)
     size_t extra_cap = 0;
     int *d_extra_count = nullptr;
     int n_extra_last = 0;            // entries of the last search (diagnostics)
@@ -442,18 +443,11 @@ struct CellList {
     int gc = 1;                  // consecutive listed cells that share their code spectra (one row workgroup walks them)
     const int *src = nullptr;    // 80 x 4096 plan only: the rows of listed cell g already lie at cell index src[g] of Bw -- no row pass
 };
-// where a column pass reports: per-tile records + the overflow list of the sieve
+// where a column pass reports: the sieve (bds_acq_sieve.h); the tile kernel writes per-tile records instead of cellmax / lb (both
+// null then) and uses the list as its overflow list
 struct SieveOut {
     Rec *recs = nullptr;
-    Extra *extra = nullptr;
-    int *extra_count = nullptr;
-    int extra_cap = 0;
-    int cell0 = 0;     // run-wide index of cell 0 of the launch
-    float keep = 1.f;  // 1 - sieve tolerance
-    // wave-private column pass (bds_acq_wcols.h) reports per cell / per PRN instead of per tile
-    unsigned long long *cellmax = nullptr;
-    float *lb = nullptr;
-    int lb_div = 1;
+    SieveArgs sieve{nullptr, nullptr, 1, nullptr, nullptr, 0, 0, 1.f};
     hipEvent_t mid = nullptr;  // recorded between the two passes of a sampled launch pair (timing)
     // overlapped passes: the column pass runs on its own stream behind ev_rows and signals ev_cols
     hipStream_t cols_stream = nullptr;
@@ -501,7 +495,7 @@ static void launch_cols_ft(bds_ctx *ctx, hipStream_t sc, const Plan2D &pl, int G
                            int hi1, int lo2, int hi2, const SieveOut &so, const CellList &cl) {
     const size_t lds = sizeof(float2) * (T * tspan<S>() + f32_tw_span<S, f32_tab_cols<S>()>());
     const ColsFArgs A{(const float2 *)(f32_tab_cols<S>() ? pl.d_ftab1 : pl.d_tw1), pl.L2, Bw, pl.L, w0, w1, lo1, hi1, lo2, hi2, so.recs, pl.ntiles, cl.rng,
-                      so.extra, so.extra_count, so.extra_cap, so.cell0, so.keep};
+                      so.sieve.extra, so.sieve.extra_count, so.sieve.extra_cap, so.sieve.cell0, so.sieve.keep};
     const bool masked = cl.rng || !(lo1 == 0 && lo2 > hi2);  // anything but "one range starting at lag 0"
     if (masked) {
         want_lds(ctx, k_cols_inv_max_f<S, T, NC, true, ST>, lds);
@@ -528,8 +522,7 @@ template <int S, int NC, class ST>
 static void launch_cols_w(bds_ctx *ctx, hipStream_t sc, const Plan2D &pl, int G, const void *Bw, float w0, float w1, int lo1,
                           int hi1, int lo2, int hi2, const SieveOut &so, const CellList &cl, bool ilv) {
     const int ntiles = pl.L2 / WCols<S>::T;  // L2 % 256 == 0 on every specialised plan: ntiles % 32 == 0 (8 XCDs x quads)
-    const WColsArgs A{(const float2 *)pl.d_wtab, pl.L2, ntiles, G, G * ntiles, Bw, pl.L, w0, w1, lo1, hi1, lo2, hi2, cl.rng,
-                      so.cellmax, so.lb, so.lb_div, so.extra, so.extra_count, so.extra_cap, so.cell0, so.keep, 1,
+    const WColsArgs A{(const float2 *)pl.d_wtab, pl.L2, ntiles, G, G * ntiles, Bw, pl.L, w0, w1, lo1, hi1, lo2, hi2, cl.rng, so.sieve, 1,
                       ctx->tune.clockprobe ? pl.d_clk : nullptr};
     const bool masked = cl.rng || !(lo1 == 0 && lo2 > hi2);  // anything but "one range starting at lag 0"
     if constexpr (S == 768 && NC == 2 && std::is_same<ST, __half2>::value) {  // (the plan with 4096-point rows: cfg3)
@@ -555,7 +548,7 @@ static void launch_cols_w(bds_ctx *ctx, hipStream_t sc, const Plan2D &pl, int G,
 template <int S, int NC, class ST>
 static void launch_cols_f(bds_ctx *ctx, hipStream_t sc, const Plan2D &pl, int G, const void *Bw, float w0, float w1, int lo1,
                           int hi1, int lo2, int hi2, const SieveOut &so, const CellList &cl, bool ilv) {
-    if (so.cellmax) return launch_cols_w<S, NC, ST>(ctx, sc, pl, G, Bw, w0, w1, lo1, hi1, lo2, hi2, so, cl, ilv);
+    if (so.sieve.cellmax) return launch_cols_w<S, NC, ST>(ctx, sc, pl, G, Bw, w0, w1, lo1, hi1, lo2, hi2, so, cl, ilv);
     if (pl.logT == 2)
         launch_cols_ft<S, 4, NC, ST>(ctx, sc, pl, G, Bw, w0, w1, lo1, hi1, lo2, hi2, so, cl);
     else
@@ -572,15 +565,14 @@ static void launch_fast_f(bds_ctx *ctx, hipStream_t st_, const Plan2D &pl, const
         if (pl.small) {  // 80 x 4096: wave-private row pass (components interleaved) + one lane per column and component
             if (!cl.src) launch_rows_f<4096, NC, ST>(ctx, st_, pl, Xs, G, bin0, Cs, Bw, out_scale, cl, true);
             if (so.mid) (void)hipEventRecord(so.mid, st_);
-            const SColsArgs A{(const float2 *)pl.d_tw80, pl.L2, G, Bw, pl.L, w0, w1, lo1, hi1, lo2, hi2, cl.rng, so.cellmax, so.lb, so.lb_div,
-                              so.extra, so.extra_count, so.extra_cap, so.cell0, so.keep, cl.src};
+            const SColsArgs A{(const float2 *)pl.d_tw80, pl.L2, G, Bw, pl.L, w0, w1, lo1, hi1, lo2, hi2, cl.rng, so.sieve, cl.src};
             want_lds(ctx, k_cols_small_f<NC>, kSColsLdsBytes);
             hipLaunchKernelGGL((k_cols_small_f<NC>), dim3((unsigned)(G * (pl.L2 / (kSColsNT / 2)))), dim3(kSColsNT), kSColsLdsBytes, st_, A);
             return;
         }
     }
     const bool ilv = NC == 2 && std::is_same<ST, __half2>::value && pl.L1 == 768 && pl.L2 == 4096 && ctx->tune.wrows != 0 &&
-                     so.cellmax && ctx->tune.ilv != 0 && !cl.rng && lo1 == 0 && lo2 > hi2;
+                     so.sieve.cellmax && ctx->tune.ilv != 0 && !cl.rng && lo1 == 0 && lo2 > hi2;
     switch (pl.L2) {
         case 1280: launch_rows_f<1280, NC, ST>(ctx, st_, pl, Xs, G, bin0, Cs, Bw, out_scale, cl, false); break;
         case 2048: launch_rows_f<2048, NC, ST>(ctx, st_, pl, Xs, G, bin0, Cs, Bw, out_scale, cl, false); break;
@@ -1141,15 +1133,16 @@ int AcqRun::setup() {
     // (the 256-point plans keep the tile kernel unless forced with BDS_ACQ_WCOLS=1: a workgroup's share of such a tile is
     //  8 points per lane and the per-workgroup constants and barriers dominate -- measured at cfg2 2.18 vs 1.39 ms per launch)
     wcols = fsearch && (pfa || pl.small || (tune.wcols != 0 && (pl.L1 != 256 || tune.wcols > 0)));
-    so = SieveOut{nullptr, a.d_extra, a.d_extra_count, kExtraCap, 0, (float)(1.0 - kDelta)};
+    so = SieveOut{};
+    so.sieve.extra = a.d_extra, so.sieve.extra_count = a.d_extra_count, so.sieve.extra_cap = kExtraCap, so.sieve.keep = (float)(1.0 - kDelta);
     if (wcols) {
         if ((rc = ensure(ctx, &a.d_cellmax, &a.cellmax_cap, (size_t)std::max(P, 1) * D))) return rc;
         if ((rc = ensure(ctx, &a.d_lb, &a.lb_cap, (size_t)std::max(P, 1)))) return rc;
         BDS_HIP(ctx, hipMemsetAsync(a.d_cellmax, 0, sizeof(unsigned long long) * (size_t)std::max(P, 1) * D, stream()));
         BDS_HIP(ctx, hipMemsetAsync(a.d_lb, 0, sizeof(float) * (size_t)std::max(P, 1), stream()));
-        so.cellmax = a.d_cellmax;
-        so.lb = a.d_lb;
-        so.lb_div = D;
+        so.sieve.cellmax = a.d_cellmax;
+        so.sieve.lb = a.d_lb;
+        so.sieve.lb_div = D;
     } else {  // per-tile records + per-row reduction (tile kernel, run-time-plan kernels)
         if ((rc = ensure(ctx, &a.d_recs, &a.recs_cap, (size_t)std::max(P, 1) * D * pl.ntiles))) return rc;
         if (a.rows_cap < (size_t)P * D) {
@@ -1261,7 +1254,7 @@ void AcqRun::launch_cells(int prn, int b0, int nb, Rec *recs, int lo1, int hi1, 
     const size_t cs_off = (size_t)a.cs_slot[prn] * ncomp * pl.L;
     SieveOut so1 = so;
     so1.recs = recs;
-    so1.cell0 = cell0;
+    so1.sieve.cell0 = cell0;
     so1.mid = mid;
     if (mid && fsearch) mids = true;
     void *const Bw_ = buf > 0 ? (void *)((char *)a.d_Bw + half_bytes) : (void *)a.d_Bw;
@@ -1305,7 +1298,7 @@ void AcqRun::launch_list(int ncells, Rec *recs, const CellList &cl, int cell0, h
     const hipStream_t s_main = stream();
     SieveOut so1 = so;
     so1.recs = recs;
-    so1.cell0 = cell0;
+    so1.sieve.cell0 = cell0;
     so1.mid = mid;
     if (mid) mids = true;
     const int hi1 = cl.rng ? -1 : (int)a.N - 1, lo2 = cl.rng ? 0 : 1, hi2 = cl.rng ? -1 : 0;
@@ -1318,8 +1311,7 @@ void AcqRun::launch_list(int ncells, Rec *recs, const CellList &cl, int cell0, h
         const int qch = ctx->tune.pfa_qchunk > 0 ? ctx->tune.pfa_qchunk : 1;
         const long items = (long)((pfa32::kTiles + qch - 1) / qch) * qch * ncells;
         const unsigned cgrid = (unsigned)std::min<long>(items, ctx->tune.pfa_cgrid > 0 ? ctx->tune.pfa_cgrid : std::max<long>(512, std::min<long>(8192, items / 24)));
-        pfa::ColsArgs ca{(const uint32_t *)a.d_Bw, a.d_pfa_coef, ncells, w0, w1, so1.cellmax, so1.lb, so1.lb_div, so1.extra, so1.extra_count,
-                         so1.extra_cap, cell0, so1.keep, qch, nullptr, nullptr, -1, -1};
+        pfa::ColsArgs ca{(const uint32_t *)a.d_Bw, a.d_pfa_coef, ncells, w0, w1, so1.sieve, qch, nullptr, nullptr, -1, -1};
         hipLaunchKernelGGL(pfa32::k_pfa32_cols, dim3(cgrid), dim3(pfa32::kColsThreads), pfa32::kColsLds, s_main, ca);
         return;
     }
@@ -1334,8 +1326,7 @@ void AcqRun::launch_list(int ncells, Rec *recs, const CellList &cl, int cell0, h
         const long items = (long)((pfa::kTiles + qch - 1) / qch) * qch * ncells;
         // (a workgroup loads the 57 KB coefficient table once: at least ~24 items each when the launch is small -- one PRN's row per pair)
         const unsigned cgrid = (unsigned)std::min<long>(items, ctx->tune.pfa_cgrid > 0 ? ctx->tune.pfa_cgrid : std::max<long>(512, std::min<long>(8192, items / 24)));
-        pfa::ColsArgs ca{(const uint32_t *)a.d_Bw, a.d_pfa_coef, ncells, w0, w1, so1.cellmax, so1.lb, so1.lb_div, so1.extra, so1.extra_count,
-                         so1.extra_cap, cell0, so1.keep, qch, nullptr, nullptr, -1, -1};
+        pfa::ColsArgs ca{(const uint32_t *)a.d_Bw, a.d_pfa_coef, ncells, w0, w1, so1.sieve, qch, nullptr, nullptr, -1, -1};
         hipLaunchKernelGGL((pfa::k_pfa_cols<2, false>), dim3(cgrid), dim3(pfa::kColsThreads), pfa::kColsLds, s_main, ca);
         return;
     }

@@ -199,16 +199,16 @@ int AcqRun::second_peak_b2a() {
     const int nb_r = ctx->tune.neigh;
     int rc;
     const bool small = pl.small && fsearch;  // the 80 x 4096 plan has no tile kernel: its column pass reports as in the search
-    so.cellmax = nullptr;
-    so.lb = nullptr;
+    so.sieve.cellmax = nullptr;
+    so.sieve.lb = nullptr;
     const long s2c = (long)std::ceil(s->samplingFreq / s->codeFreqBasis) * 2;  // samples2CodeChip :137
     std::vector<std::array<long, 4>> rng(P);
     if (small) {  // cell = PRN index: one packed maximum and one running bound per PRN
         BDS_HIP(ctx, hipMemsetAsync(a.d_cellmax, 0, sizeof(unsigned long long) * (size_t)std::max(P, 1), stream()));
         BDS_HIP(ctx, hipMemsetAsync(a.d_lb, 0, sizeof(float) * (size_t)std::max(P, 1), stream()));
-        so.cellmax = a.d_cellmax;
-        so.lb = a.d_lb;
-        so.lb_div = 1;
+        so.sieve.cellmax = a.d_cellmax;
+        so.sieve.lb = a.d_lb;
+        so.sieve.lb_div = 1;
         so.recs = nullptr;
     } else {
         if ((rc = ensure(ctx, &a.d_recs, &a.recs_cap, (size_t)std::max(P, 1) * pl.ntiles))) return rc;
@@ -537,8 +537,8 @@ int AcqRun::refine_device() {
                            reuse_bw ? d_src : (int *)nullptr, a.d_ref_g);
         const SieveOut so_keep = so;
         so.recs = nullptr;
-        so.extra = a.d_extra2, so.extra_count = a.d_extra2_count, so.extra_cap = kExtra2Cap;
-        so.cellmax = a.d_cellmax2, so.lb = a.d_lb2, so.lb_div = 1;
+        so.sieve.extra = a.d_extra2, so.sieve.extra_count = a.d_extra2_count, so.sieve.extra_cap = kExtra2Cap;
+        so.sieve.cellmax = a.d_cellmax2, so.sieve.lb = a.d_lb2, so.sieve.lb_div = 1;
         CellList cl{d_bin, d_cs, d_rng};
         if (reuse_bw) cl.src = d_src;
         launch_list(P, nullptr, cl, 0, nullptr);

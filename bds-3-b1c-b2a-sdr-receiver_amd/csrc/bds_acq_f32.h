@@ -18,6 +18,7 @@
 #pragma once
 
 #include "bds_acq_fast.h"
+#include "bds_acq_sieve.h"  // Extra, wave_max_f32
 
 namespace bds {
 
@@ -212,12 +213,6 @@ __device__ __forceinline__ void rows_inv_f_body(const RowsFArgs &A, int vb, int 
 }
 
 // ---- inverse column pass + |.| combine + maximum ---------------------------------------------------
-struct Extra {
-    float v;
-    int lag;   // 0-based
-    int cell;  // cell index within the run (PRN index * D + bin, or the second-peak pass's PRN index)
-};
-
 struct ColsFArgs {
     const float2 *tw;   // W_S table of the column transform
     int L2;
@@ -234,22 +229,6 @@ struct ColsFArgs {
     int cell0;              // run-wide index of cell 0 of this launch
     float keep;             // 1 - tolerance of the sieve
 };
-
-// maximum over the 64 lanes, wave-uniform result (DPP inside the 16-lane rows, then one read per row)
-__device__ __forceinline__ float wave_max_f32(float v) {
-    auto dpp = [](float x, auto ctrl) {
-        return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), decltype(ctrl)::value, 0xF, 0xF, true));
-    };
-    v = fmaxf(v, dpp(v, std::integral_constant<int, 0xB1>{}));   // quad_perm [1,0,3,2]
-    v = fmaxf(v, dpp(v, std::integral_constant<int, 0x4E>{}));   // quad_perm [2,3,0,1]
-    v = fmaxf(v, dpp(v, std::integral_constant<int, 0x141>{}));  // row_half_mirror
-    v = fmaxf(v, dpp(v, std::integral_constant<int, 0x140>{}));  // row_mirror
-    const float r0 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 0));
-    const float r1 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 16));
-    const float r2 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 32));
-    const float r3 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 48));
-    return fmaxf(fmaxf(r0, r1), fmaxf(r2, r3));
-}
 
 template <int S, int T, int NCOMP, bool MASKED, class ST>
 __device__ __forceinline__ void cols_inv_max_f_body(const ColsFArgs &A, int tb, int ntb, int g, int tid) {

@@ -18,7 +18,7 @@
 //                             the DFT coefficients are split hi + lo in fp16 (error ~1e-7, tools/proto_pfa53.py) --, the 12-point
 //                             transform over k2 per lane on the accumulators (a lane holds all 12 k2 of one output: data is the
 //                             A operand, so the MFMA's rows are (t3, k2) and its columns the outputs), |y|^2, the sieve protocol
-//                             of bds_acq_wcols.h.
+//                             (bds_acq_sieve.h).
 //
 // Inter-pass buffer of a cell: [mp 27][k2 12][t3 3125][component 2][row of the pair 2] fp16 complex = 16 bytes per (mp, k2, t3);
 // a lane's A fragment (k1 = 4 mg .. 4 mg + 3 of one (k2, t3), one component) is the halves of two such pieces.
@@ -29,7 +29,9 @@
 
 #include <type_traits>
 
-#include "bds_acq_wcols.h"  // Extra, wc_pack, wave_max_f32; bds_fft_pk.h, bds_lds.h
+#include "bds_acq_sieve.h"
+#include "bds_fft_pk.h"
+#include "bds_lds.h"
 
 namespace bds {
 namespace pfa {
@@ -331,14 +333,7 @@ struct ColsArgs {
     const uint4 *coef;            // make_coef_frags
     int ncells;                   // cells of the launch
     float w0, w1;                 // magnitude weights (storage scales undone)
-    unsigned long long *cellmax;  // [run-wide cell]: (value bits << 32) | ~lag, by atomic max      -- the protocol of bds_acq_wcols.h --
-    float *lb;                    // [(run-wide cell) / lb_div]: running lower bound of that PRN's sieve maximum
-    int lb_div;
-    Extra *extra;                 // candidate list
-    int *extra_count;
-    int extra_cap;
-    int cell0;                    // run-wide index of cell 0 of this launch
-    float keep;                   // 1 - tolerance of the sieve
+    SieveArgs sieve;              // where the pass reports (bds_acq_sieve.h)
     int qchunk;                   // blocks of 16 lags of a cell that follow each other in the work list
     unsigned long long *stats;    // optional (probe): [0] wave items, [1] of them through the values' pass, [2] through the exhaustive pass, [3] output blocks the values' pass visited
     float *dbg;                   // optional: |y_d|^2, |y_p|^2 of one (cell, t3 group): [2][53][12][4]
@@ -395,8 +390,7 @@ __global__ __launch_bounds__(kColsThreads, 2) void k_pfa_cols(ColsArgs A) {
         const int blk = (int)(q * uq + b);
         const int t0 = 16 * blk + 4 * wave;
         if (blk >= kBlocks || t0 >= K3) continue;
-        const int cell = A.cell0 + cl;
-        float *const lbp = A.lb + cell / A.lb_div;
+        const int cell = A.sieve.cell0 + cl;
         const int t3 = min(t0 + g, K3 - 1);
         const uint32_t *base = A.Bw + (size_t)cl * kCellElems;
         // ---- A fragments: [component][quad][ins], k1 = 4 mg .. 4 mg + 3 with mg = 4 ins + ks, of (k2 = 4 quad + r, t3)
@@ -485,12 +479,10 @@ __global__ __launch_bounds__(kColsThreads, 2) void k_pfa_cols(ColsArgs A) {
         // 201 cells; a forced 1 : 6 or 1 : 9 matrix : vector interleave by sched_group_barrier measured the same).
         f4 accp[2][NC][3];
         matrix(0, accp[0], std::integral_constant<int, kParts1>{});
-        // the cell's maximum so far and the PRN's running bound; stale values are lower values: a redundant visit of the values' pass.
-        // (Requested here, behind block 0's matrix instructions and their wait for the fragments: two device-scope loads in front of
-        //  that wait would hold up the whole item, here they have six output blocks to arrive in.)
-        const float lbv = __hip_atomic_load(lbp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        // (the value half of the packed word alone: with the 64-bit load the compiler reuses the dead low register at once and waits for it)
-        const unsigned cur = __hip_atomic_load(reinterpret_cast<const unsigned *>(A.cellmax + cell) + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        // the cell's maximum so far and the PRN's running bound.  (Requested here, behind block 0's matrix instructions and their wait for
+        //  the fragments: two device-scope loads in front of that wait would hold up the whole item, here they have six output blocks to
+        //  arrive in.)
+        const SieveBounds bd = sieve_bounds(A.sieve, cell);
 #pragma unroll
         for (int nb = 0; nb < NB; ++nb) {
             float m2[2][6];
@@ -514,9 +506,8 @@ __global__ __launch_bounds__(kColsThreads, 2) void k_pfa_cols(ColsArgs A) {
             }
         }
         if (A.stats && lane == 0) atomicAdd(A.stats, 1ull);
-        // Cauchy-Schwarz: (w_d |y_d| + w_p |y_p|)^2 <= (w_d^2 + w_p^2)(|y_d|^2 + |y_p|^2).  If even that bound, over all of the wave's
-        // outputs, stays below both the cell's maximum so far and the sieve threshold of the PRN's running bound, the wave has nothing
-        // to report (bds_acq_wcols.h).  Otherwise the exact values: the outputs are recomputed (they were never all in registers) --
+        // The skip test (bds_acq_sieve.h) over all of the wave's outputs, on the bound pass's squares widened by dlt.  Otherwise the exact
+        // values: the outputs are recomputed (they were never all in registers) --
         const float wsum2 = NC > 1 ? A.w0 * A.w0 + A.w1 * A.w1 : A.w0 * A.w0;
         float dlt = 0.f;  // what the values' pass may add to sqrt(|y_d|^2 + |y_p|^2) of this lane's outputs
         if (kParts1 == 1) {
@@ -533,9 +524,8 @@ __global__ __launch_bounds__(kColsThreads, 2) void k_pfa_cols(ColsArgs A) {
             dlt = 5.0e-4f * sqrtf(s16);
         }
         const float ub = wave_max_f32(sqrtf(best) + dlt);
-        const float bw = ub * ub * wsum2 * 1.00001f;
-        const float curv = __uint_as_float(cur), lim = fminf(curv, lbv * A.keep);
-        if (!(bw < lim * lim)) {  // (wave-uniform; also taken while the bounds are unset or not finite)
+        const float lim = sieve_limit(A.sieve, bd);
+        if (!sieve_below(ub * ub, wsum2, lim)) {  // (wave-uniform)
             if (A.stats && lane == 0) atomicAdd(A.stats + 1, 1ull);
             // -- only the output blocks in which some lane's bound reaches the limit (the same expression per lane and block as the wave's test
             // above: the block that failed it is among them); every output of the other blocks is below the cell's maximum so far and
@@ -543,97 +533,34 @@ __global__ __launch_bounds__(kColsThreads, 2) void k_pfa_cols(ColsArgs A) {
             unsigned fmask = 0;
             for (int nb = 0; nb < NB; ++nb) {
                 const float u = sqrtf(s_bm[nb * kColsThreads + tid]) + dlt;
-                if (__builtin_amdgcn_ballot_w64(!(u * u * wsum2 * 1.00001f < lim * lim))) fmask |= 1u << nb;
+                if (__builtin_amdgcn_ballot_w64(!sieve_below(u * u, wsum2, lim))) fmask |= 1u << nb;
             }
             if (A.stats && lane == 0) atomicAdd(A.stats + 3, (unsigned long long)__builtin_popcount(fmask));
-            // -- a lane keeps the two largest of its values with their lags (first lag on ties, like max()).  Two qualifying values in one
-            // lane's 42 outputs are the rare case of the rare case: then a third pass lists exhaustively.
-            float top1 = -1.f, top2 = -1.f;
-            int lag1 = 0x7fffffff, lag2 = 0x7fffffff;
-            for (int nb = 0; nb < NB; ++nb) {
-                if (!((fmask >> nb) & 1)) continue;
+            // the exact values and lags of output block nb: emit(value, lag) per slot, -1 for the slots of a pad lane
+            auto values = [&](int nb, auto emit) {
                 float m2[2][6];
                 block(nb, m2, std::integral_constant<int, 2>{});
                 const int t1 = (16 * nb + (lane & 15)) >> 1;
-                if (t1 < K1 && t3o < K3) {
+                const bool mine = t1 < K1 && t3o < K3;
 #pragma unroll
-                    for (int i = 0; i < 6; ++i) {
+                for (int i = 0; i < 6; ++i) {
+                    float a = -1.f;
+                    if (mine) {
                         // raw v_sqrt_f32 (1 ulp): the value only feeds the sieve; S + 2 x of a vanishing output may come out below zero
-                        float a = A.w0 * __builtin_amdgcn_sqrtf(fmaxf(m2[0][i], 0.f));
+                        a = A.w0 * __builtin_amdgcn_sqrtf(fmaxf(m2[0][i], 0.f));
                         if (NC > 1) a += A.w1 * __builtin_amdgcn_sqrtf(fmaxf(m2[NC - 1][i], 0.f));
-                        const int lag = (int)lag_of(t1, t2_of(i), t3o);
-                        if (a > top1 || (a == top1 && lag < lag1)) {
-                            top2 = top1, lag2 = lag1, top1 = a, lag1 = lag;
-                        } else if (a > top2 || (a == top2 && lag < lag2)) {
-                            top2 = a, lag2 = lag;
-                        }
                     }
+                    emit(a, (int)lag_of(t1, t2_of(i), t3o));
                 }
+            };
+            SieveTop2 top;
+            for (int nb = 0; nb < NB; ++nb) {
+                if (!((fmask >> nb) & 1)) continue;
+                values(nb, [&](float a, int lag) {
+                    if (a >= 0.f) top.offer(a, lag);
+                });
             }
-            const float Mw = wave_max_f32(top1);
-            if (Mw >= 0.f) {
-                const float thr = fmaxf(Mw, lbv) * A.keep;
-                const bool newmax = __float_as_uint(Mw) >= cur;  // this wave holds (a tie of) the cell's maximum so far
-                const unsigned long long hit1 = __builtin_amdgcn_ballot_w64(top1 >= thr), hit2 = __builtin_amdgcn_ballot_w64(top2 >= thr);
-                if (newmax || hit1) {
-                    if (!hit2) {
-                        const int total = __builtin_popcountll(hit1);
-                        if (total > 0) {  // one reservation per wave on the list's counter
-                            int base_i = 0;
-                            if (lane == 0) base_i = atomicAdd(A.extra_count, total);
-                            base_i = __builtin_amdgcn_readfirstlane(base_i);
-                            if (top1 >= thr) {
-                                const int idx = base_i + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(hit1 >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)hit1, 0u));
-                                if ((unsigned)idx < (unsigned)A.extra_cap) {  // (unsigned: a counter run over 2^31 must not index backwards)
-                                    Extra ex;
-                                    ex.v = top1, ex.lag = lag1, ex.cell = cell;
-                                    A.extra[idx] = ex;
-                                }
-                            }
-                        }
-                    } else {
-                        if (A.stats && lane == 0) atomicAdd(A.stats + 2, 1ull);
-                        for (int nb = 0; nb < NB; ++nb) {
-                            if (!((fmask >> nb) & 1)) continue;
-                            float m2[2][6];
-                            block(nb, m2, std::integral_constant<int, 2>{});
-                            const int t1 = (16 * nb + (lane & 15)) >> 1;
-                            const bool mine = t1 < K1 && t3o < K3;
-#pragma unroll
-                            for (int i = 0; i < 6; ++i) {
-                                float a = -1.f;
-                                if (mine) {
-                                    a = A.w0 * __builtin_amdgcn_sqrtf(fmaxf(m2[0][i], 0.f));
-                                    if (NC > 1) a += A.w1 * __builtin_amdgcn_sqrtf(fmaxf(m2[NC - 1][i], 0.f));
-                                }
-                                const unsigned long long mask = __builtin_amdgcn_ballot_w64(a >= thr);
-                                if (mask) {  // (wave-uniform)
-                                    int base_i = 0;
-                                    if (lane == 0) base_i = atomicAdd(A.extra_count, __builtin_popcountll(mask));
-                                    base_i = __builtin_amdgcn_readfirstlane(base_i);
-                                    if (a >= thr) {
-                                        const int idx = base_i + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mask, 0u));
-                                        if ((unsigned)idx < (unsigned)A.extra_cap) {  // (unsigned: a counter run over 2^31 must not index backwards)
-                                            Extra ex;
-                                            ex.v = a, ex.lag = (int)lag_of(t1, t2_of(i), t3o), ex.cell = cell;
-                                            A.extra[idx] = ex;
-                                        }
-                                    }
-                                }
-                            }
-                        }
-                    }
-                    if (newmax) {
-                        int bestlag = top1 == Mw ? lag1 : 0x7fffffff;
-#pragma unroll
-                        for (int o = 32; o > 0; o >>= 1) bestlag = min(bestlag, __shfl_xor(bestlag, o));
-                        if (lane == 0) {
-                            atomicMax(A.cellmax + cell, wc_pack(Mw, bestlag));
-                            if (Mw > lbv) atomicMax(reinterpret_cast<unsigned *>(lbp), __float_as_uint(Mw));
-                        }
-                    }
-                }
-            }
+            sieve_top2_tail<NB>(A.sieve, bd, lane, cell, top, fmask, A.stats ? A.stats + 2 : nullptr, values);
         }
     }
 }

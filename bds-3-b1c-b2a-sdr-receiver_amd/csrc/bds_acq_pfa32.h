@@ -17,8 +17,8 @@
 //                              32-point transform over k2 = 8 m + u -> t2 = ta + 4 tb: 4 points over m in the lane (the lane pair
 //                              (re, im) splits the ta: even / odd), twiddle W32^(u ta), 4 -> 8 points over rr in the lane, and the last
 //                              radix-2 level (h) across the two 16-lane rows by v_permlane16_swap: the rows split the tb.  A lane ends
-//                              with 8 of the 32 outputs of its (t1, t3).  Then w_d |y_d| + w_p |y_p| and the sieve protocol of
-//                              bds_acq_wcols.h exactly as k_pfa_cols speaks it.  (fa[2][4][4] is 128 VGPRs; all 32 k2 per lane would
+//                              with 8 of the 32 outputs of its (t1, t3).  Then w_d |y_d| + w_p |y_p| and the sieve protocol
+//                              (bds_acq_sieve.h: the top-2 tail of k_pfa_cols).  (fa[2][4][4] is 128 VGPRs; all 32 k2 per lane would
 //                              be 256.)  Every output block is computed with hi + lo coefficients once: there is no hi-only bound pass
 //                              and hence no margin to prove; the Cauchy-Schwarz test on the EXACT |y_d|^2 + |y_p|^2 only decides
 //                              whether a block's square roots and list bookkeeping are needed.
@@ -214,8 +214,7 @@ __global__ __launch_bounds__(kColsThreads, 2) void k_pfa32_cols(pfa::ColsArgs A)
         const int blk = (int)(q * uq + b);
         const int t0 = kTileLags * blk + 2 * wave;
         if (blk >= kBlocks || t0 >= K3) continue;
-        const int cell = A.cell0 + cl;
-        float *const lbp = A.lb + cell / A.lb_div;
+        const int cell = A.sieve.cell0 + cl;
         const int t3 = min(t0 + ag, K3 - 1);
         const uint32_t *base = A.Bw + (size_t)cl * kCellElems;
         // ---- A fragments: [component][m][ins], k1 = 4 mg .. 4 mg + 3 with mg = 4 ins + ks, of (k2 = 8 m + ar, t3)
@@ -294,17 +293,14 @@ __global__ __launch_bounds__(kColsThreads, 2) void k_pfa32_cols(pfa::ColsArgs A)
             }
         };
         const int t3o = t0 + og;  // the lag t3 of this lane's outputs
-        // the cell's maximum so far and the PRN's running bound; stale values are lower values: a redundant visit of the list's code
-        const float lbv = __hip_atomic_load(lbp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        const unsigned cur = __hip_atomic_load(reinterpret_cast<const unsigned *>(A.cellmax + cell) + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        // the cell's maximum so far and the PRN's running bound
+        const SieveBounds bd = sieve_bounds(A.sieve, cell);
         const float wsum2 = A.w0 * A.w0 + A.w1 * A.w1;
-        const float curv = __uint_as_float(cur), lim = fminf(curv, lbv * A.keep);
+        const float lim = sieve_limit(A.sieve, bd);
         if (A.stats && lane == 0) atomicAdd(A.stats, 1ull);
-        // A lane keeps the two largest of its values with their lags (first lag on ties, like max()).  Cauchy-Schwarz on the exact squares:
-        // (w_d |y_d| + w_p |y_p|)^2 <= (w_d^2 + w_p^2)(|y_d|^2 + |y_p|^2) -- a block in which that stays below both the cell's maximum so
-        // far and the sieve threshold of the PRN's running bound has nothing to report and skips its square roots.
-        float top1 = -1.f, top2 = -1.f;
-        int lag1 = 0x7fffffff, lag2 = 0x7fffffff;
+        // The skip test (bds_acq_sieve.h) per output block, on the exact squares: a block that passes it has nothing to report and skips
+        // its square roots.
+        SieveTop2 top;
         unsigned fmask = 0;
         for (int nb = 0; nb < NB; ++nb) {
             float m2[2][8];
@@ -315,82 +311,36 @@ __global__ __launch_bounds__(kColsThreads, 2) void k_pfa32_cols(pfa::ColsArgs A)
 #pragma unroll
             for (int i = 0; i < 8; ++i) bmax = fmaxf(bmax, m2[0][i] + m2[1][i]);
             if (!mine) bmax = 0.f;
-            if (!__builtin_amdgcn_ballot_w64(!(bmax * wsum2 * 1.00001f < lim * lim))) continue;  // (wave-uniform; taken while the bounds are unset)
+            if (!__builtin_amdgcn_ballot_w64(!sieve_below(bmax, wsum2, lim))) continue;  // (wave-uniform)
             fmask |= 1u << nb;
             if (mine) {
 #pragma unroll
-                for (int i = 0; i < 8; ++i) {
-                    const float a = A.w0 * __builtin_amdgcn_sqrtf(m2[0][i]) + A.w1 * __builtin_amdgcn_sqrtf(m2[1][i]);
-                    const int lag = (int)lag_of(t1, t2_of(i), t3o);
-                    if (a > top1 || (a == top1 && lag < lag1)) {
-                        top2 = top1, lag2 = lag1, top1 = a, lag1 = lag;
-                    } else if (a > top2 || (a == top2 && lag < lag2)) {
-                        top2 = a, lag2 = lag;
-                    }
-                }
+                for (int i = 0; i < 8; ++i)
+                    top.offer(A.w0 * __builtin_amdgcn_sqrtf(m2[0][i]) + A.w1 * __builtin_amdgcn_sqrtf(m2[1][i]), (int)lag_of(t1, t2_of(i), t3o));
             }
         }
         if (A.stats && lane == 0) atomicAdd(A.stats + 1, (unsigned long long)__builtin_popcount(fmask));
-        const float Mw = wave_max_f32(top1);
-        if (Mw >= 0.f) {
-            const float thr = fmaxf(Mw, lbv) * A.keep;
-            const bool newmax = __float_as_uint(Mw) >= cur;  // this wave holds (a tie of) the cell's maximum so far
-            const unsigned long long hit1 = __builtin_amdgcn_ballot_w64(top1 >= thr), hit2 = __builtin_amdgcn_ballot_w64(top2 >= thr);
-            if (newmax || hit1) {
-                if (!hit2) {
-                    const int total = __builtin_popcountll(hit1);
-                    if (total > 0) {  // one reservation per wave on the list's counter
-                        int base_i = 0;
-                        if (lane == 0) base_i = atomicAdd(A.extra_count, total);
-                        base_i = __builtin_amdgcn_readfirstlane(base_i);
-                        if (top1 >= thr) {
-                            const int idx = base_i + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(hit1 >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)hit1, 0u));
-                            if ((unsigned)idx < (unsigned)A.extra_cap) {
-                                Extra ex;
-                                ex.v = top1, ex.lag = lag1, ex.cell = cell;
-                                A.extra[idx] = ex;
-                            }
-                        }
-                    }
-                } else {  // two qualifying values in one lane: list exhaustively (the blocks are recomputed: their values were never all in registers)
-                    for (int nb = 0; nb < NB; ++nb) {
-                        if (!((fmask >> nb) & 1)) continue;
-                        float m2[2][8];
-                        block(nb, m2);
-                        const int t1 = (16 * nb + (lane & 15)) >> 1;
-                        const bool mine = t1 < K1 && t3o < K3;
+        // The top-2 tail in its two halves, with the relisting loop here instead of sieve_top2_tail's callback: as a callback the loop is
+        // optimised on its own before it is inlined, the compiler then keeps the item-invariant 64-bit parts of the eight lags of a lane
+        // across the whole kernel, and at this kernel's register limit that is 256 VGPRs + 23 spilled instead of 254 and none
+        // (profiles/r08_sieve_tail_resources.txt).
+        const SieveTop2Plan plan = sieve_top2_begin(A.sieve, bd, lane, cell, top);
+        if (plan.exhaustive) {
+            for (int nb = 0; nb < NB; ++nb) {
+                if (!((fmask >> nb) & 1)) continue;
+                float m2[2][8];
+                block(nb, m2);
+                const int t1 = (16 * nb + (lane & 15)) >> 1;
+                const bool mine = t1 < K1 && t3o < K3;
 #pragma unroll
-                        for (int i = 0; i < 8; ++i) {
-                            float a = -1.f;
-                            if (mine) a = A.w0 * __builtin_amdgcn_sqrtf(m2[0][i]) + A.w1 * __builtin_amdgcn_sqrtf(m2[1][i]);
-                            const unsigned long long mask = __builtin_amdgcn_ballot_w64(a >= thr);
-                            if (mask) {  // (wave-uniform)
-                                int base_i = 0;
-                                if (lane == 0) base_i = atomicAdd(A.extra_count, __builtin_popcountll(mask));
-                                base_i = __builtin_amdgcn_readfirstlane(base_i);
-                                if (a >= thr) {
-                                    const int idx = base_i + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mask, 0u));
-                                    if ((unsigned)idx < (unsigned)A.extra_cap) {
-                                        Extra ex;
-                                        ex.v = a, ex.lag = (int)lag_of(t1, t2_of(i), t3o), ex.cell = cell;
-                                        A.extra[idx] = ex;
-                                    }
-                                }
-                            }
-                        }
-                    }
-                }
-                if (newmax) {
-                    int bestlag = top1 == Mw ? lag1 : 0x7fffffff;
-#pragma unroll
-                    for (int o = 32; o > 0; o >>= 1) bestlag = min(bestlag, __shfl_xor(bestlag, o));
-                    if (lane == 0) {
-                        atomicMax(A.cellmax + cell, wc_pack(Mw, bestlag));
-                        if (Mw > lbv) atomicMax(reinterpret_cast<unsigned *>(lbp), __float_as_uint(Mw));
-                    }
+                for (int i = 0; i < 8; ++i) {
+                    float a = -1.f;
+                    if (mine) a = A.w0 * __builtin_amdgcn_sqrtf(m2[0][i]) + A.w1 * __builtin_amdgcn_sqrtf(m2[1][i]);
+                    sieve_append(A.sieve, lane, a >= plan.thr, a, (int)lag_of(t1, t2_of(i), t3o), cell);
                 }
             }
         }
+        sieve_top2_end(A.sieve, bd, lane, cell, top, plan);
     }
 }
 

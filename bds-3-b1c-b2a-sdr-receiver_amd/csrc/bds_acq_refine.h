@@ -13,6 +13,7 @@
 #pragma once
 
 #include "bds_acq_kernels.h"
+#include "bds_acq_sieve.h"  // Extra: the candidate list this chain reads
 
 namespace bds {
 

@@ -16,11 +16,12 @@
 // bytes, the partner's |y|^2 arrives by one DPP move.  ~180 VGPRs: two waves per SIMD, which a stream of packed instructions
 // without waits fills (tools/probe/coissue.hip).
 //
-// Outputs exactly as the wave-private column pass (bds_acq_wcols.h): per cell the packed maximum {value, first lag} by atomic
-// max, per PRN the running bound lb, the candidate list -- same completeness argument, same host code.
+// Outputs: the sieve protocol of bds_acq_sieve.h, as the wave-private column pass (bds_acq_wcols.h) -- same host code.
 #pragma once
 
-#include "bds_acq_wcols.h"
+#include "bds_acq_f32.h"
+#include "bds_acq_sieve.h"
+#include "bds_fft_pk.h"
 
 namespace bds {
 
@@ -38,14 +39,7 @@ struct SColsArgs {
     float w0, w1;
     int lo1, hi1, lo2, hi2;
     const int4 *cell_rng;            // optional per-cell (lo1, hi1, lo2, hi2)
-    unsigned long long *cellmax;     // as WColsArgs
-    float *lb;
-    int lb_div;
-    Extra *extra;
-    int *extra_count;
-    int extra_cap;
-    int cell0;
-    float keep;
+    SieveArgs sieve;                 // where the pass reports (bds_acq_sieve.h)
     const int *cell_src;             // optional: cell g's rows lie at cell index cell_src[g] of Bw (the B2a second-peak pass reading
                                      // the winning cells straight out of the main search's inter-pass buffer), else at g
 };
@@ -86,10 +80,8 @@ __global__ __launch_bounds__(kSColsNT, kSColsOcc) void k_cols_small_f(SColsArgs 
     uint32_t in[kSColsLen];
 #pragma unroll
     for (int k1 = 0; k1 < kSColsLen; ++k1) in[k1] = src[(long)k1 * L2 * 2];
-    const int cell = A.cell0 + g;
-    float *const lbp = A.lb + cell / A.lb_div;
-    const float lbv = __hip_atomic_load(lbp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    const unsigned cur = (unsigned)(__hip_atomic_load(A.cellmax + cell, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >> 32);
+    const int cell = A.sieve.cell0 + g;
+    const SieveBounds bd = sieve_bounds(A.sieve, cell);
 
     // ---- Y_r[d] = sum_m w16^(m d) B[5 m + r]
     v2f Y[5][16];
@@ -135,17 +127,16 @@ __global__ __launch_bounds__(kSColsNT, kSColsOcc) void k_cols_small_f(SColsArgs 
         sqp[k] = __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, sq[k]), 0xB1, 0xF, 0xF, true));
         bmax = fmaxf(bmax, sq[k] + sqp[k]);
     }
-    // ---- maximum of the wave's 32 columns, candidates: as the tail of k_cols_wave_f (Cauchy-Schwarz bound first)
+    // ---- maximum of the wave's 32 columns, candidates (bds_acq_sieve.h): the skip test on the squares first
     const float wown = comp == 0 ? A.w0 : A.w1, wpar = comp == 0 ? A.w1 : A.w0;
     const float wsum2 = A.w0 * A.w0 + A.w1 * A.w1;
-    const float bw = wave_max_f32(bmax) * wsum2 * 1.00001f;
-    const float curv = __uint_as_float(cur), lim = fminf(curv, lbv * A.keep);
-    if (!(bw < lim * lim)) {  // (wave-uniform; also taken while the bounds are unset or not finite)
+    if (!sieve_below(wave_max_f32(bmax), wsum2, sieve_limit(A.sieve, bd))) {  // (wave-uniform)
         int lo1 = A.lo1, hi1 = A.hi1, lo2 = A.lo2, hi2 = A.hi2;
         if (A.cell_rng) {
             const int4 r = A.cell_rng[g];
             lo1 = r.x, hi1 = r.y, lo2 = r.z, hi2 = r.w;
         }
+        // the exact values are staged as they are formed (49 more live registers otherwise); outputs not searched hold -1
         float *sm = sm_all + wave * (kSColsOut * 64) + lane;  // [k][lane]
         float mx = -1.f;
 #pragma unroll
@@ -157,53 +148,11 @@ __global__ __launch_bounds__(kSColsNT, kSColsOcc) void k_cols_small_f(SColsArgs 
             sm[k * 64] = a;
             mx = fmaxf(mx, a);
         }
-        const float Mw = wave_max_f32(mx);
-        if (Mw >= 0.f) {  // (wave-uniform) something of these columns is searched
-            const float thr = fmaxf(Mw, lbv) * A.keep;
-            const bool newmax = __float_as_uint(Mw) >= cur;
-            if (newmax || __builtin_amdgcn_ballot_w64(mx >= thr) != 0) {
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-                __builtin_amdgcn_wave_barrier();
-                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-                int best = 0x7fffffff, total = 0;
-#pragma nounroll
-                for (int k = 0; k < kSColsOut; ++k) {
-                    const float a = sm[k * 64];
-                    total += __builtin_popcountll(__builtin_amdgcn_ballot_w64(a >= thr));
-                    if (newmax && a == Mw) best = min(best, k * L2 + col);
-                }
-                if (total > 0) {  // one reservation per wave on the list's counter
-                    int base = 0;
-                    if (lane == 0) base = atomicAdd(A.extra_count, total);
-                    base = __builtin_amdgcn_readfirstlane(base);
-#pragma nounroll
-                    for (int k = 0; k < kSColsOut; ++k) {
-                        const float a = sm[k * 64];
-                        const unsigned long long mask = __builtin_amdgcn_ballot_w64(a >= thr);
-                        if (a >= thr) {
-                            const int idx = base + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mask, 0u));
-                            BDS_DASSERT(idx >= 0 && (long)k * L2 + col < A.L);
-                            if (idx < A.extra_cap) {
-                                Extra ex;
-                                ex.v = a;
-                                ex.lag = k * L2 + col;
-                                ex.cell = cell;
-                                A.extra[idx] = ex;
-                            }
-                        }
-                        base += __builtin_popcountll(mask);
-                    }
-                }
-                if (newmax) {
-#pragma unroll
-                    for (int o = 32; o > 0; o >>= 1) best = min(best, __shfl_xor(best, o));
-                    if (lane == 0) {
-                        atomicMax(A.cellmax + cell, wc_pack(Mw, best));
-                        if (Mw > lbv) atomicMax(reinterpret_cast<unsigned *>(lbp), __float_as_uint(Mw));
-                    }
-                }
-            }
-        }
+        auto lag_at = [&](int k) {
+            BDS_DASSERT((long)k * L2 + col < A.L);
+            return k * L2 + col;
+        };
+        sieve_staged_tail<kSColsOut>(A.sieve, bd, lane, cell, wave_max_f32(mx), mx, sm, [] {}, lag_at);
     }
 }
 

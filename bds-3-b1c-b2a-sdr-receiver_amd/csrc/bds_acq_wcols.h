@@ -24,14 +24,12 @@
 //   the rows of both components in flight before anything else happens.
 //   Every LDS access class is bank-conflict free (tools/proto_cols_wave.py models the layouts lane by lane).
 //
-// Outputs (no per-tile records): per cell the packed maximum {value, first lag} by a 64-bit atomic max (rare:
-// only when a wave beats the cell's current value), per PRN a running lower bound `lb` of the sieve maximum,
-// and the candidate list: every lag whose value is within `keep` of max(wave maximum, lb).  Both are lower
-// bounds of the PRN's final maximum M, so every lag >= keep * M is on the list -- the completeness argument of
-// DESIGN.md section 1.5 -- while the list stays a few thousand entries per PRN instead of one record per tile.
+// Outputs (no per-tile records): the sieve protocol of bds_acq_sieve.h -- per cell the packed maximum, per PRN the running
+// bound, the candidate list, which stays a few thousand entries per PRN instead of one record per tile.
 #pragma once
 
 #include "bds_acq_f32.h"
+#include "bds_acq_sieve.h"
 #include "bds_fft_pk.h"
 #include "bds_lds.h"
 
@@ -100,21 +98,10 @@ struct WColsArgs {
     float w0, w1;
     int lo1, hi1, lo2, hi2;
     const int4 *cell_rng;            // optional per-cell (lo1, hi1, lo2, hi2), MASKED kernels only
-    unsigned long long *cellmax;     // [run-wide cell]: (value bits << 32) | ~lag, by atomic max
-    float *lb;                       // [(run-wide cell) / lb_div]: running lower bound of that PRN's sieve maximum
-    int lb_div;
-    Extra *extra;                    // candidate list
-    int *extra_count;
-    int extra_cap;
-    int cell0;                       // run-wide index of cell 0 of this launch
-    float keep;                      // 1 - tolerance of the sieve
+    SieveArgs sieve;                 // where the pass reports (bds_acq_sieve.h)
     int qchunk;                      // adjacent quads (4 tiles = one 128-byte line per row) of a cell that follow each other in the list
     unsigned long long *clk;         // optional (BDS_ACQ_CLOCKPROBE): [2], [3] += shader-clock / reference-clock ticks of sampled workgroups
 };
-
-__device__ __forceinline__ unsigned long long wc_pack(float v, int lag) {
-    return ((unsigned long long)__float_as_uint(v) << 32) | (unsigned long long)(~(unsigned)lag);
-}
 
 // entries of the per-lane twiddle table of a length-S plan: (R1 - 1) x 256 for phase A (w_S^(b p), p = 1 .. R1 - 1, indexed
 // [p - 1][thread]) followed by 7 x 64 for phase B (input j of lane (ml, u = lane / 8) in stage 3 is bl = (j + u) & 7:
@@ -212,8 +199,7 @@ __global__ __launch_bounds__(WCols<S>::NT, WCols<S>::kOcc) void k_cols_wave_f(WC
         cx_set(twB1, u.x, u.y);
     }
     fetch(pre0, 0);
-    const int cell = A.cell0 + g;
-    float *const lbp = A.lb + cell / A.lb_div;
+    const int cell = A.sieve.cell0 + g;
     {
         const C w = twA[1];
 #pragma unroll
@@ -281,16 +267,10 @@ __global__ __launch_bounds__(WCols<S>::NT, WCols<S>::kOcc) void k_cols_wave_f(WC
                 asm volatile("" : "+v"(pre[q].x), "+v"(pre[q].y), "+v"(pre[q].z), "+v"(pre[q].w));
         }
     };
-    auto wave_sync = [] {  // LDS traffic of one wave is in order; this only stops the compiler from moving it
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    };
 
     float sq[NCOMP][SL][NV];  // |y|^2 per component
     float bmax = 0.f;         // maximum of |y_d|^2 (+ |y_p|^2) over the wave's outputs
-    float lbv = 0.f;
-    unsigned cur = 0;
+    SieveBounds bd{};
 #pragma unroll
     for (int comp = 0; comp < NCOMP; ++comp) {
         {
@@ -308,8 +288,7 @@ __global__ __launch_bounds__(WCols<S>::NT, WCols<S>::kOcc) void k_cols_wave_f(WC
                 for (int j = 2; j < 8; ++j) twB[j] = (j & 1) ? cx_mul(twB[j - 1], twB1) : cx_mul(twB[j / 2], twB[j / 2]);
                 // the cell's maximum so far and the PRN's running bound (L2 / fabric latency), used after the transforms;
                 // stale values are lower values, which only costs a redundant visit of the rare path below
-                lbv = __hip_atomic_load(lbp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                cur = (unsigned)(__hip_atomic_load(A.cellmax + cell, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >> 32);
+                bd = sieve_bounds(A.sieve, cell);
                 __builtin_amdgcn_sched_barrier(0);
             } else {
                 // (pinned here: moved up into the first component's last stage it doubles the live registers)
@@ -340,17 +319,17 @@ __global__ __launch_bounds__(WCols<S>::NT, WCols<S>::kOcc) void k_cols_wave_f(WC
             constexpr int s = decltype(sc)::value;
             C y[8];
             lds_read8<s * 8 * MS * (int)sizeof(C), 8 * (int)sizeof(C)>(y, rw2a);
-            wave_sync();
+            lds_wave_sync();
             cx_bfly8<false>(y, (const C *)nullptr);
 #pragma unroll
             for (int u = 0; u < 8; ++u) rw2[s * 8 * MS + 8 * u] = y[u];
-            wave_sync();
+            lds_wave_sync();
         };
         auto st3 = [&](auto sc) {
             constexpr int s = decltype(sc)::value;
             C y[8];
             lds_read8p<s * 8 * MS * (int)sizeof(C)>(y, rd3a);
-            wave_sync();
+            lds_wave_sync();
             cx_bfly8<true>(y, twB);
 #pragma unroll
             for (int v = 0; v < NV; ++v) {
@@ -374,15 +353,11 @@ __global__ __launch_bounds__(WCols<S>::NT, WCols<S>::kOcc) void k_cols_wave_f(WC
             st3(sc);
         });
     }
-    // ---- maximum of the wave's two columns, candidates ------------------------------------------
-    // Cauchy-Schwarz: (w_d |y_d| + w_p |y_p|)^2 <= (w_d^2 + w_p^2) (|y_d|^2 + |y_p|^2).  If even that bound, over all of the
-    // wave's outputs, stays below both the cell's maximum so far and the sieve threshold of the PRN's running bound, the
-    // wave has nothing to report: no square root was taken and no lag was formed -- the common case once a cell's first
-    // few workgroups are through.  (1e-5: rounding of the bound and of the squares, 40 x the fp32 unit.)
+    // ---- maximum of the wave's two columns, candidates (bds_acq_sieve.h) ----------------------------------
+    // The skip test on the squares, over all of the wave's outputs: no square root was taken and no lag was formed -- the common
+    // case once a cell's first few workgroups are through.
     const float wsum2 = NCOMP > 1 ? A.w0 * A.w0 + A.w1 * A.w1 : A.w0 * A.w0;
-    const float bw = wave_max_f32(bmax) * wsum2 * 1.00001f;
-    const float curv = __uint_as_float(cur), lim = fminf(curv, lbv * A.keep);
-    if (!(bw < lim * lim)) {  // (wave-uniform; also taken while the bounds are unset or not finite)
+    if (!sieve_below(wave_max_f32(bmax), wsum2, sieve_limit(A.sieve, bd))) {  // (wave-uniform)
         // exact values; lags outside the searched ranges hold -1 (searched values are >= 0)
         float mag[SL][NV];
         float mx = -1.f;
@@ -399,64 +374,23 @@ __global__ __launch_bounds__(WCols<S>::NT, WCols<S>::kOcc) void k_cols_wave_f(WC
                 mx = fmaxf(mx, mag[s][v]);
             }
         }
-        const float Mw = wave_max_f32(mx);
-        if (Mw >= 0.f) {  // (wave-uniform) something of these two columns is searched
-        const float thr = fmaxf(Mw, lbv) * A.keep;
-        const bool newmax = __float_as_uint(Mw) >= cur;  // this wave holds (a tie of) the cell's maximum so far
-        if (newmax || __builtin_amdgcn_ballot_w64(mx >= thr) != 0) {
-            // Rare (wave-uniform): the values go through the wave's own LDS region (nobody else touches it any more)
-            // and a compact loop picks the maximum's first lag and every lag within the sieve tolerance of the bound.
-            float *sm = reinterpret_cast<float *>(ldsf + wave * RS) + lane;  // [k = 8 s + v][lane]
-            wave_sync();
+        // the values go through the wave's own LDS region (nobody else touches it any more), [k = 8 s + v][lane]
+        float *sm = reinterpret_cast<float *>(ldsf + wave * RS) + lane;
+        auto stage = [&] {
+            lds_wave_sync();
 #pragma unroll
             for (int s = 0; s < SL; ++s) {
 #pragma unroll
                 for (int v = 0; v < 8; ++v) sm[(8 * s + v) * 64] = v < NV ? mag[s][v < NV ? v : 0] : -1.f;
             }
-            wave_sync();
-            auto lag_at = [&](int k) {
-                const int m = ml + (k & ~7), c = m >= R1 ? 1 : 0;
-                return (m - c * R1 + R1 * bl + 8 * R1 * (k & 7)) * L2 + c0 + 2 * wave + c;
-            };
-            int best = 0x7fffffff, total = 0;
-#pragma nounroll
-            for (int k = 0; k < 8 * SL; ++k) {
-                const float a = sm[k * 64];
-                total += __builtin_popcountll(__builtin_amdgcn_ballot_w64(a >= thr));
-                if (newmax && a == Mw) best = min(best, lag_at(k));
-            }
-            if (total > 0) {  // one reservation per wave on the list's counter
-                int base = 0;
-                if (lane == 0) base = atomicAdd(A.extra_count, total);
-                base = __builtin_amdgcn_readfirstlane(base);
-#pragma nounroll
-                for (int k = 0; k < 8 * SL; ++k) {
-                    const float a = sm[k * 64];
-                    const unsigned long long mask = __builtin_amdgcn_ballot_w64(a >= thr);
-                    if (a >= thr) {
-                        const int idx = base + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mask, 0u));
-                        BDS_DASSERT(idx >= 0 && lag_at(k) >= 0 && (long)lag_at(k) < L && cell >= A.cell0 && cell < A.cell0 + A.G);
-                        if (idx < A.extra_cap) {
-                            Extra ex;
-                            ex.v = a;
-                            ex.lag = lag_at(k);
-                            ex.cell = cell;
-                            A.extra[idx] = ex;
-                        }
-                    }
-                    base += __builtin_popcountll(mask);
-                }
-            }
-            if (newmax) {
-#pragma unroll
-                for (int o = 32; o > 0; o >>= 1) best = min(best, __shfl_xor(best, o));
-                if (lane == 0) {
-                    atomicMax(A.cellmax + cell, wc_pack(Mw, best));
-                    if (Mw > lbv) atomicMax(reinterpret_cast<unsigned *>(lbp), __float_as_uint(Mw));
-                }
-            }
-        }
-        }
+        };
+        auto lag_at = [&](int k) {
+            const int m = ml + (k & ~7), c = m >= R1 ? 1 : 0;
+            const int lag = (m - c * R1 + R1 * bl + 8 * R1 * (k & 7)) * L2 + c0 + 2 * wave + c;
+            BDS_DASSERT((long)lag < L && g < A.G);
+            return lag;
+        };
+        sieve_staged_tail<8 * SL>(A.sieve, bd, lane, cell, wave_max_f32(mx), mx, sm, stage, lag_at);
     }
     clkp.finish(tid);
 }

@@ -20,6 +20,14 @@ __device__ __forceinline__ unsigned lds_offset(const void *p) {
     return (unsigned)(unsigned long)(__attribute__((address_space(3))) const char *)p;
 }
 
+// LDS traffic of ONE wave is in order: between a wave's writes to a region only it uses and its reads of them this is all that is
+// needed, and it only stops the compiler from moving them
+__device__ __forceinline__ void lds_wave_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
 // y[k] = *(a + BASE + k STEP), k = 0 .. 7 (byte offsets, compile-time)
 template <int BASE, int STEP>
 __device__ __forceinline__ void lds_read8(v2f (&y)[8], unsigned a) {

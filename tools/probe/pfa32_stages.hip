@@ -147,7 +147,7 @@ static void run_cols(const uint32_t *d_Bw, int bw_cells, const Bytes &table, Wri
         fill_words(d_extra, (size_t)kGuardExtra * 3, kGuardWord);
         fill_words(d_extra + kGuardExtra + cap, (size_t)kGuardExtra * 3, kGuardWord);
         CK(hipMemset(d_extra + kGuardExtra, 0, (size_t)cap * sizeof(bds::Extra)));
-        ColsArgs ca{d_Bw, d_coef, ncells, w0, w1, d_cellmax, d_lb, lb_div, d_extra + kGuardExtra, d_count, (int)cap, cell0, keep, qchunk,
+        ColsArgs ca{d_Bw, d_coef, ncells, w0, w1, {d_cellmax, d_lb, lb_div, d_extra + kGuardExtra, d_count, (int)cap, cell0, keep}, qchunk,
                     want_stats ? d_stats : nullptr, nullptr, -1, -1};
         hipLaunchKernelGGL(k_pfa32_cols, dim3((unsigned)grid), dim3(kColsThreads), kColsLds, 0, ca);
         CK(hipGetLastError());

@@ -191,7 +191,7 @@ int main(int argc, char **argv) {
             CK(hipMemset(d_lb, 0, ncell_t * sizeof(float)));
             CK(hipMemset(d_extra_count, 0, sizeof(int)));
             CK(hipMemset(d_dbg, 0, sizeof(float) * 2 * K1 * 12 * 4));
-            ColsArgs ca{d_Bw, d_coef, ncell_t, 0.52440442f, 0.85146932f, d_cellmax, d_lb, 1, d_extra, d_extra_count, extra_cap, 0, 0.996f, 4, nullptr, d_dbg, cell, grp};
+            ColsArgs ca{d_Bw, d_coef, ncell_t, 0.52440442f, 0.85146932f, {d_cellmax, d_lb, 1, d_extra, d_extra_count, extra_cap, 0, 0.996f}, 4, nullptr, d_dbg, cell, grp};
             hipLaunchKernelGGL((k_pfa_cols<2, true>), dim3(512), dim3(kColsThreads), kColsLds, 0, ca);
             CK(hipDeviceSynchronize());
             std::vector<float> dbg(2 * K1 * 12 * 4);
@@ -309,7 +309,7 @@ int main(int argc, char **argv) {
                 CK(hipMemset(d_lb, 0, ncells * sizeof(float)));
                 CK(hipMemset(d_extra_count, 0, sizeof(int)));
                 CK(hipMemset(d_stats, 0, 4 * sizeof(unsigned long long)));
-                ColsArgs ct{d_Bw, d_coef, ncells, 0.52440442f, 0.85146932f, d_cellmax, d_lb, D, d_extra, d_extra_count, extra_cap, 0, 0.996f, qch, counting ? d_stats : nullptr, nullptr, -1, -1};
+                ColsArgs ct{d_Bw, d_coef, ncells, 0.52440442f, 0.85146932f, {d_cellmax, d_lb, D, d_extra, d_extra_count, extra_cap, 0, 0.996f}, qch, counting ? d_stats : nullptr, nullptr, -1, -1};
                 CK(hipEventRecord(e0));
                 hipLaunchKernelGGL(k_pfa_rows<2>, dim3(MP * K2 * chunks), dim3(kRowsThreads), rows_lds, 0, rt);
                 CK(hipEventRecord(e1));
@@ -347,7 +347,7 @@ int main(int argc, char **argv) {
             hipLaunchKernelGGL(k_pfa_rows<2>, dim3(MP * K2 * ((n + gc - 1) / gc)), dim3(kRowsThreads), rows_lds, st, r);
         };
         auto cols = [&](hipStream_t st, int off, int n) {
-            ColsArgs c{d_Bw + (size_t)off * kCellElems, d_coef, n, 0.52440442f, 0.85146932f, d_cellmax, d_lb, D, d_extra, d_extra_count, extra_cap, off, 0.996f, 1, nullptr, nullptr, -1, -1};
+            ColsArgs c{d_Bw + (size_t)off * kCellElems, d_coef, n, 0.52440442f, 0.85146932f, {d_cellmax, d_lb, D, d_extra, d_extra_count, extra_cap, off, 0.996f}, 1, nullptr, nullptr, -1, -1};
             hipLaunchKernelGGL((k_pfa_cols<2, false>), dim3(8192), dim3(kColsThreads), kColsLds, st, c);
         };
         float best_seq = 1e9f, best_ovl = 1e9f;
