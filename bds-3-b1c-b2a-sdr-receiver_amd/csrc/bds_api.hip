@@ -119,6 +119,8 @@ Tuning tuning_from_env() {
     t.trk_persample = has("BDS_TRK_PERSAMPLE");
     t.trk_seg = geti("BDS_TRK_SEG", 0);
     t.trk_nofuse_update = has("BDS_TRK_NOFUSE_UPDATE");
+    if (const char *e = std::getenv("BDS_TRK_STREAM_MARGIN")) t.trk_stream_margin = std::max(0.0, std::atof(e));
+    t.trk_window_nomem = has("BDS_TRK_WINDOW_NOMEM");
 #endif
     return t;
 }

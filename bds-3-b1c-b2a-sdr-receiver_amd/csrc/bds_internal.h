@@ -72,6 +72,9 @@ struct Tuning {
     bool trk_persample = false;      // BDS_TRK_PERSAMPLE: per-sample tracking correlator instead of the run-based one
     int trk_prec = 4;                // BDS_TRK_PREC: carrier / prefix-sum numerics of the run-based correlator (bds_track.hip, TrkParams::prec; 4 = strict, the default: a sin / cos of the reference's trigarg per sample; 5 = the same argument by angle addition)
     int trk_seg = 0;                 // BDS_TRK_SEG: samples per lane and pass of the run-based correlator (8 / 16; 0 = per-signal default)
+    double trk_stream_margin = -1;   // BDS_TRK_STREAM_MARGIN: test hook, margin of a streamed batch's plan in blocks (bds_track.hip, do_track; < 0 = the default, 1);
+                                     // 0 plans every epoch that STARTS inside the resident span, so the window guard fires and the batch is repeated
+    bool trk_window_nomem = false;   // BDS_TRK_WINDOW_NOMEM: test hook, the allocation of the one window is taken to have failed (the call streams)
 };
 Tuning tuning_from_env();
 

@@ -18,6 +18,8 @@
 // The host enqueues all epochs back to back and never synchronises inside the loop: the
 // sequential dependence (next blksize / phases depend on this epoch's discriminators) is
 // carried entirely by device memory.
+// A window that does not fit (or exceeds bds_track_set_resident_limit) is STREAMED: the same launches in batches of epochs
+// over a span of the record that slides through two half-size buffers, the next piece loading while a batch runs (do_track).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -25,6 +27,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <functional>
+#include <thread>
 #include <type_traits>
 
 #include "bds_debug.h"
@@ -47,7 +50,8 @@ struct ChanState {
     long long pos;         // sample offset of the next read: ftell / dataAdaptCoeff (tracking.m:226)
     int prn;               // 0 = channel unused
     int active;            // 1 while the channel keeps tracking; 0 stopped at a short read (end of file);
-                           // -2 its reads left the loaded window of the record (the host reloads the whole file)
+                           // -2 its reads left the part of the record held in HBM (one window: the host reloads the whole
+                           // file; streamed: the host repeats the batch from the state it started with)
     int completed;         // epochs finished
     int pad;
 };
@@ -69,7 +73,8 @@ struct TrkParams {
     double spacing;  // dllCorrelatorSpacing (earlyLateSpc)
     double tau1, tau2, pdi, pf1, pf2, pf3, factor;
     long long n_bytes;  // samples in the record: file bytes / dataAdaptCoeff
-    long long base;     // first sample of the record held in HBM (only the window the channels can touch is loaded)
+    long long base;     // first sample of the record held in HBM (only the window the channels can touch is loaded;
+                        // streamed: the resident span, which moves between launches)
     long long win_end;  // one past the last sample held
 };
 
@@ -927,8 +932,8 @@ __device__ __forceinline__ void apply_update(const TrkParams &p, ChanState &s, c
         [&] {
     const long e = (long)ch * p.n_epochs + epoch;
     if (g.pos + g.blk <= p.n_bytes && (g.pos < p.base || g.pos + g.blk > p.win_end)) {
-        // inside the file but outside the part of it that was loaded: nothing of this epoch is valid;
-        // the host repeats the call with the whole record in HBM
+        // inside the file but outside the part of it that is held: nothing of this epoch is valid; the host repeats the
+        // call with the whole record in HBM (one window) or the batch with a wider margin (streamed)
         s.active = -2;
         return;
     }
@@ -1024,14 +1029,24 @@ __global__ __launch_bounds__(kUpdThreads) void k_trk_update(TrkParams p, ChanSta
 struct TrackState {
     int8_t *d_data = nullptr;
     size_t data_cap = 0;
-    size_t loaded_bytes = 0;  // bytes of the record the last call copied to HBM (diagnostics)
+    size_t loaded_bytes = 0;  // bytes of the record the last call copied host-to-device (diagnostics)
     int8_t *d_prim = nullptr;
     int prim_signal = 0;
+    // streamed mode: the resident span of the record slides through two buffers of span_cap bytes each
+    int8_t *d_span[2] = {nullptr, nullptr};
+    size_t span_cap = 0;
+    size_t resident_limit = 0;  // bds_track_set_resident_limit (0: none)
+    // bds_track_stream_info of the last call
+    int pieces = 0;           // loads of a part of the record (1: one window)
+    size_t resident_max = 0;  // most bytes of the record resident at a time
+    int repeated = 0;         // batches run again after the window guard fired
 };
 
 void track_state_free(TrackState *t) {
     if (!t) return;
     if (t->d_data) (void)hipFree(t->d_data);
+    for (int8_t *q : t->d_span)
+        if (q) (void)hipFree(q);
     if (t->d_prim) (void)hipFree(t->d_prim);
     delete t;
 }
@@ -1211,8 +1226,107 @@ __global__ __launch_bounds__(256) void k_trk_cno(TrkOut o, const ChanState *__re
     }
 }
 
-// Source of the IF record: copies bytes [off, off + n) of the file into device memory at dst.
-using RecordLoader = std::function<int(size_t off, size_t n, int8_t *dst)>;
+// Source of the IF record: copies bytes [off, off + n) of the file into device memory at dst, ordered on `stream`.
+// (Streamed tracking calls it from its loader thread, with the context's second stream, while a batch of epochs runs.)
+using RecordLoader = std::function<int(size_t off, size_t n, int8_t *dst, hipStream_t stream)>;
+
+// Streamed tracking: the resident span of the record and the one being prepared (do_track plans the batches).
+//   cur  the span the epochs of the current batch read, on the context's main stream
+//   nxt  the span in preparation: its tail [pre_lo, pre_hi) is loaded by a host thread on the second stream while the batch
+//        runs (start_load .. join); at the batch boundary move_to() copies what it shares with cur in front of that tail,
+//        device-to-device on the main stream, and the two change places
+// Who may touch a buffer when (the two streams are non-blocking: nothing orders them but what is written here):
+//   * the loader's writes into nxt are complete before the main stream reads them: the thread synchronises its stream, and the
+//     host joins it before move_to();
+//   * after the exchange the OLD cur is nxt, and the main stream may still be reading it -- the carry copy just enqueued (the
+//     kernels of earlier batches are done: the host synchronises the main stream at every batch end).  The next load writes
+//     into that buffer, so move_to() records ev_carry behind the copy and the loader's stream waits for it before its first byte;
+//   * loads that move_to() issues itself are on the main stream, behind the copy.
+// Between start_load() and join() the loader may set the context's error message (the RecordLoader reports its own failures):
+// the main thread must not call fail() in that interval -- it keeps error codes in locals and reports them after join().
+struct SpanStream {
+    struct Span {  // samples [base, end) of the record at buf
+        int8_t *buf = nullptr;
+        long long base = 0, end = 0;
+    } cur, nxt;
+    bds_ctx *ctx;
+    TrackState &t;
+    const RecordLoader &load;
+    hipStream_t main_stream, ld_stream;
+    long long coeff, span_n;  // bytes per sample; samples a span buffer holds
+    hipEvent_t ev_carry = nullptr;
+    bool carry_pending = false;  // ev_carry is recorded behind a copy that reads nxt.buf
+    // the prediction: the next span starts at sample pre_nb, its tail [pre_lo, pre_hi) goes behind what it shares with cur
+    bool pre_valid = false;
+    long long pre_nb = 0, pre_lo = 0, pre_hi = 0;
+    std::thread th;
+    int th_rc = BDS_OK;
+    hipError_t th_err = hipSuccess;
+
+    SpanStream(bds_ctx *c, TrackState &ts, const RecordLoader &l, hipStream_t ms, hipStream_t ls, long long cf, long long sn)
+        : ctx(c), t(ts), load(l), main_stream(ms), ld_stream(ls), coeff(cf), span_n(sn) {}
+    SpanStream(const SpanStream &) = delete;
+    SpanStream &operator=(const SpanStream &) = delete;
+    ~SpanStream() {
+        if (th.joinable()) th.join();
+        if (ev_carry) (void)hipEventDestroy(ev_carry);
+    }
+    // nxt becomes the span that starts at sample nb: what it shares with cur is carried device-to-device, the rest up to hi
+    // is loaded here (main stream) unless the loader thread has put it there already; then the two change places
+    int move_to(long long nb, long long hi, bool tail_loaded) {
+        const bool carry = nb >= cur.base && nb < cur.end;
+        if (carry) {
+            if (!ev_carry) BDS_HIP(ctx, hipEventCreateWithFlags(&ev_carry, hipEventDisableTiming));
+            BDS_HIP(ctx, hipMemcpyAsync(nxt.buf, cur.buf + (nb - cur.base) * coeff, (size_t)((cur.end - nb) * coeff), hipMemcpyDeviceToDevice, main_stream));
+            BDS_HIP(ctx, hipEventRecord(ev_carry, main_stream));
+            carry_pending = true;
+        }
+        const long long from = carry ? cur.end : nb;
+        if (!tail_loaded && hi > from) {
+            const size_t nbytes = (size_t)((hi - from) * coeff);
+            int r = load((size_t)(from * coeff), nbytes, nxt.buf + (from - nb) * coeff, main_stream);
+            if (r) return r;
+            t.loaded_bytes += nbytes, t.pieces += 1;
+        }
+        nxt.base = nb, nxt.end = std::max(hi, from);
+        t.resident_max = std::max(t.resident_max, (size_t)((cur.end - cur.base + nxt.end - nxt.base) * coeff));
+        std::swap(cur, nxt);
+        pre_valid = false;
+        return BDS_OK;
+    }
+    void predict(long long nb, long long hi) { pre_nb = nb, pre_lo = cur.end, pre_hi = hi, pre_valid = true; }
+    // the predicted tail, on the loader's stream beside the batch just enqueued (nothing to do when a prediction kept over a
+    // repeated batch is loaded already).  The bytes are counted when they are copied: a prediction that is discarded later
+    // (the channels are not where it put them) is loaded, and counted, again by move_to().
+    void start_load() {
+        if (!pre_valid || th.joinable() || pre_lo >= pre_hi) return;
+        int8_t *dst = nxt.buf + (pre_lo - pre_nb) * coeff;
+        const size_t off = (size_t)(pre_lo * coeff), nbytes = (size_t)((pre_hi - pre_lo) * coeff);
+        pre_lo = pre_hi;
+        t.resident_max = std::max(t.resident_max, (size_t)((cur.end - cur.base) * coeff) + nbytes);
+        t.loaded_bytes += nbytes, t.pieces += 1;
+        const bool wait_carry = carry_pending && ld_stream != main_stream;
+        carry_pending = false;
+        th_rc = BDS_OK, th_err = hipSuccess;
+        th = std::thread([this, dst, off, nbytes, wait_carry] {
+            th_err = hipSetDevice(ctx->device);
+            if (th_err == hipSuccess && wait_carry) th_err = hipStreamWaitEvent(ld_stream, ev_carry, 0);  // nxt.buf is still being read
+            if (th_err != hipSuccess) return;
+            th_rc = load(off, nbytes, dst, ld_stream);
+            if (th_rc == BDS_OK) th_err = hipStreamSynchronize(ld_stream);
+        });
+    }
+    int join() {
+        if (th.joinable()) th.join();
+        if (th_rc) return th_rc;  // (the loader has set the message)
+        if (th_err != hipSuccess) {
+            const hipError_t e = th_err;
+            th_err = hipSuccess;
+            return fail(ctx, BDS_ERR_HIP, "loading the next piece of the IF record: %s", hipGetErrorString(e));
+        }
+        return BDS_OK;
+    }
+};
 
 // whole_file: load every byte (second attempt after a channel's reads left the window of the first)
 static int do_track(bds_ctx *ctx, const bds_settings *s, const RecordLoader &load, size_t n_bytes, int n_ch,
@@ -1270,12 +1384,57 @@ static int do_track(bds_ctx *ctx, const bds_settings *s, const RecordLoader &loa
     // start + n_epochs blocks at a code rate 2 % low (the reference streams blksize samples per epoch with fread,
     // tracking.m:237-240; a recording is usually far longer than msToProcess).  End-of-file is still judged against
     // the real file size (p.n_bytes).
+    // That window is held whole (one window) when it fits and does not exceed the resident limit; otherwise the record is
+    // STREAMED through a span of span_n samples that slides through two buffers (the epoch loop below).
+    const long long coeff = p.cplx ? 2 : 1;
+    // bounds of a block while the channel's code rate stays within 2 % of f: hi is the rule the window is sized with
+    auto blk_hi = [&](double f) { return (long long)((long)std::ceil((double)s->codeLength / (f * 0.98 / s->samplingFreq)) + 2); };
+    auto blk_lo = [&](double f) { return std::max(1LL, (long long)std::floor((double)s->codeLength / (f * 1.02 / s->samplingFreq)) - 2); };
+    bool any_live = false;
+    for (int c = 0; c < n_ch; ++c) any_live |= hs[c].active == 1;
+    bool stream = false;
+    using Span = SpanStream::Span;
+    Span cur, nxt;  // one window: cur is the window; streamed: the two span buffers, handed to a SpanStream below
+    long long span_n = 0;  // samples a span buffer holds
+    // margin of a streamed batch's plan, in worst-case blocks kept behind the start of a channel's last planned epoch: 1 is
+    // the window's own rule (n blocks at a code rate 2 % low fit); the guard of the update kernel catches a plan that was
+    // too tight, and the batch is repeated with the margin doubled
+    double margin = ctx->tune.trk_stream_margin >= 0 ? ctx->tune.trk_stream_margin : 1.0;
+    // one past the last sample the remaining epochs (k done) can touch
+    auto need_end = [&](const std::vector<ChanState> &v, int k) {
+        long long e = 0;
+        for (int c = 0; c < n_ch; ++c) {
+            if (v[c].active != 1) continue;
+            const long long B = blk_hi(v[c].codeFreq);
+            e = std::max(e, v[c].pos + (long long)(n_epochs - k - 1) * B + (long long)std::ceil(std::max(1.0, margin) * (double)B));
+        }
+        return std::min(e, p.n_bytes);
+    };
+    // epochs every live channel can take inside the span
+    auto plan = [&](const std::vector<ChanState> &v, const Span &sp, double m) {
+        long long n = n_epochs;
+        for (int c = 0; c < n_ch; ++c) {
+            if (v[c].active != 1) continue;
+            if (v[c].pos < sp.base) return 0LL;
+            if (sp.end >= p.n_bytes) continue;  // the span reaches the end of the file: a block past it is a short read
+            const long long B = blk_hi(v[c].codeFreq), Blo = blk_lo(v[c].codeFreq);
+            const long long per = m >= 1 ? B : Blo + (long long)(m * (double)(B - Blo));
+            const long long room = sp.end - v[c].pos - std::max(1LL, (long long)std::ceil(m * (double)B));
+            n = std::min(n, room < 0 ? 0LL : room / per + 1);
+        }
+        return n;
+    };
+    auto live_min_pos = [&](const std::vector<ChanState> &v) {
+        long long m = p.n_bytes;
+        for (int c = 0; c < n_ch; ++c)
+            if (v[c].active == 1) m = std::min(m, v[c].pos);
+        return m;
+    };
     {
-        const long long coeff = p.cplx ? 2 : 1;
         long long first = p.n_bytes, last = 0;
         for (int c = 0; c < n_ch; ++c) {
             if (!hs[c].active) continue;
-            const long blk_c = (long)std::ceil((double)s->codeLength / (hs[c].codeFreq * 0.98 / s->samplingFreq)) + 2;
+            const long blk_c = (long)blk_hi(hs[c].codeFreq);
             first = std::min(first, hs[c].pos);
             last = std::max(last, hs[c].pos + (long long)n_epochs * blk_c);
         }
@@ -1285,15 +1444,73 @@ static int do_track(bds_ctx *ctx, const bds_settings *s, const RecordLoader &loa
         p.base = first;
         p.win_end = last;
         const size_t wbytes = (size_t)((last - first) * coeff);
-        if (t.data_cap < wbytes || !t.d_data) {
+        stream = any_live && t.resident_limit && wbytes > t.resident_limit;
+        if (!stream && (t.data_cap < wbytes || !t.d_data || ctx->tune.trk_window_nomem)) {
             if (t.d_data) (void)hipFree(t.d_data), t.d_data = nullptr, t.data_cap = 0;
-            hipError_t e = hipMalloc((void **)&t.d_data, wbytes + kDataSlack);
-            if (e != hipSuccess)
-                return fail(ctx, BDS_ERR_NOMEM, "IF record window of %zu bytes does not fit in HBM: %s", wbytes, hipGetErrorString(e));
-            t.data_cap = std::max<size_t>(wbytes, 1);
+            hipError_t e = ctx->tune.trk_window_nomem ? hipErrorOutOfMemory : hipMalloc((void **)&t.d_data, wbytes + kDataSlack);
+            if (e != hipSuccess) {
+                (void)hipGetLastError();
+                if (!any_live)
+                    return fail(ctx, BDS_ERR_NOMEM, "IF record window of %zu bytes does not fit in HBM: %s", wbytes, hipGetErrorString(e));
+                stream = true;  // the record passes through HBM in pieces instead
+            } else {
+                t.data_cap = std::max<size_t>(wbytes, 1);
+            }
         }
-        if (wbytes && (rc = load((size_t)(first * coeff), wbytes, t.d_data))) return rc;
-        t.loaded_bytes = wbytes;
+        if (!stream) {
+            for (int8_t *&q : t.d_span)
+                if (q) (void)hipFree(q), q = nullptr;
+            t.span_cap = 0;
+            if (wbytes && (rc = load((size_t)(first * coeff), wbytes, t.d_data, st(ctx)))) return rc;
+            t.loaded_bytes = wbytes, t.pieces = 1, t.resident_max = wbytes, t.repeated = 0;
+            cur.buf = t.d_data, cur.base = first, cur.end = last;
+        } else {
+            if (t.d_data) (void)hipFree(t.d_data), t.d_data = nullptr, t.data_cap = 0;  // no stale window beside the span
+            // A span must hold, from the (16-sample aligned) smallest position, every channel's position plus one block
+            // at a code rate 2 % low, plus what the start of the NEXT span -- predicted at a code rate 2 % high while
+            // this one is in use -- can fall behind the channels in one epoch.
+            const long long base0 = live_min_pos(hs) & ~15LL;
+            long long need = 0, hi_max = 0, lo_min = p.n_bytes + 1;
+            for (int c = 0; c < n_ch; ++c) {
+                if (hs[c].active != 1) continue;
+                const long long B = blk_hi(hs[c].codeFreq);
+                need = std::max(need, std::min(hs[c].pos + B, p.n_bytes) - base0);
+                hi_max = std::max(hi_max, B), lo_min = std::min(lo_min, blk_lo(hs[c].codeFreq));
+            }
+            const long long min_half = (std::max(0LL, need) + std::max(0LL, hi_max - lo_min) + 16 + 15) & ~15LL;
+            const size_t min_limit = (size_t)(2 * min_half * coeff);
+            size_t limit = t.resident_limit;
+            if (!limit || wbytes <= limit) {  // no limit that applies: the window allocation failed
+                size_t fr = 0, tot = 0;
+                (void)hipMemGetInfo(&fr, &tot);
+                limit = std::max(min_limit, std::min<size_t>(fr / 2, (size_t)1 << 30));
+            } else if (limit < min_limit) {
+                return fail(ctx, BDS_ERR_ARG, "resident limit of %zu bytes is too small for these channels: the spread of their positions plus "
+                            "one block, in each of the two span buffers, needs at least %zu bytes", limit, min_limit);
+            }
+            span_n = (long long)(limit / (size_t)(2 * coeff)) & ~15LL;
+            const size_t cap = (size_t)(span_n * coeff);
+            if (t.span_cap != cap || !t.d_span[0] || !t.d_span[1]) {
+                for (int8_t *&q : t.d_span)
+                    if (q) (void)hipFree(q), q = nullptr;
+                t.span_cap = 0;
+                for (int8_t *&q : t.d_span) {
+                    hipError_t e = hipMalloc((void **)&q, cap + kDataSlack);
+                    if (e != hipSuccess) {
+                        (void)hipGetLastError();
+                        q = nullptr;
+                        return fail(ctx, BDS_ERR_NOMEM, "resident span of 2 x %zu bytes of the IF record does not fit in HBM: %s", cap, hipGetErrorString(e));
+                    }
+                }
+                t.span_cap = cap;
+            }
+            cur.buf = t.d_span[0], cur.base = base0, cur.end = base0;
+            nxt.buf = t.d_span[1];
+            cur.end = std::max(cur.base, std::min(cur.base + span_n, need_end(hs, 0)));
+            const size_t nb0 = (size_t)((cur.end - cur.base) * coeff);
+            if (nb0 && (rc = load((size_t)(cur.base * coeff), nb0, cur.buf, st(ctx)))) return rc;
+            t.loaded_bytes = nb0, t.pieces = 1, t.resident_max = nb0, t.repeated = 0;
+        }
     }
     // per-call device buffers, released on every exit path
     struct DevScope {
@@ -1349,7 +1566,6 @@ static int do_track(bds_ctx *ctx, const bds_settings *s, const RecordLoader &loa
     BDS_HIP(ctx, hipEventCreate(&ev1));
     scope.ev.push_back(ev1);
     BDS_HIP(ctx, hipEventRecord(ev0, st(ctx)));
-    const int8_t *data = t.d_data;
     dim3 gc(nblocks, n_ch);
     TrkOut *d_out = nullptr;  // the table of result arrays, for the correlate launches that carry the previous epoch's update
     BDS_HIP(ctx, hipMalloc((void **)&d_out, sizeof(TrkOut)));
@@ -1370,20 +1586,101 @@ static int do_track(bds_ctx *ctx, const bds_settings *s, const RecordLoader &loa
     };
     ChanState *st_final = d_st;  // where the state ends up
     RoctxRange rg_epochs("trk.epoch_loop");
-    for (int k = 0; k < n_epochs; ++k) {
-        if (fuse) {
-            const int cur = k & 1;
-            ChanState *st_in = d_st + (size_t)cur * n_ch, *st_out = d_st + (size_t)(cur ^ 1) * n_ch;
-            const double *part_prev = k > 0 ? d_part + (size_t)(cur ^ 1) * part_n : nullptr;
-            double *part_cur = d_part + (size_t)cur * part_n;
-            BDS_TRK_LAUNCH(k_trk_correlate, gc, (p.runs ? runs_lds_bytes(p.runs, p.prec) : 0), st(ctx), data, (const int8_t *)t.d_prim, p,
-                           (const ChanState *)st_in, st_out, part_prev, part_cur, nblocks, k, (const TrkOut *)d_out);
-            st_final = st_out;
-            if (k == n_epochs - 1) launch_update(st_final, part_cur, k);  // the last epoch's update has no next launch to ride on
-        } else {
-            BDS_TRK_LAUNCH(k_trk_correlate, gc, (p.runs ? runs_lds_bytes(p.runs, p.prec) : 0), st(ctx), data, (const int8_t *)t.d_prim, p,
-                           (const ChanState *)d_st, d_st, (const double *)nullptr, d_part, nblocks, k, (const TrkOut *)d_out);
-            launch_update(d_st, d_part, k);
+    // epochs k0 .. k0 + n - 1 on span `sp`, from the state in half `slot` of d_st; the state ends up at st_final.  The last
+    // epoch of a batch is closed by k_trk_update, the first one carries no update
+    auto run_batch = [&](const Span &sp, int k0, int n, int slot) {
+        p.base = sp.base, p.win_end = sp.end;
+        const int8_t *data = sp.buf;
+        for (int k = k0; k < k0 + n; ++k) {
+            if (fuse) {
+                const int curh = (slot + k - k0) & 1;
+                ChanState *st_in = d_st + (size_t)curh * n_ch, *st_out = d_st + (size_t)(curh ^ 1) * n_ch;
+                const double *part_prev = k > k0 ? d_part + (size_t)(curh ^ 1) * part_n : nullptr;
+                double *part_cur = d_part + (size_t)curh * part_n;
+                BDS_TRK_LAUNCH(k_trk_correlate, gc, (p.runs ? runs_lds_bytes(p.runs, p.prec) : 0), st(ctx), data, (const int8_t *)t.d_prim, p,
+                               (const ChanState *)st_in, st_out, part_prev, part_cur, nblocks, k, (const TrkOut *)d_out);
+                st_final = st_out;
+                if (k == k0 + n - 1) launch_update(st_final, part_cur, k);  // the last epoch's update has no next launch to ride on
+            } else {
+                ChanState *stp = d_st + (size_t)slot * n_ch;
+                BDS_TRK_LAUNCH(k_trk_correlate, gc, (p.runs ? runs_lds_bytes(p.runs, p.prec) : 0), st(ctx), data, (const int8_t *)t.d_prim, p,
+                               (const ChanState *)stp, stp, (const double *)nullptr, d_part, nblocks, k, (const TrkOut *)d_out);
+                launch_update(stp, d_part, k);
+                st_final = stp;
+            }
+        }
+    };
+    if (!stream) {
+        run_batch(cur, 0, n_epochs, 0);
+    } else {
+        // Streamed: batches of epochs on the resident span.  At a batch boundary the host reads the channel states back,
+        // moves on to the span whose tail the loader thread filled meanwhile (the overlap with the current span is carried
+        // device-to-device) and enqueues as many epochs as every live channel can take inside it.
+        SpanStream ss(ctx, t, load, st(ctx), ctx->stream2 ? (hipStream_t)ctx->stream2 : st(ctx), coeff, span_n);
+        ss.cur = cur, ss.nxt = nxt;
+        int slot = 0, k = 0;
+        std::vector<ChanState> h0;
+        while (k < n_epochs) {
+            bool live = false;
+            for (int c = 0; c < n_ch; ++c) live |= hs[c].active == 1;
+            if (!live) break;
+            const long long minp = live_min_pos(hs);
+            if (ss.pre_valid && minp >= ss.pre_nb && (rc = ss.move_to(ss.pre_nb, ss.pre_hi, true))) return rc;
+            long long n = plan(hs, ss.cur, margin);
+            if (n == 0) {  // no prefetched span, or the channels are not where it was predicted: a span from their smallest position
+                const long long nb = minp & ~15LL, hi = std::max(nb, std::min(nb + span_n, need_end(hs, k)));
+                ss.pre_valid = false;
+                if (nb != ss.cur.base || hi > ss.cur.end) {
+                    if ((rc = ss.move_to(nb, hi, false))) return rc;
+                    n = plan(hs, ss.cur, margin);
+                }
+                if (n == 0) {
+                    long long need = 0;
+                    for (int c = 0; c < n_ch; ++c)
+                        if (hs[c].active == 1)
+                            need = std::max(need, hs[c].pos - nb + (long long)std::ceil(std::max(1.0, margin) * (double)blk_hi(hs[c].codeFreq)));
+                    return fail(ctx, BDS_ERR_ARG, "epoch %d: the resident span of %lld bytes (half the resident limit) cannot hold the channels' spread of positions "
+                                "plus a block any more: it needs %lld bytes", k + 1, (long long)(span_n * coeff), (long long)(((need + 31) & ~15LL) * coeff));
+                }
+            }
+            n = std::min<long long>(n, n_epochs - k);
+            const long long want_end = need_end(hs, k);
+            if (!ss.pre_valid && k + n < n_epochs && ss.cur.end < want_end) {
+                // the next span starts where the slowest channel is after the epochs a plan at the regular margin gives this
+                // span, at the shortest blocks a code rate within 2 % allows: never past a channel, and still right when
+                // this batch has to be repeated
+                const long long n_safe = std::min(n, plan(hs, ss.cur, std::max(margin, 1.0)));
+                long long nb = p.n_bytes;
+                for (int c = 0; c < n_ch; ++c)
+                    if (hs[c].active == 1) nb = std::min(nb, hs[c].pos + n_safe * blk_lo(hs[c].codeFreq));
+                nb = std::max(ss.cur.base, nb & ~15LL);
+                const long long hi = std::min(nb + span_n, want_end);
+                if (nb <= ss.cur.end && hi > ss.cur.end) ss.predict(nb, hi);
+            }
+            h0 = hs;
+            run_batch(ss.cur, k, (int)n, slot);
+            // (from here to join() the loader may report an error of its own: codes are kept and reported after it)
+            const hipError_t e_launch = hipGetLastError();
+            if (e_launch == hipSuccess) ss.start_load();
+            const hipError_t e_copy = e_launch == hipSuccess ? hipMemcpyAsync(hs.data(), st_final, sizeof(ChanState) * n_ch, hipMemcpyDeviceToHost, st(ctx)) : e_launch;
+            const hipError_t e_sync = e_copy == hipSuccess ? hipStreamSynchronize(st(ctx)) : e_copy;
+            if ((rc = ss.join())) return rc;
+            BDS_HIP(ctx, e_sync);
+            bool left = false;
+            for (int c = 0; c < n_ch; ++c) left |= hs[c].active == -2;
+            if (left) {
+                // a block reached past the span (or a channel fell behind it): the batch runs again from the state it
+                // started with -- the kernels are deterministic, what it rewrites is identical -- with a wider margin
+                t.repeated += 1;
+                margin = margin < 1 ? 1.0 : margin * 2;
+                if (margin > 64) return fail(ctx, BDS_ERR_HIP, "bds_track: epoch %d: a channel keeps leaving the resident span of the record", k + 1);
+                hs = h0;
+                BDS_HIP(ctx, hipMemcpyAsync(d_st + (size_t)slot * n_ch, hs.data(), sizeof(ChanState) * n_ch, hipMemcpyHostToDevice, st(ctx)));
+                BDS_HIP(ctx, hipStreamSynchronize(st(ctx)));
+                continue;
+            }
+            slot = (int)((st_final - d_st) / n_ch);
+            k += (int)n;
         }
     }
     BDS_HIP(ctx, hipGetLastError());
@@ -1397,7 +1694,7 @@ static int do_track(bds_ctx *ctx, const bds_settings *s, const RecordLoader &loa
     ctx->timing.n_pairs = n_epochs;
     for (int c = 0; c < n_ch; ++c)
         if (hs[c].active == -2) {  // a channel read past the loaded window (code rate > 2 % low): redo with the whole record
-            if (whole_file) return fail(ctx, BDS_ERR_HIP, "bds_track: channel %d left the loaded record", c + 1);
+            if (whole_file || stream) return fail(ctx, BDS_ERR_HIP, "bds_track: channel %d left the loaded record", c + 1);
             scope.release();  // the retry allocates its own result arrays: do not hold this attempt's beside them
             return do_track(ctx, s, load, n_bytes, n_ch, channel, out, true);
         }
@@ -1463,8 +1760,8 @@ using namespace bds;
 extern "C" int bds_track_mem(bds_ctx *ctx, const bds_settings *s, const int8_t *file_bytes, size_t n_bytes, int n_ch,
                              const bds_channel *channel, bds_track_out *out) {
     if (!ctx || !file_bytes) return BDS_ERR_ARG;
-    const RecordLoader load = [&](size_t off, size_t n, int8_t *dst) -> int {
-        BDS_HIP(ctx, hipMemcpyAsync(dst, file_bytes + off, n, hipMemcpyHostToDevice, (hipStream_t)ctx->stream));
+    const RecordLoader load = [&](size_t off, size_t n, int8_t *dst, hipStream_t stream) -> int {
+        BDS_HIP(ctx, hipMemcpyAsync(dst, file_bytes + off, n, hipMemcpyHostToDevice, stream));
         return BDS_OK;
     };
     return do_track(ctx, s, load, n_bytes, n_ch, channel, out);
@@ -1489,7 +1786,7 @@ extern "C" int bds_track(bds_ctx *ctx, const bds_settings *s, const char *path, 
     BDS_HIP(ctx, hipSetDevice(ctx->device));
     // the window of the record the channels can touch, staged through pinned memory in 256 MiB pieces
     const size_t piece = 256u << 20;
-    const RecordLoader load = [&](size_t off, size_t n, int8_t *dst) -> int {
+    const RecordLoader load = [&](size_t off, size_t n, int8_t *dst, hipStream_t stream) -> int {
         if (!guard.pin && hipHostMalloc(&guard.pin, std::min<size_t>(piece, (size_t)sz), 0) != hipSuccess)
             return fail(ctx, BDS_ERR_NOMEM, "pinned staging buffer");
         if (fseeko(f, (off_t)off, SEEK_SET)) return fail(ctx, BDS_ERR_IO, "seek in %s failed", path);
@@ -1497,7 +1794,8 @@ extern "C" int bds_track(bds_ctx *ctx, const bds_settings *s, const char *path, 
         while (done < n) {
             const size_t m = std::min(piece, n - done);
             if (fread(guard.pin, 1, m, f) != m) return fail(ctx, BDS_ERR_IO, "short read on %s", path);
-            const hipError_t e = hipMemcpy(dst + done, guard.pin, m, hipMemcpyHostToDevice);
+            hipError_t e = hipMemcpyAsync(dst + done, guard.pin, m, hipMemcpyHostToDevice, stream);
+            if (e == hipSuccess) e = hipStreamSynchronize(stream);  // the staging buffer is filled again next
             if (e != hipSuccess) return fail(ctx, BDS_ERR_HIP, "H2D copy: %s", hipGetErrorString(e));
             done += m;
         }
@@ -1508,6 +1806,22 @@ extern "C" int bds_track(bds_ctx *ctx, const bds_settings *s, const char *path, 
 
 extern "C" long long bds_track_loaded_bytes(bds_ctx *ctx) {
     return (ctx && ctx->trk) ? (long long)ctx->trk->loaded_bytes : 0;
+}
+
+extern "C" int bds_track_set_resident_limit(bds_ctx *ctx, size_t bytes) {
+    if (!ctx) return BDS_ERR_ARG;
+    if (!ctx->trk) ctx->trk = new TrackState();
+    ctx->trk->resident_limit = bytes;
+    return BDS_OK;
+}
+
+extern "C" int bds_track_stream_info(bds_ctx *ctx, int32_t *pieces, long long *resident_max_bytes, int32_t *repeated_batches) {
+    if (!ctx) return BDS_ERR_ARG;
+    const TrackState *t = ctx->trk;
+    if (pieces) *pieces = t ? t->pieces : 0;
+    if (resident_max_bytes) *resident_max_bytes = t ? (long long)t->resident_max : 0;
+    if (repeated_batches) *repeated_batches = t ? t->repeated : 0;
+    return BDS_OK;
 }
 
 extern "C" int bds_track_correlate(bds_ctx *ctx, const bds_settings *s, const int8_t *file_bytes, size_t n_bytes,

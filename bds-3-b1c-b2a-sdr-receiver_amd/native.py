@@ -84,7 +84,7 @@ class AcqJob(C.Structure):
 EXPORTS = [
     "bds_create", "bds_destroy", "bds_reload_tuning", "bds_last_error", "bds_device_name", "bds_abi_check", "bds_build_flags", "bds_gen_code", "bds_acquire",
     "bds_acq_load", "bds_acq_prepare", "bds_acq_run", "bds_acq_set_pair_budget_gb", "bds_resample_plan", "bds_fir1_bandpass", "bds_frame_sync", "bds_sync_pattern", "bds_unpack_cplx", "bds_unpack_cplx_file", "bds_acq_grid", "bds_acq_peaks", "bds_acq_candidates", "bds_acq_coherent_sums", "bds_get_timing",
-    "bds_track", "bds_track_mem", "bds_track_loaded_bytes", "bds_track_correlate", "bds_track_colon", "bds_calc_loop_coef", "bds_calc_loop_coef_carr",
+    "bds_track", "bds_track_mem", "bds_track_loaded_bytes", "bds_track_set_resident_limit", "bds_track_stream_info", "bds_track_correlate", "bds_track_colon", "bds_calc_loop_coef", "bds_calc_loop_coef_carr",
     "bds_calc_weighing_factor", "bds_pre_run", "bds_pre_run_device", "bds_acquire_track",
     "bds_multi_create", "bds_multi_destroy", "bds_multi_last_error", "bds_multi_size", "bds_multi_ctx",
     "bds_multi_rccl_ranks", "bds_acquire_multi", "bds_shard_jobs", "bds_acq_job_cost",
@@ -150,6 +150,10 @@ def lib():
     L.bds_track.argtypes = [vp, SP, C.c_char_p, i32, C.POINTER(Channel), C.POINTER(TrackOut)]
     L.bds_track_mem.restype = i32
     L.bds_track_mem.argtypes = [vp, SP, i8p, sz, i32, C.POINTER(Channel), C.POINTER(TrackOut)]
+    if hasattr(L, "bds_track_set_resident_limit"):  # (a build of an older commit, loaded through BDS_LIB_PATH for an A/B run, has no streamed mode)
+        L.bds_track_set_resident_limit.restype, L.bds_track_set_resident_limit.argtypes = i32, [vp, sz]
+        L.bds_track_stream_info.restype = i32
+        L.bds_track_stream_info.argtypes = [vp, _IP, C.POINTER(C.c_longlong), _IP]
     L.bds_track_correlate.restype = i32
     L.bds_track_correlate.argtypes = [vp, SP, i8p, sz, i32, _IP, _DP, _DP]
     L.bds_track_colon.restype, L.bds_track_colon.argtypes = i32, [vp, i32, _DP, _DP, _DP, _IP, _DP, _DP, _IP]
@@ -578,8 +582,27 @@ class Context:
         return (carr, cph, pm, det), ch, arrays
 
     def track_loaded_bytes(self) -> int:
-        """Bytes of the record the last track() call copied to HBM (the window the channels can touch)."""
+        """Bytes of the record the last track() call copied host-to-device: the window the channels can touch; for a streamed
+        run the total over its pieces, which is about that window."""
         return int(self._lib.bds_track_loaded_bytes(self._h))
+
+    def track_set_resident_limit(self, n_bytes: int) -> None:
+        """bds_track_set_resident_limit: at most `n_bytes` of the IF record are resident in HBM in the tracking calls that
+        follow on this context -- a larger window is streamed through in pieces, with identical results.  0 = no limit (the
+        default: one window when it can be allocated, streamed when it cannot)."""
+        self._check(self._lib.bds_track_set_resident_limit(self._h, int(n_bytes)))
+        self._track_limit = int(n_bytes)
+
+    def track_resident_limit(self) -> int:
+        """The limit set with track_set_resident_limit (0: none)."""
+        return getattr(self, "_track_limit", 0)
+
+    def track_stream_info(self) -> dict:
+        """bds_track_stream_info of the last tracking call: `pieces` loaded (1 for a one-window run), `resident_max_bytes` of
+        the record in HBM at a time, `repeated_batches` run again because a block left the resident span."""
+        pieces, rep, res = C.c_int32(0), C.c_int32(0), C.c_longlong(0)
+        self._check(self._lib.bds_track_stream_info(self._h, C.byref(pieces), C.byref(res), C.byref(rep)))
+        return {"pieces": int(pieces.value), "resident_max_bytes": int(res.value), "repeated_batches": int(rep.value)}
 
     def track_correlate(self, settings, file_bytes, prns, state6):
         cs = pack_settings(settings)

@@ -10,6 +10,7 @@ per-channel structs with exactly the field set the reference variant creates
 """
 from __future__ import annotations
 
+import contextlib
 import os
 from types import SimpleNamespace
 
@@ -62,7 +63,24 @@ def field_set(settings, mode):
     return n, m, ep, cn, pilot
 
 
-def tracking(fid, channel, settings, mode=None, device: int = 0):
+@contextlib.contextmanager
+def _resident_limit(ctx, resident_limit):
+    """The context's resident limit set to `resident_limit` bytes for one call (None: left as it is)."""
+    if resident_limit is None:
+        yield
+        return
+    before = ctx.track_resident_limit()
+    ctx.track_set_resident_limit(resident_limit)
+    try:
+        yield
+    finally:
+        ctx.track_set_resident_limit(before)
+
+
+def tracking(fid, channel, settings, mode=None, device: int = 0, resident_limit=None):
+    """resident_limit: bytes of the IF record that may be resident in HBM during this call -- a larger window is streamed
+    through in pieces, bit-identical results (bds_track_set_resident_limit; 0 = no limit).  None leaves the context's
+    setting alone: by default a window is held whole when it can be allocated and streamed when it cannot."""
     mode = _mode(settings, mode)
     s = settings.copy() if hasattr(settings, "copy") else settings
     if mode in ("NB", "WB") and str(settings.signal).upper() != "B1C":
@@ -82,7 +100,8 @@ def tracking(fid, channel, settings, mode=None, device: int = 0):
         s = settings.copy(pilotTRKflag=0)
     if mode == "WB" and int(s.pilotTRKflag) != 2:  # WB_tracking.m:78 only tests == 2
         s = settings.copy(pilotTRKflag=0)
-    arr = ctx.track(s, source, channel, n, m, ep + cn)
+    with _resident_limit(ctx, resident_limit):
+        arr = ctx.track(s, source, channel, n, m, ep + cn)
     sig_name = "B2a_CNo" if mode == "B2A" else "B1C_CNo"
     out = []
     for c in range(len(channel)):
@@ -114,11 +133,12 @@ def _results(arr, channel_prns, n_ch, ep, cn, mode):
     return out
 
 
-def acquire_track(long_signal, path, settings, device: int = 0):
+def acquire_track(long_signal, path, settings, device: int = 0, resident_limit=None):
     """The acquisition -> preRun -> tracking section of postProcessing.m (B2a/postProcessing.m:100-123,
     B1C/postProcessing.m:105-143) as ONE native call: bds_acquire_track runs the search, allocates the channels with a
     device kernel (bds_pre_run_device) and tracks the record at `path` with the variant the settings select, without
-    returning to the host language in between.  Returns (acqResults, channel, trackResults)."""
+    returning to the host language in between.  Returns (acqResults, channel, trackResults).
+    resident_limit: as in tracking()."""
     mode = _mode(settings, None)
     n, m, ep, cn, pilot = field_set(settings, mode)
     x = np.asarray(long_signal)
@@ -128,7 +148,8 @@ def acquire_track(long_signal, path, settings, device: int = 0):
         pairs[0::2], pairs[1::2] = x.real.astype(np.int8), x.imag.astype(np.int8)
         x = pairs
     ctx = get_context(device)
-    (carr, cph, pm, det), ch, arr = ctx.acquire_track(settings, np.ascontiguousarray(x, dtype=np.int8), is_complex, path, n, m, ep + cn)
+    with _resident_limit(ctx, resident_limit):
+        (carr, cph, pm, det), ch, arr = ctx.acquire_track(settings, np.ascontiguousarray(x, dtype=np.int8), is_complex, path, n, m, ep + cn)
     acq = SimpleNamespace(carrFreq=carr, codePhase=cph, peakMetric=pm)
     channel = [SimpleNamespace(PRN=int(c.PRN), acquiredFreq=float(c.acquiredFreq), codePhase=float(c.codePhase),
                                codeFreq=float(c.codeFreq), status=chr(c.status)) for c in ch]

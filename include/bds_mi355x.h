@@ -304,10 +304,29 @@ BDS_API int bds_track(bds_ctx *ctx, const bds_settings *s, const char *path, int
 BDS_API int bds_track_mem(bds_ctx *ctx, const bds_settings *s, const int8_t *file_bytes,
                           size_t n_bytes, int n_ch, const bds_channel *channel,
                           bds_track_out *out);
-/* Bytes of the IF record the last bds_track / bds_track_mem call copied to HBM: only the window the channels can
- * touch (earliest start sample .. latest start + msToProcess at a code rate 2 % low) is loaded, so a recording far
- * longer than msToProcess (or than HBM) tracks fine; end-of-file is still judged against the real file size. */
+/* Bytes of the IF record the last bds_track / bds_track_mem call copied host-to-device.  One window (the default when it
+ * fits): only the window the channels can touch (earliest start sample .. latest start + msToProcess at a code rate 2 % low)
+ * is loaded, so a recording far longer than msToProcess tracks fine.  Streamed (below): the total over all pieces, which is
+ * about that window -- what consecutive pieces share moves device-to-device and is not loaded again.  (Bytes are counted when
+ * they are copied.  A piece is loaded ahead to where the channels are predicted to be; should a channel's code rate leave the
+ * +-2 % the prediction allows, that piece is discarded and its part of the record is loaded, and counted, a second time.)
+ * End-of-file is always judged against the real file size. */
 BDS_API long long bds_track_loaded_bytes(bds_ctx *ctx);
+/* Streamed tracking.  A window that cannot be allocated, or that is larger than the resident limit, is not held whole: the
+ * record passes through a resident span in HBM in successive pieces, the next piece loading (host thread, second stream)
+ * while the epochs of the current one run, so a run may be as long as the file.  The kernels, the samples, the order of the
+ * partial sums and the loop state are those of the one-window path: the results are the same bit for bit.
+ * bds_track_set_resident_limit: at most `bytes` of the record are resident (two span buffers of half that each) in the
+ *   bds_track / bds_track_mem / bds_acquire_track calls that follow on this context; 0 (the default) = no limit: one window
+ *   when its allocation succeeds, streamed when it fails.  A limit at or above the window changes nothing.  A limit too
+ *   small for the channels' spread of positions plus one block per span buffer makes the tracking call return BDS_ERR_ARG
+ *   with the minimum in the message.
+ * bds_track_stream_info: of the last tracking call, the pieces loaded (1 for a one-window run), the most bytes of the record
+ *   that were resident at a time, and the batches of epochs that were run again because a block left the resident span (a
+ *   code rate more than 2 % off: the batch restarts from the state it began with, so the results do not change).  Any
+ *   pointer may be NULL. */
+BDS_API int bds_track_set_resident_limit(bds_ctx *ctx, size_t bytes);
+BDS_API int bds_track_stream_info(bds_ctx *ctx, int32_t *pieces, long long *resident_max_bytes, int32_t *repeated_batches);
 /* Open-loop check entry: one correlate-and-dump epoch per channel with the caller's
  * NCO state (no loop update).  state: per channel {sample offset (0-based), blksize,
  * remCodePhase, codeFreq, remCarrPhase, carrFreq}; sums: [n_ch][18] raw correlator
