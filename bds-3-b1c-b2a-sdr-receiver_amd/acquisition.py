@@ -36,7 +36,19 @@ class AcqResults(SimpleNamespace):
     """acqResults struct (B2a/acquisition.m:161-165)."""
 
 
+def packed_bytes(long_signal, field="longSignal"):
+    """The uint8 bytes of a packed record (settings.fileType 3: two 2+2-bit I/Q samples per byte, B2a/include/unpack_cplx.m:18-30).
+    Sample values -- real or complex -- are refused: the packed format carries bytes, as fread(fid, n, 'uint8=>uint8') returns them."""
+    a = np.asarray(long_signal)
+    if a.dtype != np.uint8:
+        raise ValueError(f"{field} must be a uint8 array of packed bytes when settings.fileType is 3 (two 2+2-bit I/Q samples per "
+                         f"byte), not {a.dtype}: unpacked samples go with fileType 1 or 2")
+    return np.ascontiguousarray(a).reshape(-1)
+
+
 def _as_int8(long_signal, settings):
+    if int(getattr(settings, "fileType", 1)) == 3:
+        return packed_bytes(long_signal), 2
     a = np.asarray(long_signal)
     if np.iscomplexobj(a):
         # fileType 2: data = I + 1i*Q (B2a/postProcessing.m:92-96)

@@ -88,6 +88,8 @@ struct AcqState {
     // device buffers
     int8_t *d_sig = nullptr;        // int8 record as loaded (pairs when complex)
     size_t sig_cap = 0;
+    uint8_t *d_packed = nullptr;    // packed bytes of a fileType-3 block, before they are unpacked into d_sig
+    size_t packed_cap = 0;
     double *d_sig64 = nullptr;      // conditioned f64 block of the resampling branch (acquisition.m:56-124)
     size_t sig64_cap = 0;
     double *d_ffa = nullptr, *d_ffb = nullptr, *d_fir = nullptr;  // filtfilt work buffers, fir1 taps
@@ -206,7 +208,7 @@ struct AcqState {
 void acq_state_free(AcqState *a) {
     if (!a) return;
     plan_free(a->plan);
-    for (void *p : {(void *)a->d_sig, (void *)a->d_prim, (void *)a->d_Cs, (void *)a->d_Xs, (void *)a->d_Bw, (void *)a->d_pfa_coef,
+    for (void *p : {(void *)a->d_sig, (void *)a->d_packed, (void *)a->d_prim, (void *)a->d_Cs, (void *)a->d_Xs, (void *)a->d_Bw, (void *)a->d_pfa_coef,
                     (void *)a->d_recs, (void *)a->d_rowmax, (void *)a->d_rowarg, (void *)a->d_jobs, (void *)a->d_codes,
                     (void *)a->d_jobout, (void *)a->d_sig64, (void *)a->d_ffa, (void *)a->d_ffb, (void *)a->d_fir, (void *)a->d_cells, (void *)a->d_mcells,
                     (void *)a->d_extra, (void *)a->d_extra_count, (void *)a->d_cellmax, (void *)a->d_lb, (void *)a->d_ref_zero,
@@ -700,8 +702,10 @@ extern "C" int bds_acq_load(bds_ctx *ctx, const bds_settings *s_in, const int8_t
     if (int rc0 = check_settings(ctx, *s_in)) return rc0;  // (the resampling band edges are only visible here)
     bds_settings eff;
     const bds_settings *s = effective(s_in, &eff);
-    // n_samples counts complex samples when is_complex: `samples` then holds 2*n_samples int8 (I,Q pairs)
-    const bool cplx = is_complex != 0;
+    // n_samples counts complex samples when is_complex: `samples` then holds 2*n_samples int8 (I,Q pairs), or, is_complex == 2,
+    // ceil(n_samples / 2) packed bytes (fileType 3)
+    if (is_complex < 0 || is_complex > 2) return fail(ctx, BDS_ERR_ARG, "is_complex must be 0 (real), 1 (I/Q int8 pairs) or 2 (packed 2+2-bit I/Q)");
+    const bool cplx = is_complex != 0, packed = is_complex == 2;
     if (ctx->acq && ctx->acq->fell_back) {  // a new block: back to the default storage and kernels (acq_configure re-derives them)
         ctx->acq->fell_back = false;
         ctx->acq->no_small = false;
@@ -713,8 +717,21 @@ extern "C" int bds_acq_load(bds_ctx *ctx, const bds_settings *s_in, const int8_t
     const ResamplePlan r = resample_plan(*s_in);
     BDS_HIP(ctx, hipSetDevice(ctx->device));
     const size_t nb = n_samples * (cplx ? 2 : 1);
-    if ((rc = ensure(ctx, &a.d_sig, &a.sig_cap, nb + 16))) return rc;  // (+16: k_corr reads whole dwords, bds_acq_corr.h)
-    BDS_HIP(ctx, hipMemcpyAsync(a.d_sig, samples, nb, hipMemcpyHostToDevice, st(ctx)));
+    const size_t npk = packed ? (n_samples + 1) / 2 : 0;  // packed bytes: each becomes four int8 (the last pair is unused when n_samples is odd)
+    if ((rc = ensure(ctx, &a.d_sig, &a.sig_cap, std::max(nb, 4 * npk) + 16))) return rc;  // (+16: k_corr reads whole dwords, bds_acq_corr.h)
+    std::vector<int8_t> h_unpacked;
+    if (packed) {
+        // The bytes go to the device as they are; the search, and the host's sums below, work on the int8 I/Q block unpacked there
+        if ((rc = ensure(ctx, &a.d_packed, &a.packed_cap, npk))) return rc;
+        BDS_HIP(ctx, hipMemcpyAsync(a.d_packed, samples, npk, hipMemcpyHostToDevice, st(ctx)));
+        if ((rc = unpack_cplx_device(ctx, a.d_packed, npk, a.d_sig))) return rc;
+        h_unpacked.resize(nb);
+        BDS_HIP(ctx, hipMemcpyAsync(h_unpacked.data(), a.d_sig, nb, hipMemcpyDeviceToHost, st(ctx)));
+        BDS_HIP(ctx, hipStreamSynchronize(st(ctx)));
+        samples = h_unpacked.data();
+    } else {
+        BDS_HIP(ctx, hipMemcpyAsync(a.d_sig, samples, nb, hipMemcpyHostToDevice, st(ctx)));
+    }
     a.cplx = cplx;
     a.rs = r;
     long n_eff = (long)n_samples;

@@ -59,6 +59,15 @@ __global__ __launch_bounds__(256) void k_unpack_cplx(const uint8_t *__restrict__
 
 static hipStream_t st(bds_ctx *ctx) { return (hipStream_t)ctx->stream; }
 
+// device to device on the context's stream: n_bytes packed bytes -> 4 n_bytes int8 (I, Q pairs); d_out is dword-aligned
+int unpack_cplx_device(bds_ctx *ctx, const uint8_t *d_in, size_t n_bytes, int8_t *d_out) {
+    if (!n_bytes) return BDS_OK;
+    hipLaunchKernelGGL(k_unpack_cplx, dim3((unsigned)std::min<size_t>(8192, (n_bytes + 255) / 256)), dim3(256), 0, st(ctx), d_in, n_bytes,
+                       reinterpret_cast<uint32_t *>(d_out));
+    BDS_HIP(ctx, hipGetLastError());
+    return BDS_OK;
+}
+
 }  // namespace bds
 
 using namespace bds;
@@ -149,11 +158,7 @@ extern "C" int bds_unpack_cplx(bds_ctx *ctx, const uint8_t *in, size_t n_bytes, 
     hipError_t e = hipMalloc((void **)&d_in, n_bytes);
     if (e == hipSuccess) e = hipMalloc((void **)&d_out, 4 * n_bytes);
     if (e == hipSuccess) e = hipMemcpyAsync(d_in, in, n_bytes, hipMemcpyHostToDevice, st(ctx));
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(k_unpack_cplx, dim3((unsigned)std::min<size_t>(8192, (n_bytes + 255) / 256)), dim3(256), 0, st(ctx),
-                           (const uint8_t *)d_in, n_bytes, d_out);
-        e = hipGetLastError();
-    }
+    if (e == hipSuccess && unpack_cplx_device(ctx, d_in, n_bytes, reinterpret_cast<int8_t *>(d_out))) e = hipErrorLaunchFailure;
     if (e == hipSuccess) e = hipMemcpyAsync(out, d_out, 4 * n_bytes, hipMemcpyDeviceToHost, st(ctx));
     if (e == hipSuccess) e = hipStreamSynchronize(st(ctx));
     if (d_in) (void)hipFree(d_in);

@@ -63,7 +63,8 @@ static constexpr int kUpdScratch = (1 + kUpdGroups) * kNSums * 8 + 48 + (int)siz
 struct TrkParams {
     int mode;        // BDS_TRACK_*
     int pilot;       // pilot correlators on
-    int cplx;        // fileType 2: the record is interleaved I/Q int8 pairs (tracking.m:132-136,242-246)
+    int cplx;        // sample format (kFmt*): fileType 2, the record is interleaved I/Q int8 pairs (tracking.m:132-136,242-246);
+                     // fileType 3, two 2+2-bit I/Q samples per byte (unpack_cplx.m:18-30)
     int chunk;       // samples per correlate workgroup
     int runs;        // 1: run-based correlator (correlate_runs), chunk = kTrkThreads * 8 or * 16
     int prec;        // numerics of the run-based correlator's carrier wipe-off and prefix sums (Tuning::trk_prec)
@@ -72,11 +73,25 @@ struct TrkParams {
     double fs, inv_fs;
     double spacing;  // dllCorrelatorSpacing (earlyLateSpc)
     double tau1, tau2, pdi, pf1, pf2, pf3, factor;
-    long long n_bytes;  // samples in the record: file bytes / dataAdaptCoeff
+    long long n_bytes;  // samples in the record: file bytes / dataAdaptCoeff (packed: 2 per byte)
     long long base;     // first sample of the record held in HBM (only the window the channels can touch is loaded;
                         // streamed: the resident span, which moves between launches)
     long long win_end;  // one past the last sample held
 };
+
+// Sample formats of the IF record.  Packed (the input of B2a/include/unpack_cplx.m:18-30): complex sample n is nibble n & 1 of
+// byte n >> 1, low nibble first; per nibble bit 0 / 1 = I / Q negative, bit 2 / 3 = |I| / |Q| is 3 (else 1).
+enum : int { kFmtReal = 0, kFmtIQ = 1, kFmtPacked = 2 };
+__host__ __device__ constexpr int fmt_align(int fmt) { return fmt == kFmtPacked ? 32 : 16; }  // samples: 16 bytes at least
+// bytes of n samples (packed: n even -- window and span bounds are kept even, the file itself holds whole bytes)
+__host__ __device__ constexpr long long fmt_bytes(int fmt, long long n) { return fmt == kFmtPacked ? n / 2 : fmt == kFmtIQ ? n * 2 : n; }
+// one packed byte -> the int8 quadruple (I1, Q1, I2, Q2) unpack_cplx writes for it, without a branch: magnitudes 1 | 2 bit,
+// then two's complement in every byte whose sign bit is set ((m ^ 0xff) + 1 never carries out of a byte for m = 1, 3)
+__device__ __forceinline__ uint32_t iq_of_packed(uint32_t b) {
+    const uint32_t sg = (b & 1u) | ((b & 2u) << 7) | ((b & 0x10u) << 12) | ((b & 0x20u) << 19);
+    const uint32_t mg = 0x01010101u | ((b & 4u) >> 1) | ((b & 8u) << 6) | ((b & 0x40u) << 11) | ((b & 0x80u) << 18);
+    return (mg ^ (sg * 0xffu)) + sg;
+}
 
 struct TrkOut {  // device arrays [n_ch][n_epochs]
     double *absoluteSample, *codeFreq, *carrFreq, *I_P, *I_E, *I_L, *Q_E, *Q_P, *Q_L;
@@ -183,7 +198,8 @@ __device__ __forceinline__ void correlate_slice(const int8_t *__restrict__ data,
         sincospi(2.0 * (dcyc - floor(dcyc)), &wi, &wr);
     }
     int it = 0;
-    const int8_t *__restrict__ dwin = data - (p.base * (p.cplx ? 2 : 1));  // data[] starts at sample p.base of the record
+    // data[] starts at sample p.base of the record (packed: p.base is even)
+    const int8_t *__restrict__ dwin = p.cplx == kFmtPacked ? data - (p.base >> 1) : data - (p.base * (p.cplx ? 2 : 1));
     // chunk k0 .. k0+chunk of the block, then (only when blksize outgrew the grid the call was sized for:
     // a code rate more than 2 % below the slowest channel's initial one) every k_stride-th chunk after it
     for (long k0 = k0_first; k0 < g.blk; k0 += k_stride) {
@@ -191,7 +207,12 @@ __device__ __forceinline__ void correlate_slice(const int8_t *__restrict__ data,
     for (int k = (int)k0 + (int)threadIdx.x; k < (int)k1; k += (int)blockDim.x) {  // blksize < 2^31
         float raw, raw_q = 0.f;
         BDS_DASSERT(g.pos + k >= p.base && g.pos + k < p.win_end);  // inside the window of the record held in HBM
-        if (p.cplx) {  // rawSignal = data(1:2:end) + 1i*data(2:2:end)  (tracking.m:242-246)
+        if (p.cplx == kFmtPacked) {  // nibble (pos + k) & 1 of byte (pos + k) >> 1
+            const long long n = g.pos + k;
+            const uint32_t v = iq_of_packed(((uint32_t)(uint8_t)dwin[n >> 1] >> (4 * (int)(n & 1))) & 15u);
+            raw = (float)(int8_t)(v & 0xffu);
+            raw_q = (float)(int8_t)(v >> 8);
+        } else if (p.cplx) {  // rawSignal = data(1:2:end) + 1i*data(2:2:end)  (tracking.m:242-246)
             const char2 v = reinterpret_cast<const char2 *>(dwin)[g.pos + k];
             raw = (float)v.x;
             raw_q = (float)v.y;
@@ -346,7 +367,7 @@ __device__ __forceinline__ double lane_f64(double v, int l) {  // broadcast of l
 // The waves of a workgroup work independently (wave w on samples k0 + w 64 SEG .. of each chunk, its own LDS
 // slice, no workgroup barrier before the final reduction): the kernel is bound by latency -- HBM reads,
 // dependent f64 evaluations -- and independent waves hide it where barrier-separated phases cannot.
-template <int MODE, int SEG, bool CPLX, int PREC>
+template <int MODE, int SEG, int FMT, int PREC>
 __device__ __forceinline__ void correlate_runs(const int8_t *__restrict__ data, const int8_t *__restrict__ prim_d,
                                                const int8_t *__restrict__ prim_p, const TrkParams &p,
                                                const EpochGeom &g, long k0_first, long k_stride, bool pilot, double *sums) {
@@ -374,9 +395,18 @@ __device__ __forceinline__ void correlate_runs(const int8_t *__restrict__ data, 
     epoch_colons<(MODE != BDS_TRACK_B2A)>(g.rem, g.step, p.spacing, g.blk, cv3);
     const double two_pi = 6.283185307179586476925286766559;
     const double cyc0 = g.remCarr / two_pi;
+    constexpr bool CPLX = FMT != kFmtReal;
     constexpr int coeff = CPLX ? 2 : 1;
     constexpr int nwd = CPLX ? 2 * NWD : NWD;  // dwords of a segment
-    const int8_t *__restrict__ dwin = data - p.base * coeff;
+    constexpr int nrd = FMT == kFmtPacked ? SEG / 8 : nwd;  // ... as the record holds it (packed: SEG / 2 bytes)
+    const int8_t *__restrict__ dwin = FMT == kFmtPacked ? data - (p.base >> 1) : data - p.base * coeff;  // (packed: p.base is even)
+    // address of the byte that holds sample pos + kb
+    auto seg_addr = [&](long kb) {
+        if constexpr (FMT == kFmtPacked)
+            return (uintptr_t)(dwin + ((g.pos + kb) >> 1));
+        else
+            return (uintptr_t)(dwin + (g.pos + kb) * coeff);
+    };
     double acc[kNSums];
 #pragma unroll
     for (int i = 0; i < kNSums; ++i) acc[i] = 0.0;
@@ -390,16 +420,16 @@ __device__ __forceinline__ void correlate_runs(const int8_t *__restrict__ data, 
     //   trigarg = (carrFreq*2*pi) .* ((0:blksize) ./ fs) + remCarrPhase   (tracking.m:303-304; left to right, one rounding
     // per operation: the translation unit is built with -ffp-contract=off), then sin / cos of that f64 value
     const double w_ref = (g.carrFreq * 2.0) * 3.14159265358979323846;
-    // the segment's bytes (I/Q pairs: 2 SEG bytes), whole aligned dwords around it
-    uint32_t raw[nwd + 1];
+    // the segment's bytes (I/Q pairs: 2 SEG bytes; packed: SEG / 2, from either nibble of the first), whole aligned dwords around it
+    uint32_t raw[nrd + 1];
     auto fetch = [&](long kw) {
         const long kb = kw + (long)lane * SEG;
         if (kb < g.blk) {
             BDS_DASSERT(g.pos + kb >= p.base && g.pos + kb < p.win_end);  // first sample of the segment inside the window held in HBM
-            const uintptr_t a = (uintptr_t)(dwin + (g.pos + kb) * coeff);
+            const uintptr_t a = seg_addr(kb);
             const uint32_t *__restrict__ q = reinterpret_cast<const uint32_t *>(a & ~(uintptr_t)3);
 #pragma unroll
-            for (int i = 0; i <= nwd; ++i) raw[i] = q[i];
+            for (int i = 0; i <= nrd; ++i) raw[i] = q[i];
         }
     };
     const long kw_first = k0_first + (long)wave * WCH;
@@ -446,8 +476,17 @@ __device__ __forceinline__ void correlate_runs(const int8_t *__restrict__ data, 
         PT run_i = 0, run_q = 0;
         if (n_here > 0) {
             uint32_t wr[nwd];
-            {
-                const uint32_t sh = (uint32_t)((uintptr_t)(dwin + (g.pos + kb) * coeff) & 3);
+            if constexpr (FMT == kFmtPacked) {
+                // funnel shift by the byte offset and the nibble, then every byte to the (I, Q, I, Q) dword of the I/Q record
+                const uint32_t sh = 8u * (uint32_t)(seg_addr(kb) & 3) + 4u * (uint32_t)((g.pos + kb) & 1);
+#pragma unroll
+                for (int i = 0; i < nrd; ++i) {
+                    const uint32_t w = __builtin_amdgcn_alignbit(raw[i + 1], raw[i], sh);
+#pragma unroll
+                    for (int b = 0; b < 4; ++b) wr[4 * i + b] = iq_of_packed((w >> (8 * b)) & 0xffu);
+                }
+            } else {
+                const uint32_t sh = (uint32_t)(seg_addr(kb) & 3);
 #pragma unroll
                 for (int i = 0; i < nwd; ++i) wr[i] = __builtin_amdgcn_alignbyte(raw[i + 1], raw[i], sh);
             }
@@ -720,7 +759,7 @@ __device__ __forceinline__ void apply_update(const TrkParams &p, ChanState &s, c
 // wait for another and an epoch is one launch instead of two (the update as its own kernel costs ~5 us, mostly the
 // floor of a small dependent launch).  State and partial sums ping-pong between two buffers; workgroup 0 of the channel
 // writes the results of the previous epoch and the state the current one starts from.
-template <int MODE, int SEG, bool CPLX, int PREC>
+template <int MODE, int SEG, int FMT, int PREC>
 __global__ __launch_bounds__(kTrkThreads, 1) void k_trk_correlate(const int8_t *__restrict__ data,
                                                               const int8_t *__restrict__ prim, TrkParams p,
                                                               const ChanState *__restrict__ st_in, ChanState *__restrict__ st_out,
@@ -751,13 +790,13 @@ __global__ __launch_bounds__(kTrkThreads, 1) void k_trk_correlate(const int8_t *
     const int8_t *pd = prim + ((long)(s.prn - 1) * 2 + 0) * kTabStride;  // (data, pilot) pairs
     const int8_t *pp = prim + ((long)(s.prn - 1) * 2 + 1) * kTabStride;  // pilot BOC(6,1)
     if constexpr (SEG > 0)  // run-based correlator, SEG samples per lane and pass
-        correlate_runs<MODE, SEG, CPLX, PREC>(data, pd, pp, p, g, k0, (long)nblocks * p.chunk, p.pilot != 0, out);
+        correlate_runs<MODE, SEG, FMT, PREC>(data, pd, pp, p, g, k0, (long)nblocks * p.chunk, p.pilot != 0, out);
     else  // per-sample correlator (reads p.cplx itself)
         correlate_slice<MODE>(data, pd, pp, p, g, k0, (long)nblocks * p.chunk, p.pilot != 0, out);
 }
 
 // Open-loop variant: geometry supplied by the caller (bds_track_correlate).
-template <int MODE, int SEG, bool CPLX, int PREC>
+template <int MODE, int SEG, int FMT, int PREC>
 __global__ __launch_bounds__(kTrkThreads) void k_trk_correlate_open(const int8_t *__restrict__ data,
                                                                    const int8_t *__restrict__ prim, TrkParams p,
                                                                    const int *__restrict__ prn,
@@ -781,12 +820,12 @@ __global__ __launch_bounds__(kTrkThreads) void k_trk_correlate_open(const int8_t
     const int8_t *pd = prim + ((long)(prn[ch] - 1) * 2 + 0) * kTabStride;  // (data, pilot) pairs
     const int8_t *pp = prim + ((long)(prn[ch] - 1) * 2 + 1) * kTabStride;  // pilot BOC(6,1)
     if constexpr (SEG > 0)  // run-based correlator, SEG samples per lane and pass
-        correlate_runs<MODE, SEG, CPLX, PREC>(data, pd, pp, p, g, k0, (long)nblocks * p.chunk, p.pilot != 0, out);
+        correlate_runs<MODE, SEG, FMT, PREC>(data, pd, pp, p, g, k0, (long)nblocks * p.chunk, p.pilot != 0, out);
     else  // per-sample correlator (reads p.cplx itself)
         correlate_slice<MODE>(data, pd, pp, p, g, k0, (long)nblocks * p.chunk, p.pilot != 0, out);
 }
 
-// launch k<MODE, SEG, CPLX, PREC> for the run-time (mode, runs, cplx, prec) of p; the f64 prefix sums of PREC >= 1 need
+// launch k<MODE, SEG, FMT, PREC> for the run-time (mode, runs, cplx, prec) of p; the f64 prefix sums of PREC >= 1 need
 // more dynamic LDS than the default limit of a kernel: raised once per kernel and context
 #define BDS_TRK_LAUNCH(KERN, grid, lds, stream, ...)                                                        \
     do {                                                                                                    \
@@ -797,11 +836,13 @@ __global__ __launch_bounds__(kTrkThreads) void k_trk_correlate_open(const int8_t
         };                                                                                                  \
         auto go = [&](auto mode_c, auto prec_c) {                                                           \
             constexpr int M = decltype(mode_c)::value, PR = decltype(prec_c)::value;                        \
-            if (p.runs == 16 && !p.cplx) fire(KERN<M, 16, false, PR>);                                      \
-            else if (p.runs == 16) fire(KERN<M, 16, true, PR>);                                             \
-            else if (p.runs == 8 && !p.cplx) fire(KERN<M, 8, false, PR>);                                   \
-            else if (p.runs == 8) fire(KERN<M, 8, true, PR>);                                               \
-            else fire(KERN<M, 0, false, 0>);                                                                \
+            if (p.runs == 16 && p.cplx == kFmtReal) fire(KERN<M, 16, kFmtReal, PR>);                        \
+            else if (p.runs == 16 && p.cplx == kFmtIQ) fire(KERN<M, 16, kFmtIQ, PR>);                       \
+            else if (p.runs == 16) fire(KERN<M, 16, kFmtPacked, PR>);                                       \
+            else if (p.runs == 8 && p.cplx == kFmtReal) fire(KERN<M, 8, kFmtReal, PR>);                     \
+            else if (p.runs == 8 && p.cplx == kFmtIQ) fire(KERN<M, 8, kFmtIQ, PR>);                         \
+            else if (p.runs == 8) fire(KERN<M, 8, kFmtPacked, PR>);                                         \
+            else fire(KERN<M, 0, kFmtReal, 0>);                                                             \
         };                                                                                                  \
         auto gp = [&](auto mode_c) {                                                                        \
             if (p.prec == 0) go(mode_c, std::integral_constant<int, 0>{});                                  \
@@ -1100,7 +1141,8 @@ static int ensure_prim(bds_ctx *ctx, TrackState &t, int signal) {
 
 static int fill_params(bds_ctx *ctx, const bds_settings &s, TrkParams &p, int n_epochs, size_t n_bytes) {
     if (s.signal != BDS_SIGNAL_B1C && s.signal != BDS_SIGNAL_B2A) return fail(ctx, BDS_ERR_ARG, "settings.signal invalid");
-    if (s.fileType != 1 && s.fileType != 2) return fail(ctx, BDS_ERR_ARG, "settings.fileType must be 1 (real) or 2 (I/Q)");
+    if (s.fileType != 1 && s.fileType != 2 && s.fileType != 3)
+        return fail(ctx, BDS_ERR_ARG, "settings.fileType must be 1 (real), 2 (I/Q) or 3 (packed 2+2-bit I/Q)");
     if (s.dataType != 0)  // fread(fid, ..., settings.dataType), tracking.m:237-238
         return fail(ctx, BDS_ERR_UNSUPPORTED, "settings.dataType: only 'schar' (int8 samples) is supported");
     if (s.codeLength != 10230 || !(s.samplingFreq > 0) || !(s.intTime > 0))
@@ -1116,7 +1158,7 @@ static int fill_params(bds_ctx *ctx, const bds_settings &s, TrkParams &p, int n_
     bds_calc_loop_coef_carr(&s, &p.pf3, &p.pf2, &p.pf1);                                 // :116
     p.pdi = s.intTime;                                                                   // :107
     p.factor = p.mode == BDS_TRACK_WB ? bds_calc_weighing_factor(&s) : 0.0;              // WB_tracking.m:138
-    p.cplx = s.fileType == 2;
+    p.cplx = s.fileType == 3 ? kFmtPacked : s.fileType == 2 ? kFmtIQ : kFmtReal;
     if (ctx->tune.trk_persample) {  // per-sample correlator (the round-1 kernel; A/B and cross-check)
         p.chunk = s.signal == BDS_SIGNAL_B2A ? 2048 : 8192;
         if (ctx->tune.trk_chunk > 0) p.chunk = std::max(256, ctx->tune.trk_chunk);
@@ -1129,7 +1171,8 @@ static int fill_params(bds_ctx *ctx, const bds_settings &s, TrkParams &p, int n_
         p.prec = std::max(0, std::min(5, ctx->tune.trk_prec));
         if (ctx->tune.trk_seg == 8 || ctx->tune.trk_seg == 16) p.runs = ctx->tune.trk_seg, p.chunk = kTrkThreads * p.runs;
     }
-    p.n_bytes = (long long)(n_bytes / (p.cplx ? 2 : 1));  // whole samples an fread can deliver
+    // whole samples an fread can deliver
+    p.n_bytes = p.cplx == kFmtPacked ? (long long)n_bytes * 2 : (long long)(n_bytes / (p.cplx ? 2 : 1));
     return BDS_OK;
 }
 
@@ -1253,7 +1296,9 @@ struct SpanStream {
     TrackState &t;
     const RecordLoader &load;
     hipStream_t main_stream, ld_stream;
-    long long coeff, span_n;  // bytes per sample; samples a span buffer holds
+    int fmt;            // sample format (kFmt*): span bounds are multiples of fmt_align(fmt) or even, so they fall on whole bytes
+    long long span_n;   // samples a span buffer holds
+    long long nb_of(long long n) const { return fmt_bytes(fmt, n); }  // bytes of n samples
     hipEvent_t ev_carry = nullptr;
     bool carry_pending = false;  // ev_carry is recorded behind a copy that reads nxt.buf
     // the prediction: the next span starts at sample pre_nb, its tail [pre_lo, pre_hi) goes behind what it shares with cur
@@ -1263,8 +1308,8 @@ struct SpanStream {
     int th_rc = BDS_OK;
     hipError_t th_err = hipSuccess;
 
-    SpanStream(bds_ctx *c, TrackState &ts, const RecordLoader &l, hipStream_t ms, hipStream_t ls, long long cf, long long sn)
-        : ctx(c), t(ts), load(l), main_stream(ms), ld_stream(ls), coeff(cf), span_n(sn) {}
+    SpanStream(bds_ctx *c, TrackState &ts, const RecordLoader &l, hipStream_t ms, hipStream_t ls, int fm, long long sn)
+        : ctx(c), t(ts), load(l), main_stream(ms), ld_stream(ls), fmt(fm), span_n(sn) {}
     SpanStream(const SpanStream &) = delete;
     SpanStream &operator=(const SpanStream &) = delete;
     ~SpanStream() {
@@ -1277,19 +1322,19 @@ struct SpanStream {
         const bool carry = nb >= cur.base && nb < cur.end;
         if (carry) {
             if (!ev_carry) BDS_HIP(ctx, hipEventCreateWithFlags(&ev_carry, hipEventDisableTiming));
-            BDS_HIP(ctx, hipMemcpyAsync(nxt.buf, cur.buf + (nb - cur.base) * coeff, (size_t)((cur.end - nb) * coeff), hipMemcpyDeviceToDevice, main_stream));
+            BDS_HIP(ctx, hipMemcpyAsync(nxt.buf, cur.buf + nb_of(nb - cur.base), (size_t)nb_of(cur.end - nb), hipMemcpyDeviceToDevice, main_stream));
             BDS_HIP(ctx, hipEventRecord(ev_carry, main_stream));
             carry_pending = true;
         }
         const long long from = carry ? cur.end : nb;
         if (!tail_loaded && hi > from) {
-            const size_t nbytes = (size_t)((hi - from) * coeff);
-            int r = load((size_t)(from * coeff), nbytes, nxt.buf + (from - nb) * coeff, main_stream);
+            const size_t nbytes = (size_t)nb_of(hi - from);
+            int r = load((size_t)nb_of(from), nbytes, nxt.buf + nb_of(from - nb), main_stream);
             if (r) return r;
             t.loaded_bytes += nbytes, t.pieces += 1;
         }
         nxt.base = nb, nxt.end = std::max(hi, from);
-        t.resident_max = std::max(t.resident_max, (size_t)((cur.end - cur.base + nxt.end - nxt.base) * coeff));
+        t.resident_max = std::max(t.resident_max, (size_t)nb_of(cur.end - cur.base + nxt.end - nxt.base));
         std::swap(cur, nxt);
         pre_valid = false;
         return BDS_OK;
@@ -1300,10 +1345,10 @@ struct SpanStream {
     // (the channels are not where it put them) is loaded, and counted, again by move_to().
     void start_load() {
         if (!pre_valid || th.joinable() || pre_lo >= pre_hi) return;
-        int8_t *dst = nxt.buf + (pre_lo - pre_nb) * coeff;
-        const size_t off = (size_t)(pre_lo * coeff), nbytes = (size_t)((pre_hi - pre_lo) * coeff);
+        int8_t *dst = nxt.buf + nb_of(pre_lo - pre_nb);
+        const size_t off = (size_t)nb_of(pre_lo), nbytes = (size_t)nb_of(pre_hi - pre_lo);
         pre_lo = pre_hi;
-        t.resident_max = std::max(t.resident_max, (size_t)((cur.end - cur.base) * coeff) + nbytes);
+        t.resident_max = std::max(t.resident_max, (size_t)nb_of(cur.end - cur.base) + nbytes);
         t.loaded_bytes += nbytes, t.pieces += 1;
         const bool wait_carry = carry_pending && ld_stream != main_stream;
         carry_pending = false;
@@ -1386,7 +1431,13 @@ static int do_track(bds_ctx *ctx, const bds_settings *s, const RecordLoader &loa
     // the real file size (p.n_bytes).
     // That window is held whole (one window) when it fits and does not exceed the resident limit; otherwise the record is
     // STREAMED through a span of span_n samples that slides through two buffers (the epoch loop below).
-    const long long coeff = p.cplx ? 2 : 1;
+    // Positions stay in samples; bytes appear only where memory is sized and the loader is called.  A packed record holds two
+    // samples per byte: window and span bounds are kept even there (bases multiples of 32 samples = 16 bytes), so that every
+    // range is whole bytes.
+    const int fmt = p.cplx;
+    const long long al = fmt_align(fmt);
+    const bool packed = fmt == kFmtPacked;
+    auto nb_of = [&](long long n) { return fmt_bytes(fmt, n); };
     // bounds of a block while the channel's code rate stays within 2 % of f: hi is the rule the window is sized with
     auto blk_hi = [&](double f) { return (long long)((long)std::ceil((double)s->codeLength / (f * 0.98 / s->samplingFreq)) + 2); };
     auto blk_lo = [&](double f) { return std::max(1LL, (long long)std::floor((double)s->codeLength / (f * 1.02 / s->samplingFreq)) - 2); };
@@ -1408,6 +1459,7 @@ static int do_track(bds_ctx *ctx, const bds_settings *s, const RecordLoader &loa
             const long long B = blk_hi(v[c].codeFreq);
             e = std::max(e, v[c].pos + (long long)(n_epochs - k - 1) * B + (long long)std::ceil(std::max(1.0, margin) * (double)B));
         }
+        if (packed) e = (e + 1) & ~1LL;  // (p.n_bytes is even)
         return std::min(e, p.n_bytes);
     };
     // epochs every live channel can take inside the span
@@ -1441,9 +1493,10 @@ static int do_track(bds_ctx *ctx, const bds_settings *s, const RecordLoader &loa
         if (whole_file || first > last) first = 0, last = p.n_bytes;
         first = std::max(0LL, std::min(first, p.n_bytes));
         last = std::max(first, std::min(last, p.n_bytes));
+        if (packed) first &= ~(al - 1), last = std::min((last + 1) & ~1LL, p.n_bytes);
         p.base = first;
         p.win_end = last;
-        const size_t wbytes = (size_t)((last - first) * coeff);
+        const size_t wbytes = (size_t)nb_of(last - first);
         stream = any_live && t.resident_limit && wbytes > t.resident_limit;
         if (!stream && (t.data_cap < wbytes || !t.d_data || ctx->tune.trk_window_nomem)) {
             if (t.d_data) (void)hipFree(t.d_data), t.d_data = nullptr, t.data_cap = 0;
@@ -1461,15 +1514,15 @@ static int do_track(bds_ctx *ctx, const bds_settings *s, const RecordLoader &loa
             for (int8_t *&q : t.d_span)
                 if (q) (void)hipFree(q), q = nullptr;
             t.span_cap = 0;
-            if (wbytes && (rc = load((size_t)(first * coeff), wbytes, t.d_data, st(ctx)))) return rc;
+            if (wbytes && (rc = load((size_t)nb_of(first), wbytes, t.d_data, st(ctx)))) return rc;
             t.loaded_bytes = wbytes, t.pieces = 1, t.resident_max = wbytes, t.repeated = 0;
             cur.buf = t.d_data, cur.base = first, cur.end = last;
         } else {
             if (t.d_data) (void)hipFree(t.d_data), t.d_data = nullptr, t.data_cap = 0;  // no stale window beside the span
-            // A span must hold, from the (16-sample aligned) smallest position, every channel's position plus one block
+            // A span must hold, from the (16-sample aligned; packed: 32) smallest position, every channel's position plus one block
             // at a code rate 2 % low, plus what the start of the NEXT span -- predicted at a code rate 2 % high while
             // this one is in use -- can fall behind the channels in one epoch.
-            const long long base0 = live_min_pos(hs) & ~15LL;
+            const long long base0 = live_min_pos(hs) & ~(al - 1);
             long long need = 0, hi_max = 0, lo_min = p.n_bytes + 1;
             for (int c = 0; c < n_ch; ++c) {
                 if (hs[c].active != 1) continue;
@@ -1477,8 +1530,8 @@ static int do_track(bds_ctx *ctx, const bds_settings *s, const RecordLoader &loa
                 need = std::max(need, std::min(hs[c].pos + B, p.n_bytes) - base0);
                 hi_max = std::max(hi_max, B), lo_min = std::min(lo_min, blk_lo(hs[c].codeFreq));
             }
-            const long long min_half = (std::max(0LL, need) + std::max(0LL, hi_max - lo_min) + 16 + 15) & ~15LL;
-            const size_t min_limit = (size_t)(2 * min_half * coeff);
+            const long long min_half = (std::max(0LL, need) + std::max(0LL, hi_max - lo_min) + al + al - 1) & ~(al - 1);
+            const size_t min_limit = (size_t)nb_of(2 * min_half);
             size_t limit = t.resident_limit;
             if (!limit || wbytes <= limit) {  // no limit that applies: the window allocation failed
                 size_t fr = 0, tot = 0;
@@ -1486,10 +1539,11 @@ static int do_track(bds_ctx *ctx, const bds_settings *s, const RecordLoader &loa
                 limit = std::max(min_limit, std::min<size_t>(fr / 2, (size_t)1 << 30));
             } else if (limit < min_limit) {
                 return fail(ctx, BDS_ERR_ARG, "resident limit of %zu bytes is too small for these channels: the spread of their positions plus "
-                            "one block, in each of the two span buffers, needs at least %zu bytes", limit, min_limit);
+                            "one block, in each of the two span buffers, needs at least %zu bytes%s", limit, min_limit,
+                            packed ? " of the packed record" : "");
             }
-            span_n = (long long)(limit / (size_t)(2 * coeff)) & ~15LL;
-            const size_t cap = (size_t)(span_n * coeff);
+            span_n = (packed ? (long long)(limit / 2) * 2 : (long long)(limit / (size_t)(2 * (fmt == kFmtIQ ? 2 : 1)))) & ~(al - 1);
+            const size_t cap = (size_t)nb_of(span_n);
             if (t.span_cap != cap || !t.d_span[0] || !t.d_span[1]) {
                 for (int8_t *&q : t.d_span)
                     if (q) (void)hipFree(q), q = nullptr;
@@ -1507,8 +1561,8 @@ static int do_track(bds_ctx *ctx, const bds_settings *s, const RecordLoader &loa
             cur.buf = t.d_span[0], cur.base = base0, cur.end = base0;
             nxt.buf = t.d_span[1];
             cur.end = std::max(cur.base, std::min(cur.base + span_n, need_end(hs, 0)));
-            const size_t nb0 = (size_t)((cur.end - cur.base) * coeff);
-            if (nb0 && (rc = load((size_t)(cur.base * coeff), nb0, cur.buf, st(ctx)))) return rc;
+            const size_t nb0 = (size_t)nb_of(cur.end - cur.base);
+            if (nb0 && (rc = load((size_t)nb_of(cur.base), nb0, cur.buf, st(ctx)))) return rc;
             t.loaded_bytes = nb0, t.pieces = 1, t.resident_max = nb0, t.repeated = 0;
         }
     }
@@ -1616,7 +1670,7 @@ static int do_track(bds_ctx *ctx, const bds_settings *s, const RecordLoader &loa
         // Streamed: batches of epochs on the resident span.  At a batch boundary the host reads the channel states back,
         // moves on to the span whose tail the loader thread filled meanwhile (the overlap with the current span is carried
         // device-to-device) and enqueues as many epochs as every live channel can take inside it.
-        SpanStream ss(ctx, t, load, st(ctx), ctx->stream2 ? (hipStream_t)ctx->stream2 : st(ctx), coeff, span_n);
+        SpanStream ss(ctx, t, load, st(ctx), ctx->stream2 ? (hipStream_t)ctx->stream2 : st(ctx), fmt, span_n);
         ss.cur = cur, ss.nxt = nxt;
         int slot = 0, k = 0;
         std::vector<ChanState> h0;
@@ -1628,7 +1682,7 @@ static int do_track(bds_ctx *ctx, const bds_settings *s, const RecordLoader &loa
             if (ss.pre_valid && minp >= ss.pre_nb && (rc = ss.move_to(ss.pre_nb, ss.pre_hi, true))) return rc;
             long long n = plan(hs, ss.cur, margin);
             if (n == 0) {  // no prefetched span, or the channels are not where it was predicted: a span from their smallest position
-                const long long nb = minp & ~15LL, hi = std::max(nb, std::min(nb + span_n, need_end(hs, k)));
+                const long long nb = minp & ~(al - 1), hi = std::max(nb, std::min(nb + span_n, need_end(hs, k)));
                 ss.pre_valid = false;
                 if (nb != ss.cur.base || hi > ss.cur.end) {
                     if ((rc = ss.move_to(nb, hi, false))) return rc;
@@ -1640,7 +1694,7 @@ static int do_track(bds_ctx *ctx, const bds_settings *s, const RecordLoader &loa
                         if (hs[c].active == 1)
                             need = std::max(need, hs[c].pos - nb + (long long)std::ceil(std::max(1.0, margin) * (double)blk_hi(hs[c].codeFreq)));
                     return fail(ctx, BDS_ERR_ARG, "epoch %d: the resident span of %lld bytes (half the resident limit) cannot hold the channels' spread of positions "
-                                "plus a block any more: it needs %lld bytes", k + 1, (long long)(span_n * coeff), (long long)(((need + 31) & ~15LL) * coeff));
+                                "plus a block any more: it needs %lld bytes", k + 1, nb_of(span_n), nb_of((need + 2 * al - 1) & ~(al - 1)));
                 }
             }
             n = std::min<long long>(n, n_epochs - k);
@@ -1653,7 +1707,7 @@ static int do_track(bds_ctx *ctx, const bds_settings *s, const RecordLoader &loa
                 long long nb = p.n_bytes;
                 for (int c = 0; c < n_ch; ++c)
                     if (hs[c].active == 1) nb = std::min(nb, hs[c].pos + n_safe * blk_lo(hs[c].codeFreq));
-                nb = std::max(ss.cur.base, nb & ~15LL);
+                nb = std::max(ss.cur.base, nb & ~(al - 1));
                 const long long hi = std::min(nb + span_n, want_end);
                 if (nb <= ss.cur.end && hi > ss.cur.end) ss.predict(nb, hi);
             }

@@ -247,8 +247,33 @@ def pack_settings(s) -> Settings:
 
 
 def _i8(a):
+    a = np.asarray(a)
+    if a.dtype == np.uint8:  # raw bytes (a packed fileType-3 record): the same bytes, not a conversion of values above 127
+        a = np.ascontiguousarray(a).view(np.int8)
     a = np.ascontiguousarray(a, dtype=np.int8)
     return a, a.ctypes.data_as(C.POINTER(C.c_int8))
+
+
+def sample_format(is_complex) -> int:
+    """is_complex of the C ABI: 0 real int8, 1 (True) interleaved I/Q int8 pairs, 2 packed 2+2-bit I/Q bytes (fileType 3)."""
+    f = int(is_complex)
+    if f not in (0, 1, 2):
+        raise ValueError(f"is_complex must be 0 (real), 1 (I/Q int8 pairs) or 2 (packed 2+2-bit I/Q), not {is_complex!r}")
+    return f
+
+
+def n_samples_of(n_values: int, is_complex, n_samples=None) -> int:
+    """Samples in an array of n_values int8 values (bytes, when packed) of the given format; n_samples, if given, is checked
+    against what the array holds (a packed array of B bytes holds 2 B samples: an odd count ignores the last high nibble)."""
+    f = sample_format(is_complex)
+    if f == 1 and n_values % 2:
+        raise ValueError(f"an I/Q record holds int8 pairs: {n_values} values is an odd count (packed bytes go with is_complex = 2)")
+    have = n_values * 2 if f == 2 else n_values // 2 if f == 1 else n_values
+    if n_samples is None:
+        return have
+    if not 0 <= int(n_samples) <= have:
+        raise ValueError(f"n_samples = {n_samples} but the array holds {have} samples")
+    return int(n_samples)
 
 
 def gen_code(signal: str, kind: str, prn: int) -> np.ndarray:
@@ -317,7 +342,7 @@ class MultiContext:
         return int(self._lib.bds_multi_rccl_ranks(self._h))
 
     def acquire(self, jobs):
-        """jobs: list of (settings, int8 samples, is_complex) -- one entry per signal.
+        """jobs: list of (settings, int8 samples, is_complex) -- one entry per signal (is_complex 2: uint8 packed bytes).
         Returns a list of (carrFreq, codePhase, peakMetric, detected), one per signal."""
         n = len(jobs)
         arr = (AcqJob * n)()
@@ -330,8 +355,8 @@ class MultiContext:
             det = np.zeros(max_prn, dtype=np.int32)
             arr[i].settings = C.pointer(cs)
             arr[i].samples = p
-            arr[i].n_samples = a.size // (2 if is_complex else 1)
-            arr[i].is_complex = int(bool(is_complex))
+            arr[i].n_samples = n_samples_of(a.size, is_complex)
+            arr[i].is_complex = sample_format(is_complex)
             arr[i].max_prn = max_prn
             arr[i].carrFreq, arr[i].codePhase, arr[i].peakMetric = (v.ctypes.data_as(_DP) for v in (carr, cph, pm))
             arr[i].detected = det.ctypes.data_as(_IP)
@@ -388,11 +413,13 @@ class Context:
         return buf.value.decode()
 
     # -- acquisition -----------------------------------------------------------------
-    def acq_load(self, settings, samples, is_complex=False):
+    def acq_load(self, settings, samples, is_complex=False, n_samples=None):
+        """is_complex: 0 / False real int8, 1 / True I/Q int8 pairs, 2 packed 2+2-bit I/Q bytes (uint8, fileType 3).
+        n_samples: use only the first n_samples of the array (default: all it holds)."""
         cs = pack_settings(settings)
         a, p = _i8(samples)
-        n = a.size // 2 if is_complex else a.size
-        self._check(self._lib.bds_acq_load(self._h, C.byref(cs), p, n, int(is_complex)))
+        n = n_samples_of(a.size, is_complex, n_samples)
+        self._check(self._lib.bds_acq_load(self._h, C.byref(cs), p, n, sample_format(is_complex)))
 
     def acq_prepare(self, settings):
         cs = pack_settings(settings)
@@ -422,16 +449,16 @@ class Context:
                                           pm.ctypes.data_as(_DP), det.ctypes.data_as(_IP)))
         return carr, cph, pm, det
 
-    def acquire(self, settings, samples, is_complex=False):
+    def acquire(self, settings, samples, is_complex=False, n_samples=None):
         cs = pack_settings(settings)
         a, p = _i8(samples)
-        n = a.size // 2 if is_complex else a.size
+        n = n_samples_of(a.size, is_complex, n_samples)
         max_prn = max(int(q) for q in np.atleast_1d(settings.acqSatelliteList))
         carr = np.zeros(max_prn)
         cph = np.zeros(max_prn)
         pm = np.zeros(max_prn)
         det = np.zeros(max_prn, dtype=np.int32)
-        self._check(self._lib.bds_acquire(self._h, C.byref(cs), p, n, int(is_complex), max_prn,
+        self._check(self._lib.bds_acquire(self._h, C.byref(cs), p, n, sample_format(is_complex), max_prn,
                                           carr.ctypes.data_as(_DP), cph.ctypes.data_as(_DP),
                                           pm.ctypes.data_as(_DP), det.ctypes.data_as(_IP)))
         return carr, cph, pm, det
@@ -507,7 +534,7 @@ class Context:
 
     # -- tracking --------------------------------------------------------------------
     def track(self, settings, source, channels, n_epochs, n_cno, fields):
-        """source: file path (str/bytes) or int8 array of raw file bytes.
+        """source: file path (str/bytes) or int8 array of raw file bytes (uint8 for a packed fileType-3 record).
         Returns dict field -> array [n_ch, n_epochs] (C/N0 fields [n_ch, n_cno])."""
         cs = pack_settings(settings)
         nch = len(channels)
@@ -569,14 +596,14 @@ class Context:
         Returns ((carrFreq, codePhase, peakMetric, detected), channel array, dict of trackResults arrays)."""
         cs = pack_settings(settings)
         a, p = _i8(samples)
-        n = a.size // 2 if is_complex else a.size
+        n = n_samples_of(a.size, is_complex)
         max_prn = max(int(q) for q in np.atleast_1d(settings.acqSatelliteList))
         carr, cph, pm = np.zeros(max_prn), np.zeros(max_prn), np.zeros(max_prn)
         det = np.zeros(max_prn, dtype=np.int32)
         nch = int(settings.numberOfChannels)
         ch = (Channel * nch)()
         out, arrays = self._track_out(nch, n_epochs, n_cno, fields)
-        self._check(self._lib.bds_acquire_track(self._h, C.byref(cs), p, n, int(bool(is_complex)), max_prn, carr.ctypes.data_as(_DP),
+        self._check(self._lib.bds_acquire_track(self._h, C.byref(cs), p, n, sample_format(is_complex), max_prn, carr.ctypes.data_as(_DP),
                                                 cph.ctypes.data_as(_DP), pm.ctypes.data_as(_DP), det.ctypes.data_as(_IP),
                                                 os.fsencode(path), ch, C.byref(out)))
         return (carr, cph, pm, det), ch, arrays

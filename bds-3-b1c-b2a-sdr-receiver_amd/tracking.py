@@ -4,7 +4,8 @@ BDS-3_B2a/tracking.m:1, BDS-3_B1C/NB_tracking.m:1, BDS-3_B1C/WB_tracking.m:1 and
 
 ``fid`` may be a file path, an open binary file object (its ``.name`` is used: the
 reference seeks absolutely from 'bof', B2a/tracking.m:151-153, so the handle position
-is irrelevant) or an int8 array holding the raw file bytes.  The result is a list of
+is irrelevant) or an int8 array holding the raw file bytes (uint8 for the packed
+records of ``settings.fileType = 3``).  The result is a list of
 per-channel structs with exactly the field set the reference variant creates
 (SURVEY.md Appendix D).
 """
@@ -17,7 +18,7 @@ from types import SimpleNamespace
 import numpy as np
 
 from . import native
-from .acquisition import get_context
+from .acquisition import get_context, packed_bytes
 
 
 class TrackResults(SimpleNamespace):
@@ -90,6 +91,9 @@ def tracking(fid, channel, settings, mode=None, device: int = 0, resident_limit=
         source = fid
     elif hasattr(fid, "name") and not isinstance(fid, np.ndarray):
         source = fid.name
+    elif int(settings.fileType) == 3:  # packed bytes: never through a conversion to int8 values
+        a = np.asarray(fid)
+        source = packed_bytes(a.view(np.uint8) if a.dtype == np.int8 else a, field="fid")
     else:
         source = np.ascontiguousarray(fid, dtype=np.int8)
     ctx = get_context(device)
@@ -143,13 +147,15 @@ def acquire_track(long_signal, path, settings, device: int = 0, resident_limit=N
     n, m, ep, cn, pilot = field_set(settings, mode)
     x = np.asarray(long_signal)
     is_complex = np.iscomplexobj(x)
-    if is_complex:  # fileType 2: interleaved int8 pairs, as acquisition() hands them over
+    if int(settings.fileType) == 3:  # packed bytes, in the block as in the file
+        x, is_complex = packed_bytes(x), 2
+    elif is_complex:  # fileType 2: interleaved int8 pairs, as acquisition() hands them over
         pairs = np.empty(2 * x.size, dtype=np.int8)
         pairs[0::2], pairs[1::2] = x.real.astype(np.int8), x.imag.astype(np.int8)
         x = pairs
     ctx = get_context(device)
     with _resident_limit(ctx, resident_limit):
-        (carr, cph, pm, det), ch, arr = ctx.acquire_track(settings, np.ascontiguousarray(x, dtype=np.int8), is_complex, path, n, m, ep + cn)
+        (carr, cph, pm, det), ch, arr = ctx.acquire_track(settings, x if is_complex == 2 else np.ascontiguousarray(x, dtype=np.int8), is_complex, path, n, m, ep + cn)
     acq = SimpleNamespace(carrFreq=carr, codePhase=cph, peakMetric=pm)
     channel = [SimpleNamespace(PRN=int(c.PRN), acquiredFreq=float(c.acquiredFreq), codePhase=float(c.codePhase),
                                codeFreq=float(c.codeFreq), status=chr(c.status)) for c in ch]

@@ -57,7 +57,7 @@ enum {
  */
 typedef struct bds_settings {
     int32_t signal; /* BDS_SIGNAL_*: which receiver directory the struct came from */
-    int32_t fileType;              /* 1 = real int8, 2 = interleaved I/Q int8        */
+    int32_t fileType;              /* 1 = real int8, 2 = interleaved I/Q int8, 3 = packed 2+2-bit I/Q (below) */
     double samplingFreq;           /* [Hz] */
     double IF;                     /* [Hz] */
     double codeFreqBasis;          /* [Hz] */
@@ -190,7 +190,16 @@ BDS_API int bds_gen_code(int signal, int kind, int prn, int8_t *out, int n);
  *   B2a/acquisition.m:1, B1C/acquisition.m:1, B1C/GPU_acquisition.m:1
  * samples: int8 IF samples as fread(...,'schar') delivers them
  *   (B2a/postProcessing.m:89-90, B1C/postProcessing.m:94); n_samples real samples
- *   (or I/Q pairs when is_complex, fileType 2).
+ *   (or I/Q pairs when is_complex == 1, fileType 2).
+ * Packed records: settings.fileType == 3 (tracking) and is_complex == 2 (acquisition) mean the input format of
+ *   B2a/include/unpack_cplx.m:18-30 -- one byte holds two complex samples, 2-bit sign/magnitude I and Q each.  Complex sample n
+ *   (0-based) is nibble n & 1 of byte n >> 1, low nibble first; within a nibble bit 0 = I negative, bit 1 = Q negative,
+ *   bit 2 = |I| is 3 (else 1), bit 3 = |Q| is 3 (else 1).  `samples` then points at ceil(n_samples / 2) packed bytes (for an odd
+ *   n_samples the last high nibble is ignored); in tracking everything that is counted in samples stays in samples (a channel
+ *   starts at sample skipNumberOfBytes + codePhase - 1, which may be a high nibble), a file of B bytes holds 2 B samples, and
+ *   end of file is judged in samples.  Every output equals, bit for bit, that of the same call with fileType 2 (is_complex 1)
+ *   on the int8 pairs bds_unpack_cplx makes of the same bytes; bds_track_loaded_bytes / bds_track_stream_info count real bytes
+ *   (a quarter of the fileType-2 record's), and so does the resident limit.
  * carrFreq/codePhase/peakMetric: double[max_prn], max_prn >= max(acqSatelliteList);
  *   zero where not searched / not detected (B2a/acquisition.m:161-165).
  * detected (optional, may be NULL): int32[max_prn], 1 where the PRN passed the
@@ -271,7 +280,7 @@ typedef struct bds_acq_job {
     const bds_settings *settings; /* one receiver's settings (signal, acqSatelliteList, ...)          */
     const int8_t *samples;        /* its IF block (host), as for bds_acquire                           */
     size_t n_samples;
-    int32_t is_complex;
+    int32_t is_complex;           /* 0 real, 1 I/Q int8 pairs, 2 packed 2+2-bit I/Q bytes              */
     int32_t max_prn;              /* >= max(acqSatelliteList), <= 63                                   */
     double *carrFreq, *codePhase, *peakMetric; /* out: double[max_prn] each                            */
     int32_t *detected;            /* out, optional: int32[max_prn]                                     */
@@ -300,7 +309,7 @@ BDS_API double bds_acq_job_cost(const bds_settings *s);
  */
 BDS_API int bds_track(bds_ctx *ctx, const bds_settings *s, const char *path, int n_ch,
                       const bds_channel *channel, bds_track_out *out);
-/* Same, on an IF record already in host memory (n_bytes raw file bytes). */
+/* Same, on an IF record already in host memory (n_bytes raw file bytes; fileType 3: packed bytes, 2 n_bytes samples). */
 BDS_API int bds_track_mem(bds_ctx *ctx, const bds_settings *s, const int8_t *file_bytes,
                           size_t n_bytes, int n_ch, const bds_channel *channel,
                           bds_track_out *out);

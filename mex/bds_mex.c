@@ -10,7 +10,9 @@
  *
  * Usage from the drop-in wrappers in this directory:
  *   [carrFreq, codePhase, peakMetric, detected] = bds_mex('acquire', int8(longSignal), settings, signal, iq)
- *       iq (optional, default false): longSignal holds interleaved I/Q pairs (fileType 2)
+ *       iq (optional, default false): longSignal holds interleaved I/Q pairs (fileType 2);
+ *       iq = 2: longSignal is a uint8 array of packed bytes, two 2+2-bit I/Q samples each (fileType 3, the input of
+ *       B2a/include/unpack_cplx.m:18-30), as fread(fid, n/2, 'uint8=>uint8') returns them
  *   out = bds_mex('track', path, channel, settings, signal)        % struct of [nCh x nEpochs] arrays
  *   code = bds_mex('gen_code', signal, kind, prn)
  *   [XcorrResult, index] = bds_mex('frame_sync', signal, PRN, bits)   % one channel: second half of
@@ -28,6 +30,15 @@
 
 #include "bds_mi355x.h"
 #include "mex.h"
+
+/* The packed input of 'acquire' needs the uint8 part of the Matrix API.  MATLAB's mex defines MATLAB_MEX_FILE; a stand-in for
+ * the MEX runtime that declares mxIsUint8 / mxGetUint8s says so with BDS_MEX_HAVE_UINT8 (tests/mex_stub_packed); one that
+ * does not (tests/mex_stub) builds a gateway that refuses iq = 2. */
+#if defined(MATLAB_MEX_FILE) || defined(BDS_MEX_HAVE_UINT8)
+#define BDS_MEX_UINT8 1
+#else
+#define BDS_MEX_UINT8 0
+#endif
 
 /* One bds_multi for the MATLAB session: one GPU by default, BDS_MEX_DEVICES=n GPUs (0 = all visible).  Acquisition
  * goes through bds_acquire_multi (PRN shards + RCCL all-reduce inside the library); tracking, frame sync and the
@@ -124,10 +135,29 @@ static void do_acquire(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[
     bds_settings s;
     int max_prn = 0, i, rc, iq;
     mxArray *det;
-    if ((nrhs != 4 && nrhs != 5) || !mxIsInt8(prhs[1]))
-        mexErrMsgIdAndTxt("bds:args", "acquire: (int8 longSignal, settings, signal[, iq])");
-    iq = nrhs == 5 && mxGetScalar(prhs[4]) != 0;
+    const int8_t *samples;
+    size_t n_samples;
+    if (nrhs != 4 && nrhs != 5) mexErrMsgIdAndTxt("bds:args", "acquire: (int8 longSignal, settings, signal[, iq])");
+    iq = nrhs == 5 ? (int)mxGetScalar(prhs[4]) : 0;
+    if (iq == 2) { /* packed bytes: two samples each */
+#if BDS_MEX_UINT8
+        if (!mxIsUint8(prhs[1])) mexErrMsgIdAndTxt("bds:args", "acquire: iq = 2 takes a uint8 longSignal of packed bytes (fileType 3)");
+        if (mxGetNumberOfElements(prhs[1]) == 0) mexErrMsgIdAndTxt("bds:args", "acquire: longSignal holds 0 packed bytes");
+        samples = (const int8_t *)mxGetUint8s(prhs[1]);
+        n_samples = mxGetNumberOfElements(prhs[1]) * 2;
+#else
+        mexErrMsgIdAndTxt("bds:args", "acquire: iq = 2 (packed uint8 longSignal) is not built into this gateway");
+        return;
+#endif
+    } else {
+        if (!mxIsInt8(prhs[1])) mexErrMsgIdAndTxt("bds:args", "acquire: (int8 longSignal, settings, signal[, iq])");
+        iq = iq != 0;
+        samples = (const int8_t *)mxGetInt8s(prhs[1]);
+        n_samples = mxGetNumberOfElements(prhs[1]) / (iq ? 2 : 1);
+    }
     pack_settings(prhs[2], (int)mxGetScalar(prhs[3]), &s);
+    if ((iq == 2) != (s.fileType == 3))
+        mexErrMsgIdAndTxt("bds:args", "acquire: iq = 2 (packed uint8 longSignal) and settings.fileType = 3 go together");
     for (i = 0; i < s.n_acq; ++i)
         if (s.acqSatelliteList[i] > max_prn) max_prn = s.acqSatelliteList[i];
     plhs[0] = mxCreateDoubleMatrix(1, max_prn, mxREAL);
@@ -138,8 +168,8 @@ static void do_acquire(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[
         bds_acq_job job;
         memset(&job, 0, sizeof(job));
         job.settings = &s;
-        job.samples = (const int8_t *)mxGetInt8s(prhs[1]);
-        job.n_samples = mxGetNumberOfElements(prhs[1]) / (iq ? 2 : 1);
+        job.samples = samples;
+        job.n_samples = n_samples;
         job.is_complex = iq;
         job.max_prn = max_prn;
         job.carrFreq = mxGetDoubles(plhs[0]);
