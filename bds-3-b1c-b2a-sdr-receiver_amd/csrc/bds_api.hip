@@ -367,6 +367,7 @@ extern "C" int bds_acquire_track(bds_ctx *ctx, const bds_settings *s, const int8
                                  int max_prn, double *carrFreq, double *codePhase, double *peakMetric, int32_t *detected,
                                  const char *path, bds_channel *channel, bds_track_out *out) {
     if (!ctx || !s || !path || !channel || !out) return BDS_ERR_ARG;
+    if (int g = bds::track_session_guard(ctx, "bds_acquire_track")) return g;
     int rc = bds_acquire(ctx, s, samples, n_samples, is_complex, max_prn, carrFreq, codePhase, peakMetric, detected);
     if (rc) return rc;
     if ((rc = bds_pre_run_device(ctx, s, max_prn, carrFreq, codePhase, peakMetric, channel))) return rc;

@@ -83,6 +83,9 @@ struct TrackState;  // bds_track.hip
 void acq_state_free(AcqState *);
 void acq_state_invalidate(AcqState *);  // forget the configuration (plan, storage mode, cached spectra): re-derived by the next prepare
 void track_state_free(TrackState *);
+// BDS_OK, or BDS_ERR_ARG with a message naming the context's open tracking session: `who` (a one-shot tracking call, a
+// second bds_track_open*) cannot run beside it
+int track_session_guard(bds_ctx *ctx, const char *who);
 // bds_sync.hip: packed 2+2-bit I/Q bytes (unpack_cplx.m:18-30) -> int8 (I, Q) pairs, device to device on the context's stream
 int unpack_cplx_device(bds_ctx *ctx, const uint8_t *d_in, size_t n_bytes, int8_t *d_out);
 

@@ -27,6 +27,11 @@
 #include <cstdio>
 #include <cstdlib>
 #include <functional>
+#include <initializer_list>
+#include <memory>
+#include <mutex>
+#include <set>
+#include <string>
 #include <thread>
 #include <type_traits>
 
@@ -1081,10 +1086,16 @@ struct TrackState {
     int pieces = 0;           // loads of a part of the record (1: one window)
     size_t resident_max = 0;  // most bytes of the record resident at a time
     int repeated = 0;         // batches run again after the window guard fired
+    // the open tracking session of the context (at most one): it owns its channel states, launch geometry, span buffers and
+    // C/N0 carry, and counts its pieces / repeated batches in the three fields above from bds_track_open* on
+    bds_track_session *session = nullptr;
 };
+
+static void session_close(bds_track_session *h);
 
 void track_state_free(TrackState *t) {
     if (!t) return;
+    if (t->session) session_close(t->session);
     if (t->d_data) (void)hipFree(t->d_data);
     for (int8_t *q : t->d_span)
         if (q) (void)hipFree(q);
@@ -1269,6 +1280,82 @@ __global__ __launch_bounds__(256) void k_trk_cno(TrkOut o, const ChanState *__re
     }
 }
 
+// The same post-pass for ONE bds_track_advance of a session.  The call's arrays hold the `done` epochs the channel ran in this
+// call, and an interval may have begun in an earlier one, so the session keeps per channel
+//   carry   [4][M] = I_P, Q_P, Pilot_I_P, Pilot_Q_P of the unfinished interval (n_carry < M epochs each)
+//   prev3   the three raw values of the last finished interval, for the smoothing (0 before the first)
+// Interval q of the call (q < nd = (n_carry + done) / M) covers entries [q M, (q + 1) M) of the carried prompts followed by this
+// call's, in epoch order: the first is completed in the carry rows and evaluated there, the others lie whole in the call's
+// arrays -- cno_pld_one sees the M values k_trk_cno gives it in the one-shot call, in the same order, and the smoothing is
+// the same expression, so the values are the same bits.  What is left over becomes the new carry.
+__global__ __launch_bounds__(256) void k_trk_cno_seg(TrkOut o, const ChanState *__restrict__ st, int n_epochs, int M, int n_cno,
+                                                     int pm, double T, double *__restrict__ carry, int *__restrict__ n_carry,
+                                                     double *__restrict__ prev3, double *__restrict__ raw3,
+                                                     double *__restrict__ cno5) {
+    const int ch = blockIdx.x, n_ch = gridDim.x;
+    const int done = st[ch].prn ? st[ch].completed : 0;
+    const int nc = n_carry[ch];
+    const int nd = min((nc + done) / M, n_cno);  // (the host sized n_cno for every interval that can complete)
+    const size_t plane = (size_t)n_ch * n_cno, row = (size_t)ch * n_epochs;
+    double *cr = carry + (size_t)ch * 4 * M;
+    const double *src[4] = {o.I_P + row, o.Q_P + row, o.Pilot_I_P + row, o.Pilot_Q_P + row};
+    double *r = raw3 + (size_t)ch * n_cno * 3;
+    double *p3 = prev3 + (size_t)ch * 3;
+    for (int q = threadIdx.x; q < n_cno; q += blockDim.x)
+        for (int f = 0; f < 5; ++f) cno5[f * plane + (size_t)ch * n_cno + q] = 0;
+    const int fill = min(M - nc, nd > 0 ? M - nc : done);  // this call's epochs that belong to the carried interval
+    for (int i = threadIdx.x; i < fill; i += blockDim.x)
+        for (int f = 0; f < 4; ++f) cr[f * M + nc + i] = src[f][i];
+    __syncthreads();
+    for (int q = threadIdx.x; q < nd; q += blockDim.x) {
+        const size_t e = (size_t)ch * n_cno + q;
+        const int o0 = q * M - nc;  // (q > 0)
+        const double *I = q ? src[0] + o0 : cr, *Q = q ? src[1] + o0 : cr + M;
+        const double *PI = q ? src[2] + o0 : cr + 2 * M, *PQ = q ? src[3] + o0 : cr + 3 * M;
+        double dlin, dcno, dpld, plin = 0, pcno = 0, ppld = 0;
+        cno_pld_one(I, Q, M, T, &dlin, &dcno, &dpld);
+        if (pm == 2)
+            cno_pld_one(PI, PQ, M, T, &plin, &pcno, &ppld);
+        else if (pm == 1)
+            cno_pld_one(PQ, PI, M, T, &plin, &pcno, &ppld);
+        r[q * 3 + 0] = dcno;
+        r[q * 3 + 1] = pcno;
+        r[q * 3 + 2] = 10 * log10(dlin + plin);
+        cno5[1 * plane + e] = dpld;
+        if (pm) cno5[3 * plane + e] = ppld;
+    }
+    __syncthreads();
+    for (int q = threadIdx.x; q < nd; q += blockDim.x) {
+        const size_t e = (size_t)ch * n_cno + q;
+        const double p0 = q ? r[(q - 1) * 3 + 0] : p3[0], p1 = q ? r[(q - 1) * 3 + 1] : p3[1], p2 = q ? r[(q - 1) * 3 + 2] : p3[2];
+        cno5[0 * plane + e] = r[q * 3 + 0] * 0.5 + p0 * 0.5;
+        if (pm) {
+            cno5[2 * plane + e] = r[q * 3 + 1] * 0.5 + p1 * 0.5;
+            cno5[4 * plane + e] = r[q * 3 + 2] * 0.5 + p2 * 0.5;
+        }
+    }
+    __syncthreads();
+    if (nd > 0) {
+        const int left = nc + done - nd * M, o0 = nd * M - nc;
+        for (int i = threadIdx.x; i < left && i < M; i += blockDim.x)
+            for (int f = 0; f < 4; ++f) cr[f * M + i] = src[f][o0 + i];
+        if (threadIdx.x == 0) {
+            p3[0] = r[(nd - 1) * 3 + 0], p3[1] = r[(nd - 1) * 3 + 1], p3[2] = r[(nd - 1) * 3 + 2];
+            n_carry[ch] = min(left, M - 1);
+        }
+    } else if (threadIdx.x == 0) {
+        n_carry[ch] = min(nc + done, M - 1);
+    }
+}
+
+// the result arrays of a session's advance, one block of n_fields x n doubles, back to the reference's template values
+// (tracking.m:48-82): Inf where bit f of inf_mask is set, else 0
+__global__ void k_trk_fill_out(double *__restrict__ a, size_t n, int n_fields, uint32_t inf_mask) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n * n_fields) return;
+    a[i] = ((inf_mask >> (int)(i / n)) & 1u) ? INFINITY : 0.0;
+}
+
 // Source of the IF record: copies bytes [off, off + n) of the file into device memory at dst, ordered on `stream`.
 // (Streamed tracking calls it from its loader thread, with the context's second stream, while a batch of epochs runs.)
 using RecordLoader = std::function<int(size_t off, size_t n, int8_t *dst, hipStream_t stream)>;
@@ -1373,32 +1460,32 @@ struct SpanStream {
     }
 };
 
-// whole_file: load every byte (second attempt after a channel's reads left the window of the first)
-static int do_track(bds_ctx *ctx, const bds_settings *s, const RecordLoader &load, size_t n_bytes, int n_ch,
-                    const bds_channel *channel, bds_track_out *out, bool whole_file = false) {
-    if (!ctx || !s || !channel || !out) return BDS_ERR_ARG;
-    if (n_ch < 1 || out->n_ch != n_ch || out->n_epochs < 1) return fail(ctx, BDS_ERR_ARG, "bds_track: n_ch / n_epochs mismatch");
-    if (!out->completed || !out->status || !out->absoluteSample || !out->I_P || !out->Q_P)
-        return fail(ctx, BDS_ERR_ARG, "bds_track: required output arrays missing");
-    BDS_HIP(ctx, hipSetDevice(ctx->device));
-    if (!ctx->trk) ctx->trk = new TrackState();
-    TrackState &t = *ctx->trk;
+// ---- the three parts of a tracking call: set-up, "run one planned batch" (TrkRun::run_batch; run_streamed plans the batches of
+// the resident-span path), finish.  bds_track / bds_track_mem run them in sequence (do_track); a tracking session
+// (bds_track_open*) keeps what the first made and calls the second across bds_track_advance calls.
+
+// Set-up: parameters, code tables, the channel states the acquisition's table gives (tracking.m:170-188), the correlate grid.
+// Nothing of it depends on the number of epochs, so a session gets the geometry of the one-shot call on the same channels.
+struct TrkSetup {
     TrkParams p{};
-    const int n_epochs = out->n_epochs;
+    std::vector<ChanState> hs;
+    int nblocks = 0;
+    bool any_live = false;
+};
+static int track_setup(bds_ctx *ctx, TrackState &t, const bds_settings *s, int n_epochs, size_t n_bytes, int n_ch,
+                       const bds_channel *channel, TrkSetup &u) {
+    TrkParams &p = u.p;
     int rc = fill_params(ctx, *s, p, n_epochs, n_bytes);
     if (rc) return rc;
     if ((rc = ensure_prim(ctx, t, s->signal))) return rc;
     // channel state (tracking.m:170-188)
-    std::vector<ChanState> hs((size_t)n_ch);
-    const double max_step_inv = 0;
-    (void)max_step_inv;
+    std::vector<ChanState> &hs = u.hs;
+    hs.assign((size_t)n_ch, ChanState{});
     double min_code_freq = 1e300;
     for (int c = 0; c < n_ch; ++c) {
         ChanState &cs = hs[c];
         memset(&cs, 0, sizeof(cs));
         cs.prn = channel[c].PRN;
-        out->completed[c] = 0;
-        out->status[c] = '-';
         if (cs.prn == 0) continue;
         if (cs.prn < 1 || cs.prn > BDS_MAX_PRN) return fail(ctx, BDS_ERR_ARG, "channel(%d).PRN = %d out of range", c + 1, cs.prn);
         cs.active = 1;
@@ -1408,6 +1495,7 @@ static int do_track(bds_ctx *ctx, const bds_settings *s, const RecordLoader &loa
         if (cs.pos < 0) return fail(ctx, BDS_ERR_ARG, "channel(%d): negative file offset", c + 1);
         if (!(cs.codeFreq > 0)) return fail(ctx, BDS_ERR_ARG, "channel(%d).codeFreq must be > 0", c + 1);
         min_code_freq = std::min(min_code_freq, cs.codeFreq);
+        u.any_live = true;
     }
     // correlate grid: blksize stays near codeLength*fs/codeFreq; sized for code rates down to 2 % below the slowest
     // channel's (a longer block is walked by the same workgroups in further strides)
@@ -1425,6 +1513,229 @@ static int do_track(bds_ctx *ctx, const bds_settings *s, const RecordLoader &loa
         }
     }
     if (ctx->tune.trk_nblocks > 0) nblocks = ctx->tune.trk_nblocks;
+    u.nblocks = nblocks;
+    return BDS_OK;
+}
+
+// The planning rules of the resident-span path: how far the channels can get inside a span of the record.
+static constexpr long long kNoEnd = 1LL << 36;  // "epochs still to run" of a call without a preset end (a session)
+struct TrkPlanner {
+    const bds_settings *s;
+    const TrkParams &p;
+    int n_ch;
+    bool packed;
+    // margin of a streamed batch's plan, in worst-case blocks kept behind the start of a channel's last planned epoch: 1 is
+    // the window's own rule (n blocks at a code rate 2 % low fit); the guard of the update kernel catches a plan that was
+    // too tight, and the batch is repeated with the margin doubled
+    double margin;
+    TrkPlanner(bds_ctx *ctx, const bds_settings *st, const TrkParams &pp, int nc)
+        : s(st), p(pp), n_ch(nc), packed(pp.cplx == kFmtPacked), margin(ctx->tune.trk_stream_margin >= 0 ? ctx->tune.trk_stream_margin : 1.0) {}
+    // bounds of a block while the channel's code rate stays within 2 % of f: hi is the rule the window is sized with
+    long long blk_hi(double f) const { return (long long)((long)std::ceil((double)s->codeLength / (f * 0.98 / s->samplingFreq)) + 2); }
+    long long blk_lo(double f) const { return std::max(1LL, (long long)std::floor((double)s->codeLength / (f * 1.02 / s->samplingFreq)) - 2); }
+    // one past the last sample the `remaining` epochs still to run can touch
+    long long need_end(const std::vector<ChanState> &v, long long remaining) const {
+        long long e = 0;
+        for (int c = 0; c < n_ch; ++c) {
+            if (v[c].active != 1) continue;
+            const long long B = blk_hi(v[c].codeFreq);
+            e = std::max(e, v[c].pos + (remaining - 1) * B + (long long)std::ceil(std::max(1.0, margin) * (double)B));
+        }
+        if (packed) e = (e + 1) & ~1LL;  // (p.n_bytes is even)
+        return std::min(e, p.n_bytes);
+    }
+    // epochs (n_max at the most) every live channel can take inside the span
+    long long plan(const std::vector<ChanState> &v, const SpanStream::Span &sp, double m, long long n_max) const {
+        long long n = n_max;
+        for (int c = 0; c < n_ch; ++c) {
+            if (v[c].active != 1) continue;
+            if (v[c].pos < sp.base) return 0LL;
+            if (sp.end >= p.n_bytes) continue;  // the span reaches the end of the file: a block past it is a short read
+            const long long B = blk_hi(v[c].codeFreq), Blo = blk_lo(v[c].codeFreq);
+            const long long per = m >= 1 ? B : Blo + (long long)(m * (double)(B - Blo));
+            const long long room = sp.end - v[c].pos - std::max(1LL, (long long)std::ceil(m * (double)B));
+            n = std::min(n, room < 0 ? 0LL : room / per + 1);
+        }
+        return n;
+    }
+    long long live_min_pos(const std::vector<ChanState> &v) const {
+        long long m = p.n_bytes;
+        for (int c = 0; c < n_ch; ++c)
+            if (v[c].active == 1) m = std::min(m, v[c].pos);
+        return m;
+    }
+    // samples a span buffer must hold at the least, from the aligned smallest position base0
+    long long min_half(const std::vector<ChanState> &hs, long long base0, long long al) const {
+        long long need = 0, hi_max = 0, lo_min = p.n_bytes + 1;
+        for (int c = 0; c < n_ch; ++c) {
+            if (hs[c].active != 1) continue;
+            const long long B = blk_hi(hs[c].codeFreq);
+            need = std::max(need, std::min(hs[c].pos + B, p.n_bytes) - base0);
+            hi_max = std::max(hi_max, B), lo_min = std::min(lo_min, blk_lo(hs[c].codeFreq));
+        }
+        return (std::max(0LL, need) + std::max(0LL, hi_max - lo_min) + al + al - 1) & ~(al - 1);
+    }
+};
+
+// The device side of the epoch loop (buffers owned by the caller) and "run one planned batch".
+struct TrkRun {
+    bds_ctx *ctx;
+    TrackState &t;
+    TrkParams &p;      // base / win_end follow the span of the batch; n_epochs is the row length of the result arrays
+    ChanState *d_st;   // [2][n_ch]: state and partial sums ping-pong between two halves (fuse) ...
+    double *d_part;    // [2][part_n]
+    size_t part_n;
+    TrkOut d;          // device result arrays [n_ch][p.n_epochs]
+    TrkOut *d_out;     // the same table in device memory
+    int nblocks, n_ch;
+    bool fuse;
+    ChanState *st_final;  // where the state ends up
+
+    void launch_update(ChanState *stp, const double *partp, int k) {
+        switch (p.mode) {
+            case BDS_TRACK_B2A:
+                hipLaunchKernelGGL(k_trk_update<BDS_TRACK_B2A>, dim3(n_ch), dim3(kUpdThreads), 0, st(ctx), p, stp, partp, nblocks, k, d);
+                break;
+            case BDS_TRACK_NB:
+                hipLaunchKernelGGL(k_trk_update<BDS_TRACK_NB>, dim3(n_ch), dim3(kUpdThreads), 0, st(ctx), p, stp, partp, nblocks, k, d);
+                break;
+            default:
+                hipLaunchKernelGGL(k_trk_update<BDS_TRACK_WB>, dim3(n_ch), dim3(kUpdThreads), 0, st(ctx), p, stp, partp, nblocks, k, d);
+                break;
+        }
+    }
+    // epochs k0 .. k0 + n - 1 on span `sp`, from the state in half `slot` of d_st; the state ends up at st_final.  The last
+    // epoch of a batch is closed by k_trk_update, the first one carries no update
+    void run_batch(const SpanStream::Span &sp, int k0, int n, int slot) {
+        p.base = sp.base, p.win_end = sp.end;
+        const int8_t *data = sp.buf;
+        const dim3 gc(nblocks, n_ch);
+        for (int k = k0; k < k0 + n; ++k) {
+            if (fuse) {
+                const int curh = (slot + k - k0) & 1;
+                ChanState *st_in = d_st + (size_t)curh * n_ch, *st_out = d_st + (size_t)(curh ^ 1) * n_ch;
+                const double *part_prev = k > k0 ? d_part + (size_t)(curh ^ 1) * part_n : nullptr;
+                double *part_cur = d_part + (size_t)curh * part_n;
+                BDS_TRK_LAUNCH(k_trk_correlate, gc, (p.runs ? runs_lds_bytes(p.runs, p.prec) : 0), st(ctx), data, (const int8_t *)t.d_prim, p,
+                               (const ChanState *)st_in, st_out, part_prev, part_cur, nblocks, k, (const TrkOut *)d_out);
+                st_final = st_out;
+                if (k == k0 + n - 1) launch_update(st_final, part_cur, k);  // the last epoch's update has no next launch to ride on
+            } else {
+                ChanState *stp = d_st + (size_t)slot * n_ch;
+                BDS_TRK_LAUNCH(k_trk_correlate, gc, (p.runs ? runs_lds_bytes(p.runs, p.prec) : 0), st(ctx), data, (const int8_t *)t.d_prim, p,
+                               (const ChanState *)stp, stp, (const double *)nullptr, d_part, nblocks, k, (const TrkOut *)d_out);
+                launch_update(stp, d_part, k);
+                st_final = stp;
+            }
+        }
+    }
+};
+
+// Streamed: epochs k .. n_call - 1 of a call in batches on the resident span.  At a batch boundary the host reads the channel
+// states back, moves on to the span whose tail the loader thread filled meanwhile (the overlap with the current span is carried
+// device-to-device) and enqueues as many epochs as every live channel can take inside it.  `hs` is the state at epoch k on
+// entry (in half `slot` of d_st) and the state reached on return; the loop also ends when no channel is live any more.
+//   open_end  the run has no preset end (a session): the span is sized and the next one prefetched for the record, not the call
+//   feed      the span holds what the caller has fed so far and only the caller extends it: the loop ends (no error) at the
+//             first plan that gives no epoch
+static int run_streamed(TrkRun &run, TrkPlanner &pl, SpanStream &ss, std::vector<ChanState> &hs, int n_call, bool open_end,
+                        bool feed, int &slot, int &k) {
+    bds_ctx *ctx = run.ctx;
+    TrackState &t = run.t;
+    const TrkParams &p = run.p;
+    const int n_ch = run.n_ch;
+    const long long al = fmt_align(ss.fmt), span_n = ss.span_n;
+    double &margin = pl.margin;
+    int rc;
+    std::vector<ChanState> h0;
+    while (k < n_call) {
+        bool live = false;
+        for (int c = 0; c < n_ch; ++c) live |= hs[c].active == 1;
+        if (!live) break;
+        const long long remaining = open_end ? kNoEnd : n_call - k;
+        const long long minp = pl.live_min_pos(hs);
+        if (ss.pre_valid && minp >= ss.pre_nb && (rc = ss.move_to(ss.pre_nb, ss.pre_hi, true))) return rc;
+        long long n = pl.plan(hs, ss.cur, margin, open_end ? kNoEnd : n_call);
+        if (n == 0 && feed) break;
+        if (n == 0) {  // no prefetched span, or the channels are not where it was predicted: a span from their smallest position
+            const long long nb = minp & ~(al - 1), hi = std::max(nb, std::min(nb + span_n, pl.need_end(hs, remaining)));
+            ss.pre_valid = false;
+            if (nb != ss.cur.base || hi > ss.cur.end) {
+                if ((rc = ss.move_to(nb, hi, false))) return rc;
+                n = pl.plan(hs, ss.cur, margin, open_end ? kNoEnd : n_call);
+            }
+            if (n == 0) {
+                long long need = 0;
+                for (int c = 0; c < n_ch; ++c)
+                    if (hs[c].active == 1)
+                        need = std::max(need, hs[c].pos - nb + (long long)std::ceil(std::max(1.0, margin) * (double)pl.blk_hi(hs[c].codeFreq)));
+                return fail(ctx, BDS_ERR_ARG, "epoch %d: the resident span of %lld bytes (half the resident limit) cannot hold the channels' spread of positions "
+                            "plus a block any more: it needs %lld bytes", k + 1, ss.nb_of(span_n), ss.nb_of((need + 2 * al - 1) & ~(al - 1)));
+            }
+        }
+        // (a call without a preset end prefetches only when this batch uses the span up)
+        const bool more = open_end ? n <= n_call - k : k + n < n_call;
+        n = std::min<long long>(n, n_call - k);
+        const long long want_end = pl.need_end(hs, remaining);
+        if (!feed && !ss.pre_valid && more && ss.cur.end < want_end) {
+            // the next span starts where the slowest channel is after the epochs a plan at the regular margin gives this
+            // span, at the shortest blocks a code rate within 2 % allows: never past a channel, and still right when
+            // this batch has to be repeated
+            const long long n_safe = std::min(n, pl.plan(hs, ss.cur, std::max(margin, 1.0), open_end ? kNoEnd : n_call));
+            long long nb = p.n_bytes;
+            for (int c = 0; c < n_ch; ++c)
+                if (hs[c].active == 1) nb = std::min(nb, hs[c].pos + n_safe * pl.blk_lo(hs[c].codeFreq));
+            nb = std::max(ss.cur.base, nb & ~(al - 1));
+            const long long hi = std::min(nb + span_n, want_end);
+            if (nb <= ss.cur.end && hi > ss.cur.end) ss.predict(nb, hi);
+        }
+        h0 = hs;
+        run.run_batch(ss.cur, k, (int)n, slot);
+        // (from here to join() the loader may report an error of its own: codes are kept and reported after it)
+        const hipError_t e_launch = hipGetLastError();
+        if (e_launch == hipSuccess) ss.start_load();
+        const hipError_t e_copy = e_launch == hipSuccess ? hipMemcpyAsync(hs.data(), run.st_final, sizeof(ChanState) * n_ch, hipMemcpyDeviceToHost, st(ctx)) : e_launch;
+        const hipError_t e_sync = e_copy == hipSuccess ? hipStreamSynchronize(st(ctx)) : e_copy;
+        if ((rc = ss.join())) return rc;
+        BDS_HIP(ctx, e_sync);
+        bool left = false;
+        for (int c = 0; c < n_ch; ++c) left |= hs[c].active == -2;
+        if (left) {
+            // a block reached past the span (or a channel fell behind it): the batch runs again from the state it
+            // started with -- the kernels are deterministic, what it rewrites is identical -- with a wider margin
+            t.repeated += 1;
+            margin = margin < 1 ? 1.0 : margin * 2;
+            if (margin > 64) return fail(ctx, BDS_ERR_HIP, "bds_track: epoch %d: a channel keeps leaving the resident span of the record", k + 1);
+            hs = h0;
+            BDS_HIP(ctx, hipMemcpyAsync(run.d_st + (size_t)slot * n_ch, hs.data(), sizeof(ChanState) * n_ch, hipMemcpyHostToDevice, st(ctx)));
+            BDS_HIP(ctx, hipStreamSynchronize(st(ctx)));
+            continue;
+        }
+        slot = (int)((run.st_final - run.d_st) / n_ch);
+        k += (int)n;
+    }
+    return BDS_OK;
+}
+
+// whole_file: load every byte (second attempt after a channel's reads left the window of the first)
+static int do_track(bds_ctx *ctx, const bds_settings *s, const RecordLoader &load, size_t n_bytes, int n_ch,
+                    const bds_channel *channel, bds_track_out *out, bool whole_file = false) {
+    if (!ctx || !s || !channel || !out) return BDS_ERR_ARG;
+    if (n_ch < 1 || out->n_ch != n_ch || out->n_epochs < 1) return fail(ctx, BDS_ERR_ARG, "bds_track: n_ch / n_epochs mismatch");
+    if (!out->completed || !out->status || !out->absoluteSample || !out->I_P || !out->Q_P)
+        return fail(ctx, BDS_ERR_ARG, "bds_track: required output arrays missing");
+    if (int g = track_session_guard(ctx, "bds_track")) return g;
+    BDS_HIP(ctx, hipSetDevice(ctx->device));
+    if (!ctx->trk) ctx->trk = new TrackState();
+    TrackState &t = *ctx->trk;
+    const int n_epochs = out->n_epochs;
+    for (int c = 0; c < n_ch; ++c) out->completed[c] = 0, out->status[c] = '-';
+    TrkSetup u;
+    int rc = track_setup(ctx, t, s, n_epochs, n_bytes, n_ch, channel, u);
+    if (rc) return rc;
+    TrkParams &p = u.p;
+    std::vector<ChanState> &hs = u.hs;
+    const int nblocks = u.nblocks;
     // Only the part of the record the channels can touch goes to HBM: from the earliest start sample to the latest
     // start + n_epochs blocks at a code rate 2 % low (the reference streams blksize samples per epoch with fread,
     // tracking.m:237-240; a recording is usually far longer than msToProcess).  End-of-file is still judged against
@@ -1438,50 +1749,14 @@ static int do_track(bds_ctx *ctx, const bds_settings *s, const RecordLoader &loa
     const long long al = fmt_align(fmt);
     const bool packed = fmt == kFmtPacked;
     auto nb_of = [&](long long n) { return fmt_bytes(fmt, n); };
-    // bounds of a block while the channel's code rate stays within 2 % of f: hi is the rule the window is sized with
-    auto blk_hi = [&](double f) { return (long long)((long)std::ceil((double)s->codeLength / (f * 0.98 / s->samplingFreq)) + 2); };
-    auto blk_lo = [&](double f) { return std::max(1LL, (long long)std::floor((double)s->codeLength / (f * 1.02 / s->samplingFreq)) - 2); };
-    bool any_live = false;
-    for (int c = 0; c < n_ch; ++c) any_live |= hs[c].active == 1;
+    const bool any_live = u.any_live;
     bool stream = false;
     using Span = SpanStream::Span;
     Span cur, nxt;  // one window: cur is the window; streamed: the two span buffers, handed to a SpanStream below
     long long span_n = 0;  // samples a span buffer holds
-    // margin of a streamed batch's plan, in worst-case blocks kept behind the start of a channel's last planned epoch: 1 is
-    // the window's own rule (n blocks at a code rate 2 % low fit); the guard of the update kernel catches a plan that was
-    // too tight, and the batch is repeated with the margin doubled
-    double margin = ctx->tune.trk_stream_margin >= 0 ? ctx->tune.trk_stream_margin : 1.0;
-    // one past the last sample the remaining epochs (k done) can touch
-    auto need_end = [&](const std::vector<ChanState> &v, int k) {
-        long long e = 0;
-        for (int c = 0; c < n_ch; ++c) {
-            if (v[c].active != 1) continue;
-            const long long B = blk_hi(v[c].codeFreq);
-            e = std::max(e, v[c].pos + (long long)(n_epochs - k - 1) * B + (long long)std::ceil(std::max(1.0, margin) * (double)B));
-        }
-        if (packed) e = (e + 1) & ~1LL;  // (p.n_bytes is even)
-        return std::min(e, p.n_bytes);
-    };
-    // epochs every live channel can take inside the span
-    auto plan = [&](const std::vector<ChanState> &v, const Span &sp, double m) {
-        long long n = n_epochs;
-        for (int c = 0; c < n_ch; ++c) {
-            if (v[c].active != 1) continue;
-            if (v[c].pos < sp.base) return 0LL;
-            if (sp.end >= p.n_bytes) continue;  // the span reaches the end of the file: a block past it is a short read
-            const long long B = blk_hi(v[c].codeFreq), Blo = blk_lo(v[c].codeFreq);
-            const long long per = m >= 1 ? B : Blo + (long long)(m * (double)(B - Blo));
-            const long long room = sp.end - v[c].pos - std::max(1LL, (long long)std::ceil(m * (double)B));
-            n = std::min(n, room < 0 ? 0LL : room / per + 1);
-        }
-        return n;
-    };
-    auto live_min_pos = [&](const std::vector<ChanState> &v) {
-        long long m = p.n_bytes;
-        for (int c = 0; c < n_ch; ++c)
-            if (v[c].active == 1) m = std::min(m, v[c].pos);
-        return m;
-    };
+    TrkPlanner pl(ctx, s, p, n_ch);
+    auto blk_hi = [&](double f) { return pl.blk_hi(f); };
+    auto need_end = [&](const std::vector<ChanState> &v, int k) { return pl.need_end(v, n_epochs - k); };
     {
         long long first = p.n_bytes, last = 0;
         for (int c = 0; c < n_ch; ++c) {
@@ -1522,15 +1797,8 @@ static int do_track(bds_ctx *ctx, const bds_settings *s, const RecordLoader &loa
             // A span must hold, from the (16-sample aligned; packed: 32) smallest position, every channel's position plus one block
             // at a code rate 2 % low, plus what the start of the NEXT span -- predicted at a code rate 2 % high while
             // this one is in use -- can fall behind the channels in one epoch.
-            const long long base0 = live_min_pos(hs) & ~(al - 1);
-            long long need = 0, hi_max = 0, lo_min = p.n_bytes + 1;
-            for (int c = 0; c < n_ch; ++c) {
-                if (hs[c].active != 1) continue;
-                const long long B = blk_hi(hs[c].codeFreq);
-                need = std::max(need, std::min(hs[c].pos + B, p.n_bytes) - base0);
-                hi_max = std::max(hi_max, B), lo_min = std::min(lo_min, blk_lo(hs[c].codeFreq));
-            }
-            const long long min_half = (std::max(0LL, need) + std::max(0LL, hi_max - lo_min) + al + al - 1) & ~(al - 1);
+            const long long base0 = pl.live_min_pos(hs) & ~(al - 1);
+            const long long min_half = pl.min_half(hs, base0, al);
             const size_t min_limit = (size_t)nb_of(2 * min_half);
             size_t limit = t.resident_limit;
             if (!limit || wbytes <= limit) {  // no limit that applies: the window allocation failed
@@ -1620,123 +1888,21 @@ static int do_track(bds_ctx *ctx, const bds_settings *s, const RecordLoader &loa
     BDS_HIP(ctx, hipEventCreate(&ev1));
     scope.ev.push_back(ev1);
     BDS_HIP(ctx, hipEventRecord(ev0, st(ctx)));
-    dim3 gc(nblocks, n_ch);
     TrkOut *d_out = nullptr;  // the table of result arrays, for the correlate launches that carry the previous epoch's update
     BDS_HIP(ctx, hipMalloc((void **)&d_out, sizeof(TrkOut)));
     scope.add(d_out);
     BDS_HIP(ctx, hipMemcpyAsync(d_out, &d, sizeof(TrkOut), hipMemcpyHostToDevice, st(ctx)));
-    auto launch_update = [&](ChanState *stp, const double *partp, int k) {
-        switch (p.mode) {
-            case BDS_TRACK_B2A:
-                hipLaunchKernelGGL(k_trk_update<BDS_TRACK_B2A>, dim3(n_ch), dim3(kUpdThreads), 0, st(ctx), p, stp, partp, nblocks, k, d);
-                break;
-            case BDS_TRACK_NB:
-                hipLaunchKernelGGL(k_trk_update<BDS_TRACK_NB>, dim3(n_ch), dim3(kUpdThreads), 0, st(ctx), p, stp, partp, nblocks, k, d);
-                break;
-            default:
-                hipLaunchKernelGGL(k_trk_update<BDS_TRACK_WB>, dim3(n_ch), dim3(kUpdThreads), 0, st(ctx), p, stp, partp, nblocks, k, d);
-                break;
-        }
-    };
-    ChanState *st_final = d_st;  // where the state ends up
+    TrkRun run{ctx, t, p, d_st, d_part, part_n, d, d_out, nblocks, n_ch, fuse, d_st};
     RoctxRange rg_epochs("trk.epoch_loop");
-    // epochs k0 .. k0 + n - 1 on span `sp`, from the state in half `slot` of d_st; the state ends up at st_final.  The last
-    // epoch of a batch is closed by k_trk_update, the first one carries no update
-    auto run_batch = [&](const Span &sp, int k0, int n, int slot) {
-        p.base = sp.base, p.win_end = sp.end;
-        const int8_t *data = sp.buf;
-        for (int k = k0; k < k0 + n; ++k) {
-            if (fuse) {
-                const int curh = (slot + k - k0) & 1;
-                ChanState *st_in = d_st + (size_t)curh * n_ch, *st_out = d_st + (size_t)(curh ^ 1) * n_ch;
-                const double *part_prev = k > k0 ? d_part + (size_t)(curh ^ 1) * part_n : nullptr;
-                double *part_cur = d_part + (size_t)curh * part_n;
-                BDS_TRK_LAUNCH(k_trk_correlate, gc, (p.runs ? runs_lds_bytes(p.runs, p.prec) : 0), st(ctx), data, (const int8_t *)t.d_prim, p,
-                               (const ChanState *)st_in, st_out, part_prev, part_cur, nblocks, k, (const TrkOut *)d_out);
-                st_final = st_out;
-                if (k == k0 + n - 1) launch_update(st_final, part_cur, k);  // the last epoch's update has no next launch to ride on
-            } else {
-                ChanState *stp = d_st + (size_t)slot * n_ch;
-                BDS_TRK_LAUNCH(k_trk_correlate, gc, (p.runs ? runs_lds_bytes(p.runs, p.prec) : 0), st(ctx), data, (const int8_t *)t.d_prim, p,
-                               (const ChanState *)stp, stp, (const double *)nullptr, d_part, nblocks, k, (const TrkOut *)d_out);
-                launch_update(stp, d_part, k);
-                st_final = stp;
-            }
-        }
-    };
     if (!stream) {
-        run_batch(cur, 0, n_epochs, 0);
+        run.run_batch(cur, 0, n_epochs, 0);
     } else {
-        // Streamed: batches of epochs on the resident span.  At a batch boundary the host reads the channel states back,
-        // moves on to the span whose tail the loader thread filled meanwhile (the overlap with the current span is carried
-        // device-to-device) and enqueues as many epochs as every live channel can take inside it.
         SpanStream ss(ctx, t, load, st(ctx), ctx->stream2 ? (hipStream_t)ctx->stream2 : st(ctx), fmt, span_n);
         ss.cur = cur, ss.nxt = nxt;
         int slot = 0, k = 0;
-        std::vector<ChanState> h0;
-        while (k < n_epochs) {
-            bool live = false;
-            for (int c = 0; c < n_ch; ++c) live |= hs[c].active == 1;
-            if (!live) break;
-            const long long minp = live_min_pos(hs);
-            if (ss.pre_valid && minp >= ss.pre_nb && (rc = ss.move_to(ss.pre_nb, ss.pre_hi, true))) return rc;
-            long long n = plan(hs, ss.cur, margin);
-            if (n == 0) {  // no prefetched span, or the channels are not where it was predicted: a span from their smallest position
-                const long long nb = minp & ~(al - 1), hi = std::max(nb, std::min(nb + span_n, need_end(hs, k)));
-                ss.pre_valid = false;
-                if (nb != ss.cur.base || hi > ss.cur.end) {
-                    if ((rc = ss.move_to(nb, hi, false))) return rc;
-                    n = plan(hs, ss.cur, margin);
-                }
-                if (n == 0) {
-                    long long need = 0;
-                    for (int c = 0; c < n_ch; ++c)
-                        if (hs[c].active == 1)
-                            need = std::max(need, hs[c].pos - nb + (long long)std::ceil(std::max(1.0, margin) * (double)blk_hi(hs[c].codeFreq)));
-                    return fail(ctx, BDS_ERR_ARG, "epoch %d: the resident span of %lld bytes (half the resident limit) cannot hold the channels' spread of positions "
-                                "plus a block any more: it needs %lld bytes", k + 1, nb_of(span_n), nb_of((need + 2 * al - 1) & ~(al - 1)));
-                }
-            }
-            n = std::min<long long>(n, n_epochs - k);
-            const long long want_end = need_end(hs, k);
-            if (!ss.pre_valid && k + n < n_epochs && ss.cur.end < want_end) {
-                // the next span starts where the slowest channel is after the epochs a plan at the regular margin gives this
-                // span, at the shortest blocks a code rate within 2 % allows: never past a channel, and still right when
-                // this batch has to be repeated
-                const long long n_safe = std::min(n, plan(hs, ss.cur, std::max(margin, 1.0)));
-                long long nb = p.n_bytes;
-                for (int c = 0; c < n_ch; ++c)
-                    if (hs[c].active == 1) nb = std::min(nb, hs[c].pos + n_safe * blk_lo(hs[c].codeFreq));
-                nb = std::max(ss.cur.base, nb & ~(al - 1));
-                const long long hi = std::min(nb + span_n, want_end);
-                if (nb <= ss.cur.end && hi > ss.cur.end) ss.predict(nb, hi);
-            }
-            h0 = hs;
-            run_batch(ss.cur, k, (int)n, slot);
-            // (from here to join() the loader may report an error of its own: codes are kept and reported after it)
-            const hipError_t e_launch = hipGetLastError();
-            if (e_launch == hipSuccess) ss.start_load();
-            const hipError_t e_copy = e_launch == hipSuccess ? hipMemcpyAsync(hs.data(), st_final, sizeof(ChanState) * n_ch, hipMemcpyDeviceToHost, st(ctx)) : e_launch;
-            const hipError_t e_sync = e_copy == hipSuccess ? hipStreamSynchronize(st(ctx)) : e_copy;
-            if ((rc = ss.join())) return rc;
-            BDS_HIP(ctx, e_sync);
-            bool left = false;
-            for (int c = 0; c < n_ch; ++c) left |= hs[c].active == -2;
-            if (left) {
-                // a block reached past the span (or a channel fell behind it): the batch runs again from the state it
-                // started with -- the kernels are deterministic, what it rewrites is identical -- with a wider margin
-                t.repeated += 1;
-                margin = margin < 1 ? 1.0 : margin * 2;
-                if (margin > 64) return fail(ctx, BDS_ERR_HIP, "bds_track: epoch %d: a channel keeps leaving the resident span of the record", k + 1);
-                hs = h0;
-                BDS_HIP(ctx, hipMemcpyAsync(d_st + (size_t)slot * n_ch, hs.data(), sizeof(ChanState) * n_ch, hipMemcpyHostToDevice, st(ctx)));
-                BDS_HIP(ctx, hipStreamSynchronize(st(ctx)));
-                continue;
-            }
-            slot = (int)((st_final - d_st) / n_ch);
-            k += (int)n;
-        }
+        if ((rc = run_streamed(run, pl, ss, hs, n_epochs, false, false, slot, k))) return rc;
     }
+    ChanState *st_final = run.st_final;
     BDS_HIP(ctx, hipGetLastError());
     BDS_HIP(ctx, hipEventRecord(ev1, st(ctx)));
     BDS_HIP(ctx, hipMemcpyAsync(hs.data(), st_final, sizeof(ChanState) * n_ch, hipMemcpyDeviceToHost, st(ctx)));
@@ -1809,7 +1975,383 @@ static int do_track(bds_ctx *ctx, const bds_settings *s, const RecordLoader &loa
 
 }  // namespace bds
 
+// ---- tracking sessions (bds_track_open* .. bds_track_close) ---------------------------------------------------------------
+// A session is the batch boundary of the resident-span path made public: between two bds_track_advance calls the host holds
+// the ChanState of every channel, the first epoch of an advance carries no update and the last is closed by k_trk_update.
+// Geometry (nblocks, chunk, SEG) is what track_setup gives the one-shot call on the same channels and settings -- the
+// fixed-order sum of the partial sums depends on it --, so the concatenated arrays equal that call's bit for bit.
+struct bds_track_session {
+    bds_ctx *ctx = nullptr;
+    bds_settings s{};
+    int n_ch = 0;
+    bds::TrkSetup u;        // parameters, host copy of the channel states (completed: epochs of the CURRENT advance), grid
+    double margin = 1.0;    // of the batch plans; doubled for good when the window guard fires
+    std::vector<long long> epochs_done;
+    // the record
+    bool feed = false, fed_last = false;
+    const int8_t *mem = nullptr;
+    FILE *file = nullptr;
+    void *pin = nullptr;
+    size_t pin_bytes = 0;
+    std::string path;
+    bds::RecordLoader load;
+    std::unique_ptr<bds::SpanStream> ss;
+    int8_t *span[2] = {nullptr, nullptr};
+    // the epoch loop's device buffers
+    bds::ChanState *d_st = nullptr;
+    double *d_part = nullptr;
+    size_t part_n = 0;
+    int slot = 0;
+    bds::TrkOut d{};
+    bds::TrkOut *d_out = nullptr;
+    double *d_fields = nullptr;  // one block [21][n_ch][row]: the result arrays of an advance
+    size_t fields_cap = 0;
+    int row = 0;                 // row length the table at d_out was made for
+    uint32_t inf_mask = 0;
+    std::vector<double> h_fields;
+    // C/N0 carry (k_trk_cno_seg)
+    double *d_carry = nullptr, *d_prev3 = nullptr, *d_raw = nullptr, *d_cno = nullptr;
+    int *d_ncarry = nullptr;
+    int cno_cap = 0;
+};
+
+namespace bds {
+
+static constexpr size_t kSessionResident = (size_t)256 << 20;  // resident limit of a session when the context has none
+static constexpr long long kFeedOpen = 1LL << 60;              // "samples in the record" while a feed session has not seen `last`
+
+static std::mutex g_sess_mu;
+static std::set<const bds_track_session *> g_sessions;  // handles that are open: anything else is refused unread
+static bds_track_session *live_session(bds_track_session *h) {
+    std::lock_guard<std::mutex> lk(g_sess_mu);
+    return h && g_sessions.count(h) ? h : nullptr;
+}
+
+int track_session_guard(bds_ctx *ctx, const char *who) {
+    if (!ctx || !ctx->trk || !ctx->trk->session) return BDS_OK;
+    const bds_track_session *h = ctx->trk->session;
+    return fail(ctx, BDS_ERR_ARG, "%s: the context has an open tracking session (%d channels on %s): bds_track_close it first", who, h->n_ch,
+                h->feed ? "a fed record" : h->mem ? "a record in memory" : h->path.c_str());
+}
+
+static void session_close(bds_track_session *h) {
+    {
+        std::lock_guard<std::mutex> lk(g_sess_mu);
+        g_sessions.erase(h);
+    }
+    bds_ctx *ctx = h->ctx;
+    (void)hipSetDevice(ctx->device);
+    h->ss.reset();  // joins the loader
+    (void)hipStreamSynchronize(st(ctx));
+    if (ctx->stream2) (void)hipStreamSynchronize((hipStream_t)ctx->stream2);
+    for (void *q : {(void *)h->span[0], (void *)h->span[1], (void *)h->d_st, (void *)h->d_part, (void *)h->d_out, (void *)h->d_fields,
+                    (void *)h->d_carry, (void *)h->d_prev3, (void *)h->d_raw, (void *)h->d_cno, (void *)h->d_ncarry})
+        if (q) (void)hipFree(q);
+    if (h->pin) (void)hipHostFree(h->pin);
+    if (h->file) fclose(h->file);
+    if (ctx->trk && ctx->trk->session == h) ctx->trk->session = nullptr;
+    delete h;
+}
+
+// kind: 0 file at `path`, 1 `n_bytes` bytes at `mem`, 2 fed by the caller from sample `origin` on
+static bds_track_session *session_open(bds_ctx *ctx, const bds_settings *s, int kind, const char *path, const int8_t *mem,
+                                       size_t n_bytes, long long origin, int n_ch, const bds_channel *channel) {
+    const char *who = kind == 0 ? "bds_track_open" : kind == 1 ? "bds_track_open_mem" : "bds_track_open_feed";
+    if (!ctx) return nullptr;
+    if (!s || !channel || n_ch < 1 || (kind == 0 && !path) || (kind == 1 && !mem)) {
+        fail(ctx, BDS_ERR_ARG, "%s: settings, channel table (n_ch >= 1) and the record are required", who);
+        return nullptr;
+    }
+    if (track_session_guard(ctx, who)) return nullptr;
+    if (hipSetDevice(ctx->device) != hipSuccess) {
+        fail(ctx, BDS_ERR_HIP, "%s: hipSetDevice failed", who);
+        return nullptr;
+    }
+    if (!ctx->trk) ctx->trk = new TrackState();
+    TrackState &t = *ctx->trk;
+    bds_track_session *h = new bds_track_session();
+    h->ctx = ctx, h->s = *s, h->n_ch = n_ch, h->feed = kind == 2, h->mem = kind == 1 ? mem : nullptr;
+    h->epochs_done.assign((size_t)n_ch, 0);
+    h->margin = ctx->tune.trk_stream_margin >= 0 ? ctx->tune.trk_stream_margin : 1.0;
+    // (not registered yet: every failure below frees it here)
+    auto body = [&]() -> int {
+        if (kind == 0) {
+            h->path = path;
+            h->file = fopen(path, "rb");
+            if (!h->file) return fail(ctx, BDS_ERR_IO, "Unable to read file %s", path);  // postProcessing.m:152-154
+            fseeko(h->file, 0, SEEK_END);
+            const long long sz = ftello(h->file);
+            if (sz <= 0) return fail(ctx, BDS_ERR_IO, "file %s is empty", path);
+            n_bytes = (size_t)sz;
+        }
+        int rc = track_setup(ctx, t, &h->s, 1, kind == 2 ? 0 : n_bytes, n_ch, channel, h->u);
+        if (rc) return rc;
+        TrkParams &p = h->u.p;
+        std::vector<ChanState> &hs = h->u.hs;
+        const int fmt = p.cplx;
+        const long long al = fmt_align(fmt);
+        if (kind == 2) {
+            if (origin < 0 || origin % 32) return fail(ctx, BDS_ERR_ARG, "%s: origin_sample = %lld must be a non-negative multiple of 32 samples", who, origin);
+            for (int c = 0; c < n_ch; ++c)
+                if (hs[c].active == 1 && hs[c].pos < origin)
+                    return fail(ctx, BDS_ERR_ARG, "%s: channel(%d) starts at sample %lld of the record, before origin_sample = %lld", who, c + 1, hs[c].pos, origin);
+            p.n_bytes = kFeedOpen;
+        }
+        // the resident span: sized like do_track's streamed path, from the context's resident limit or the session's default
+        TrkPlanner pl(ctx, &h->s, p, n_ch);
+        const long long base0 = kind == 2 ? origin : pl.live_min_pos(hs) & ~(al - 1);
+        const long long min_half = pl.min_half(hs, base0, al);
+        const size_t min_limit = (size_t)fmt_bytes(fmt, 2 * min_half);
+        size_t limit = t.resident_limit ? t.resident_limit : std::max(kSessionResident, min_limit);
+        if (limit < min_limit)
+            return fail(ctx, BDS_ERR_ARG, "resident limit of %zu bytes is too small for these channels: the spread of their positions plus "
+                        "one block, in each of the two span buffers, needs at least %zu bytes%s", limit, min_limit,
+                        fmt == kFmtPacked ? " of the packed record" : "");
+        long long span_n = (fmt == kFmtPacked ? (long long)(limit / 2) * 2 : (long long)(limit / (size_t)(2 * (fmt == kFmtIQ ? 2 : 1)))) & ~(al - 1);
+        if (kind != 2)  // no more than the record from the first channel on
+            span_n = std::min(span_n, std::max(min_half, (std::max(0LL, p.n_bytes - base0) + al - 1) & ~(al - 1)));
+        const size_t cap = (size_t)fmt_bytes(fmt, span_n);
+        for (int8_t *&q : h->span)
+            if (hipMalloc((void **)&q, cap + kDataSlack) != hipSuccess) {
+                (void)hipGetLastError();
+                q = nullptr;
+                return fail(ctx, BDS_ERR_NOMEM, "resident span of 2 x %zu bytes of the IF record does not fit in HBM", cap);
+            }
+        // the record's source
+        if (kind == 1) {
+            h->load = [ctx, mem](size_t off, size_t n, int8_t *dst, hipStream_t stream) -> int {
+                BDS_HIP(ctx, hipMemcpyAsync(dst, mem + off, n, hipMemcpyHostToDevice, stream));
+                return BDS_OK;
+            };
+        } else if (kind == 0) {
+            h->pin_bytes = std::min<size_t>((size_t)64 << 20, n_bytes);
+            BDS_HIP(ctx, hipHostMalloc(&h->pin, h->pin_bytes, 0));
+            h->load = [ctx, h](size_t off, size_t n, int8_t *dst, hipStream_t stream) -> int {
+                if (fseeko(h->file, (off_t)off, SEEK_SET)) return fail(ctx, BDS_ERR_IO, "seek in %s failed", h->path.c_str());
+                size_t done = 0;
+                while (done < n) {
+                    const size_t m = std::min(h->pin_bytes, n - done);
+                    if (fread(h->pin, 1, m, h->file) != m) return fail(ctx, BDS_ERR_IO, "short read on %s", h->path.c_str());
+                    hipError_t e = hipMemcpyAsync(dst + done, h->pin, m, hipMemcpyHostToDevice, stream);
+                    if (e == hipSuccess) e = hipStreamSynchronize(stream);  // the staging buffer is filled again next
+                    if (e != hipSuccess) return fail(ctx, BDS_ERR_HIP, "H2D copy: %s", hipGetErrorString(e));
+                    done += m;
+                }
+                return BDS_OK;
+            };
+        } else {
+            h->load = [ctx](size_t, size_t, int8_t *, hipStream_t) -> int {
+                return fail(ctx, BDS_ERR_ARG, "a feed session has no record to load from");
+            };
+        }
+        // (feed: the caller's thread is the loader -- one stream)
+        h->ss.reset(new SpanStream(ctx, t, h->load, st(ctx), kind != 2 && ctx->stream2 ? (hipStream_t)ctx->stream2 : st(ctx), fmt, span_n));
+        h->ss->cur.buf = h->span[0], h->ss->cur.base = h->ss->cur.end = base0;  // (the first advance / feed fills it)
+        h->ss->nxt.buf = h->span[1];
+        t.loaded_bytes = 0, t.pieces = 0, t.resident_max = 0, t.repeated = 0;
+        // the epoch loop's buffers; the state starts in half 0
+        h->part_n = (size_t)n_ch * h->u.nblocks * kNSums;
+        BDS_HIP(ctx, hipMalloc((void **)&h->d_st, sizeof(ChanState) * n_ch * 2));
+        BDS_HIP(ctx, hipMalloc((void **)&h->d_part, sizeof(double) * h->part_n * 2));
+        BDS_HIP(ctx, hipMalloc((void **)&h->d_out, sizeof(TrkOut)));
+        const int M = h->s.CNoInterval;
+        if (M > 1) {
+            BDS_HIP(ctx, hipMalloc((void **)&h->d_carry, sizeof(double) * (size_t)n_ch * 4 * M));
+            BDS_HIP(ctx, hipMalloc((void **)&h->d_prev3, sizeof(double) * (size_t)n_ch * 3));
+            BDS_HIP(ctx, hipMalloc((void **)&h->d_ncarry, sizeof(int) * (size_t)n_ch));
+            BDS_HIP(ctx, hipMemsetAsync(h->d_carry, 0, sizeof(double) * (size_t)n_ch * 4 * M, st(ctx)));
+            BDS_HIP(ctx, hipMemsetAsync(h->d_prev3, 0, sizeof(double) * (size_t)n_ch * 3, st(ctx)));
+            BDS_HIP(ctx, hipMemsetAsync(h->d_ncarry, 0, sizeof(int) * (size_t)n_ch, st(ctx)));
+        }
+        BDS_HIP(ctx, hipStreamSynchronize(st(ctx)));
+        return BDS_OK;
+    };
+    if (body() != BDS_OK) {
+        session_close(h);
+        return nullptr;
+    }
+    t.session = h;
+    std::lock_guard<std::mutex> lk(g_sess_mu);
+    g_sessions.insert(h);
+    return h;
+}
+
+}  // namespace bds
+
 using namespace bds;
+
+extern "C" bds_track_session *bds_track_open(bds_ctx *ctx, const bds_settings *s, const char *path, int n_ch, const bds_channel *channel) {
+    return session_open(ctx, s, 0, path, nullptr, 0, 0, n_ch, channel);
+}
+
+extern "C" bds_track_session *bds_track_open_mem(bds_ctx *ctx, const bds_settings *s, const int8_t *file_bytes, size_t n_bytes, int n_ch,
+                                                 const bds_channel *channel) {
+    return session_open(ctx, s, 1, nullptr, file_bytes, n_bytes, 0, n_ch, channel);
+}
+
+extern "C" bds_track_session *bds_track_open_feed(bds_ctx *ctx, const bds_settings *s, long long origin_sample, int n_ch,
+                                                  const bds_channel *channel) {
+    return session_open(ctx, s, 2, nullptr, nullptr, 0, origin_sample, n_ch, channel);
+}
+
+extern "C" void bds_track_close(bds_track_session *sess) {
+    if (bds_track_session *h = live_session(sess)) session_close(h);
+}
+
+extern "C" int bds_track_feed(bds_track_session *sess, const int8_t *bytes, size_t n_bytes, int last) {
+    bds_track_session *h = live_session(sess);
+    if (!h) return BDS_ERR_ARG;
+    bds_ctx *ctx = h->ctx;
+    if (!h->feed) return fail(ctx, BDS_ERR_ARG, "bds_track_feed: this session reads its record itself (it was not opened with bds_track_open_feed)");
+    if (h->fed_last) return fail(ctx, BDS_ERR_ARG, "bds_track_feed: the end of the record has been fed already");
+    if (n_bytes && !bytes) return fail(ctx, BDS_ERR_ARG, "bds_track_feed: bytes missing");
+    TrkParams &p = h->u.p;
+    if (p.cplx == kFmtIQ && (n_bytes & 1)) return fail(ctx, BDS_ERR_ARG, "bds_track_feed: an I/Q record takes whole int8 pairs, %zu bytes is an odd count", n_bytes);
+    BDS_HIP(ctx, hipSetDevice(ctx->device));
+    TrackState &t = *ctx->trk;
+    SpanStream &ss = *h->ss;
+    const long long al = fmt_align(ss.fmt);
+    const size_t offered = std::min<size_t>(n_bytes, (size_t)1 << 30);  // (the count returned is an int)
+    auto room = [&] { return (size_t)(ss.nb_of(ss.span_n) - ss.nb_of(ss.cur.end - ss.cur.base)); };
+    if (room() < offered) {
+        // release what lies behind the slowest live channel: the rest is carried to the other buffer, device to device
+        long long nb = ss.cur.end;
+        for (const ChanState &c : h->u.hs)
+            if (c.active == 1) nb = std::min(nb, c.pos);
+        nb &= ~(al - 1);
+        if (nb > ss.cur.base) {
+            int rc = ss.move_to(nb, ss.cur.end, true);
+            if (rc) return rc;
+        }
+    }
+    const size_t take = std::min(offered, room()) & ~(size_t)(p.cplx == kFmtIQ ? 1 : 0);
+    if (take) {
+        BDS_HIP(ctx, hipMemcpyAsync(ss.cur.buf + ss.nb_of(ss.cur.end - ss.cur.base), bytes, take, hipMemcpyHostToDevice, st(ctx)));
+        BDS_HIP(ctx, hipStreamSynchronize(st(ctx)));  // the bytes are the caller's again on return
+        ss.cur.end += p.cplx == kFmtPacked ? (long long)take * 2 : p.cplx == kFmtIQ ? (long long)take / 2 : (long long)take;
+        t.loaded_bytes += take, t.pieces += 1;
+        t.resident_max = std::max(t.resident_max, (size_t)ss.nb_of(ss.cur.end - ss.cur.base));
+    }
+    if (last && take == n_bytes) h->fed_last = true, p.n_bytes = ss.cur.end;  // end of file is judged against the fed length from here on
+    return (int)take;
+}
+
+extern "C" int bds_track_session_info(bds_track_session *sess, int32_t *epochs_done, long long *next_sample, long long *fed_end,
+                                      long long *resident_bytes) {
+    bds_track_session *h = live_session(sess);
+    if (!h) return BDS_ERR_ARG;
+    for (int c = 0; c < h->n_ch; ++c) {
+        if (epochs_done) epochs_done[c] = (int32_t)h->epochs_done[c];
+        if (next_sample) next_sample[c] = h->u.hs[c].prn ? h->u.hs[c].pos : 0;
+    }
+    if (fed_end) *fed_end = h->feed ? h->ss->cur.end : h->u.p.n_bytes;
+    if (resident_bytes) *resident_bytes = h->ss->nb_of(h->ss->cur.end - h->ss->cur.base);
+    return BDS_OK;
+}
+
+extern "C" int bds_track_advance(bds_track_session *sess, int max_epochs, bds_track_out *out, int32_t *n_cno_done) {
+    bds_track_session *h = live_session(sess);
+    if (!h) return BDS_ERR_ARG;
+    bds_ctx *ctx = h->ctx;
+    const int n_ch = h->n_ch;
+    if (!out || max_epochs < 1 || out->n_ch != n_ch || out->n_epochs < max_epochs)
+        return fail(ctx, BDS_ERR_ARG, "bds_track_advance: n_ch / n_epochs mismatch (out->n_epochs is the capacity: >= max_epochs)");
+    if (!out->completed || !out->status || !out->absoluteSample || !out->I_P || !out->Q_P)
+        return fail(ctx, BDS_ERR_ARG, "bds_track_advance: required output arrays missing");
+    TrkParams &p = h->u.p;
+    std::vector<ChanState> &hs = h->u.hs;
+    // C/N0 intervals that can complete in this call: checked before anything runs
+    const int M = h->s.CNoInterval;
+    int need_cno = 0;
+    if (M > 1)
+        for (int c = 0; c < n_ch; ++c)
+            if (hs[c].active == 1) need_cno = std::max(need_cno, (int)((h->epochs_done[c] + max_epochs) / M - h->epochs_done[c] / M));
+    if (out->DataCNo && out->n_cno < need_cno)
+        return fail(ctx, BDS_ERR_ARG, "bds_track_advance: out->n_cno = %d, but %d C/N0 intervals can complete in this call", out->n_cno, need_cno);
+    BDS_HIP(ctx, hipSetDevice(ctx->device));
+    TrackState &t = *ctx->trk;
+    // the call's result arrays: one device block [21][n_ch][row], row = out->n_epochs, at the reference's template values
+    const int row = out->n_epochs;
+    const size_t n = (size_t)n_ch * row;
+    constexpr int kFields = sizeof(TrkOut) / sizeof(double *);
+    if (h->fields_cap < n * kFields) {
+        if (h->d_fields) (void)hipFree(h->d_fields), h->d_fields = nullptr, h->fields_cap = 0;
+        BDS_HIP(ctx, hipMalloc((void **)&h->d_fields, sizeof(double) * n * kFields));
+        h->fields_cap = n * kFields;
+        h->row = 0;
+    }
+    if (h->row != row) {
+        int f = 0;
+        h->inf_mask = 0;
+        for_each_field(out, &h->d, [&](double *, double *&dev, double v0) {
+            dev = h->d_fields + (size_t)f * n;
+            if (v0 != 0.0) h->inf_mask |= 1u << f;
+            ++f;
+        });
+        BDS_HIP(ctx, hipMemcpyAsync(h->d_out, &h->d, sizeof(TrkOut), hipMemcpyHostToDevice, st(ctx)));
+        BDS_HIP(ctx, hipStreamSynchronize(st(ctx)));  // (h->d may not change while the copy reads it)
+        h->row = row;
+    }
+    hipLaunchKernelGGL(k_trk_fill_out, dim3((unsigned)((n * kFields + 255) / 256)), dim3(256), 0, st(ctx), h->d_fields, n, kFields, h->inf_mask);
+    const int nq = std::max(need_cno, 1);
+    if (M > 1 && h->cno_cap < nq) {
+        if (h->d_raw) (void)hipFree(h->d_raw), h->d_raw = nullptr;
+        if (h->d_cno) (void)hipFree(h->d_cno), h->d_cno = nullptr;
+        h->cno_cap = 0;
+        BDS_HIP(ctx, hipMalloc((void **)&h->d_raw, sizeof(double) * (size_t)n_ch * nq * 3));
+        BDS_HIP(ctx, hipMalloc((void **)&h->d_cno, sizeof(double) * (size_t)n_ch * nq * 5));
+        h->cno_cap = nq;
+    }
+    // the epochs: `completed` counts within the call, the result arrays are indexed by the call's own epoch number
+    for (ChanState &c : hs) c.completed = 0;
+    BDS_HIP(ctx, hipMemcpyAsync(h->d_st + (size_t)h->slot * n_ch, hs.data(), sizeof(ChanState) * n_ch, hipMemcpyHostToDevice, st(ctx)));
+    p.n_epochs = row;
+    TrkRun run{ctx, t, p, h->d_st, h->d_part, h->part_n, h->d, h->d_out, h->u.nblocks, n_ch, !ctx->tune.trk_nofuse_update,
+               h->d_st + (size_t)h->slot * n_ch};
+    TrkPlanner pl(ctx, &h->s, p, n_ch);
+    pl.margin = h->margin;
+    int k = 0, rc;
+    {
+        RoctxRange rg_epochs("trk.epoch_loop");
+        rc = run_streamed(run, pl, *h->ss, hs, max_epochs, true, h->feed, h->slot, k);
+    }
+    h->margin = pl.margin;
+    if (rc) return rc;
+    BDS_HIP(ctx, hipGetLastError());
+    const int pm = p.pilot ? (p.mode == BDS_TRACK_WB ? 2 : 1) : 0;
+    if (M > 1 && k > 0)
+        hipLaunchKernelGGL(k_trk_cno_seg, dim3(n_ch), dim3(256), 0, st(ctx), h->d, (const ChanState *)(h->d_st + (size_t)h->slot * n_ch), row, M, nq,
+                           pm, h->s.intTime, h->d_carry, h->d_ncarry, h->d_prev3, h->d_raw, h->d_cno);
+    h->h_fields.resize(n * kFields + (size_t)n_ch * nq * 5);
+    BDS_HIP(ctx, hipMemcpyAsync(h->h_fields.data(), h->d_fields, sizeof(double) * n * kFields, hipMemcpyDeviceToHost, st(ctx)));
+    double *hc = h->h_fields.data() + n * kFields;
+    if (M > 1 && k > 0) BDS_HIP(ctx, hipMemcpyAsync(hc, h->d_cno, sizeof(double) * (size_t)n_ch * nq * 5, hipMemcpyDeviceToHost, st(ctx)));
+    BDS_HIP(ctx, hipStreamSynchronize(st(ctx)));
+    {
+        int f = 0;
+        TrkOut unused{};
+        for_each_field(out, &unused, [&](double *host, double *&, double) {
+            if (host) memcpy(host, h->h_fields.data() + (size_t)f * n, sizeof(double) * n);
+            ++f;
+        });
+    }
+    double *dst[5] = {out->DataCNo, out->DataPLD, out->PilotCNo, out->PilotPLD, out->SigCNo};
+    for (int c = 0; c < n_ch; ++c) {
+        const int done = hs[c].prn ? hs[c].completed : 0;
+        const long long e0 = h->epochs_done[c];
+        const int nd = M > 1 ? (int)((e0 + done) / M - e0 / M) : 0;
+        out->completed[c] = done;
+        out->status[c] = hs[c].prn && k > 0 && done == k ? 'T' : '-';
+        if (n_cno_done) n_cno_done[c] = nd;
+        h->epochs_done[c] = e0 + done;
+        for (int f = 0; f < 5; ++f) {
+            if (!dst[f] || !out->DataCNo) continue;
+            for (int q = 0; q < out->n_cno; ++q)
+                dst[f][(size_t)c * out->n_cno + q] = q < nd && (pm || f < 2) ? hc[(size_t)f * n_ch * nq + (size_t)c * nq + q] : 0.0;
+        }
+    }
+    return k;
+}
 
 extern "C" int bds_track_mem(bds_ctx *ctx, const bds_settings *s, const int8_t *file_bytes, size_t n_bytes, int n_ch,
                              const bds_channel *channel, bds_track_out *out) {

@@ -84,7 +84,9 @@ class AcqJob(C.Structure):
 EXPORTS = [
     "bds_create", "bds_destroy", "bds_reload_tuning", "bds_last_error", "bds_device_name", "bds_abi_check", "bds_build_flags", "bds_gen_code", "bds_acquire",
     "bds_acq_load", "bds_acq_prepare", "bds_acq_run", "bds_acq_set_pair_budget_gb", "bds_resample_plan", "bds_fir1_bandpass", "bds_frame_sync", "bds_sync_pattern", "bds_unpack_cplx", "bds_unpack_cplx_file", "bds_acq_grid", "bds_acq_peaks", "bds_acq_candidates", "bds_acq_coherent_sums", "bds_get_timing",
-    "bds_track", "bds_track_mem", "bds_track_loaded_bytes", "bds_track_set_resident_limit", "bds_track_stream_info", "bds_track_correlate", "bds_track_colon", "bds_calc_loop_coef", "bds_calc_loop_coef_carr",
+    "bds_track", "bds_track_mem", "bds_track_loaded_bytes", "bds_track_set_resident_limit", "bds_track_stream_info", "bds_track_correlate", "bds_track_colon",
+    "bds_track_open", "bds_track_open_mem", "bds_track_open_feed", "bds_track_feed", "bds_track_advance", "bds_track_session_info", "bds_track_close",
+    "bds_calc_loop_coef", "bds_calc_loop_coef_carr",
     "bds_calc_weighing_factor", "bds_pre_run", "bds_pre_run_device", "bds_acquire_track",
     "bds_multi_create", "bds_multi_destroy", "bds_multi_last_error", "bds_multi_size", "bds_multi_ctx",
     "bds_multi_rccl_ranks", "bds_acquire_multi", "bds_shard_jobs", "bds_acq_job_cost",
@@ -154,6 +156,15 @@ def lib():
         L.bds_track_set_resident_limit.restype, L.bds_track_set_resident_limit.argtypes = i32, [vp, sz]
         L.bds_track_stream_info.restype = i32
         L.bds_track_stream_info.argtypes = [vp, _IP, C.POINTER(C.c_longlong), _IP]
+    if hasattr(L, "bds_track_open"):  # (as above: a build of an older commit has no tracking sessions)
+        CP, OP, LLP = C.POINTER(Channel), C.POINTER(TrackOut), C.POINTER(C.c_longlong)
+        L.bds_track_open.restype, L.bds_track_open.argtypes = vp, [vp, SP, C.c_char_p, i32, CP]
+        L.bds_track_open_mem.restype, L.bds_track_open_mem.argtypes = vp, [vp, SP, i8p, sz, i32, CP]
+        L.bds_track_open_feed.restype, L.bds_track_open_feed.argtypes = vp, [vp, SP, C.c_longlong, i32, CP]
+        L.bds_track_feed.restype, L.bds_track_feed.argtypes = i32, [vp, i8p, sz, i32]
+        L.bds_track_advance.restype, L.bds_track_advance.argtypes = i32, [vp, i32, OP, _IP]
+        L.bds_track_session_info.restype, L.bds_track_session_info.argtypes = i32, [vp, _IP, LLP, LLP, LLP]
+        L.bds_track_close.restype, L.bds_track_close.argtypes = None, [vp]
     L.bds_track_correlate.restype = i32
     L.bds_track_correlate.argtypes = [vp, SP, i8p, sz, i32, _IP, _DP, _DP]
     L.bds_track_colon.restype, L.bds_track_colon.argtypes = i32, [vp, i32, _DP, _DP, _DP, _IP, _DP, _DP, _IP]
@@ -274,6 +285,26 @@ def n_samples_of(n_values: int, is_complex, n_samples=None) -> int:
     if not 0 <= int(n_samples) <= have:
         raise ValueError(f"n_samples = {n_samples} but the array holds {have} samples")
     return int(n_samples)
+
+
+def check_feed_origin(origin) -> int:
+    """origin_sample of a feed session: a non-negative multiple of 32 samples (checked before any native call)."""
+    if int(origin) != origin or int(origin) < 0 or int(origin) % 32:
+        raise ValueError(f"origin = {origin!r}: the first sample fed must be a non-negative multiple of 32 samples")
+    return int(origin)
+
+
+def check_feed_bytes(sess, data) -> np.ndarray:
+    """The bytes of one track_feed call as a contiguous int8 array; argument errors raise before any native call."""
+    if not sess.get("feed"):
+        raise ValueError("feed on a session that reads its record itself (it was opened on a file or an array, not with origin=)")
+    a = np.asarray(data)
+    if a.dtype == np.uint8:
+        a = a.view(np.int8)
+    a = np.ascontiguousarray(a, dtype=np.int8).reshape(-1)
+    if sess["fileType"] == 2 and a.size % 2:
+        raise ValueError(f"an I/Q record is fed in whole int8 pairs: {a.size} bytes is an odd count")
+    return a
 
 
 def gen_code(signal: str, kind: str, prn: int) -> np.ndarray:
@@ -565,6 +596,72 @@ class Context:
         arrays["completed"] = completed
         arrays["status"] = status
         return arrays
+
+    @staticmethod
+    def _channels(channels):
+        carr = (Channel * len(channels))()
+        for i, ch in enumerate(channels):
+            carr[i].PRN = int(ch.PRN)
+            carr[i].status = ord(ch.status) if isinstance(ch.status, str) else int(ch.status)
+            carr[i].acquiredFreq = float(ch.acquiredFreq)
+            carr[i].codePhase = float(ch.codePhase)
+            carr[i].codeFreq = float(ch.codeFreq)
+        return carr
+
+    # -- tracking sessions (bds_track_open* .. bds_track_close): a session handle is the dict these return -------------
+    def _session(self, h, settings, channels, keep=None):
+        if not h:
+            raise BdsError(-1, self._lib.bds_last_error(self._h).decode())
+        return {"handle": h, "n_ch": len(channels), "fileType": int(settings.fileType), "keep": keep, "feed": False}
+
+    def track_open(self, settings, path_or_bytes, channel):
+        """bds_track_open (a path) / bds_track_open_mem (int8 array of raw file bytes, uint8 for a packed fileType-3 record;
+        the array is kept alive until track_close)."""
+        cs = pack_settings(settings)
+        carr = self._channels(channel)
+        if isinstance(path_or_bytes, (str, bytes, os.PathLike)):
+            h = self._lib.bds_track_open(self._h, C.byref(cs), os.fsencode(path_or_bytes), len(channel), carr)
+            return self._session(h, settings, channel)
+        a, p = _i8(path_or_bytes)
+        h = self._lib.bds_track_open_mem(self._h, C.byref(cs), p, a.size, len(channel), carr)
+        return self._session(h, settings, channel, keep=a)
+
+    def track_open_feed(self, settings, origin, channel):
+        """bds_track_open_feed: the record is what track_feed appends; sample `origin` (a multiple of 32) is the first one fed."""
+        check_feed_origin(origin)
+        cs = pack_settings(settings)
+        h = self._lib.bds_track_open_feed(self._h, C.byref(cs), int(origin), len(channel), self._channels(channel))
+        sess = self._session(h, settings, channel)
+        sess["feed"] = True
+        return sess
+
+    def track_feed(self, sess, data, last=False) -> int:
+        """bds_track_feed: bytes of the settings' fileType; returns how many were taken (fewer than offered: the span is full)."""
+        a = check_feed_bytes(sess, data)
+        return self._check(self._lib.bds_track_feed(sess["handle"], a.ctypes.data_as(C.POINTER(C.c_int8)), a.size, int(bool(last))))
+
+    def track_advance(self, sess, max_epochs, n_cno, fields):
+        """bds_track_advance: (k, dict field -> array [n_ch, max_epochs] (C/N0 fields [n_ch, n_cno]) plus completed, status and
+        n_cno_done [n_ch])."""
+        out, arrays = self._track_out(sess["n_ch"], int(max_epochs), int(n_cno), fields)
+        arrays["n_cno_done"] = np.zeros(sess["n_ch"], dtype=np.int32)
+        k = self._check(self._lib.bds_track_advance(sess["handle"], int(max_epochs), C.byref(out), arrays["n_cno_done"].ctypes.data_as(_IP)))
+        return k, arrays
+
+    def track_session_info(self, sess) -> dict:
+        """bds_track_session_info: epochs_done / next_sample per channel, fed_end (samples), resident_bytes."""
+        done = np.zeros(sess["n_ch"], dtype=np.int32)
+        nxt = np.zeros(sess["n_ch"], dtype=np.int64)
+        fed, res = C.c_longlong(0), C.c_longlong(0)
+        self._check(self._lib.bds_track_session_info(sess["handle"], done.ctypes.data_as(_IP), nxt.ctypes.data_as(C.POINTER(C.c_longlong)),
+                                                     C.byref(fed), C.byref(res)))
+        return {"epochs_done": done, "next_sample": nxt, "fed_end": int(fed.value), "resident_bytes": int(res.value)}
+
+    def track_close(self, sess) -> None:
+        """bds_track_close (a second close does nothing)."""
+        if sess.get("handle"):
+            self._lib.bds_track_close(sess["handle"])
+        sess["keep"] = None
 
     def _track_out(self, nch, n_epochs, n_cno, fields):
         out = TrackOut()

@@ -162,6 +162,103 @@ def acquire_track(long_signal, path, settings, device: int = 0, resident_limit=N
     return acq, channel, _results(arr, [c.PRN for c in channel], len(channel), ep, cn, mode)
 
 
+class TrackSession:
+    """A tracking run whose loop state survives the call (bds_track_open* .. bds_track_close): advance in pieces of any size, or
+    on samples fed by the caller.  The concatenation of the arrays of successive ``advance`` calls equals, bit for bit, what ONE
+    ``tracking()`` call over the same epochs returns (settings.msToProcess is not read: a session has no preset end, and every
+    channel stops at its own short read).
+
+    source: a file path, an open binary file (its ``.name``), or the raw file bytes (int8; uint8 for settings.fileType = 3).
+    origin=N (a multiple of 32) instead opens a FEED session: pass source=None; the record is what ``feed`` appends, sample N
+    of the record first.  resident_limit: bytes of the record resident in HBM (None: the context's limit, else 256 MiB).
+    One session may be open per context; tracking() on that context raises until it is closed."""
+
+    def __init__(self, source, channel, settings, *, origin=None, resident_limit=None, ctx=None, mode=None, device: int = 0):
+        self._sess = None
+        mode = _mode(settings, mode)
+        if mode in ("NB", "WB") and str(settings.signal).upper() != "B1C":
+            raise ValueError("NB/WB tracking are B1C variants")
+        s = settings
+        if mode == "NB" and int(s.pilotTRKflag) == 2:
+            s = settings.copy(pilotTRKflag=0)
+        if mode == "WB" and int(s.pilotTRKflag) != 2:
+            s = settings.copy(pilotTRKflag=0)
+        self.mode, self.settings, self.channel = mode, s, list(channel)
+        _, _, self._ep, self._cn, _ = field_set(settings, mode)
+        self._M = int(settings.CNoInterval)
+        if origin is not None:
+            if source is not None:
+                raise ValueError("a feed session (origin=) has no source: the record is what feed() appends")
+            native.check_feed_origin(origin)
+        elif source is None:
+            raise ValueError("source is required (or origin= for a feed session)")
+        self._ctx = ctx if ctx is not None else get_context(device)
+        with _resident_limit(self._ctx, resident_limit):  # (read at the open)
+            if origin is not None:
+                self._sess = self._ctx.track_open_feed(s, origin, self.channel)
+            elif isinstance(source, (str, bytes, os.PathLike)):
+                self._sess = self._ctx.track_open(s, source, self.channel)
+            elif hasattr(source, "name") and not isinstance(source, np.ndarray):
+                self._sess = self._ctx.track_open(s, source.name, self.channel)
+            elif int(settings.fileType) == 3:
+                a = np.asarray(source)
+                self._sess = self._ctx.track_open(s, packed_bytes(a.view(np.uint8) if a.dtype == np.int8 else a, field="source"), self.channel)
+            else:
+                self._sess = self._ctx.track_open(s, np.ascontiguousarray(source, dtype=np.int8), self.channel)
+
+    def _open(self):
+        if self._sess is None:
+            raise native.BdsError(-1, "the tracking session is closed")
+        return self._sess
+
+    def feed(self, data, last=False) -> int:
+        """Append bytes of the settings' fileType to the record; returns how many were taken (fewer than offered when the
+        resident span is full: advance, then feed the rest).  last=True marks the end of the record."""
+        sess = self._open()
+        native.check_feed_bytes(sess, data)  # (argument errors raise before any native call)
+        return self._ctx.track_feed(sess, data, last)
+
+    def advance(self, n):
+        """Run the next k <= n epochs of every live channel; returns a TrackResults list with the fields of tracking(), arrays
+        cut to the k epochs of this call (C/N0 arrays to the n_cno_done intervals that completed in it); r.completed is the
+        number of epochs the channel wrote in this call, self.last_k the k of this call."""
+        sess = self._open()
+        n = int(n)
+        n_cno = (n + self._M - 1) // self._M + 1 if self._M > 1 else 0
+        k, arr = self._ctx.track_advance(sess, n, n_cno, self._ep + self._cn)
+        self.last_k = k
+        out = _results({f: (v[:, :k] if f in self._ep else v) for f, v in arr.items()}, [c.PRN for c in self.channel],
+                       len(self.channel), self._ep, self._cn, self.mode)
+        sig_name = "B2a_CNo" if self.mode == "B2A" else "B1C_CNo"
+        for c, r in enumerate(out):
+            r.n_cno_done = int(arr["n_cno_done"][c])
+            for f in self._cn:
+                f = sig_name if f == "SigCNo" else f
+                setattr(r, f, getattr(r, f)[:r.n_cno_done].copy())
+        return out
+
+    def info(self) -> dict:
+        sess = self._open()
+        return self._ctx.track_session_info(sess)
+
+    def close(self) -> None:
+        if self._sess is not None:
+            self._ctx.track_close(self._sess)
+            self._sess = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # noqa: BLE001
+            pass
+
+
 def NB_tracking(fid, channel, settings, **kw):
     """B1C/NB_tracking.m:1."""
     return tracking(fid, channel, settings, mode="NB", **kw)

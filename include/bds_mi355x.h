@@ -336,6 +336,75 @@ BDS_API long long bds_track_loaded_bytes(bds_ctx *ctx);
  *   pointer may be NULL. */
 BDS_API int bds_track_set_resident_limit(bds_ctx *ctx, size_t bytes);
 BDS_API int bds_track_stream_info(bds_ctx *ctx, int32_t *pieces, long long *resident_max_bytes, int32_t *repeated_batches);
+/* ---- tracking sessions: advance in pieces, or on samples fed by the caller ---------------------------------------
+ * bds_track / bds_track_mem / bds_acquire_track run msToProcess worth of epochs in one call and forget the loop state.  A
+ * session keeps it: the channel states, the launch geometry, the resident span of the record and the C/N0 carry survive the
+ * call, so a long record is tracked into arrays of any size, and a record that is still arriving is tracked as it comes.
+ *   bds_track_open       the record is the file at `path`
+ *   bds_track_open_mem   the record is n_bytes raw file bytes in host memory; the bytes stay the caller's until bds_track_close
+ *   bds_track_open_feed  the record is what the caller feeds with bds_track_feed (below)
+ * `channel` is the acquisition's channel table, as for bds_track.  A failing bds_track_open* returns NULL and leaves the
+ * message in bds_last_error(ctx).
+ *
+ * bds_track_advance runs the next k <= max_epochs epochs of every live channel in lock-step and returns k (or < 0).
+ *   out          an ordinary bds_track_out with n_epochs = max_epochs as capacity (the row length of its arrays); element
+ *                [ch][i] is epoch epochs_done[ch] + i of the run; rows are at the reference's template values behind the
+ *                epochs written
+ *   completed[ch] the number of epochs this call wrote for the channel: k unless the channel stopped
+ *   status[ch]   'T' when the channel ran all k epochs, else '-'
+ *   C/N0 arrays  hold, in order, the CNoIntervals that completed during this call; their number per channel goes to
+ *                n_cno_done[ch] ([n_ch], may be NULL) and equals floor((e0 + k) / M) - floor(e0 / M), e0 = the epochs done
+ *                before the call, M = CNoInterval.  If out->n_cno is smaller than that number can get, the call returns
+ *                BDS_ERR_ARG with the needed number in the message, before anything runs.
+ * The contract: whatever the sizes of the pieces, the concatenation of the arrays of successive advances equals the arrays of
+ * ONE bds_track / bds_track_mem call on the same record, settings and channels, with msToProcess set to the sum of the pieces
+ * and no end of file in it -- every field, bit for bit, DataCNo / DataPLD / PilotCNo / PilotPLD / SigCNo with the reference's
+ * two-point smoothing (whose "previous" value crosses call boundaries) included; for all three trackers, all three record
+ * formats and every BDS_TRK_PREC.
+ * Launch geometry is fixed at open: the correlate grid, the chunk and the samples per lane are exactly what the one-shot call
+ * chooses for the same channels and settings, because the fixed-order sum of the partial sums depends on them.  A session
+ * always runs on the resident-span path of streamed tracking (above), a batch of epochs per advance or several: the span is
+ * bounded by bds_track_set_resident_limit as set when the session is opened, or by 256 MiB (and never more than the record)
+ * when no limit is set; bds_track_stream_info / bds_track_loaded_bytes count over the session, from the open on.
+ * msToProcess and end of file: settings.msToProcess is not read by a session: a session has no preset end.  The reference's
+ * rule "the first channel that meets the end of file ends the call, later channels are never started" therefore has no
+ * counterpart: a session cannot take back pieces it has already returned.  Each channel stops at its own short read.  It then
+ * has active = 0, its completed stops growing, and its partial results stay valid.
+ *
+ * Feed sessions.  The record is what the caller feeds: sample origin_sample of the record is the first sample fed, and
+ * origin_sample must be a multiple of 32 samples.  skipNumberOfBytes + codePhase - 1 stays a position in the record (and
+ * absoluteSample counts from the record's sample 0); a start position before origin_sample is BDS_ERR_ARG.  Bytes are those of
+ * the settings' fileType: an I/Q record takes whole pairs (an odd count is BDS_ERR_ARG), of a packed record every byte is two
+ * samples.
+ *   bds_track_feed  appends to the resident span and returns how many bytes it took (>= 0) or < 0.  It takes fewer than
+ *                offered when the span is full -- it never drops or overwrites samples a live channel still needs; what lies
+ *                behind the slowest channel is released first, the rest carried device to device --: the caller then advances
+ *                and feeds the rest.  last != 0 (with every byte taken) marks the end of the record: from then on end of file
+ *                is judged against the fed length, exactly as a file's size is.
+ *   bds_track_advance runs the most epochs, up to max_epochs, that every live channel can complete inside the data fed so
+ *                far, by the planning rule of the streamed path (blocks at a code rate 2 % low, the window guard as the safety
+ *                net).  It may return 0; that is not an error.
+ * No loader thread runs in a feed session: the caller's thread is the loader.
+ *
+ * bds_track_session_info: per channel the epochs done and the sample the next epoch starts at, one past the last sample of the
+ *   record known so far (feed: fed; otherwise the record's length in samples) and the bytes of the record resident now.  Any
+ *   pointer may be NULL.
+ * One open session per context: bds_track, bds_track_mem, bds_acquire_track and a second bds_track_open* on that context
+ *   return BDS_ERR_ARG, naming the open session.  bds_acquire / bds_acq_* on the same context between two advances are
+ *   allowed (re-acquisition during a run) and leave both results unchanged.  bds_destroy closes an open session.  Every call
+ *   on a closed or NULL session returns BDS_ERR_ARG (bds_track_close: nothing) without touching memory. */
+typedef struct bds_track_session bds_track_session;
+BDS_API bds_track_session *bds_track_open(bds_ctx *ctx, const bds_settings *s, const char *path, int n_ch,
+                                          const bds_channel *channel);
+BDS_API bds_track_session *bds_track_open_mem(bds_ctx *ctx, const bds_settings *s, const int8_t *file_bytes, size_t n_bytes,
+                                              int n_ch, const bds_channel *channel);
+BDS_API bds_track_session *bds_track_open_feed(bds_ctx *ctx, const bds_settings *s, long long origin_sample, int n_ch,
+                                               const bds_channel *channel);
+BDS_API int bds_track_feed(bds_track_session *sess, const int8_t *bytes, size_t n_bytes, int last);
+BDS_API int bds_track_advance(bds_track_session *sess, int max_epochs, bds_track_out *out, int32_t *n_cno_done);
+BDS_API int bds_track_session_info(bds_track_session *sess, int32_t *epochs_done, long long *next_sample,
+                                   long long *fed_end, long long *resident_bytes);
+BDS_API void bds_track_close(bds_track_session *sess);
 /* Open-loop check entry: one correlate-and-dump epoch per channel with the caller's
  * NCO state (no loop update).  state: per channel {sample offset (0-based), blksize,
  * remCodePhase, codeFreq, remCarrPhase, carrFreq}; sums: [n_ch][18] raw correlator
