@@ -50,6 +50,9 @@ __host__ __device__ constexpr size_t bw_piece(int mp, int k2, int t3) {  // elem
     return (((size_t)(t3 / kTileLags) * MP + mp) * K2 + k2) * (kTileLags * 4) + (size_t)(t3 % kTileLags) * 4;
 }  // 4-byte (fp16 complex) elements of a cell in the inter-pass buffer
 constexpr int kRowsThreads = 256, kColsThreads = 256;
+// stage-1 twiddles W3125^(j (5 p0 + p1)), p0, p1 >= 1, that k_pfa_rows holds in registers of their own, in slot order (the other 16 - kTw1Held
+// slots take two products by the factors W3125^(j p1), W3125^(5 j p0)): 14 is what 256 registers hold without scratch (254 used)
+constexpr int kTw1Held = 14;
 constexpr int kCoefFrags = NB * 4 * 2;  // B fragments (16 bytes per lane): [nb][ins][hi / lo]
 constexpr size_t kCoefBytes = (size_t)kCoefFrags * 64 * 16;
 constexpr size_t kColsLds = kCoefBytes + (size_t)NB * kColsThreads * 4;  // + the lanes' maxima per output block (the values' pass visits flagged blocks only)
@@ -63,18 +66,34 @@ __host__ __device__ inline long lag_of(int t1, int t2, int t3) {
 }
 
 // ---- 5- and 25-point inverse transforms on packed fp32 pairs -------------------------------------------------------------
+// The 5-point transform behind its first sums and differences, t1 = x1 + x4, t2 = x2 + x3, t3 = x1 - x4, t4 = x2 - x3, in 12 packed
+// instructions (Linzer-Feig: every product rides on a sum):
+//   a = t1 + t2, b = t1 - t2, y0 = x0 + a, m = x0 - a / 4, m1,2 = m +- (sqrt 5 / 4) b,
+//   u1 = t3 + (s2 / s1) t4, u2 = (s2 / s1) t3 - t4, y1,4 = m1 +- j s1 u1, y2,3 = m2 +- j s1 u2          (s_k = sin(2 pi k / 5))
+__device__ __forceinline__ void pk_radix5_tail(v2f &x0, v2f &x1, v2f &x2, v2f &x3, v2f &x4, v2f t1, v2f t2, v2f t3, v2f t4) {
+    constexpr float kq = 0.25f, kr5 = 0.5590169943749475f, kr = 0.6180339887498949f, s1 = 0.9510565162951535f;
+    const v2f ks1 = {s1, s1};
+    const v2f a = t1 + t2, b = t1 - t2;
+    const v2f m = x0 - kq * a;
+    const v2f m1 = m + kr5 * b, m2 = m - kr5 * b;
+    const v2f u1 = t3 + kr * t4, u2 = kr * t3 - t4;
+    x0 = x0 + a;
+    x1 = pk_addjk(m1, u1, ks1);
+    x4 = pk_subjk(m1, u1, ks1);
+    x2 = pk_addjk(m2, u2, ks1);
+    x3 = pk_subjk(m2, u2, ks1);
+}
+// 5-point inverse transform in place: 16 packed instructions
 __device__ __forceinline__ void pk_radix5(v2f &x0, v2f &x1, v2f &x2, v2f &x3, v2f &x4) {
-    constexpr float c1 = 0.30901699437494745f, c2 = -0.80901699437494734f, s1 = 0.95105651629515353f, s2 = 0.58778525229247314f;
-    const v2f t1 = x1 + x4, t2 = x2 + x3, t3 = x1 - x4, t4 = x2 - x3;
-    const v2f m1 = x0 + c1 * t1 + c2 * t2;
-    const v2f m2 = x0 + c2 * t1 + c1 * t2;
-    const v2f n1 = s1 * t3 + s2 * t4;
-    const v2f n2 = s2 * t3 - s1 * t4;
-    x0 = x0 + t1 + t2;
-    x1 = pk_addj(m1, n1);
-    x4 = pk_subj(m1, n1);
-    x2 = pk_addj(m2, n2);
-    x3 = pk_subj(m2, n2);
+    pk_radix5_tail(x0, x1, x2, x3, x4, x1 + x4, x2 + x3, x1 - x4, x2 - x3);
+}
+// the same over x0, w1 x1, w2 x2, w3 x3, w4 x4 with compile-time w: (t1, t3) = (w1 x1 +- w4 x4) and (t2, t4) = (w2 x2 +- w3 x3) as
+// one product and one twiddled sum / difference each -- 10 instructions where four products and four sums take 12
+__device__ __forceinline__ void pk_radix5_tw_k(v2f &x0, v2f &x1, v2f &x2, v2f &x3, v2f &x4, v2f w1, v2f w2, v2f w3, v2f w4) {
+    v2f t1, t2, t3, t4;
+    pk_bf2w_k(pk_cmul_k(x1, w1), x4, w4, t1, t3);
+    pk_bf2w_k(pk_cmul_k(x2, w2), x3, w3, t2, t4);
+    pk_radix5_tail(x0, x1, x2, x3, x4, t1, t2, t3, t4);
 }
 
 // W25^k, k = q0 p1 for q0, p1 in 1..4
@@ -91,15 +110,23 @@ __device__ __forceinline__ v2f w25(int k) {
 }
 
 // x[q0 + 5 q1] -> slot p0 + 5 p1 holds Y[5 p0 + p1] = sum_q x[q] W25^(q (5 p0 + p1))
+// The twiddles W25^(q0 p1) between the layers are folded into the second layer's butterflies.
+// SUMMED: the caller hands over x[q0 + 15] = x2 + x3 and x[q0 + 20] = x1 + x4 of each first-layer butterfly in place of x3 and x4 (the
+// row pass forms them on the addend of its spectrum products); the differences are 2 x2 - t2 and 2 x1 - t1.
+template <bool SUMMED = false>
 __device__ __forceinline__ void pk_radix25(v2f (&x)[25]) {
 #pragma unroll
-    for (int q0 = 0; q0 < 5; ++q0) pk_radix5(x[q0], x[q0 + 5], x[q0 + 10], x[q0 + 15], x[q0 + 20]);
+    for (int q0 = 0; q0 < 5; ++q0) {
+        if constexpr (SUMMED)
+            pk_radix5_tail(x[q0], x[q0 + 5], x[q0 + 10], x[q0 + 15], x[q0 + 20], x[q0 + 20], x[q0 + 15], pk_twice_minus(x[q0 + 5], x[q0 + 20]),
+                           pk_twice_minus(x[q0 + 10], x[q0 + 15]));
+        else
+            pk_radix5(x[q0], x[q0 + 5], x[q0 + 10], x[q0 + 15], x[q0 + 20]);
+    }
+    pk_radix5(x[0], x[1], x[2], x[3], x[4]);
 #pragma unroll
-    for (int q0 = 1; q0 < 5; ++q0)
-#pragma unroll
-        for (int p1 = 1; p1 < 5; ++p1) x[q0 + 5 * p1] = pk_cmul_k(x[q0 + 5 * p1], w25(q0 * p1));
-#pragma unroll
-    for (int p1 = 0; p1 < 5; ++p1) pk_radix5(x[5 * p1], x[5 * p1 + 1], x[5 * p1 + 2], x[5 * p1 + 3], x[5 * p1 + 4]);
+    for (int p1 = 1; p1 < 5; ++p1)
+        pk_radix5_tw_k(x[5 * p1], x[5 * p1 + 1], x[5 * p1 + 2], x[5 * p1 + 3], x[5 * p1 + 4], w25(p1), w25(2 * p1), w25(3 * p1), w25(4 * p1));
 }
 __host__ __device__ constexpr int slot25_index(int s) { return 5 * (s % 5) + s / 5; }  // output index held by slot s
 
@@ -134,6 +161,52 @@ __device__ __forceinline__ void lds_read25(v2f (&y)[25], unsigned a) {
           "=&v"(y[23]), "=&v"(y[24])
         : "v"(a), "n"(STEP)
         : "memory");
+}
+
+// ---- spectrum product of one component: x[q] = X[q] conj(C[q]), q = 0..24, on the dot unit -------------------------------------
+// (xr, -xi).(cr', ci') and (xi, xr).(cr', ci') with C' = conj(C) stored.  The three-operand v_dot2_f32_f16, five products per asm block
+// with the dot -> VALU hazard closed by hand (s_nop 2), as bds_acq_wrows.h: the builtin compiles to the accumulating v_dot2c behind a
+// v_mov 0 per result (50 moves per cell).  The result is in the form pk_radix25<true> takes: x[15 + q0] and x[20 + q0] hold sums.
+__device__ __forceinline__ void dot25_summed(const uint32_t (&xn)[25], const uint32_t (&cv)[25], v2f (&x)[25]) {
+    // The first butterfly layer of stage 1 pairs q1 = 1 with 4 and 2 with 3: the products of q1 = 4 and 3 take those of q1 = 1 and 2
+    // as addend and leave the sums x1 + x4, x2 + x3 (pk_radix25<true>).  A block and the block its addends come from are never
+    // neighbours: 0, 1, 2, 4 (+ 1), 3 (+ 2).
+#pragma unroll
+    for (int blk = 0; blk < 5; ++blk) {
+        const int q = blk == 3 ? 20 : blk == 4 ? 15 : 5 * blk;
+        uint32_t xs[5], xc[5];
+#pragma unroll
+        for (int i = 0; i < 5; ++i) xs[i] = __builtin_amdgcn_alignbit(xn[q + i], xn[q + i], 16), xc[i] = xn[q + i];
+        float re[5], im[5];
+        // (neg_hi on the signal word: (xr, -xi) without an xor per point -- the dot instructions take neg_lo / neg_hi, not op_sel,
+        //  so the swapped word of the imaginary part is still prepared: tools/probe/dot2_mods.hip)
+        if (blk < 3) {
+            asm volatile(
+                "v_dot2_f32_f16 %0, %10, %20, 0 neg_hi:[1,0,0]\n v_dot2_f32_f16 %5, %15, %20, 0\n"
+                "v_dot2_f32_f16 %1, %11, %21, 0 neg_hi:[1,0,0]\n v_dot2_f32_f16 %6, %16, %21, 0\n"
+                "v_dot2_f32_f16 %2, %12, %22, 0 neg_hi:[1,0,0]\n v_dot2_f32_f16 %7, %17, %22, 0\n"
+                "v_dot2_f32_f16 %3, %13, %23, 0 neg_hi:[1,0,0]\n v_dot2_f32_f16 %8, %18, %23, 0\n"
+                "v_dot2_f32_f16 %4, %14, %24, 0 neg_hi:[1,0,0]\n v_dot2_f32_f16 %9, %19, %24, 0\n s_nop 2"
+                : "=&v"(re[0]), "=&v"(re[1]), "=&v"(re[2]), "=&v"(re[3]), "=&v"(re[4]), "=&v"(im[0]), "=&v"(im[1]), "=&v"(im[2]), "=&v"(im[3]), "=&v"(im[4])
+                : "v"(xc[0]), "v"(xc[1]), "v"(xc[2]), "v"(xc[3]), "v"(xc[4]), "v"(xs[0]), "v"(xs[1]), "v"(xs[2]), "v"(xs[3]), "v"(xs[4]),
+                  "v"(cv[q]), "v"(cv[q + 1]), "v"(cv[q + 2]), "v"(cv[q + 3]), "v"(cv[q + 4]));
+        } else {
+            const int qa = blk == 3 ? 5 : 10;
+            asm volatile(
+                "v_dot2_f32_f16 %0, %10, %20, %25 neg_hi:[1,0,0]\n v_dot2_f32_f16 %5, %15, %20, %30\n"
+                "v_dot2_f32_f16 %1, %11, %21, %26 neg_hi:[1,0,0]\n v_dot2_f32_f16 %6, %16, %21, %31\n"
+                "v_dot2_f32_f16 %2, %12, %22, %27 neg_hi:[1,0,0]\n v_dot2_f32_f16 %7, %17, %22, %32\n"
+                "v_dot2_f32_f16 %3, %13, %23, %28 neg_hi:[1,0,0]\n v_dot2_f32_f16 %8, %18, %23, %33\n"
+                "v_dot2_f32_f16 %4, %14, %24, %29 neg_hi:[1,0,0]\n v_dot2_f32_f16 %9, %19, %24, %34\n s_nop 2"
+                : "=&v"(re[0]), "=&v"(re[1]), "=&v"(re[2]), "=&v"(re[3]), "=&v"(re[4]), "=&v"(im[0]), "=&v"(im[1]), "=&v"(im[2]), "=&v"(im[3]), "=&v"(im[4])
+                : "v"(xc[0]), "v"(xc[1]), "v"(xc[2]), "v"(xc[3]), "v"(xc[4]), "v"(xs[0]), "v"(xs[1]), "v"(xs[2]), "v"(xs[3]), "v"(xs[4]),
+                  "v"(cv[q]), "v"(cv[q + 1]), "v"(cv[q + 2]), "v"(cv[q + 3]), "v"(cv[q + 4]),
+                  "v"(x[qa].x), "v"(x[qa + 1].x), "v"(x[qa + 2].x), "v"(x[qa + 3].x), "v"(x[qa + 4].x),
+                  "v"(x[qa].y), "v"(x[qa + 1].y), "v"(x[qa + 2].y), "v"(x[qa + 3].y), "v"(x[qa + 4].y));
+        }
+#pragma unroll
+        for (int i = 0; i < 5; ++i) x[q + i] = (v2f){re[i], im[i]};
+    }
 }
 
 // ---- row pass ----------------------------------------------------------------------------------------------------------------
@@ -174,11 +247,14 @@ __global__ __launch_bounds__(kRowsThreads, 2) void k_pfa_rows(RowsArgs A) {
             for (int q = 0; q < 25; ++q) cv[c][q] = row_ok ? crow[(size_t)c * K1 * K2 * K3 + jj + 125 * q] : 0u;
     }
     // stage twiddles: W3125^(j p) after stage 1, W125^(i u) after stage 2 (thread t = i + 25 pg)
-    // (W3125^(j p), p = 5 p0 + p1, as the product of two factors from 4 + 4 registers: all 24 of them held per thread -- 48 registers --
-    //  spill 43 dwords at two waves per SIMD; the 16 extra complex products are 5 % of the row pass's vector instructions)
+    // (W3125^(j p), p = 5 p0 + p1: the 8 with one of p0, p1 zero are held; of the other 16, kTw1Held are held as well and the rest formed as the
+    //  product of two of those 8 -- a product more per component.  All 24 held spilled 43 dwords before the butterflies were fused.)
     v2f tw1a[5], tw1b[5], tw2[5];
 #pragma unroll
     for (int p = 1; p < 5; ++p) tw1a[p] = unit((jj * p) % K3, K3), tw1b[p] = unit((jj * 5 * p) % K3, K3);
+    v2f tw1h[kTw1Held];
+#pragma unroll
+    for (int h = 0; h < kTw1Held; ++h) tw1h[h] = unit((jj * (5 * (h % 4 + 1) + h / 4 + 1)) % K3, K3);  // slot p0 + 5 p1 = (h % 4 + 1) + 5 (h / 4 + 1)
     // stage-2 thread t = 5 i + pg: its five reads / in-place writes sit at 25 (i + 25 r) + 5 pg + c = 5 t + (625 r + c) -- stride 5 over
     // the lanes, conflict-free in the 32-lane halves of a ds_read_b64 and the 16-lane groups of a ds_write_b64 (t = i + 25 pg, the
     // first version, was 2-way in every half-wave: SQ_LDS_BANK_CONFLICT 28 % of the LDS cycles, profiles/r06_b1c_pmc_first.txt)
@@ -205,39 +281,22 @@ __global__ __launch_bounds__(kRowsThreads, 2) void k_pfa_rows(RowsArgs A) {
 #pragma unroll
         for (int c = 0; c < NC; ++c) {
             v2f x[25];
-            // X conj(C): (xr, -xi).(cr', ci') and (xi, xr).(cr', ci') with C' = conj(C) stored.  The three-operand v_dot2_f32_f16 with an inline
-            // zero addend, five products per asm block with the dot -> VALU hazard closed by hand (s_nop 2), as bds_acq_wrows.h: the
-            // builtin compiles to the accumulating v_dot2c behind a v_mov 0 per result (50 moves per cell).
-#pragma unroll
-            for (int q = 0; q < 25; q += 5) {
-                uint32_t xs[5], xc[5];
-#pragma unroll
-                for (int i = 0; i < 5; ++i) xs[i] = __builtin_amdgcn_alignbit(xn[q + i], xn[q + i], 16), xc[i] = xn[q + i];
-                float re[5], im[5];
-                // (neg_hi on the signal word: (xr, -xi) without an xor per point -- the dot instructions take neg_lo / neg_hi, not op_sel,
-                //  so the swapped word of the imaginary part is still prepared: tools/probe/dot2_mods.hip)
-                asm volatile(
-                    "v_dot2_f32_f16 %0, %10, %20, 0 neg_hi:[1,0,0]\n v_dot2_f32_f16 %5, %15, %20, 0\n"
-                    "v_dot2_f32_f16 %1, %11, %21, 0 neg_hi:[1,0,0]\n v_dot2_f32_f16 %6, %16, %21, 0\n"
-                    "v_dot2_f32_f16 %2, %12, %22, 0 neg_hi:[1,0,0]\n v_dot2_f32_f16 %7, %17, %22, 0\n"
-                    "v_dot2_f32_f16 %3, %13, %23, 0 neg_hi:[1,0,0]\n v_dot2_f32_f16 %8, %18, %23, 0\n"
-                    "v_dot2_f32_f16 %4, %14, %24, 0 neg_hi:[1,0,0]\n v_dot2_f32_f16 %9, %19, %24, 0\n s_nop 2"
-                    : "=&v"(re[0]), "=&v"(re[1]), "=&v"(re[2]), "=&v"(re[3]), "=&v"(re[4]), "=&v"(im[0]), "=&v"(im[1]), "=&v"(im[2]), "=&v"(im[3]), "=&v"(im[4])
-                    : "v"(xc[0]), "v"(xc[1]), "v"(xc[2]), "v"(xc[3]), "v"(xc[4]), "v"(xs[0]), "v"(xs[1]), "v"(xs[2]), "v"(xs[3]), "v"(xs[4]),
-                      "v"(cv[c][q]), "v"(cv[c][q + 1]), "v"(cv[c][q + 2]), "v"(cv[c][q + 3]), "v"(cv[c][q + 4]));
-#pragma unroll
-                for (int i = 0; i < 5; ++i) x[q + i] = (v2f){re[i], im[i]};
-            }
+            dot25_summed(xn, cv[c], x);  // X conj(C)
             // stage 1: 25 points over q (k3 = j + 125 q) -> p, twiddle W3125^(j p), a[j][p] at 25 j + p
-            pk_radix25(x);
+            pk_radix25<true>(x);
             if (c > 0) __syncthreads();  // the previous component's stage-3 reads of the region are done
             if (live) {
 #pragma unroll
                 for (int sl = 0; sl < 25; ++sl) {
                     const int p = slot25_index(sl);  // slot p0 + 5 p1 holds output 5 p0 + p1
                     v2f v = x[sl];
-                    if (sl / 5) v = pk_cmul(v, tw1a[sl / 5]);
-                    if (sl % 5) v = pk_cmul(v, tw1b[sl % 5]);
+                    const int h = 4 * (sl / 5 - 1) + sl % 5 - 1;  // the slots with two factors, counted in slot order
+                    if (sl / 5 && sl % 5 && h < kTw1Held) {
+                        v = pk_cmul(v, tw1h[h]);
+                    } else {
+                        if (sl / 5) v = pk_cmul(v, tw1a[sl / 5]);
+                        if (sl % 5) v = pk_cmul(v, tw1b[sl % 5]);
+                    }
                     region[25 * j + p] = to_f2(v);
                 }
             }

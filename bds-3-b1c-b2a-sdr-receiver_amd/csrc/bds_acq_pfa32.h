@@ -103,27 +103,9 @@ __global__ __launch_bounds__(kRowsThreads, 2) void k_pfa32_rows(pfa::RowsArgs A)
 #pragma unroll
         for (int c = 0; c < 2; ++c) {
             v2f x[25];
-            // X conj(C) with conj(C) stored: (xr, -xi).(cr', ci') and (xi, xr).(cr', ci') (bds_acq_pfa.h)
-#pragma unroll
-            for (int q = 0; q < 25; q += 5) {
-                uint32_t xs[5], xc[5];
-#pragma unroll
-                for (int i = 0; i < 5; ++i) xs[i] = __builtin_amdgcn_alignbit(xn[q + i], xn[q + i], 16), xc[i] = xn[q + i];
-                float re[5], im[5];
-                asm volatile(
-                    "v_dot2_f32_f16 %0, %10, %20, 0 neg_hi:[1,0,0]\n v_dot2_f32_f16 %5, %15, %20, 0\n"
-                    "v_dot2_f32_f16 %1, %11, %21, 0 neg_hi:[1,0,0]\n v_dot2_f32_f16 %6, %16, %21, 0\n"
-                    "v_dot2_f32_f16 %2, %12, %22, 0 neg_hi:[1,0,0]\n v_dot2_f32_f16 %7, %17, %22, 0\n"
-                    "v_dot2_f32_f16 %3, %13, %23, 0 neg_hi:[1,0,0]\n v_dot2_f32_f16 %8, %18, %23, 0\n"
-                    "v_dot2_f32_f16 %4, %14, %24, 0 neg_hi:[1,0,0]\n v_dot2_f32_f16 %9, %19, %24, 0\n s_nop 2"
-                    : "=&v"(re[0]), "=&v"(re[1]), "=&v"(re[2]), "=&v"(re[3]), "=&v"(re[4]), "=&v"(im[0]), "=&v"(im[1]), "=&v"(im[2]), "=&v"(im[3]), "=&v"(im[4])
-                    : "v"(xc[0]), "v"(xc[1]), "v"(xc[2]), "v"(xc[3]), "v"(xc[4]), "v"(xs[0]), "v"(xs[1]), "v"(xs[2]), "v"(xs[3]), "v"(xs[4]),
-                      "v"(cv[c][q]), "v"(cv[c][q + 1]), "v"(cv[c][q + 2]), "v"(cv[c][q + 3]), "v"(cv[c][q + 4]));
-#pragma unroll
-                for (int i = 0; i < 5; ++i) x[q + i] = (v2f){re[i], im[i]};
-            }
+            pfa::dot25_summed(xn, cv[c], x);  // X conj(C), the first butterfly layer's sums formed on the addend (bds_acq_pfa.h)
             // stage 1: 25 points over q (k3 = j + 25 q) -> p, twiddle W625^(j p), a[j][p] at 25 j + p
-            pfa::pk_radix25(x);
+            pfa::pk_radix25<true>(x);
             if (live) {
 #pragma unroll
                 for (int sl = 0; sl < 25; ++sl) {

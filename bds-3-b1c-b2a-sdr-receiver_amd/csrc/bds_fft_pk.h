@@ -8,6 +8,7 @@
 // VOP3P source modifiers select (op_sel / op_sel_hi) and negate (neg_lo / neg_hi) the halves of each operand:
 //   a + b, a - b                 v_pk_add_f32 (neg on b)                                1 instead of 2
 //   a + j b, a - j b             v_pk_add_f32, b's halves swapped, one of them negated    1 instead of 2
+//   a + j k b, a - j k b         v_pk_fma_f32, b's halves swapped, one of them negated, k a constant    1 instead of 4
 //   a w                          v_pk_mul_f32 (a.x a.x)(w.x w.y), v_pk_fma_f32 (a.y a.y)(-w.y w.x) + .    2 instead of 4
 //   (a + w b, a - w b)           two v_pk_fma_f32 for the sum, 2 a - sum for the difference   3 instead of 6
 // The compiler folds whole-vector negation and broadcasts into these modifiers but not "swap and negate one half", so the
@@ -34,6 +35,23 @@ __device__ __forceinline__ v2f pk_addj(v2f a, v2f b) {
 __device__ __forceinline__ v2f pk_subj(v2f a, v2f b) {
     v2f d;
     asm("v_pk_add_f32 %0, %1, %2 op_sel:[0,1] op_sel_hi:[1,0] neg_hi:[0,1]" : "=v"(d) : "v"(a), "v"(b));
+    return d;
+}
+// a + j k u, a - j k u with k = (k, k) a compile-time constant in a scalar register pair: the product by j k rides on the sum
+__device__ __forceinline__ v2f pk_addjk(v2f a, v2f u, v2f k) {
+    v2f d;
+    asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel:[1,0,0] op_sel_hi:[0,1,1] neg_lo:[1,0,0]" : "=v"(d) : "v"(u), "s"(k), "v"(a));
+    return d;
+}
+__device__ __forceinline__ v2f pk_subjk(v2f a, v2f u, v2f k) {
+    v2f d;
+    asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel:[1,0,0] op_sel_hi:[0,1,1] neg_hi:[1,0,0]" : "=v"(d) : "v"(u), "s"(k), "v"(a));
+    return d;
+}
+// 2 a - b
+__device__ __forceinline__ v2f pk_twice_minus(v2f a, v2f b) {
+    v2f d;
+    asm("v_pk_fma_f32 %0, %1, 2.0, %2 op_sel_hi:[1,0,1] neg_lo:[0,0,1] neg_hi:[0,0,1]" : "=v"(d) : "v"(a), "v"(b));
     return d;
 }
 // a w
