@@ -66,13 +66,17 @@ def _as_int8(long_signal, settings):
     return np.ascontiguousarray(a).reshape(-1), is_complex
 
 
-def acquisition(long_signal, settings, device: int = 0, prn_list=None, verbose: bool = True) -> AcqResults:
+def acquisition(long_signal, settings, device: int = 0, prn_list=None, verbose: bool = True, b2a_npoint=None) -> AcqResults:
     """Parallel code-phase search acquisition on the GPU.
 
     prn_list (extension): the PRN shard this rank searches; results are zero outside
     the shard so an all-reduce(SUM) over ranks reassembles acqResults.
+    b2a_npoint (extension): True / False sets the device context's opt-in N-point search for B2a at 99.375 MS/s
+    (Context.acq_set_b2a_npoint; it stays set for later calls), None leaves the context as it is (off unless set).
     """
     ctx = get_context(device)
+    if b2a_npoint is not None:
+        ctx.acq_set_b2a_npoint(b2a_npoint)
     samples, is_complex = _as_int8(long_signal, settings)
     ctx.acq_load(settings, samples, is_complex)
     ctx.acq_prepare(settings)

@@ -36,6 +36,7 @@
 #include "bds_acq_wrows.h"
 #include "bds_acq_pfa.h"
 #include "bds_acq_pfa32.h"
+#include "bds_acq_pfa6.h"
 #include "bds_internal.h"
 
 namespace bds {
@@ -138,6 +139,7 @@ struct AcqState {
     size_t cells_cap = 0;
     double pair_gb = 0;              // bds_acq_set_pair_budget_gb (overrides the BDS_ACQ_PAIR_GB of the context's tuning)
     bool pair_gb_set = false;
+    bool b2a_npoint = false;         // bds_acq_set_b2a_npoint: the N-point pair of bds_acq_pfa6.h may run (default off)
     int pb_last = 0;                 // PRNs per launch pair the last run settled on, and what it was decided for: the next run with
     double pb_key[6] = {0};          // the same (P, D, L, element size, components, budget) takes it without asking the driver again
     char *d_mcells = nullptr;        // cell list of the main search of a small grid (all P x D cells in a few launch pairs) ...
@@ -197,7 +199,7 @@ struct AcqState {
     double sum_sq_ext = 0;     // sum x^2 over it: X_rms^2 (Parseval)
     long sums_N = 0, sums_next = 0;  // sizes the two sums above were computed for
     float sX = 1.f, sC = 1.f, sB = 1.f;  // power-of-two storage scales
-    // N-point plan (bds_acq_pfa.h: 1, bds_acq_pfa32.h: 2; 0: none): the cached code spectra are in its layout (CRT order), the search
+    // N-point plan (bds_acq_pfa.h: 1, bds_acq_pfa32.h: 2, bds_acq_pfa6.h: 3; 0: none): the cached code spectra are in its layout (CRT order), the search
     // runs its pair
     int cs_pfa = 0;
     uint4 *d_pfa_coef = nullptr;  // B fragments of the 53-point stage (pfa::make_coef_frags)
@@ -443,7 +445,7 @@ struct CellList {
     const long *cs = nullptr;    // element offset of its code spectra from the Cs base
     const int4 *rng = nullptr;   // searched lag ranges (lo1, hi1, lo2, hi2)
     int gc = 1;                  // consecutive listed cells that share their code spectra (one row workgroup walks them)
-    const int *src = nullptr;    // 80 x 4096 plan only: the rows of listed cell g already lie at cell index src[g] of Bw -- no row pass
+    const int *src = nullptr;    // 80 x 4096 plan and bds_acq_pfa6.h only: the rows of listed cell g already lie at cell index src[g] of Bw -- no row pass
 };
 // where a column pass reports: the sieve (bds_acq_sieve.h); the tile kernel writes per-tile records instead of cellmax / lb (both
 // null then) and uses the list as its overflow list
@@ -796,16 +798,58 @@ extern "C" int bds_acq_load(bds_ctx *ctx, const bds_settings *s_in, const int8_t
 // storage, no resampling, and whole spectrum bins per Doppler step: acqStep N / fs an integer
 // (B1C/acquisition.m:194-198: frqBins(b) = IF - band + acqStep (b - 1), so fft(carr_b x)[k] = fft(carr_1 x)[k - (b - 1) acqStep N / fs]).
 // Everything else -- and every fallback of a run (fp32 storage, run-time-plan kernels) -- takes the L-point pair.
+// LDS the device chain's fine-frequency pick (k_ref_fine_pick, bds_acq_refine.h) keeps its sums in: settings with thousands of fine
+// frequencies (acqStep / 25 large) exceed kFinePickLdsMax and are refined through the host.  One formula for device_refine_ok(),
+// refine_device() and pfa6_pick().
+constexpr size_t kFinePickLdsMax = 60000;
+static size_t fine_pick_lds(const bds_settings &s, int signal, int ncomp) {
+    const bool b1c = signal == BDS_SIGNAL_B1C;
+    const size_t nfine = b1c ? (size_t)m_round(s.acqStep / 25) * 2 + 1 : (size_t)m_round(s.acqStep / 25) + 1;  // B1C :267, B2a :265
+    return sizeof(double) * ((size_t)(b1c ? ncomp : 2 * s.fineNoncoh) * nfine + nfine);
+}
 struct PfaPick {
-    int kind = 0;   // 0: the L-point pair, 1: bds_acq_pfa.h, 2: bds_acq_pfa32.h
-    int shift = 0;  // spectrum bins per Doppler step
+    int kind = 0;   // 0: the L-point pair, 1: bds_acq_pfa.h, 2: bds_acq_pfa32.h, 3: bds_acq_pfa6.h
+    int shift = 0;  // spectrum bins per Doppler step; kind 3: p of acqStep N / fs = p / q in lowest terms
+    int q = 1;      // kind 3: signal spectra per call
 };
+// budget of the inter-pass buffer of one launch pair: the hooks build's BDS_ACQ_PBCAP_GB, else bds_acq_set_pair_budget_gb, else
+// BDS_ACQ_PAIR_GB / its default.  GiB as given (< 0: "auto", 0: minimal), and in bytes for a small grid, where 0 counts as 8 GiB.
+// "auto" is 60 % of the free device memory, which only AcqRun::setup asks the driver for: here it counts as the 8 GiB too.
+static double pair_budget_gb(const bds_ctx *ctx, const AcqState &a) {
+    const Tuning &tune = ctx->tune;
+    return tune.pbcap_gb > 0 ? tune.pbcap_gb : a.pair_gb_set ? a.pair_gb : tune.pair_gb;
+}
+static double pair_budget_bytes(const bds_ctx *ctx, const AcqState &a) {
+    const double pair_gb = pair_budget_gb(ctx, a);
+    return (pair_gb > 0 ? pair_gb : 8.0) * 1073741824.0;
+}
+// Kind 3 (opt-in, bds_acq_set_b2a_npoint): B2a on N = 53 x 6 x 625 samples (99.375 MS/s), both components, fp16 storage on the 80 x 4096
+// plan (whose refinement paths it shares), no resampling, acqStep N / fs = p / q exactly with q <= 5 (B2a/acquisition.m:187-211: bin
+// b = q m + j is spectrum j rotated by p m), every rotation below N, all P x D cells in ONE launch pair within the pair budget (the
+// second-peak pass reads the winning cells out of the main search's buffer), and the refinement as the device chain.
+static PfaPick pfa6_pick(const bds_ctx *ctx, const AcqState &a, const bds_settings &s) {
+    PfaPick pk;
+    const Tuning &tune = ctx->tune;
+    if (!a.b2a_npoint || !tune.pfa || !a.half || a.no_fast_search || a.signal != BDS_SIGNAL_B2A || a.ncomp != 2 || a.rs.on || a.N != pfa6::NP ||
+        !a.plan.small || a.skind >= kF64)
+        return pk;
+    if (tune.neigh != 0 || tune.host_refine || tune.no_bwreuse || tune.nomulti || tune.pbcells > 0) return pk;  // (hooks build: those variants stay L-point)
+    long p = 0, q = 0;
+    if (!pfa6::step_ratio(s.acqStep, s.samplingFreq, a.N, &p, &q) || q > pfa6::kMaxQ || p < 1) return pk;
+    const long D = (long)m_round(s.acqSearchBand * 2 / s.acqStep) + 1;
+    if (p * ((D + q - 1) / q) >= a.N) return pk;
+    if ((double)s.n_acq * (double)D * (double)pfa6::kCellElems * 4.0 > pair_budget_bytes(ctx, a)) return pk;
+    if (fine_pick_lds(s, a.signal, a.ncomp) > kFinePickLdsMax) return pk;  // (device_refine_ok() would send the run to the host path)
+    pk.kind = 3, pk.shift = (int)p, pk.q = (int)q;
+    return pk;
+}
 static PfaPick pfa_pick(const bds_ctx *ctx, const AcqState &a, const bds_settings &s) {
     static const struct {
         long N;
         int kind;
     } admitted[] = {{pfa::NP, 1}, {pfa32::NP, 2}};
     PfaPick pk;
+    if (a.signal == BDS_SIGNAL_B2A) return pfa6_pick(ctx, a, s);
     if (!ctx->tune.pfa || !a.half || a.no_fast_search || a.signal != BDS_SIGNAL_B1C || a.ncomp != 2 || a.rs.on) return pk;
     int kind = 0;
     for (const auto &ad : admitted)
@@ -818,9 +862,11 @@ static PfaPick pfa_pick(const bds_ctx *ctx, const AcqState &a, const bds_setting
     return pk;
 }
 // sizes of the selected pair
-static long pfa_np(int kind) { return kind == 2 ? pfa32::NP : pfa::NP; }
-static int pfa_k3(int kind) { return kind == 2 ? pfa32::K3 : pfa::K3; }
-static int pfa_rows(int kind) { return kind == 2 ? pfa32::K1 * pfa32::K2 : pfa::K1 * pfa::K2; }
+static long pfa_np(int kind) { return kind == 3 ? pfa6::NP : kind == 2 ? pfa32::NP : pfa::NP; }
+static int pfa_k3(int kind) { return kind == 3 ? pfa6::K3 : kind == 2 ? pfa32::K3 : pfa::K3; }
+static int pfa_rows(int kind) { return kind == 3 ? pfa6::K1 * pfa6::K2 : kind == 2 ? pfa32::K1 * pfa32::K2 : pfa::K1 * pfa::K2; }
+static size_t pfa_cell_elems(int kind) { return kind == 3 ? pfa6::kCellElems : kind == 2 ? pfa32::kCellElems : pfa::kCellElems; }
+static int pfa_rows_wgs(int kind) { return kind == 3 ? pfa6::kRowsWgs : kind == 2 ? pfa32::kRowsWgs : pfa::MP * pfa::K2; }
 
 extern "C" int bds_acq_prepare(bds_ctx *ctx, const bds_settings *s_in) {
     if (!ctx || !s_in) return BDS_ERR_ARG;
@@ -876,7 +922,9 @@ extern "C" int bds_acq_prepare(bds_ctx *ctx, const bds_settings *s_in) {
         float2 *cs_dst = a.half ? (float2 *)((__half2 *)a.d_Cs + (size_t)slot * a.ncomp * pl.L)
                                 : a.d_Cs + (size_t)slot * a.ncomp * pl.L;
         if (a.cs_pfa) {  // conj(fft(code)) / N in the CRT layout, [slot][component][53][K2][K3] (the slots keep the L-point stride)
-            if (a.cs_pfa == 2)
+            if (a.cs_pfa == 3)
+                pfa6::forward(st(ctx), ld, a.ncomp, a.d_Bw, (uint32_t *)cs_dst, pfa6::NP, 1, (float)((double)a.sC / (double)a.N), 0);
+            else if (a.cs_pfa == 2)
                 pfa32::forward(st(ctx), ld, a.ncomp, a.d_Bw, (uint32_t *)cs_dst, pfa32::NP, 1, (float)((double)a.sC / (double)a.N), 0);
             else
                 pfa::forward(st(ctx), ld, a.ncomp, a.d_Bw, (uint32_t *)cs_dst, pfa::NP, 1, (float)((double)a.sC / (double)a.N), 0);
@@ -1025,7 +1073,8 @@ struct AcqRun {
     float w0 = 1.f, w1 = 1.f;
     bool fsearch = false, wcols = false, multiprn = false, overlap = false;
     int pfa = 0;               // > 0: an N-point pair runs; the value = spectrum bins per Doppler step
-    int pfa_kind = 0;          // which: 1 bds_acq_pfa.h, 2 bds_acq_pfa32.h
+    int pfa_kind = 0;          // which: 1 bds_acq_pfa.h, 2 bds_acq_pfa32.h, 3 bds_acq_pfa6.h (pfa = p, pfa_q = q of the step p / q)
+    int pfa_q = 1;
     size_t cell_elems = 0;     // fp16-complex-sized elements of one cell in the inter-pass buffer (both components)
     bool dev_refined = false;  // the refinement ran as the device chain
     size_t elem = 8;  // bytes of one stored complex value
@@ -1069,6 +1118,7 @@ struct AcqRun {
     int fine_search();     // threshold + fine-Doppler search, results
     int finish();          // timing record
     // the same decisions as collect() .. fine_search() as one chain of launches with a single download (bds_acq_refine.h)
+    size_t bw_cells() const;  // cells of this run's pair the inter-pass buffer holds
     bool device_refine_ok() const;
     int refine_device();
 };
@@ -1086,12 +1136,13 @@ int AcqRun::setup() {
     G = a.group;
     if (a.cs_pfa) {  // (bds_acq_prepare laid the code spectra out for it with these very settings)
         const PfaPick pk = pfa_pick(ctx, a, *s);
-        if (pk.kind == a.cs_pfa) pfa = pk.shift, pfa_kind = pk.kind;
+        if (pk.kind == a.cs_pfa) pfa = pk.shift, pfa_kind = pk.kind, pfa_q = pk.q;
+        // (kind 3 was admitted for the settings' PRN list: a run on a part of it has fewer cells, never more)
     }
     if (a.cs_pfa && !pfa) return fail(ctx, BDS_ERR_HIP, "internal: code spectra in the N-point layout for a run that cannot use them");
     if ((rc = ensure(ctx, &a.d_Bw, &a.bw_cap, bw_batches(a, ctx->tune) * (size_t)pl.L))) return rc;
     // (N-point pair: ONE signal spectrum, every row stored twice -- 2 N fp16 complex = N float2-sized elements)
-    if ((rc = ensure(ctx, &a.d_Xs, &a.xs_cap, pfa ? (size_t)pfa_np(pfa_kind) : (size_t)D * pl.L))) return rc;
+    if ((rc = ensure(ctx, &a.d_Xs, &a.xs_cap, pfa ? (size_t)pfa_q * (size_t)pfa_np(pfa_kind) : (size_t)D * pl.L))) return rc;
 
     BDS_HIP(ctx, evp.make(&ev0));
     BDS_HIP(ctx, evp.make(&ev1));
@@ -1173,7 +1224,7 @@ int AcqRun::setup() {
         so.recs = a.d_recs;
     }
     elem = a.half ? 4 : 8;
-    cell_elems = pfa ? (pfa_kind == 2 ? pfa32::kCellElems : pfa::kCellElems) : (size_t)ncomp * pl.L;  // stored complex values of one cell in the inter-pass buffer
+    cell_elems = pfa ? pfa_cell_elems(pfa_kind) : (size_t)ncomp * pl.L;  // stored complex values of one cell in the inter-pass buffer
     // One launch pair carries the whole Doppler rows of SEVERAL PRNs through a cell list: the grids fill the chip, a row workgroup
     // walks all the bins of one PRN (its code rows and twiddles set up once per D cells), the row workgroups of different PRNs
     // read the same spectrum rows at about the same time, and a call is a few long launches instead of many short ones.
@@ -1194,7 +1245,7 @@ int AcqRun::setup() {
     // Small grids (D <= 104: cfg2's 63 x 26 cells are 4.3 GB) batch up to the budget too (8 GiB when the budget is 0).  The PRNs are dealt evenly over the
     // pairs; with room for less than two PRNs' cells a pair is one group of one PRN.
     // (BDS_ACQ_NOMULTI / BDS_ACQ_MULTI_ANY / BDS_ACQ_PBCELLS / BDS_ACQ_PBCAP_GB of the hooks build: off / on / cells per pair / budget.)
-    const double pair_gb = tune.pbcap_gb > 0 ? tune.pbcap_gb : a.pair_gb_set ? a.pair_gb : tune.pair_gb;
+    const double pair_gb = pair_budget_gb(ctx, a);
     multiprn = fsearch && P > 1 && !tune.nomulti && (D <= 104 || tune.multi_any || pair_gb != 0);
     PB = 1;
     const double pb_key[6] = {(double)P, (double)D, (double)cell_elems, (double)elem, (double)ncomp, pair_gb + (tune.pbcells ? 1e6 * tune.pbcells : 0)};
@@ -1203,7 +1254,7 @@ int AcqRun::setup() {
         PB = a.pb_last;
         multiprn = PB >= 2;
     } else if (multiprn) {
-        double budget = (pair_gb > 0 ? pair_gb : 8.0) * 1073741824.0;
+        double budget = pair_budget_bytes(ctx, a);
         if (pair_gb < 0) {
             size_t fr = 0, tot = 0;
             if (hipMemGetInfo(&fr, &tot) != hipSuccess) fr = (size_t)16 << 30;
@@ -1228,6 +1279,8 @@ int AcqRun::setup() {
     cells_per_pair = G;
     if (multiprn) n_pairs_total = (P + PB - 1) / PB, cells_per_pair = (long)PB * D;
     if (pfa && !multiprn) multiprn = true, PB = 1, n_pairs_total = P, cells_per_pair = D;  // the N-point pair always runs on cell lists
+    // (bds_acq_pfa6.h was admitted because all cells fit one pair: the second-peak pass reads them there)
+    if (pfa_kind == 3) multiprn = true, PB = P, n_pairs_total = 1, cells_per_pair = (long)P * D;
     // Overlapped passes (BDS_ACQ_OVERLAP=1, fp32-arithmetic kernels): group k's column pass runs on a second stream beside
     // group k+1's row pass, the two working in different halves of the inter-pass buffer.
     overlap = fsearch && tune.overlap && !multiprn;
@@ -1244,7 +1297,9 @@ int AcqRun::forward_all() {
     Plan2D &pl = a.plan;
     if (pfa) {  // ONE transform: the spectrum of bin 0; bin b is its rotation by b * pfa bins (bds_acq_pfa.h)
         SignalLoader ld{a.sview(), a.N, a.n_ext, f0, s->acqStep, 1.0 / a.fs, 0};
-        if (pfa_kind == 2)
+        if (pfa_kind == 3)  // q transforms: the bins 0 .. q - 1 (the loader's batch index is the bin)
+            pfa6::forward(stream(), ld, pfa_q, a.d_Bw, (uint32_t *)a.d_Xs, (long)pfa6::kSpecElems, 0, a.sX * a.sB, 1);
+        else if (pfa_kind == 2)
             pfa32::forward(stream(), ld, 1, a.d_Bw, (uint32_t *)a.d_Xs, 0, 0, a.sX * a.sB, 1);
         else
             pfa::forward(stream(), ld, 1, a.d_Bw, (uint32_t *)a.d_Xs, 0, 0, a.sX * a.sB, 1);
@@ -1319,6 +1374,27 @@ void AcqRun::launch_list(int ncells, Rec *recs, const CellList &cl, int cell0, h
     so1.mid = mid;
     if (mid) mids = true;
     const int hi1 = cl.rng ? -1 : (int)a.N - 1, lo2 = cl.rng ? 0 : 1, hi2 = cl.rng ? -1 : 0;
+    if (pfa_kind == 3) {  // the N-point pair of bds_acq_pfa6.h.  With lag ranges: the masked column pass alone on the cells cl.src names
+                          // in the main search's buffer, or (no cl.src) behind a row pass of the listed cells
+        const int gc = cl.rng ? 1 : std::max(1, cl.gc), chunks = (ncells + gc - 1) / gc;
+        if (!cl.src) {
+            pfa6::RowsArgs ra{(const uint32_t *)a.d_Xs, (const uint32_t *)a.d_Cs, (uint32_t *)a.d_Bw, cl.bin, cl.cs, ncells, gc, pfa, pfa_q};
+            hipLaunchKernelGGL(pfa6::k_pfa6_rows, dim3((unsigned)(pfa6::kRowsWgs * chunks)), dim3(pfa6::kRowsThreads), pfa6::kRowsLds, s_main, ra);
+        }
+        if (mid) (void)hipEventRecord(mid, s_main);
+        const int qch = ctx->tune.pfa_qchunk > 0 ? ctx->tune.pfa_qchunk : 1;
+        const long items = (long)((pfa6::kTiles + qch - 1) / qch) * qch * ncells;
+        const unsigned cgrid = (unsigned)std::min<long>(items, ctx->tune.pfa_cgrid > 0 ? ctx->tune.pfa_cgrid : std::max<long>(512, std::min<long>(8192, items / 24)));
+        pfa6::ColsArgs ca{(const uint32_t *)a.d_Bw, a.d_pfa_coef, ncells, w0, w1, so1.sieve, qch, nullptr, cl.rng, cl.src};
+        if (cl.rng) {
+            want_lds(ctx, pfa6::k_pfa6_cols<true>, pfa6::kColsLds);
+            hipLaunchKernelGGL(pfa6::k_pfa6_cols<true>, dim3(cgrid), dim3(pfa6::kColsThreads), pfa6::kColsLds, s_main, ca);
+        } else {
+            want_lds(ctx, pfa6::k_pfa6_cols<false>, pfa6::kColsLds);
+            hipLaunchKernelGGL(pfa6::k_pfa6_cols<false>, dim3(cgrid), dim3(pfa6::kColsThreads), pfa6::kColsLds, s_main, ca);
+        }
+        return;
+    }
     if (pfa_kind == 2) {  // the N-point pair of bds_acq_pfa32.h: the same cell list and sieve outputs, its own grids
         const int gc = std::max(1, cl.gc), chunks = (ncells + gc - 1) / gc;
         want_lds(ctx, pfa32::k_pfa32_cols, pfa32::kColsLds);
@@ -1370,9 +1446,13 @@ int AcqRun::search() {
     if (multiprn) {
         // float2-sized elements the PB*D cells of one launch pair occupy; if the device cannot give that much after all (another
         // process took it since setup() asked), halve the PRNs per pair
-        for (;;) {
+        for (int tries = 0;; ++tries) {
             const size_t need = ((size_t)PB * D * cell_elems * elem + 7) / 8;
-            if (!(rc = ensure_fit(ctx, &a.d_Bw, &a.bw_cap, std::max(need, bw_batches(a, ctx->tune) * (size_t)pl.L)))) break;
+            // (BDS_ACQ_TEST_PAIR_NOMEM of the hooks build: the first n allocations are taken to have failed)
+            if (tries < ctx->tune.test_pair_nomem && PB > 2)
+                rc = BDS_ERR_NOMEM;
+            else if (!(rc = ensure_fit(ctx, &a.d_Bw, &a.bw_cap, std::max(need, bw_batches(a, ctx->tune) * (size_t)pl.L))))
+                break;
             if (PB <= 2) return rc;
             (void)hipGetLastError();  // (the failed hipMalloc is handled here: it must not surface at the end of the search)
             PB = (PB + 1) / 2;
@@ -1419,7 +1499,7 @@ int AcqRun::search() {
                     const int gc_ = D / dv;  // dv chunks per PRN and row
                     if (gc_ < 32 && dv > 1) break;
                     cl.gc = gc_;
-                    if ((long)(pfa_kind == 2 ? pfa32::kRowsWgs : pfa ? pfa::MP * pfa::K2 : pl.L1) * np_ * dv >= want_wgs) break;
+                    if ((long)(pfa ? pfa_rows_wgs(pfa_kind) : pl.L1) * np_ * dv >= want_wgs) break;
                 }
             }
             // (a call is a handful of pairs: all of them are timed, the last, shorter one included -- cell_pair_ms and
@@ -1586,6 +1666,18 @@ extern "C" int bds_acq_set_pair_budget_gb(bds_ctx *ctx, double gib) {
     if (!ctx->acq) ctx->acq = new AcqState();
     ctx->acq->pair_gb = gib;
     ctx->acq->pair_gb_set = true;
+    return BDS_OK;
+}
+
+/* Opt-in N-point search for the B2a grid at 99.375 MS/s (bds_acq_pfa6.h; pfa6_pick has the conditions).  Takes effect at the next
+   bds_acq_prepare / bds_acq_run: the cached configuration -- plan, storage mode, layout of the code spectra -- is re-derived. */
+extern "C" int bds_acq_set_b2a_npoint(bds_ctx *ctx, int on) {
+    if (!ctx) return BDS_ERR_ARG;
+    if (!ctx->acq) ctx->acq = new AcqState();
+    if (ctx->acq->b2a_npoint != (on != 0)) {
+        ctx->acq->b2a_npoint = on != 0;
+        acq_state_invalidate(ctx->acq);
+    }
     return BDS_OK;
 }
 

@@ -216,8 +216,11 @@ int AcqRun::second_peak_b2a() {
     }
     // specialised kernels: all PRNs' (PRN, winning bin) cells in one launch pair through a cell list
     // (63 tiny launch pairs were ~1 ms of the 2.7 ms refinement at cfg2)
-    const size_t cap_cells = a.bw_cap / (size_t)pl.L * 8 / elem / (size_t)ncomp;  // cells the work buffer holds
+    const size_t cap_cells = bw_cells();  // cells the work buffer holds
     const bool batched = fsearch && (size_t)P <= cap_cells;
+    // (bds_acq_pfa6.h: its spectra are in the N-point layout, launch_cells() has no kernel for them -- always the list, in pieces of
+    //  cap_cells where the buffer holds fewer than P cells: a run whose pair was halved after a failed allocation)
+    const bool listed = batched || pfa_kind == 3;
     BDS_HIP(ctx, hipMemsetAsync(a.d_extra_count, 0, sizeof(int), stream()));  // overflow list of this pass: cell = PRN index
     std::vector<int> h_bin(P);
     std::vector<long> h_cs(P);
@@ -234,11 +237,11 @@ int AcqRun::second_peak_b2a() {
         h_bin[pi] = res[pi].fbin - 1;
         h_cs[pi] = (long)a.cs_slot[prns[pi]] * ncomp * pl.L;
         h_rng[pi] = make_int4((int)rng[pi][0], (int)rng[pi][1], (int)rng[pi][2], (int)rng[pi][3]);
-        if (!batched)
+        if (!listed)
             launch_cells(prns[pi], res[pi].fbin - 1, 1, small ? nullptr : a.d_recs + (size_t)pi * pl.ntiles, (int)rng[pi][0],
                          (int)rng[pi][1], (int)rng[pi][2], (int)rng[pi][3], pi, nullptr);
     }
-    if (batched && P > 0) {
+    if (listed && P > 0) {
         const size_t nb_ = sizeof(int) * P + sizeof(long) * P + sizeof(int4) * P + 64;
         if ((rc = ensure(ctx, &a.d_cells, &a.cells_cap, nb_))) return rc;
         int4 *d_rng = (int4 *)a.d_cells;                       // 16-byte aligned first
@@ -247,8 +250,11 @@ int AcqRun::second_peak_b2a() {
         BDS_HIP(ctx, hipMemcpyAsync(d_rng, h_rng.data(), sizeof(int4) * P, hipMemcpyHostToDevice, stream()));
         BDS_HIP(ctx, hipMemcpyAsync(d_cs, h_cs.data(), sizeof(long) * P, hipMemcpyHostToDevice, stream()));
         BDS_HIP(ctx, hipMemcpyAsync(d_bin, h_bin.data(), sizeof(int) * P, hipMemcpyHostToDevice, stream()));
-        const CellList cl{d_bin, d_cs, d_rng};
-        launch_list(P, small ? nullptr : a.d_recs, cl, 0, nullptr);
+        const int piece = batched ? P : (int)std::max<size_t>(1, cap_cells);
+        for (int g0 = 0; g0 < P; g0 += piece) {
+            const CellList cl{d_bin + g0, d_cs + g0, d_rng + g0};
+            launch_list(std::min(piece, P - g0), small ? nullptr : a.d_recs + (size_t)g0 * pl.ntiles, cl, g0, nullptr);
+        }
     }
     BDS_HIP(ctx, hipGetLastError());
     std::vector<Rec> r2(small ? 0 : (size_t)P * pl.ntiles);
@@ -429,21 +435,25 @@ constexpr int kHostRefine = -1002;   // refine_device: this run needs the host p
 constexpr int kRefCandCap = 16384;   // candidates per stage the device chain holds (cfg3: a few hundred in the band)
 constexpr int kExtra2Cap = 1 << 20;  // candidate list of the B2a second-peak pass (one cell per PRN)
 
+// (the L-point pair: ncomp x L stored values per cell; bds_acq_pfa6.h: its own cell, 0.63 of that.  bw_cap counts 8-byte elements)
+size_t AcqRun::bw_cells() const {
+    if (pfa_kind == 3) return a.bw_cap * 8 / (cell_elems * (size_t)elem);
+    return a.bw_cap / (size_t)a.plan.L * 8 / elem / (size_t)ncomp;
+}
+
 bool AcqRun::device_refine_ok() const {
     const Tuning &tune = ctx->tune;
     if (!wcols || tune.neigh != 0 || tune.host_refine || a.rs.on || a.skind >= kF64 || P < 1) return false;
     if (a.signal == BDS_SIGNAL_B2A) {
         const Plan2D &pl = a.plan;
         if (!(pl.small && fsearch)) return false;  // the tile kernel's second-peak pass reports per-tile records: host path
-        const size_t cap_cells = a.bw_cap / (size_t)pl.L * 8 / elem / (size_t)ncomp;
-        if ((size_t)P > cap_cells) return false;
+        // (bds_acq_pfa6.h: admitted on the 80 x 4096 plan only, its masked column pass reports as that plan's does; the second-peak pass
+        //  is one launch over all P winning cells, which the buffer has to hold in the layout of the pair that ran)
+        if ((size_t)P > bw_cells()) return false;
     }
-    {  // the fine-frequency pick keeps its sums in LDS: thousands of fine frequencies (acqStep / 25 large) go to the host path BEFORE
-       // anything of the device chain is enqueued (round 6, ADVICE r5: the test stood behind the whole job chain, which then ran twice)
-        const bool b1c = a.signal == BDS_SIGNAL_B1C;
-        const size_t nfine = b1c ? (size_t)m_round(s->acqStep / 25) * 2 + 1 : (size_t)m_round(s->acqStep / 25) + 1;  // B1C :267, B2a :265
-        if (sizeof(double) * ((size_t)(b1c ? ncomp : 2 * s->fineNoncoh) * nfine + nfine) > 60000) return false;
-    }
+    // the fine-frequency pick keeps its sums in LDS: thousands of fine frequencies (acqStep / 25 large) go to the host path BEFORE
+    // anything of the device chain is enqueued (round 6, ADVICE r5: the test stood behind the whole job chain, which then ran twice)
+    if (fine_pick_lds(*s, a.signal, ncomp) > kFinePickLdsMax) return false;
     return true;
 }
 
@@ -526,7 +536,7 @@ int AcqRun::refine_device() {
         // The main search of a small grid ran ALL P x D cells in one launch pair (multiprn, cfg2: 1 638 cells, 4.3 GB): the rows of every
         // winning cell still lie in the inter-pass buffer, so the second-peak pass needs no row pass of its own -- its column pass
         // reads cell pi D + b (round 5: 0.11 ms of cfg2's 0.5 ms refinement; BDS_ACQ_NO_BWREUSE of the hooks build switches back)
-        const bool reuse_bw = multiprn && n_pairs_total == 1 && pl.small && !tune.no_bwreuse;
+        const bool reuse_bw = multiprn && n_pairs_total == 1 && pl.small && !tune.no_bwreuse;  // (either pair: launch_list knows which ran)
         const size_t nb_ = 2 * sizeof(int) * P + sizeof(long) * P + sizeof(int4) * P + 64;
         if ((rc = ensure(ctx, &a.d_cells, &a.cells_cap, nb_))) return rc;
         int4 *d_rng = (int4 *)a.d_cells;  // 16-byte aligned first
@@ -566,8 +576,8 @@ int AcqRun::refine_device() {
     const int fine_units = P * fine_per / fine_nc;
     launch_corr<kCorrFreqs>(sm, dim3((unsigned)std::min(fine_units, 1024), kCorrSlices), a.sview(), fine_nc, a.N, (const int8_t *)a.d_codes,
                             a.code_stride, 1.0 / a.fs, (const CorrJob *)a.d_jobs, a.d_jobout, (const int *)&a.d_ref_g->nfine_units, fine_units);
-    const size_t pick_lds = sizeof(double) * ((size_t)(b1c ? ncomp : 2 * s->fineNoncoh) * rp.nfine + rp.nfine);
-    if (pick_lds > 60000) return kHostRefine;  // (cannot happen: device_refine_ok() sends such settings to the host path up front)
+    const size_t pick_lds = fine_pick_lds(*s, a.signal, ncomp);
+    if (pick_lds > kFinePickLdsMax) return kHostRefine;  // (cannot happen: device_refine_ok() sends such settings to the host path up front)
     hipLaunchKernelGGL(k_ref_fine_pick, dim3(P), dim3(256), pick_lds, sm, rp, a.d_ref_prn, (const double2 *)a.d_jobout, kCorrSlices);
     BDS_HIP(ctx, hipGetLastError());
 

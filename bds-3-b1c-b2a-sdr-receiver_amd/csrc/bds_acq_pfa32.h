@@ -329,8 +329,10 @@ __global__ __launch_bounds__(kColsThreads, 2) void k_pfa32_cols(pfa::ColsArgs A)
 // ---- forward transforms: the spectra of the signal (one per call) and of the codes (cached), in the CRT layout ---------------------
 // X[k1, k2, k3] = sum x[n] W_N^(-n k) with n = (n1 N/53 + n2 N/32 + n3 N/625) mod N: rows over n3 (625 = 25 x 25 on conjugates), then
 // 53 points over n1 and 32 over n2 as plain fp32 sums -- the conventions of pfa::forward.
-template <class Loader>
-__global__ __launch_bounds__(32) void k_pfa32_fwd_rows(Loader ld, float2 *T /* [batch][1696][625] */) {
+// (both kernels are templates on K2: bds_acq_pfa6.h runs them for its 53 x 6 x 625)
+template <int K2, class Loader>
+__global__ __launch_bounds__(32) void k_pfa32_fwd_rows(Loader ld, float2 *T /* [batch][53 K2][625] */) {
+    constexpr long NP = (long)K1 * K2 * K3;
     __shared__ float2 region[kRowRegion];
     const int row = blockIdx.x, batch = blockIdx.y, j = threadIdx.x;
     const bool live = j < 25;
@@ -362,7 +364,9 @@ __global__ __launch_bounds__(32) void k_pfa32_fwd_rows(Loader ld, float2 *T /* [
 }
 
 // U[batch][k1][n2][k3] = sum_n1 T[batch][n1][n2][k3] W53^(-n1 k1)
+template <int K2>
 __global__ __launch_bounds__(256) void k_pfa32_fwd_53(const float2 *T, float2 *U) {
+    constexpr long NP = (long)K1 * K2 * K3;
     __shared__ float2 w[K1];
     if (threadIdx.x < K1) {
         float sn, cs;
@@ -436,8 +440,8 @@ __global__ __launch_bounds__(256) void k_pfa32_fwd_32(const float2 *U, uint32_t 
 template <class Loader>
 inline void forward(hipStream_t st, Loader ld, int nb, float2 *tmp, uint32_t *dst, long dst_batch_stride, int conj_flag, float scale, int doubled) {
     float2 *T = tmp, *U = tmp + (size_t)nb * NP;
-    hipLaunchKernelGGL(k_pfa32_fwd_rows<Loader>, dim3(K1 * K2, nb), dim3(32), 0, st, ld, T);
-    hipLaunchKernelGGL(k_pfa32_fwd_53, dim3((K2 * K3 + 255) / 256, nb), dim3(256), 0, st, (const float2 *)T, U);
+    hipLaunchKernelGGL((k_pfa32_fwd_rows<K2, Loader>), dim3(K1 * K2, nb), dim3(32), 0, st, ld, T);
+    hipLaunchKernelGGL(k_pfa32_fwd_53<K2>, dim3((K2 * K3 + 255) / 256, nb), dim3(256), 0, st, (const float2 *)T, U);
     hipLaunchKernelGGL(k_pfa32_fwd_32, dim3((K1 * K3 + 255) / 256, nb), dim3(256), 0, st, (const float2 *)U, dst, dst_batch_stride, conj_flag, scale, doubled);
 }
 

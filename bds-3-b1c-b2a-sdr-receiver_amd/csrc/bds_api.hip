@@ -102,6 +102,7 @@ Tuning tuning_from_env() {
     if (const char *e = std::getenv("BDS_ACQ_KDELTA")) t.kdelta = std::max(0.0, std::min(0.9, std::atof(e)));
     t.no_selfcheck = has("BDS_ACQ_NO_SELFCHECK");
     t.test_force_fallback = has("BDS_ACQ_TEST_FORCE_FALLBACK");
+    t.test_pair_nomem = std::max(0, geti("BDS_ACQ_TEST_PAIR_NOMEM", 0));
     t.wcols = geti("BDS_ACQ_WCOLS", -1);
     t.wrows = geti("BDS_ACQ_WROWS", -1);
     t.ilv = geti("BDS_ACQ_ILV", 1);

@@ -141,8 +141,8 @@ typedef struct bds_timing {
     double shader_clock_GHz; /* engine clock the search kernels ran at (sampled workgroups time themselves with the shader
                                 clock against the reference clock); 0 unless BDS_ACQ_CLOCKPROBE=1              */
     int32_t plan_l1, plan_l2; /* two-pass factorisation of fft_len: column length x row length                          */
-    int32_t rows_kernel;    /* row pass of the search: 0 run-time plan (k_rows_inv), 1 k_rows_inv_f, 2 k_rows_wave_f, 3 N-point pair: k_pfa_rows (fft_len 1 987 500 = 53 x 12 x 3125, B1C at 99.375 MS/s) or k_pfa32_rows (fft_len 1 060 000 = 53 x 32 x 625, B1C at 53 MS/s) */
-    int32_t cols_kernel;    /* column pass: 0 run-time plan (k_cols_inv_max), 1 tile kernel k_cols_inv_max_f, 2 k_cols_wave_f, 3 k_cols_small_f, 4 k_pfa_cols / k_pfa32_cols */
+    int32_t rows_kernel;    /* row pass of the search: 0 run-time plan (k_rows_inv), 1 k_rows_inv_f, 2 k_rows_wave_f, 3 N-point pair: k_pfa_rows (fft_len 1 987 500 = 53 x 12 x 3125, B1C at 99.375 MS/s), k_pfa32_rows (fft_len 1 060 000 = 53 x 32 x 625, B1C at 53 MS/s) or k_pfa6_rows (fft_len 198 750 = 53 x 6 x 625, B2a at 99.375 MS/s, bds_acq_set_b2a_npoint) */
+    int32_t cols_kernel;    /* column pass: 0 run-time plan (k_cols_inv_max), 1 tile kernel k_cols_inv_max_f, 2 k_cols_wave_f, 3 k_cols_small_f, 4 k_pfa_cols / k_pfa32_cols / k_pfa6_cols */
     int32_t kernel_flags;   /* bit 0: components interleaved in the inter-pass buffer; bit 1: packed-fp32 butterflies     */
     int32_t refine_path;     /* 1: candidates -> f64 sums -> peak / second peak / fine search as one device chain with a single download (csrc/bds_acq_refine.h); 0: through the host */
 } bds_timing;
@@ -243,6 +243,24 @@ BDS_API int bds_acq_run(bds_ctx *ctx, const bds_settings *s, const int32_t *prn_
  * (+256 MiB) larger than the new budget needs frees it and allocates the smaller one at that run (round 6; until then only
  * bds_destroy returned the memory). */
 BDS_API int bds_acq_set_pair_budget_gb(bds_ctx *ctx, double gib);
+
+/* Opt-in N-point search for B2a at 99.375 MS/s (csrc/bds_acq_pfa6.h), default 0 (off): the circular correlation over the reference's
+ * own N = 2 code periods = 198 750 = 53 x 6 x 625 samples instead of the zero-padded 327 680.  B2a/acquisition.m:187-211 mixes the
+ * block with one carrier per Doppler bin, frqBins(b) = IF - band + acqStep (b - 1); with acqStep N / fs = p / q in lowest terms the
+ * spectrum of bin q m + j (0-based) is the spectrum of bin j rotated by p m, so a call transforms q signal blocks (5 at the default
+ * 400 Hz step) instead of one per bin.  With the switch on a run takes this pair when ALL of these hold, and the L-point pair -- exactly
+ * as with the switch off -- otherwise:
+ *   - signal B2a (both components), N = 198 750 (samplingFreq 99.375e6), no resampling, int8 input;
+ *   - fp16 storage on the 80 x 4096 plan (the defaults; BDS_ACQ_FP16=0 and every re-run of a call with fp32 storage stay L-point);
+ *   - acqStep and samplingFreq whole numbers of hertz with acqStep N / fs = p / q, q <= 5, p >= 1 (400, 250, 500, 1000 Hz; not 410);
+ *   - p ceil(bins / q) < N;
+ *   - all (PRN of acqSatelliteList) x bin cells fit ONE launch pair within the pair budget (1.66 MB per cell: 2.7 GB for 63 x 26) --
+ *     the second-peak pass (acquisition.m:224-249) reads the winning cells out of the main search's buffer;
+ *   - the refinement runs as the device chain (bds_timing.refine_path 1).
+ * bds_get_timing then reports rows_kernel 3, cols_kernel 4, fft_len 198750, plan_l1 x plan_l2 = 318 x 625.  acqResults are the same
+ * numbers either way (they are decided in f64 on the candidates of the search).  Takes effect at the next bds_acq_prepare /
+ * bds_acq_run and invalidates the cached configuration as bds_reload_tuning does. */
+BDS_API int bds_acq_set_b2a_npoint(bds_ctx *ctx, int on);
 
 /* Diagnostics of the last bds_acq_run: per searched PRN (in search order) and Doppler
  * bin, the maximum of results(bin,:) (fp32 search value) and its 1-based lag.

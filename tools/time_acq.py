@@ -1,8 +1,11 @@
 #!/usr/bin/env python3
 """Time bds_acq_run for any settings, with nothing but native.Context and its timing():
-    python tools/time_acq.py [--set name=value ...] [--prns 19,20 | --prns all] [--repeats 5] [--calls 10] [--sieve-error]
-The settings start from init_settings_b1c() (53 MS/s, the reference's B1C/initSettings.m); --set overrides fields (numbers are parsed).
-A synthetic 40 ms block is loaded once and stays in HBM, the code spectra are prepared and one warm-up call runs before the clock
+    python tools/time_acq.py [--b2a [--b2a-npoint 1]] [--set name=value ...] [--prns 19,20 | --prns all] [--repeats 5] [--calls 10] [--sieve-error]
+The settings start from init_settings_b1c() (53 MS/s, the reference's B1C/initSettings.m), with --b2a from init_settings_b2a() (99.375 MS/s,
+26 bins: `--b2a --prns all` is the grid of BASELINE.json configs[1]); --set overrides fields (numbers are parsed).  --b2a-npoint 1 / 0 sets
+the context's switch for the opt-in N-point search of csrc/bds_acq_pfa6.h (bds_acq_set_b2a_npoint; not given: the library's default, and no
+call of the entry, so that a library of an earlier commit can be timed).
+A synthetic 40 ms block (--b2a: 17 ms) is loaded once and stays in HBM, the code spectra are prepared and one warm-up call runs before the clock
 starts.  Per repeat: the mean over --calls calls of the wall time of acq_run and of the library's own total_ms; then the median and
 max - min of the repeats.  BDS_LIB_PATH selects the library (a build of another commit, for instance): run the tool once per library.
 --sieve-error: also the search grid against the same grid with fp32 storage (BDS_ACQ_FP16=0, test-hooks build), as
@@ -25,6 +28,8 @@ def main():
     ap.add_argument("--calls", type=int, default=10)
     ap.add_argument("--seed", type=int, default=53)
     ap.add_argument("--sieve-error", action="store_true")
+    ap.add_argument("--b2a", action="store_true")
+    ap.add_argument("--b2a-npoint", type=int, choices=(0, 1), default=None)
     a = ap.parse_args()
     if a.sieve_error:
         os.environ.setdefault("BDS_LIB_PATH", os.path.join(ROOT, "bds-3-b1c-b2a-sdr-receiver_amd", "libbds_mi355x_hooks.so"))
@@ -42,16 +47,18 @@ def main():
             except ValueError:
                 over[k] = v
     prns = list(range(1, 64)) if a.prns == "all" else [int(p) for p in a.prns.split(",")]
-    s = bds_amd.init_settings_b1c(**over).copy(acqSatelliteList=prns)
-    spc = int(round(s.samplingFreq * 10e-3))
+    s = (bds_amd.init_settings_b2a if a.b2a else bds_amd.init_settings_b1c)(**over).copy(acqSatelliteList=prns)
+    spc = int(round(s.samplingFreq * (1e-3 if a.b2a else 10e-3)))
     sats = [synth.Sat(prns[0], -1730.0, 0.613 * spc, 0.7, 45.0)] + ([synth.Sat(prns[-1], 2210.0, 0.2 * spc, 2.0, 46.0)] if len(prns) > 2 else [])
-    x = synth.make_if(s, sats, 4 * spc, seed=a.seed)
+    x = synth.make_if(s, sats, (17 if a.b2a else 4) * spc, seed=a.seed)
 
     def context(env):
         os.environ.update(env)
         c = bds_amd.native.Context(0)
         for k in env:
             del os.environ[k]
+        if a.b2a_npoint is not None:
+            c.acq_set_b2a_npoint(a.b2a_npoint)
         c.acq_load(s, x)
         c.acq_prepare(s)
         return c
