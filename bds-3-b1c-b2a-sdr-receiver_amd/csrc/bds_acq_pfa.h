@@ -523,6 +523,42 @@ __global__ __launch_bounds__(kColsThreads, 2) void k_pfa_cols(ColsArgs A) {
                 }
             }
         };
+        // The bound pass needs e = |y_d|^2 + |y_p|^2 only, so the components are summed BEFORE anything crosses the lane pair.  Per t, with
+        //   s = sum_c P_c^2 + Q_c^2 and w = sum_c Q_c P_c' (' = the partner lane's):  S = s + s', x = w - w', and
+        //   e = S + 2 x = (s + 2 w) + (s - 2 w)'
+        // -- three DPP moves and 12 instructions per t where two calls of the form above and their sum take six and 19; t = 0 / 6: each
+        // lane sends the square its partner reports.  1 581 -> 1 350 vector instructions per wave item, columns 10.25 -> 9.88 ms per launch
+        // pair (profiles/r13_cols_teams.txt).  Rounding: |2 w| <= S, so every intermediate is at most 2 S and e is off by a few ulp of S, like
+        // S + 2 x; S <= the larger of e[t], e[12 - t], so that is < 1e-6 of the wave's maximum: inside the 1e-5 of sieve_below.  The values'
+        // pass keeps the form above: what the sieve reports does not change by a bit.
+        auto epilogue_sum = [&](const f4 (&acc2)[NC][3], float (&e)[6]) {
+            float P[NC][7], Q[NC][7];
+#pragma unroll
+            for (int c = 0; c < NC; ++c) {
+                float v[12];
+#pragma unroll
+                for (int k = 0; k < 12; ++k) v[k] = acc2[c][k >> 2][k & 3];
+                real_dft12(v, P[c], Q[c]);
+            }
+            auto partner = [](float a) { return __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, a), 0xB1, 0xf, 0xf, true)); };
+            {
+                float p0 = P[0][0] * P[0][0], p6 = P[0][6] * P[0][6];  // Q[0] = Q[6] = 0
+#pragma unroll
+                for (int c = 1; c < NC; ++c) p0 = fmaf(P[c][0], P[c][0], p0), p6 = fmaf(P[c][6], P[c][6], p6);
+                e[0] = (odd ? p6 : p0) + partner(odd ? p0 : p6);  // even: t2 = 0, odd: t2 = 6
+            }
+#pragma unroll
+            for (int t = 1; t < 6; ++t) {
+                float sl = P[0][t] * P[0][t], w = Q[0][t] * partner(P[0][t]);
+                sl = fmaf(Q[0][t], Q[0][t], sl);
+#pragma unroll
+                for (int c = 1; c < NC; ++c) {
+                    sl = fmaf(P[c][t], P[c][t], sl), sl = fmaf(Q[c][t], Q[c][t], sl);
+                    w = fmaf(Q[c][t], partner(P[c][t]), w);
+                }
+                e[t] = fmaf(2.f, w, sl) + partner(fmaf(-2.f, w, sl));
+            }
+        };
         auto block = [&](int nb, float (&m2)[2][6], auto parts_tag) {
             f4 acc2[NC][3];
             matrix(nb, acc2, parts_tag);
@@ -535,7 +571,9 @@ __global__ __launch_bounds__(kColsThreads, 2) void k_pfa_cols(ColsArgs A) {
         // The bound pass, software-pipelined: the matrix instructions of output block nb + 1 are in flight while the vector pipe works on
         // block nb's accumulators (two waves per SIMD that started together stay in step -- both in their matrix phase, then both in
         // their epilogue -- so the overlap has to come from inside the wave).  Fully unrolled: one scheduling region (0.93 -> 0.905 ms per
-        // 201 cells; a forced 1 : 6 or 1 : 9 matrix : vector interleave by sched_group_barrier measured the same).
+        // 201 cells; a forced 1 : 6 or 1 : 9 matrix : vector interleave by sched_group_barrier measured the same).  (The two waves of a SIMD as
+        // teams of one 512-thread workgroup -- plain, one of them at s_setprio 1, or one of them not pipelined -- measured 0 to +5 %, and
+        // the K tail on the 16-deep instruction, which issues in the same 16 cycles, +4 %: HISTORY.md 8.)
         f4 accp[2][NC][3];
         matrix(0, accp[0], std::integral_constant<int, kParts1>{});
         // the cell's maximum so far and the PRN's running bound.  (Requested here, behind block 0's matrix instructions and their wait for
@@ -544,14 +582,15 @@ __global__ __launch_bounds__(kColsThreads, 2) void k_pfa_cols(ColsArgs A) {
         const SieveBounds bd = sieve_bounds(A.sieve, cell);
 #pragma unroll
         for (int nb = 0; nb < NB; ++nb) {
-            float m2[2][6];
+            float m2[2][6], es[6];
             if (nb + 1 < NB) matrix(nb + 1, accp[(nb + 1) & 1], std::integral_constant<int, kParts1>{});
-            epilogue(accp[nb & 1], m2);
+            if (DBG) epilogue(accp[nb & 1], m2);  // (the debug instantiation reports the components)
+            else epilogue_sum(accp[nb & 1], es);
             const int t1 = (16 * nb + (lane & 15)) >> 1;
             float bmax = 0.f, bsum = 0.f;
 #pragma unroll
             for (int i = 0; i < 6; ++i) {
-                const float e = NC == 2 ? m2[0][i] + m2[1][i] : m2[0][i];
+                const float e = !DBG ? es[i] : NC == 2 ? m2[0][i] + m2[1][i] : m2[0][i];
                 bmax = fmaxf(bmax, e), bsum += e;
             }
             if (!(t1 < K1 && t3o < K3)) bmax = 0.f, bsum = 0.f;  // (selects, no branch: the seven blocks stay one scheduling region)
