@@ -1,0 +1,454 @@
+// bds_synth / bds_synth_file / bds_synth_noise: synthetic IF records made on the device (include/bds_mi355x.h, "synthetic IF
+// records").  The signal is bds_amd/synth.py:make_if's, sample by sample in its own float64 operation order; the random stream is
+// counter-based (bds_synth_math.h), so sample n depends on (seed, n, settings, satellites) alone and a record can be made in any
+// pieces.  Built with -ffp-contract=off like the tracking correlator: the index arithmetic rounds as NumPy's does.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cmath>
+
+#include "bds_internal.h"
+#include "bds_synth_math.h"
+
+namespace bds {
+namespace synth {
+
+constexpr int kCodeLen = 10230;
+constexpr int kCodeWords = 320;  // a primary code as bits: 10230 bits = 1 279 bytes, held in 320 dwords
+constexpr int kUnitBytes = 16;   // what one lane stores: one 16-byte store of consecutive samples
+
+struct Sat {            // one satellite entry, everything the host can form once (same IEEE operations as synth.py:88-90,97)
+    double delay;       // samples
+    double ratio;       // fcode / fs
+    double fcarr;       // IF + doppler
+    double phase;
+    double amp;         // sigma sqrt(4 10^(cn0 / 10) / fs)
+    int64_t pmin;       // first code period of this call's symbol table
+    int64_t sym_off;    // offset of its D row in the symbol table; the S row follows at + sym_len
+    int32_t sym_len;    // periods in the table
+    int32_t code_slot;  // which bit-packed (data, pilot) code pair
+};
+
+struct Params {
+    const Sat *sats;
+    const uint32_t *codes;  // [slot][data, pilot][kCodeWords], bit i = chip i is +1
+    const int8_t *sym;      // +-1
+    double fs, ncode, sigma, threshold, k61, k29;
+    uint64_t seed;
+    int32_t n_sat, b1c, conj, p61s;
+};
+
+// the record before the noise: sum over the satellites, in list order, of make_if's z (synth.py:87-112)
+template <bool IQ>
+__device__ __forceinline__ void clean_sum(const Params &p, int64_t n, double &acc_i, double &acc_q) {
+    const double nd = (double)n;
+    acc_i = 0.0;
+    acc_q = 0.0;
+    for (int k = 0; k < p.n_sat; ++k) {
+        const Sat s = p.sats[k];
+        const double chips = (nd - s.delay) * s.ratio;  // code phase in chips (may be < 0)
+        const double period = floor(chips / p.ncode);
+        const double cph = chips - period * p.ncode;
+        const int ci = min((int)cph, kCodeLen - 1);
+        int64_t pi = (int64_t)period - s.pmin;  // the table covers every period of the call; the clamp keeps a lane in bounds whatever happens
+        pi = pi < 0 ? 0 : (pi >= s.sym_len ? s.sym_len - 1 : pi);
+        const double d_sym = (double)p.sym[s.sym_off + pi], p_sym = (double)p.sym[s.sym_off + s.sym_len + pi];
+        const uint32_t *code = p.codes + (size_t)s.code_slot * (2 * kCodeWords) + (ci >> 5);
+        const double cd = ((code[0] >> (ci & 31)) & 1u) ? 1.0 : -1.0;
+        const double cp = ((code[kCodeWords] >> (ci & 31)) & 1u) ? 1.0 : -1.0;
+        double x = (s.fcarr * nd) / p.fs;
+        x = x - trunc(x);  // fmod(x, 1), exactly
+        const double th = 6.283185307179586 * x + s.phase;
+        double br, bi;
+        if (p.b1c) {
+            const double boc11 = ((int64_t)floor(cph * 2.0) & 1) ? 1.0 : -1.0;  // 0 -> -c, 1 -> +c
+            const double boc61 = ((int64_t)floor(cph * 12.0) & 1) ? 1.0 : -1.0;  // sub-chip ii - 1 -> (-1)^ii (the parity of a (mod 12) is the parity of a)
+            br = 0.5 * d_sym * cd * boc11 - p.k61 * cp * boc61 * (p.p61s ? p_sym : 1.0);
+            bi = p.k29 * cp * boc11 * p_sym;
+        } else {  // d sin(th) + p cos(th) = Re[(p - j d) e^{j th}]
+            br = p_sym * cp;
+            bi = -(d_sym * cd);
+        }
+        const double ar = s.amp * br, ai = s.amp * bi;
+        double sn, cs;
+        sincos_strict(th, sn, cs);
+        acc_i += ar * cs - ai * sn;
+        if (IQ) {
+            const double im = ar * sn + ai * cs;
+            acc_q += p.conj ? -im : im;
+        }
+    }
+}
+
+__device__ __forceinline__ int quantise8(double v) {  // np.clip(np.rint(v), -127, 127).astype(int8)
+    return (int)fmin(fmax(rint(v), -127.0), 127.0);
+}
+
+// FMT 0: float64 clean sum; 1: real int8; 2: interleaved I/Q int8; 3: packed 2+2-bit I/Q.  A lane makes the consecutive samples
+// of one 16-byte unit (2 / 16 / 8 / 32 of them) and stores the unit whole; unit u starts at sample first + u * samples-per-unit.
+// `out` holds n_units units (the host pads the device buffer to whole units and copies out what was asked for).
+template <int FMT>
+__global__ __launch_bounds__(256) void k_synth_if(Params p, int64_t first, int64_t n_units, uint4 *__restrict__ out) {
+    constexpr int kPerDword = FMT == 1 ? 4 : FMT == 2 ? 2 : 8;  // samples per dword (FMT 0: a sample is two dwords)
+    for (int64_t u = (int64_t)blockIdx.x * 256 + threadIdx.x; u < n_units; u += (int64_t)gridDim.x * 256) {
+        uint4 unit;
+        if (FMT == 0) {
+            double a, b, q;
+            clean_sum<false>(p, first + 2 * u, a, q);
+            clean_sum<false>(p, first + 2 * u + 1, b, q);
+            unit.x = (uint32_t)__double2loint(a), unit.y = (uint32_t)__double2hiint(a);
+            unit.z = (uint32_t)__double2loint(b), unit.w = (uint32_t)__double2hiint(b);
+        } else {
+            const int64_t n0 = first + u * (4 * kPerDword);
+            uint32_t w0 = 0, w1 = 0, w2 = 0, w3 = 0;
+            for (int d = 0; d < 4; ++d) {
+                uint32_t w = 0;
+                for (int j = 0; j < kPerDword; ++j) {
+                    const int64_t n = n0 + d * kPerDword + j;
+                    double si, sq, gi, gq;
+                    clean_sum<FMT != 1>(p, n, si, sq);
+                    noise_normals(p.seed, n, gi, gq);
+                    const int vi = quantise8(si + p.sigma * gi);
+                    if (FMT == 1) {
+                        w |= (uint32_t)(uint8_t)vi << (8 * j);
+                    } else {
+                        const int vq = quantise8(sq + p.sigma * gq);
+                        if (FMT == 2)
+                            w |= ((uint32_t)(uint8_t)vi | ((uint32_t)(uint8_t)vq << 8)) << (16 * j);
+                        else  // bit 0 = I negative, bit 1 = Q negative, bit 2 = |I| is 3, bit 3 = |Q| is 3; 0 counts as positive
+                            w |= ((vi < 0 ? 1u : 0u) | (vq < 0 ? 2u : 0u) | ((double)abs(vi) > p.threshold ? 4u : 0u) |
+                                  ((double)abs(vq) > p.threshold ? 8u : 0u))
+                                 << (4 * j);
+                    }
+                }
+                w0 = d == 0 ? w : w0, w1 = d == 1 ? w : w1, w2 = d == 2 ? w : w2, w3 = d == 3 ? w : w3;
+            }
+            unit = make_uint4(w0, w1, w2, w3);
+        }
+        out[u] = unit;
+    }
+}
+
+__global__ __launch_bounds__(256) void k_synth_noise(uint64_t seed, int64_t first, int64_t n, double *__restrict__ g_i, double *__restrict__ g_q) {
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+        double a, b;
+        noise_normals(seed, first + i, a, b);
+        if (g_i) g_i[i] = a;
+        if (g_q) g_q[i] = b;
+    }
+}
+
+static int samples_per_unit(int fmt) { return fmt == 0 ? 2 : fmt == 1 ? 16 : fmt == 2 ? 8 : 32; }
+// bytes of n samples (format 3: n even)
+static size_t bytes_of(int fmt, int64_t n) { return fmt == 0 ? (size_t)n * 8 : fmt == 1 ? (size_t)n : fmt == 2 ? (size_t)n * 2 : (size_t)n / 2; }
+static int64_t units_of(int fmt, int64_t n) { return (n + samples_per_unit(fmt) - 1) / samples_per_unit(fmt); }
+
+// what a call needs on the device besides its output buffers
+struct Plan {
+    Params p{};
+    int fmt = 0;
+    std::vector<Sat> sats;
+    std::vector<uint32_t> codes;
+    std::vector<int8_t> sym;
+    void *d_sats = nullptr, *d_codes = nullptr, *d_sym = nullptr;
+};
+
+// Every argument check of bds_synth / bds_synth_file, and the host side of the plan.  No device call in here.
+static int make_plan(bds_ctx *ctx, const char *who, const bds_settings *s, int n_sat, const bds_synth_sat *sats, const bds_synth_opts *o,
+                     int64_t first, int64_t n, Plan &pl) {
+    if (!s || !o) return fail(ctx, BDS_ERR_ARG, "%s: settings / opts is NULL", who);
+    if (o->size != (int32_t)sizeof(bds_synth_opts))
+        return fail(ctx, BDS_ERR_ARG, "%s: opts.size = %d, sizeof(bds_synth_opts) = %d", who, o->size, (int)sizeof(bds_synth_opts));
+    if (o->format < 0 || o->format > 3) return fail(ctx, BDS_ERR_ARG, "%s: opts.format = %d (0 float64 clean, 1 int8, 2 I/Q int8, 3 packed I/Q)", who, o->format);
+    if (s->signal != BDS_SIGNAL_B1C && s->signal != BDS_SIGNAL_B2A) return fail(ctx, BDS_ERR_ARG, "%s: settings.signal invalid", who);
+    if (s->codeLength != kCodeLen) return fail(ctx, BDS_ERR_ARG, "%s: settings.codeLength = %d, the primary codes have %d chips", who, s->codeLength, kCodeLen);
+    if (!(s->samplingFreq > 0) || !std::isfinite(s->samplingFreq) || !(s->codeFreqBasis > 0) || !std::isfinite(s->codeFreqBasis) || !std::isfinite(s->IF))
+        return fail(ctx, BDS_ERR_ARG, "%s: settings.samplingFreq / codeFreqBasis / IF invalid", who);
+    if (o->code_doppler && (!(s->carrFreqBasis != 0) || !std::isfinite(s->carrFreqBasis)))
+        return fail(ctx, BDS_ERR_ARG, "%s: settings.carrFreqBasis invalid (code_doppler is on)", who);
+    if (n_sat < 0 || n_sat > BDS_MAX_PRN || (n_sat && !sats)) return fail(ctx, BDS_ERR_ARG, "%s: n_sat = %d (0 .. %d satellites)", who, n_sat, BDS_MAX_PRN);
+    if (!(o->sigma >= 0) || !std::isfinite(o->sigma) || !std::isfinite(o->threshold)) return fail(ctx, BDS_ERR_ARG, "%s: opts.sigma / threshold invalid", who);
+    if (first < 0 || n < 0 || first > (1LL << 53) - n) return fail(ctx, BDS_ERR_ARG, "%s: samples %lld .. +%lld outside 0 .. 2^53", who, (long long)first, (long long)n);
+    if (o->format == 3 && ((first | n) & 1))
+        return fail(ctx, BDS_ERR_ARG, "%s: a packed record holds two samples per byte: first_sample = %lld and n_samples = %lld must be even", who, (long long)first, (long long)n);
+    if (o->symbols && o->n_sym < 1) return fail(ctx, BDS_ERR_ARG, "%s: opts.n_sym = %lld with symbols given", who, (long long)o->n_sym);
+    for (int k = 0; k < n_sat; ++k) {
+        if (sats[k].prn < 1 || sats[k].prn > BDS_MAX_PRN) return fail(ctx, BDS_ERR_ARG, "%s: satellite %d: PRN %d out of range (1 .. %d)", who, k + 1, sats[k].prn, BDS_MAX_PRN);
+        if (!std::isfinite(sats[k].doppler) || !std::isfinite(sats[k].delay) || !std::isfinite(sats[k].phase) || !std::isfinite(sats[k].cn0_dbhz) ||
+            std::fabs(sats[k].phase) > 1e6)
+            return fail(ctx, BDS_ERR_ARG, "%s: satellite %d: doppler / delay / phase / cn0_dbhz invalid", who, k + 1);
+    }
+    const double fs = s->samplingFreq, fc = s->codeFreqBasis, ncode = (double)kCodeLen;
+    pl.fmt = o->format;
+    Params &p = pl.p;
+    p.fs = fs, p.ncode = ncode, p.sigma = o->sigma, p.threshold = o->threshold > 0 ? o->threshold : o->sigma;
+    p.k61 = std::sqrt(1.0 / 11.0), p.k29 = std::sqrt(29.0 / 44.0);
+    p.seed = o->seed, p.n_sat = n_sat, p.b1c = s->signal == BDS_SIGNAL_B1C, p.conj = o->iq_sign < 0, p.p61s = o->pilot61_secondary != 0;
+    // the samples the device evaluates: every piece of the call makes its last 16-byte unit whole (at most 31 samples more)
+    const int64_t last = first + n + 32;
+    int slot_of[BDS_MAX_PRN + 1];
+    std::fill(slot_of, slot_of + BDS_MAX_PRN + 1, -1);
+    int n_slots = 0;
+    int64_t sym_total = 0;
+    pl.sats.resize((size_t)n_sat);
+    for (int k = 0; k < n_sat; ++k) {
+        Sat &d = pl.sats[(size_t)k];
+        const bds_synth_sat &a = sats[k];
+        const double fcode = o->code_doppler ? fc * (1.0 + a.doppler / s->carrFreqBasis) : fc;
+        d.delay = a.delay, d.ratio = fcode / fs, d.fcarr = s->IF + a.doppler, d.phase = a.phase;
+        d.amp = o->sigma * std::sqrt(4.0 * std::pow(10.0, a.cn0_dbhz / 10.0) / fs);
+        if (!(d.ratio > 0) || !std::isfinite(d.ratio) || !std::isfinite(d.amp))
+            return fail(ctx, BDS_ERR_ARG, "%s: satellite %d: code rate / amplitude not finite and positive", who, k + 1);
+        // the code period is monotone in n: the first and the last sample bound it (one period of margin either side)
+        const double p0 = std::floor(((double)first - d.delay) * d.ratio / ncode), p1 = std::floor(((double)last - d.delay) * d.ratio / ncode);
+        if (!(std::fabs(p0) < 4e18) || !(std::fabs(p1) < 4e18) || p1 - p0 > (double)(1 << 28))
+            return fail(ctx, BDS_ERR_ARG, "%s: satellite %d: code periods %g .. %g: too many for one call", who, k + 1, p0, p1);
+        d.pmin = (int64_t)p0 - 1;
+        d.sym_len = (int32_t)((int64_t)p1 + 1 - d.pmin + 1);
+        d.sym_off = sym_total;
+        sym_total += 2 * (int64_t)d.sym_len;
+        if (sym_total > (1LL << 30)) return fail(ctx, BDS_ERR_ARG, "%s: symbol table of more than 2^30 entries: make the record in shorter calls", who);
+        if (slot_of[a.prn] < 0) slot_of[a.prn] = n_slots++;
+        d.code_slot = slot_of[a.prn];
+    }
+    pl.sym.resize((size_t)sym_total);
+    for (int k = 0; k < n_sat; ++k) {
+        const Sat &d = pl.sats[(size_t)k];
+        for (int c = 0; c < 2; ++c)
+            for (int32_t i = 0; i < d.sym_len; ++i) {
+                const int64_t period = d.pmin + i;
+                int v;
+                if (o->symbols) {  // (period + 1) mod n_sym, non-negative, as make_if's pidx
+                    int64_t m = (period + 1) % o->n_sym;
+                    if (m < 0) m += o->n_sym;
+                    v = o->symbols[((size_t)k * 2 + (size_t)c) * (size_t)o->n_sym + (size_t)m];
+                    if (v != 1 && v != -1) return fail(ctx, BDS_ERR_ARG, "%s: opts.symbols[%d][%d][%lld] = %d is not +-1", who, k, c, (long long)m, v);
+                } else {
+                    v = symbol(o->seed, period, sats[k].prn, c);
+                }
+                pl.sym[(size_t)d.sym_off + (size_t)c * (size_t)d.sym_len + (size_t)i] = (int8_t)v;
+            }
+    }
+    pl.codes.assign((size_t)n_slots * 2 * kCodeWords, 0u);
+    for (int prn = 1; prn <= BDS_MAX_PRN; ++prn) {
+        if (slot_of[prn] < 0) continue;
+        int8_t chips[kCodeLen];
+        for (int c = 0; c < 2; ++c) {
+            if (gen_primary(s->signal, c == 1, prn, chips) != kCodeLen) return fail(ctx, BDS_ERR_ARG, "%s: no primary code for PRN %d", who, prn);
+            uint32_t *w = &pl.codes[((size_t)slot_of[prn] * 2 + (size_t)c) * kCodeWords];
+            for (int i = 0; i < kCodeLen; ++i)
+                if (chips[i] > 0) w[i >> 5] |= 1u << (i & 31);
+        }
+    }
+    return BDS_OK;
+}
+
+static void plan_free(Plan &pl) {
+    if (pl.d_sats) (void)hipFree(pl.d_sats);
+    if (pl.d_codes) (void)hipFree(pl.d_codes);
+    if (pl.d_sym) (void)hipFree(pl.d_sym);
+    pl.d_sats = pl.d_codes = pl.d_sym = nullptr;
+}
+
+static int plan_upload(bds_ctx *ctx, Plan &pl) {
+    auto up = [&](void *&d, const void *h, size_t bytes) -> hipError_t {
+        hipError_t e = hipMalloc(&d, std::max<size_t>(bytes, 16));
+        if (e == hipSuccess && bytes) e = hipMemcpy(d, h, bytes, hipMemcpyHostToDevice);
+        return e;
+    };
+    BDS_HIP(ctx, up(pl.d_sats, pl.sats.data(), pl.sats.size() * sizeof(Sat)));
+    BDS_HIP(ctx, up(pl.d_codes, pl.codes.data(), pl.codes.size() * sizeof(uint32_t)));
+    BDS_HIP(ctx, up(pl.d_sym, pl.sym.data(), pl.sym.size()));
+    pl.p.sats = (const Sat *)pl.d_sats, pl.p.codes = (const uint32_t *)pl.d_codes, pl.p.sym = (const int8_t *)pl.d_sym;
+    return BDS_OK;
+}
+
+// n samples from `first` into d_out (whole units: units_of(fmt, n) * 16 bytes), on `stream`
+static int launch(bds_ctx *ctx, const Plan &pl, hipStream_t stream, int64_t first, int64_t n, void *d_out) {
+    const int64_t units = units_of(pl.fmt, n);
+    if (units < 1) return BDS_OK;
+    const unsigned grid = (unsigned)std::min<int64_t>((units + 255) / 256, (int64_t)(ctx->n_cu > 0 ? ctx->n_cu : 256) * 8);
+    uint4 *out = (uint4 *)d_out;
+    switch (pl.fmt) {
+        case 0: hipLaunchKernelGGL(k_synth_if<0>, dim3(grid), dim3(256), 0, stream, pl.p, first, units, out); break;
+        case 1: hipLaunchKernelGGL(k_synth_if<1>, dim3(grid), dim3(256), 0, stream, pl.p, first, units, out); break;
+        case 2: hipLaunchKernelGGL(k_synth_if<2>, dim3(grid), dim3(256), 0, stream, pl.p, first, units, out); break;
+        default: hipLaunchKernelGGL(k_synth_if<3>, dim3(grid), dim3(256), 0, stream, pl.p, first, units, out); break;
+    }
+    BDS_HIP(ctx, hipGetLastError());
+    return BDS_OK;
+}
+
+// samples per piece: a multiple of 32 (a whole unit in every format), at least 32
+static int64_t piece_of(int fmt, int64_t piece_samples) {
+    if (piece_samples <= 0) piece_samples = (int64_t)((64u << 20) / (fmt == 0 ? 8 : fmt == 2 ? 2 : 1));  // 64 MiB per piece (packed: 32 MiB)
+    return piece_samples;
+}
+
+static void timing_of(bds_ctx *ctx, double total, double gen, double copy) {
+    ctx->timing = bds_timing{};
+    ctx->timing.total_ms = total, ctx->timing.forward_ms = gen, ctx->timing.search_ms = copy;
+}
+
+}  // namespace synth
+}  // namespace bds
+
+using namespace bds;
+using namespace bds::synth;
+
+extern "C" int bds_synth(bds_ctx *ctx, const bds_settings *s, int n_sat, const bds_synth_sat *sats, const bds_synth_opts *opts,
+                         int64_t first_sample, int64_t n_samples, void *out, size_t out_bytes) {
+    Plan pl;
+    if (int rc = make_plan(ctx, "bds_synth", s, n_sat, sats, opts, first_sample, n_samples, pl)) return rc;
+    const size_t need = bytes_of(pl.fmt, n_samples);
+    if (out_bytes < need || (need && !out))
+        return fail(ctx, BDS_ERR_ARG, "bds_synth: out holds %zu bytes, %lld samples of format %d take %zu", out ? out_bytes : (size_t)0, (long long)n_samples, pl.fmt, need);
+    if (!ctx) return fail(ctx, BDS_ERR_ARG, "bds_synth: ctx is NULL");
+    if (n_samples == 0) return BDS_OK;
+    BDS_HIP(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = (hipStream_t)ctx->stream;
+    const int64_t piece = std::min<int64_t>(n_samples, (piece_of(pl.fmt, 0) * 4 + 31) / 32 * 32);  // up to 256 MiB of the record on the device at a time
+    void *d_out = nullptr;
+    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
+    double t_gen = 0, t_copy = 0;
+    int rc = plan_upload(ctx, pl);
+    hipError_t e = hipSuccess;
+    if (!rc) e = hipMalloc(&d_out, (size_t)units_of(pl.fmt, piece) * kUnitBytes);
+    for (int i = 0; i < 3 && !rc && e == hipSuccess; ++i) e = hipEventCreate(&ev[i]);
+    for (int64_t a = 0; a < n_samples && !rc && e == hipSuccess; a += piece) {
+        const int64_t m = std::min(piece, n_samples - a);
+        e = hipEventRecord(ev[0], st);
+        if (e == hipSuccess) rc = launch(ctx, pl, st, first_sample + a, m, d_out);
+        if (!rc && e == hipSuccess) e = hipEventRecord(ev[1], st);
+        if (!rc && e == hipSuccess) e = hipMemcpyAsync((char *)out + bytes_of(pl.fmt, a), d_out, bytes_of(pl.fmt, m), hipMemcpyDeviceToHost, st);
+        if (!rc && e == hipSuccess) e = hipEventRecord(ev[2], st);
+        if (!rc && e == hipSuccess) e = hipStreamSynchronize(st);
+        float g = 0, c = 0;
+        if (!rc && e == hipSuccess) e = hipEventElapsedTime(&g, ev[0], ev[1]);
+        if (!rc && e == hipSuccess) e = hipEventElapsedTime(&c, ev[1], ev[2]);
+        t_gen += g, t_copy += c;
+    }
+    for (auto v : ev)
+        if (v) (void)hipEventDestroy(v);
+    if (d_out) (void)hipFree(d_out);
+    plan_free(pl);
+    if (rc) return rc;
+    if (e != hipSuccess) return fail(ctx, e == hipErrorOutOfMemory ? BDS_ERR_NOMEM : BDS_ERR_HIP, "bds_synth: %s", hipGetErrorString(e));
+    timing_of(ctx, t_gen + t_copy, t_gen, t_copy);
+    return BDS_OK;
+}
+
+extern "C" int bds_synth_file(bds_ctx *ctx, const bds_settings *s, int n_sat, const bds_synth_sat *sats, const bds_synth_opts *opts,
+                              int64_t first_sample, int64_t n_samples, const char *path, int64_t piece_samples) {
+    Plan pl;
+    if (int rc = make_plan(ctx, "bds_synth_file", s, n_sat, sats, opts, first_sample, n_samples, pl)) return rc;
+    if (!path) return fail(ctx, BDS_ERR_ARG, "bds_synth_file: path is NULL");
+    if (piece_samples < 0) return fail(ctx, BDS_ERR_ARG, "bds_synth_file: piece_samples = %lld", (long long)piece_samples);
+    if (!ctx) return fail(ctx, BDS_ERR_ARG, "bds_synth_file: ctx is NULL");
+    int64_t piece = piece_of(pl.fmt, piece_samples);
+    if (pl.fmt == 3) piece += piece & 1;  // a byte holds two samples
+    piece = std::min(piece, std::max<int64_t>(n_samples, 2));
+    FILE *fo = fopen(path, "wb");
+    if (!fo) return fail(ctx, BDS_ERR_IO, "Unable to write file %s", path);
+    const int64_t n_pieces = (n_samples + piece - 1) / piece;
+    const size_t buf_bytes = (size_t)units_of(pl.fmt, piece) * kUnitBytes;
+    hipStream_t s_copy = (hipStream_t)ctx->stream, s_gen = (hipStream_t)ctx->stream2;
+    void *d_buf[2] = {nullptr, nullptr}, *h_buf[2] = {nullptr, nullptr};
+    hipEvent_t g0[3] = {}, g1[3] = {}, c0[2] = {}, c1[2] = {}, t0 = nullptr, t1 = nullptr;  // (g: per piece mod 3 -- piece k + 2 is launched before piece k's times are read)
+    double t_gen = 0, t_copy = 0;
+    float total = 0;
+    int rc = BDS_OK;
+    hipError_t e = hipSetDevice(ctx->device);
+    if (e == hipSuccess && n_pieces) {
+        rc = plan_upload(ctx, pl);
+        for (int i = 0; i < 2 && !rc && e == hipSuccess; ++i) {
+            e = hipMalloc(&d_buf[i], buf_bytes);
+            if (e == hipSuccess) e = hipHostMalloc(&h_buf[i], buf_bytes, hipHostMallocDefault);
+            for (hipEvent_t *v : {&c0[i], &c1[i]})
+                if (e == hipSuccess) e = hipEventCreate(v);
+        }
+        for (int i = 0; i < 3; ++i)
+            for (hipEvent_t *v : {&g0[i], &g1[i]})
+                if (e == hipSuccess) e = hipEventCreate(v);
+        if (e == hipSuccess) e = hipEventCreate(&t0);
+        if (e == hipSuccess) e = hipEventCreate(&t1);
+    }
+    auto span = [&](int64_t k) { return std::min(piece, n_samples - k * piece); };
+    // piece k is generated on the second stream into device buffer k & 1 (after the copy that last read it), copied out on the first
+    // stream into pinned buffer k & 1, and written by this thread while piece k + 1 is copied and piece k + 2 generated
+    auto generate = [&](int64_t k) {
+        const int b = (int)(k & 1);
+        if (k >= 2) e = hipStreamWaitEvent(s_gen, c1[b], 0);
+        if (e == hipSuccess) e = hipEventRecord(g0[k % 3], s_gen);
+        if (e == hipSuccess) rc = launch(ctx, pl, s_gen, first_sample + k * piece, span(k), d_buf[b]);
+        if (!rc && e == hipSuccess) e = hipEventRecord(g1[k % 3], s_gen);
+    };
+    auto finish = [&](int64_t k) {  // wait for the copy of piece k, write it
+        const int b = (int)(k & 1);
+        e = hipEventSynchronize(c1[b]);
+        float g = 0, c = 0;
+        if (e == hipSuccess) e = hipEventElapsedTime(&g, g0[k % 3], g1[k % 3]);
+        if (e == hipSuccess) e = hipEventElapsedTime(&c, c0[b], c1[b]);
+        t_gen += g, t_copy += c;
+        const size_t nb = bytes_of(pl.fmt, span(k));
+        if (e == hipSuccess && fwrite(h_buf[b], 1, nb, fo) != nb) rc = fail(ctx, BDS_ERR_IO, "short write on %s", path);
+    };
+    if (!rc && e == hipSuccess && n_pieces) {
+        e = hipEventRecord(t0, s_gen);
+        if (e == hipSuccess) generate(0);
+        for (int64_t k = 0; k < n_pieces && !rc && e == hipSuccess; ++k) {
+            const int b = (int)(k & 1);
+            if (k + 1 < n_pieces) generate(k + 1);
+            if (!rc && e == hipSuccess) e = hipStreamWaitEvent(s_copy, g1[k % 3], 0);
+            if (!rc && e == hipSuccess) e = hipEventRecord(c0[b], s_copy);
+            if (!rc && e == hipSuccess) e = hipMemcpyAsync(h_buf[b], d_buf[b], bytes_of(pl.fmt, span(k)), hipMemcpyDeviceToHost, s_copy);
+            if (!rc && e == hipSuccess) e = hipEventRecord(c1[b], s_copy);
+            if (!rc && e == hipSuccess && k >= 1) finish(k - 1);
+        }
+        if (!rc && e == hipSuccess) finish(n_pieces - 1);
+        if (!rc && e == hipSuccess) e = hipEventRecord(t1, s_copy);
+        if (!rc && e == hipSuccess) e = hipEventSynchronize(t1);
+        if (!rc && e == hipSuccess) e = hipEventElapsedTime(&total, t0, t1);
+    }
+    // nothing of this call may still run when its buffers go
+    (void)hipStreamSynchronize(s_gen);
+    (void)hipStreamSynchronize(s_copy);
+    for (int i = 0; i < 2; ++i) {
+        if (d_buf[i]) (void)hipFree(d_buf[i]);
+        if (h_buf[i]) (void)hipHostFree(h_buf[i]);
+        for (hipEvent_t v : {c0[i], c1[i]})
+            if (v) (void)hipEventDestroy(v);
+    }
+    for (int i = 0; i < 3; ++i)
+        for (hipEvent_t v : {g0[i], g1[i]})
+            if (v) (void)hipEventDestroy(v);
+    if (t0) (void)hipEventDestroy(t0);
+    if (t1) (void)hipEventDestroy(t1);
+    plan_free(pl);
+    if (fclose(fo) != 0 && !rc && e == hipSuccess) rc = fail(ctx, BDS_ERR_IO, "short write on %s", path);
+    if (rc) return rc;
+    if (e != hipSuccess) return fail(ctx, e == hipErrorOutOfMemory ? BDS_ERR_NOMEM : BDS_ERR_HIP, "bds_synth_file: %s", hipGetErrorString(e));
+    timing_of(ctx, total, t_gen, t_copy);
+    return BDS_OK;
+}
+
+extern "C" int bds_synth_noise(bds_ctx *ctx, uint64_t seed, int64_t first, int64_t n, double *g_i, double *g_q) {
+    if (first < 0 || n < 0 || first > (1LL << 53) - n) return fail(ctx, BDS_ERR_ARG, "bds_synth_noise: samples %lld .. +%lld outside 0 .. 2^53", (long long)first, (long long)n);
+    if (n > (1LL << 28)) return fail(ctx, BDS_ERR_ARG, "bds_synth_noise: n = %lld: at most 2^28 draws per call", (long long)n);
+    if (!ctx) return fail(ctx, BDS_ERR_ARG, "bds_synth_noise: ctx is NULL");
+    if (n == 0 || (!g_i && !g_q)) return BDS_OK;
+    BDS_HIP(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = (hipStream_t)ctx->stream;
+    double *d = nullptr;
+    hipError_t e = hipMalloc((void **)&d, (size_t)n * 2 * sizeof(double));
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(k_synth_noise, dim3((unsigned)std::min<int64_t>((n + 255) / 256, 2048)), dim3(256), 0, st, seed, first, n, d, d + n);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess && g_i) e = hipMemcpyAsync(g_i, d, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess && g_q) e = hipMemcpyAsync(g_q, d + n, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (d) (void)hipFree(d);
+    if (e != hipSuccess) return fail(ctx, BDS_ERR_HIP, "bds_synth_noise: %s", hipGetErrorString(e));
+    return BDS_OK;
+}

@@ -81,6 +81,20 @@ class AcqJob(C.Structure):
                 ("peakMetric", _DP), ("detected", _IP)]
 
 
+class SynthSat(C.Structure):
+    _fields_ = [("prn", C.c_int32), ("reserved0", C.c_int32), ("doppler", C.c_double), ("delay", C.c_double),
+                ("phase", C.c_double), ("cn0_dbhz", C.c_double)]
+
+
+class SynthOpts(C.Structure):
+    _fields_ = [("size", C.c_int32), ("format", C.c_int32), ("iq_sign", C.c_int32), ("code_doppler", C.c_int32),
+                ("pilot61_secondary", C.c_int32), ("reserved0", C.c_int32), ("seed", C.c_uint64), ("sigma", C.c_double),
+                ("threshold", C.c_double), ("symbols", C.POINTER(C.c_int8)), ("n_sym", C.c_int64)]
+
+
+SYNTH_FORMATS = {0: (np.float64, 1, 1), 1: (np.int8, 1, 1), 2: (np.int8, 2, 1), 3: (np.uint8, 1, 2)}  # dtype, elements per `den` samples
+
+
 EXPORTS = [
     "bds_create", "bds_destroy", "bds_reload_tuning", "bds_last_error", "bds_device_name", "bds_abi_check", "bds_build_flags", "bds_gen_code", "bds_acquire",
     "bds_acq_load", "bds_acq_prepare", "bds_acq_run", "bds_acq_set_pair_budget_gb", "bds_acq_set_b2a_npoint", "bds_resample_plan", "bds_fir1_bandpass", "bds_frame_sync", "bds_sync_pattern", "bds_unpack_cplx", "bds_unpack_cplx_file", "bds_acq_grid", "bds_acq_peaks", "bds_acq_candidates", "bds_acq_coherent_sums", "bds_get_timing",
@@ -90,6 +104,7 @@ EXPORTS = [
     "bds_calc_weighing_factor", "bds_pre_run", "bds_pre_run_device", "bds_acquire_track",
     "bds_multi_create", "bds_multi_destroy", "bds_multi_last_error", "bds_multi_size", "bds_multi_ctx",
     "bds_multi_rccl_ranks", "bds_acquire_multi", "bds_shard_jobs", "bds_acq_job_cost",
+    "bds_synth", "bds_synth_file", "bds_synth_noise",
 ]
 
 _lib = None
@@ -184,6 +199,11 @@ def lib():
     L.bds_pre_run_device.restype, L.bds_pre_run_device.argtypes = i32, [vp, SP, i32, _DP, _DP, _DP, C.POINTER(Channel)]
     L.bds_acquire_track.restype = i32
     L.bds_acquire_track.argtypes = [vp, SP, i8p, sz, i32, i32, _DP, _DP, _DP, _IP, C.c_char_p, C.POINTER(Channel), C.POINTER(TrackOut)]
+    if hasattr(L, "bds_synth"):  # (as above: a build of an older commit has no device generator)
+        YP, OP, i64 = C.POINTER(SynthSat), C.POINTER(SynthOpts), C.c_int64
+        L.bds_synth.restype, L.bds_synth.argtypes = i32, [vp, SP, i32, YP, OP, i64, i64, vp, sz]
+        L.bds_synth_file.restype, L.bds_synth_file.argtypes = i32, [vp, SP, i32, YP, OP, i64, i64, C.c_char_p, i64]
+        L.bds_synth_noise.restype, L.bds_synth_noise.argtypes = i32, [vp, C.c_uint64, i64, i64, _DP, _DP]
     L.bds_abi_check.restype, L.bds_abi_check.argtypes = i32, [i32, i32, i32, i32]
     if L.bds_abi_check(C.sizeof(Settings), C.sizeof(Channel), C.sizeof(TrackOut), C.sizeof(Timing)) != 0:
         raise ImportError("ctypes struct layout does not match libbds_mi355x.so (include/bds_mi355x.h changed?)")
@@ -305,6 +325,37 @@ def check_feed_bytes(sess, data) -> np.ndarray:
     if sess["fileType"] == 2 and a.size % 2:
         raise ValueError(f"an I/Q record is fed in whole int8 pairs: {a.size} bytes is an odd count")
     return a
+
+
+def pack_synth(sats, fmt, seed=3550, sigma=20.0, iq_sign=0, threshold=None, code_doppler=True, pilot61_secondary=False,
+               symbols=None):
+    """(bds_synth_sat array, bds_synth_opts, what must stay alive) of one bds_synth / bds_synth_file call.  sats: objects with prn,
+    doppler, delay, phase, cn0_dbhz (synth.Sat); symbols: None or int8-valued [n_sat, 2, n_sym] of +-1."""
+    arr = (SynthSat * max(len(sats), 1))()
+    for i, t in enumerate(sats):
+        arr[i].prn, arr[i].doppler, arr[i].delay = int(t.prn), float(t.doppler), float(t.delay)
+        arr[i].phase, arr[i].cn0_dbhz = float(t.phase), float(t.cn0_dbhz)
+    o = SynthOpts()
+    o.size, o.format, o.iq_sign = C.sizeof(SynthOpts), int(fmt), int(iq_sign)
+    o.code_doppler, o.pilot61_secondary = int(bool(code_doppler)), int(bool(pilot61_secondary))
+    o.seed, o.sigma, o.threshold = int(seed) & (2 ** 64 - 1), float(sigma), 0.0 if threshold is None else float(threshold)
+    sym = None
+    if symbols is not None:
+        sym = np.ascontiguousarray(symbols, dtype=np.int8)
+        if sym.ndim != 3 or sym.shape[:2] != (len(sats), 2) or sym.shape[2] < 1:
+            raise ValueError(f"symbols must have shape [n_sat = {len(sats)}, 2, n_sym >= 1], not {sym.shape}")
+        o.symbols, o.n_sym = sym.ctypes.data_as(C.POINTER(C.c_int8)), sym.shape[2]
+    return arr, o, sym
+
+
+def synth_out(fmt, n_samples) -> np.ndarray:
+    """The array n_samples samples of a format take (0: float64, 1: int8, 2: int8 pairs, 3: packed uint8, two samples a byte)."""
+    if fmt not in SYNTH_FORMATS:
+        raise ValueError(f"format must be 0 (float64 clean sum), 1 (int8), 2 (I/Q int8 pairs) or 3 (packed 2+2-bit I/Q), not {fmt!r}")
+    dtype, num, den = SYNTH_FORMATS[fmt]
+    if int(n_samples) < 0 or int(n_samples) % den:
+        raise ValueError(f"n_samples = {n_samples}: a packed record holds two samples per byte" if den > 1 else f"n_samples = {n_samples}")
+    return np.empty(int(n_samples) * num // den, dtype=dtype)
 
 
 def gen_code(signal: str, kind: str, prn: int) -> np.ndarray:
@@ -499,6 +550,31 @@ class Context:
                                           carr.ctypes.data_as(_DP), cph.ctypes.data_as(_DP),
                                           pm.ctypes.data_as(_DP), det.ctypes.data_as(_IP)))
         return carr, cph, pm, det
+
+    # -- synthetic IF records (bds_synth*) -----------------------------------------------
+    def synth(self, settings, sats, first_sample, n_samples, fmt, **opts):
+        """bds_synth: samples first_sample .. + n_samples of the record as float64 (fmt 0), int8 (1), int8 I/Q pairs (2) or packed
+        uint8 (3); opts as pack_synth."""
+        cs = pack_settings(settings)
+        arr, o, keep = pack_synth(sats, fmt, **opts)
+        out = synth_out(fmt, n_samples)
+        self._check(self._lib.bds_synth(self._h, C.byref(cs), len(sats), arr, C.byref(o), int(first_sample), int(n_samples),
+                                        out.ctypes.data_as(C.c_void_p), out.nbytes))
+        return out
+
+    def synth_file(self, settings, sats, first_sample, n_samples, fmt, path, piece_samples=0, **opts):
+        """bds_synth_file: the same record written to `path`, piece by piece."""
+        cs = pack_settings(settings)
+        arr, o, keep = pack_synth(sats, fmt, **opts)
+        self._check(self._lib.bds_synth_file(self._h, C.byref(cs), len(sats), arr, C.byref(o), int(first_sample), int(n_samples),
+                                             os.fsencode(path), int(piece_samples)))
+
+    def synth_noise(self, seed, first, n):
+        """bds_synth_noise (test aid): the N(0, 1) pairs (g_I, g_Q) of samples first .. first + n - 1."""
+        gi, gq = np.empty(int(n)), np.empty(int(n))
+        self._check(self._lib.bds_synth_noise(self._h, int(seed) & (2 ** 64 - 1), int(first), int(n), gi.ctypes.data_as(_DP),
+                                              gq.ctypes.data_as(_DP)))
+        return gi, gq
 
     def frame_sync(self, signal, prns, prompt, cap=64):
         """bds_frame_sync: prompt [n_ch, n] -> (xcorr int32 [n_ch, M], [1-based index arrays])."""

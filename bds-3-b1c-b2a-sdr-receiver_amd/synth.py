@@ -118,3 +118,46 @@ def make_if(settings, sats, n_samples, seed=3550, sigma=20.0, codegen=None, chun
         else:
             out[a:b] = np.clip(np.rint(acc), -127, 127).astype(np.int8)
     return out
+
+
+def _device_format(iq_sign, clean, packed):
+    if clean:
+        if iq_sign or packed:
+            raise ValueError("clean=True is the real float64 sum: neither iq_sign nor packed goes with it")
+        return 0
+    if packed:
+        if not iq_sign:
+            raise ValueError("a packed record is an I/Q record: give iq_sign = +1 or -1")
+        return 3
+    return 2 if iq_sign else 1
+
+
+def make_if_device(settings, sats, n_samples, seed=3550, sigma=20.0, first_sample=0, iq_sign=0, clean=False, packed=False,
+                   threshold=None, code_doppler=True, pilot61_secondary=False, symbols=None, device=0):
+    """make_if's signal generated on the device (bds_synth): samples first_sample .. first_sample + n_samples of the record, as
+    int8[n_samples] (real), int8[2 n_samples] (iq_sign = +1 / -1, as in make_if), float64[n_samples] (clean=True: no noise, not
+    quantised) or uint8[n_samples / 2] (packed=True with an iq_sign: the 2+2-bit bytes of fileType 3 -- magnitude 3 where the
+    int8 value exceeds `threshold`, default sigma).  Every sample is make_if's, in the same float64 operation order; the random
+    stream is not: noise and symbols are counter-based (Philox4x32-10 keyed by `seed`, include/bds_mi355x.h), so sample n does not
+    depend on where a call starts -- a record made in pieces equals the record made at once -- and a seed gives another record
+    than make_if's.  symbols: int8 [n_sat, 2, n_sym] of +-1 (data, secondary per satellite entry; code period p reads index
+    (p + 1) mod n_sym) instead of the generated ones.  There is no CPU fallback."""
+    from .acquisition import get_context
+
+    fmt = _device_format(iq_sign, clean, packed)
+    return get_context(device).synth(settings, list(sats), first_sample, n_samples, fmt, seed=seed, sigma=sigma, iq_sign=iq_sign,
+                                     threshold=threshold, code_doppler=code_doppler, pilot61_secondary=pilot61_secondary,
+                                     symbols=symbols)
+
+
+def write_if(path, settings, sats, n_samples, seed=3550, sigma=20.0, first_sample=0, iq_sign=0, clean=False, packed=False,
+             threshold=None, code_doppler=True, pilot61_secondary=False, symbols=None, device=0, piece_samples=0):
+    """The bytes of make_if_device(...) written to `path` (bds_synth_file): the record is generated piece by piece, the next
+    piece on a second stream while the last one is copied out and written, so its length is bounded by the disk alone.  The file
+    is byte-identical whatever piece_samples is (0: 64 MiB per piece)."""
+    from .acquisition import get_context
+
+    fmt = _device_format(iq_sign, clean, packed)
+    get_context(device).synth_file(settings, list(sats), first_sample, n_samples, fmt, path, piece_samples=piece_samples, seed=seed,
+                                   sigma=sigma, iq_sign=iq_sign, threshold=threshold, code_doppler=code_doppler,
+                                   pilot61_secondary=pilot61_secondary, symbols=symbols)

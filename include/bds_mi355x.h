@@ -493,6 +493,60 @@ BDS_API int bds_unpack_cplx_file(bds_ctx *ctx, const char *path_in, const char *
 BDS_API int bds_resample_plan(const bds_settings *s, double *new_fs, double *new_if, double *wp);
 BDS_API int bds_fir1_bandpass(int n_taps, double wp1, double wp2, double *b);
 
+/* ---- synthetic IF records, generated on the device ------------------------------------------------------
+ * The reference ships no recording; bds_amd/synth.py:make_if (a NumPy loop) is the model the tests' inputs come from.  bds_synth
+ * makes the same signal on the device, per sample and satellite in make_if's own float64 operation order (synth.py:87-119):
+ *   chips = (n - delay) (fcode / fs), fcode = codeFreqBasis (1 + doppler / carrFreqBasis) (code_doppler 0: codeFreqBasis)
+ *   period = floor(chips / codeLength), cph = chips - period codeLength, chip = min((int)cph, codeLength - 1)
+ *   th = (2 pi) fmod(((IF + doppler) n) / fs, 1) + phase
+ *   B1C: s_I = 1/2 D c_d boc11 - sqrt(1/11) c_p boc61 [S], s_Q = sqrt(29/44) c_p boc11 S;  B2a: s_I = S c_p, s_Q = -D c_d
+ *   z = amp (s_I + j s_Q) e^{j th}, amp = sigma sqrt(4 10^(cn0 / 10) / fs), summed over the satellites in list order
+ * n is the GLOBAL sample index of the record (first_sample + the index in `out`): a record made in pieces, in any order, is the
+ * same bytes as the record made in one call.  What differs from make_if is the random stream, which is counter-based
+ * (csrc/bds_synth_math.h: Philox4x32-10 keyed by the seed) instead of sequential:
+ *   noise of sample n   counter (n low, n high, 0, 0) -> words w0..w3; u1 = (((w0 2^32 + w1) >> 12) + 0.5) 2^-52,
+ *                       u2 = ((w2 2^32 + w3) >> 11) 2^-53; r = sqrt(-2 log u1), g_I = r cos(2 pi u2), g_Q = r sin(2 pi u2);
+ *                       a real record adds sigma g_I, an I/Q record sigma (g_I + j g_Q)
+ *   symbols             D (component 0) and S (component 1) of code period p of satellite prn: counter (p + 1 as int64: low, high;
+ *                       1; 2 prn + component), +1 when bit 0 of w0 is set, else -1 -- or, when opts.symbols is given
+ *                       (int8[n_sat][2][n_sym], +-1, [satellite][D, S][index]), element (p + 1) mod n_sym (non-negative)
+ * Formats (opts.format), and what `out` holds for n_samples samples:
+ *   0  double[n_samples]      the clean real sum: no noise, not quantised (make_if(clean=True))
+ *   1  int8[n_samples]        real record (fileType 1): rint(sum + sigma g_I), clipped to +-127
+ *   2  int8[2 n_samples]      interleaved I/Q (fileType 2): the analytic signal (iq_sign >= 0; make_if's iq_sign +1) or its conjugate (< 0)
+ *   3  uint8[n_samples / 2]   packed 2+2-bit I/Q (fileType 3, the nibble layout above): of each int8 value of format 2 the sign (0 is
+ *                             positive) and magnitude 3 where |value| > threshold, else 1; first_sample and n_samples must be even
+ * Up to 63 satellites; n_sat = 0 is noise alone.  A PRN may repeat (multipath: the entries share code and symbols; with
+ * opts.symbols every entry has its own rows).  opts.threshold <= 0 means sigma.  opts.size must be sizeof(bds_synth_opts).
+ * All argument errors (BDS_ERR_ARG, message in bds_last_error -- of ctx, or of NULL when ctx is NULL) are raised before any
+ * device call. */
+typedef struct bds_synth_sat {
+    int32_t prn, reserved0;
+    double doppler;   /* [Hz] */
+    double delay;     /* [samples] 0-based sample at which a primary-code period starts */
+    double phase;     /* [rad] */
+    double cn0_dbhz;
+} bds_synth_sat;
+typedef struct bds_synth_opts {
+    int32_t size;     /* sizeof(bds_synth_opts), else BDS_ERR_ARG */
+    int32_t format, iq_sign, code_doppler, pilot61_secondary, reserved0;
+    uint64_t seed;
+    double sigma, threshold;
+    const int8_t *symbols; /* NULL: symbols from the counter-based stream */
+    int64_t n_sym;
+} bds_synth_opts;
+BDS_API int bds_synth(bds_ctx *ctx, const bds_settings *s, int n_sat, const bds_synth_sat *sats, const bds_synth_opts *opts,
+                      int64_t first_sample, int64_t n_samples, void *out, size_t out_bytes);
+/* The same record written to `path` in pieces of piece_samples samples (0: 64 MiB of the record per piece, 32 MiB of a packed one):
+ * piece k + 1 is generated on the context's second stream while piece k is copied out and written (two device buffers, two pinned
+ * host buffers).  The file is byte-identical to the one-call result whatever piece_samples is (format 3: an odd piece_samples is
+ * rounded up to even).  After either call bds_get_timing reports total_ms (stream time of the call), forward_ms (the generation
+ * kernels, summed over the pieces) and search_ms (the pieces' device-to-host copies); every other field is 0. */
+BDS_API int bds_synth_file(bds_ctx *ctx, const bds_settings *s, int n_sat, const bds_synth_sat *sats, const bds_synth_opts *opts,
+                           int64_t first_sample, int64_t n_samples, const char *path, int64_t piece_samples);
+/* Test aid: the raw N(0, 1) stream of samples first .. first + n - 1 as the device forms it (either pointer may be NULL). */
+BDS_API int bds_synth_noise(bds_ctx *ctx, uint64_t seed, int64_t first, int64_t n, double *g_i, double *g_q);
+
 #ifdef __cplusplus
 }
 #endif
