@@ -1052,6 +1052,10 @@ __device__ __forceinline__ void apply_update(const TrkParams &p, ChanState &s, c
     s.remCarrPhase = carr_next;
     s.pos += g.blk;
     s.completed = epoch + 1;
+    // A code NCO that is not a positive finite number (an epoch of all-zero samples: atan(0/0), 0/0 in the DLL) has no next
+    // block: MATLAB stops in fread.  The epoch's results stand as computed (NaN discriminators); the channel stops as at
+    // a short read, so no later launch or host plan derives a block length from this state.
+    if (!(isfinite(s.codeFreq) && isfinite(s.remCodePhase) && s.codeFreq > 0)) s.active = 0;
         }();
         s_next = s;
     }
@@ -1223,9 +1227,18 @@ __device__ static void cno_pld_one(const double *I, const double *Q, int M, doub
         zv += (z - zm) * (z - zm);
     }
     zv /= (M - 1);  // var(): N-1
-    const double pav = sqrt(zm * zm - zv);
-    const double nv = 0.5 * (zm - pav);
-    *lin = fabs((1 / T) * pav / (2 * nv));
+    const double d = zm * zm - zv;
+    if (d < 0) {
+        // MATLAB's sqrt of a negative number is complex: Pav = j s, Nv = 0.5 (Zm - j s), and the abs() of B2a :58 / B1C :65 is
+        // there for this case: |(1/T) j s / (Zm - j s)| = ((1/T) s) / |Zm - j s| -- finite, where a real sqrt gives NaN.
+        // (Noise-only prompts take this branch in 37-47 % of their intervals.)
+        const double s = sqrt(-d);
+        *lin = ((1 / T) * s) / hypot(zm, s);
+    } else {  // (a NaN d comes here and stays NaN)
+        const double pav = sqrt(d);
+        const double nv = 0.5 * (zm - pav);
+        *lin = fabs((1 / T) * pav / (2 * nv));
+    }
     *cno = 10 * log10(*lin);
     double sp = 0, sn = 0, sq = 0;
     for (int i = 0; i < M; ++i) {
@@ -2506,6 +2519,176 @@ extern "C" int bds_track_colon(bds_ctx *ctx, int n, const double *a, const doubl
     BDS_HIP(ctx, hipMemcpyAsync(c_end, d_out + n, nd, hipMemcpyDeviceToHost, st(ctx)));
     BDS_HIP(ctx, hipMemcpyAsync(n_intervals, d_n, ni, hipMemcpyDeviceToHost, st(ctx)));
     BDS_HIP(ctx, hipStreamSynchronize(st(ctx)));
+    return BDS_OK;
+}
+
+// device memory of a test aid, released on every exit path
+struct AidScope {
+    std::vector<void *> v;
+    template <class T>
+    hipError_t alloc(T **q, size_t bytes) {
+        const hipError_t e = hipMalloc((void **)q, std::max<size_t>(bytes, 8));
+        if (e == hipSuccess) v.push_back(*q);
+        return e;
+    }
+    ~AidScope() {
+        for (void *q : v) (void)hipFree(q);
+    }
+};
+
+// Test aid (bds_track_cno): k_trk_cno, or k_trk_cno_seg once per piece, on prompt arrays of the caller.  The host side only
+// places the arrays and gathers the intervals of each piece, as do_track / bds_track_advance do.
+extern "C" int bds_track_cno(bds_ctx *ctx, const bds_settings *s, int n_ch, int n_epochs, const double *prompts,
+                             const int32_t *done, int n_pieces, const int32_t *pieces, int n_cno, double *cno5) {
+    if (!ctx) return BDS_ERR_ARG;
+    if (!s || !prompts || !done || !cno5 || n_ch < 1 || n_epochs < 1 || n_cno < 1 || n_pieces < 0 || (n_pieces > 0 && !pieces))
+        return fail(ctx, BDS_ERR_ARG, "bds_track_cno: missing argument or empty shape");
+    const int M = s->CNoInterval;
+    if (M < 2 || !(s->intTime > 0)) return fail(ctx, BDS_ERR_ARG, "bds_track_cno: CNoInterval must be >= 2 and intTime > 0");
+    if (s->signal != BDS_SIGNAL_B1C && s->signal != BDS_SIGNAL_B2A) return fail(ctx, BDS_ERR_ARG, "settings.signal invalid");
+    for (int c = 0; c < n_ch; ++c)
+        if (done[c] < 0 || done[c] > n_epochs) return fail(ctx, BDS_ERR_ARG, "bds_track_cno: done[%d] outside 0 .. n_epochs", c);
+    long long total = 0;
+    for (int i = 0; i < n_pieces; ++i) {
+        if (pieces[i] < 1) return fail(ctx, BDS_ERR_ARG, "bds_track_cno: pieces[%d] must be >= 1", i);
+        total += pieces[i];
+    }
+    if (n_pieces > 0 && total != n_epochs) return fail(ctx, BDS_ERR_ARG, "bds_track_cno: the pieces must add up to n_epochs");
+    BDS_HIP(ctx, hipSetDevice(ctx->device));
+    const int mode = track_mode(*s);
+    const int pm = pilot_on(*s, mode) ? (mode == BDS_TRACK_WB ? 2 : 1) : 0;
+    const size_t ne = (size_t)n_ch * n_epochs;
+    const int nq_max = std::max(n_cno, n_epochs / M + 2);  // intervals one launch can report
+    AidScope scope;
+    double *d_p = nullptr, *d_raw = nullptr, *d_cno = nullptr, *d_carry = nullptr, *d_prev3 = nullptr;
+    int *d_ncarry = nullptr;
+    ChanState *d_st = nullptr;
+    BDS_HIP(ctx, scope.alloc(&d_p, sizeof(double) * 4 * ne));
+    BDS_HIP(ctx, scope.alloc(&d_raw, sizeof(double) * (size_t)n_ch * nq_max * 3));
+    BDS_HIP(ctx, scope.alloc(&d_cno, sizeof(double) * (size_t)n_ch * nq_max * 5));
+    BDS_HIP(ctx, scope.alloc(&d_st, sizeof(ChanState) * n_ch));
+    BDS_HIP(ctx, hipMemcpyAsync(d_p, prompts, sizeof(double) * 4 * ne, hipMemcpyHostToDevice, st(ctx)));
+    std::vector<ChanState> hs(n_ch);
+    for (int c = 0; c < n_ch; ++c) {
+        hs[c] = ChanState{};
+        hs[c].prn = 1;
+    }
+    const size_t out_plane = (size_t)n_ch * n_cno;
+    if (n_pieces == 0) {  // the post-pass of bds_track
+        for (int c = 0; c < n_ch; ++c) hs[c].completed = done[c];
+        TrkOut d{};
+        d.I_P = d_p, d.Q_P = d_p + ne, d.Pilot_I_P = d_p + 2 * ne, d.Pilot_Q_P = d_p + 3 * ne;
+        BDS_HIP(ctx, hipMemcpyAsync(d_st, hs.data(), sizeof(ChanState) * n_ch, hipMemcpyHostToDevice, st(ctx)));
+        hipLaunchKernelGGL(k_trk_cno, dim3(n_ch), dim3(256), 0, st(ctx), d, (const ChanState *)d_st, n_epochs, M, n_cno, pm, s->intTime,
+                           d_raw, d_cno);
+        BDS_HIP(ctx, hipGetLastError());
+        BDS_HIP(ctx, hipMemcpyAsync(cno5, d_cno, sizeof(double) * 5 * out_plane, hipMemcpyDeviceToHost, st(ctx)));
+        BDS_HIP(ctx, hipStreamSynchronize(st(ctx)));
+        return BDS_OK;
+    }
+    // the post-pass of a session: one k_trk_cno_seg per piece, the carry buffers as bds_track_open* makes them
+    BDS_HIP(ctx, scope.alloc(&d_carry, sizeof(double) * (size_t)n_ch * 4 * M));
+    BDS_HIP(ctx, scope.alloc(&d_prev3, sizeof(double) * (size_t)n_ch * 3));
+    BDS_HIP(ctx, scope.alloc(&d_ncarry, sizeof(int) * (size_t)n_ch));
+    BDS_HIP(ctx, hipMemsetAsync(d_carry, 0, sizeof(double) * (size_t)n_ch * 4 * M, st(ctx)));
+    BDS_HIP(ctx, hipMemsetAsync(d_prev3, 0, sizeof(double) * (size_t)n_ch * 3, st(ctx)));
+    BDS_HIP(ctx, hipMemsetAsync(d_ncarry, 0, sizeof(int) * (size_t)n_ch, st(ctx)));
+    std::fill(cno5, cno5 + 5 * out_plane, 0.0);
+    std::vector<int> q_done(n_ch, 0);
+    std::vector<double> h;
+    int e0 = 0;
+    for (int i = 0; i < n_pieces; ++i) {
+        const int len = pieces[i];
+        int nq = 1;  // (bds_track_advance: the most intervals a channel can complete in the call, at least one slot)
+        for (int c = 0; c < n_ch; ++c) {
+            const int before = std::min(done[c], e0);
+            hs[c].completed = std::max(0, std::min(done[c] - e0, len));  // epochs the channel ran in this piece
+            nq = std::max(nq, (before + len) / M - before / M);
+        }
+        // the piece's arrays are epochs [e0, e0 + len) of the caller's rows (row length n_epochs)
+        TrkOut d{};
+        d.I_P = d_p + e0, d.Q_P = d_p + ne + e0, d.Pilot_I_P = d_p + 2 * ne + e0, d.Pilot_Q_P = d_p + 3 * ne + e0;
+        BDS_HIP(ctx, hipMemcpyAsync(d_st, hs.data(), sizeof(ChanState) * n_ch, hipMemcpyHostToDevice, st(ctx)));
+        hipLaunchKernelGGL(k_trk_cno_seg, dim3(n_ch), dim3(256), 0, st(ctx), d, (const ChanState *)d_st, n_epochs, M, nq, pm, s->intTime,
+                           d_carry, d_ncarry, d_prev3, d_raw, d_cno);
+        BDS_HIP(ctx, hipGetLastError());
+        h.resize((size_t)n_ch * nq * 5);
+        BDS_HIP(ctx, hipMemcpyAsync(h.data(), d_cno, sizeof(double) * h.size(), hipMemcpyDeviceToHost, st(ctx)));
+        BDS_HIP(ctx, hipStreamSynchronize(st(ctx)));  // (hs and h are reused by the next piece)
+        for (int c = 0; c < n_ch; ++c) {
+            const int before = std::min(done[c], e0);
+            const int nd = (before + hs[c].completed) / M - before / M;
+            for (int q = 0; q < nd && q_done[c] + q < n_cno; ++q)
+                for (int f = 0; f < 5; ++f)
+                    cno5[f * out_plane + (size_t)c * n_cno + q_done[c] + q] = h[(size_t)f * n_ch * nq + (size_t)c * nq + q];
+            q_done[c] += nd;
+        }
+        e0 += len;
+    }
+    return BDS_OK;
+}
+
+// Test aid (bds_track_update): k_trk_update for ONE epoch on the caller's channel states and correlator sums (nblocks = 1: the
+// fixed-order sum of the partial sums returns the 18 values given), the record bounds set so the epoch lies inside the window.
+extern "C" int bds_track_update(bds_ctx *ctx, const bds_settings *s, int n_ch, const double *state10, const double *sums18,
+                                double *state10_out, int32_t *active, int32_t *completed, double *out21) {
+    if (!ctx) return BDS_ERR_ARG;
+    if (!s || !state10 || !sums18 || !state10_out || !active || !completed || !out21 || n_ch < 1)
+        return fail(ctx, BDS_ERR_ARG, "bds_track_update: missing argument");
+    TrkParams p{};
+    int rc = fill_params(ctx, *s, p, 1, 0);
+    if (rc) return rc;
+    p.n_bytes = 1LL << 60, p.base = 0, p.win_end = p.n_bytes;  // no end of file, everything resident
+    static_assert(offsetof(ChanState, pos) == 10 * sizeof(double), "the ten doubles of ChanState come first");
+    std::vector<ChanState> hs(n_ch);
+    for (int c = 0; c < n_ch; ++c) {
+        hs[c] = ChanState{};
+        memcpy(&hs[c], state10 + (size_t)c * 10, sizeof(double) * 10);
+        // the state an epoch starts in gives a block length (epoch_geom); one that cannot was stopped by the update before it
+        if (!(std::isfinite(hs[c].codeFreq) && hs[c].codeFreq > 0 && std::isfinite(hs[c].remCodePhase) && hs[c].remCodePhase < p.code_len))
+            return fail(ctx, BDS_ERR_ARG, "bds_track_update: state of channel %d has no block length (codeFreq, remCodePhase)", c);
+        hs[c].prn = 1, hs[c].active = 1;
+    }
+    BDS_HIP(ctx, hipSetDevice(ctx->device));
+    constexpr int kFields = sizeof(TrkOut) / sizeof(double *);
+    AidScope scope;
+    ChanState *d_st = nullptr;
+    double *d_part = nullptr, *d_fields = nullptr;
+    BDS_HIP(ctx, scope.alloc(&d_st, sizeof(ChanState) * n_ch));
+    BDS_HIP(ctx, scope.alloc(&d_part, sizeof(double) * (size_t)n_ch * kNSums));
+    BDS_HIP(ctx, scope.alloc(&d_fields, sizeof(double) * (size_t)n_ch * kFields));
+    TrkOut d{};
+    bds_track_out unused{};
+    uint32_t inf_mask = 0;
+    int f = 0;
+    for_each_field(&unused, &d, [&](double *, double *&dev, double v0) {  // [21][n_ch], at the reference's template values
+        dev = d_fields + (size_t)f * n_ch;
+        if (v0 != 0.0) inf_mask |= 1u << f;
+        ++f;
+    });
+    BDS_HIP(ctx, hipMemcpyAsync(d_st, hs.data(), sizeof(ChanState) * n_ch, hipMemcpyHostToDevice, st(ctx)));
+    BDS_HIP(ctx, hipMemcpyAsync(d_part, sums18, sizeof(double) * (size_t)n_ch * kNSums, hipMemcpyHostToDevice, st(ctx)));
+    hipLaunchKernelGGL(k_trk_fill_out, dim3((unsigned)(((size_t)n_ch * kFields + 255) / 256)), dim3(256), 0, st(ctx), d_fields, (size_t)n_ch, kFields, inf_mask);
+    switch (p.mode) {
+        case BDS_TRACK_B2A:
+            hipLaunchKernelGGL(k_trk_update<BDS_TRACK_B2A>, dim3(n_ch), dim3(kUpdThreads), 0, st(ctx), p, d_st, (const double *)d_part, 1, 0, d);
+            break;
+        case BDS_TRACK_NB:
+            hipLaunchKernelGGL(k_trk_update<BDS_TRACK_NB>, dim3(n_ch), dim3(kUpdThreads), 0, st(ctx), p, d_st, (const double *)d_part, 1, 0, d);
+            break;
+        default:
+            hipLaunchKernelGGL(k_trk_update<BDS_TRACK_WB>, dim3(n_ch), dim3(kUpdThreads), 0, st(ctx), p, d_st, (const double *)d_part, 1, 0, d);
+            break;
+    }
+    BDS_HIP(ctx, hipGetLastError());
+    BDS_HIP(ctx, hipMemcpyAsync(hs.data(), d_st, sizeof(ChanState) * n_ch, hipMemcpyDeviceToHost, st(ctx)));
+    BDS_HIP(ctx, hipMemcpyAsync(out21, d_fields, sizeof(double) * (size_t)n_ch * kFields, hipMemcpyDeviceToHost, st(ctx)));
+    BDS_HIP(ctx, hipStreamSynchronize(st(ctx)));
+    for (int c = 0; c < n_ch; ++c) {
+        memcpy(state10_out + (size_t)c * 10, &hs[c], sizeof(double) * 10);
+        active[c] = hs[c].active;
+        completed[c] = hs[c].completed;
+    }
     return BDS_OK;
 }
 

@@ -95,10 +95,14 @@ class SynthOpts(C.Structure):
 SYNTH_FORMATS = {0: (np.float64, 1, 1), 1: (np.int8, 1, 1), 2: (np.int8, 2, 1), 3: (np.uint8, 1, 2)}  # dtype, elements per `den` samples
 
 
+# per-channel state of the update test aid (bds_track_update), in the order of its state10 rows
+UPDATE_STATE = ["codeFreq", "remCodePhase", "carrFreq", "carrFreqBasis", "remCarrPhase", "oldCodeNco", "oldCodeError", "d2CarrError",
+                "dCarrError", "codeFreqBasis"]
+
 EXPORTS = [
     "bds_create", "bds_destroy", "bds_reload_tuning", "bds_last_error", "bds_device_name", "bds_abi_check", "bds_build_flags", "bds_gen_code", "bds_acquire",
     "bds_acq_load", "bds_acq_prepare", "bds_acq_run", "bds_acq_set_pair_budget_gb", "bds_acq_set_b2a_npoint", "bds_resample_plan", "bds_fir1_bandpass", "bds_frame_sync", "bds_sync_pattern", "bds_unpack_cplx", "bds_unpack_cplx_file", "bds_acq_grid", "bds_acq_peaks", "bds_acq_candidates", "bds_acq_coherent_sums", "bds_get_timing",
-    "bds_track", "bds_track_mem", "bds_track_loaded_bytes", "bds_track_set_resident_limit", "bds_track_stream_info", "bds_track_correlate", "bds_track_colon",
+    "bds_track", "bds_track_mem", "bds_track_loaded_bytes", "bds_track_set_resident_limit", "bds_track_stream_info", "bds_track_correlate", "bds_track_colon", "bds_track_cno", "bds_track_update",
     "bds_track_open", "bds_track_open_mem", "bds_track_open_feed", "bds_track_feed", "bds_track_advance", "bds_track_session_info", "bds_track_close",
     "bds_calc_loop_coef", "bds_calc_loop_coef_carr",
     "bds_calc_weighing_factor", "bds_pre_run", "bds_pre_run_device", "bds_acquire_track",
@@ -183,6 +187,9 @@ def lib():
     L.bds_track_correlate.restype = i32
     L.bds_track_correlate.argtypes = [vp, SP, i8p, sz, i32, _IP, _DP, _DP]
     L.bds_track_colon.restype, L.bds_track_colon.argtypes = i32, [vp, i32, _DP, _DP, _DP, _IP, _DP, _DP, _IP]
+    if hasattr(L, "bds_track_cno"):  # (as above: a build of an older commit has no scalar-stage test aids)
+        L.bds_track_cno.restype, L.bds_track_cno.argtypes = i32, [vp, SP, i32, i32, _DP, _IP, i32, _IP, i32, _DP]
+        L.bds_track_update.restype, L.bds_track_update.argtypes = i32, [vp, SP, i32, _DP, _DP, _DP, _IP, _IP, _DP]
     L.bds_calc_loop_coef.restype = None
     L.bds_calc_loop_coef.argtypes = [C.c_double, C.c_double, C.c_double, _DP, _DP]
     L.bds_calc_loop_coef_carr.restype, L.bds_calc_loop_coef_carr.argtypes = None, [SP, _DP, _DP, _DP]
@@ -831,6 +838,40 @@ class Context:
                                               k.ctypes.data_as(_IP), val.ctypes.data_as(_DP), c_end.ctypes.data_as(_DP),
                                               n_int.ctypes.data_as(_IP)))
         return val, c_end, n_int
+
+    def track_cno(self, settings, prompts, done, n_cno, pieces=None):
+        """Test aid: the C/N0 + lock-detector post-pass on the caller's prompts [4, n_ch, n_epochs] (I_P, Q_P, Pilot_I_P, Pilot_Q_P)
+        with done[ch] completed epochs; pieces=None: the kernel of bds_track, once; a list of piece lengths: the kernel of
+        bds_track_advance once per piece.  Returns cno5 [5, n_ch, n_cno] (DataCNo, DataPLD, PilotCNo, PilotPLD, SigCNo)."""
+        cs = pack_settings(settings)
+        pr = np.ascontiguousarray(prompts, dtype=np.float64)
+        if pr.ndim != 3 or pr.shape[0] != 4:
+            raise ValueError("prompts must be [4, n_ch, n_epochs]")
+        _, n_ch, n_epochs = pr.shape
+        dn = np.ascontiguousarray(done, dtype=np.int32)
+        if dn.shape != (n_ch,):
+            raise ValueError("done must be [n_ch]")
+        pc = np.ascontiguousarray(pieces if pieces is not None else [], dtype=np.int32)
+        out = np.zeros((5, n_ch, int(n_cno)))
+        self._check(self._lib.bds_track_cno(self._h, C.byref(cs), n_ch, n_epochs, pr.ctypes.data_as(_DP), dn.ctypes.data_as(_IP),
+                                            pc.size, pc.ctypes.data_as(_IP) if pc.size else None, int(n_cno), out.ctypes.data_as(_DP)))
+        return out
+
+    def track_update(self, settings, state10, sums18):
+        """Test aid: the loop update of one epoch by the update kernel.  state10 [n_ch, 10] (UPDATE_STATE order), sums18 [n_ch, 18].
+        Returns (next state [n_ch, 10], active [n_ch], completed [n_ch], dict per-epoch field -> [n_ch])."""
+        cs = pack_settings(settings)
+        st = np.ascontiguousarray(state10, dtype=np.float64)
+        sm = np.ascontiguousarray(sums18, dtype=np.float64)
+        if st.ndim != 2 or st.shape[1] != 10 or sm.shape != (st.shape[0], 18):
+            raise ValueError("state10 must be [n_ch, 10] and sums18 [n_ch, 18]")
+        n_ch = st.shape[0]
+        new = np.zeros((n_ch, 10))
+        active, completed = np.zeros(n_ch, dtype=np.int32), np.zeros(n_ch, dtype=np.int32)
+        out = np.zeros((21, n_ch))
+        self._check(self._lib.bds_track_update(self._h, C.byref(cs), n_ch, st.ctypes.data_as(_DP), sm.ctypes.data_as(_DP), new.ctypes.data_as(_DP),
+                                               active.ctypes.data_as(_IP), completed.ctypes.data_as(_IP), out.ctypes.data_as(_DP)))
+        return new, active, completed, {f: out[i] for i, f in enumerate(TRACK_FIELDS[:21])}
 
 
 def calc_loop_coef(lbw, zeta, k):

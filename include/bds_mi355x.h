@@ -438,6 +438,25 @@ BDS_API int bds_track_correlate(bds_ctx *ctx, const bds_settings *s, const int8_
  * oracle's restatement of MathWorks' colonop. */
 BDS_API int bds_track_colon(bds_ctx *ctx, int n, const double *a, const double *d, const double *b, const int32_t *k,
                             double *value, double *c_end, int32_t *n_intervals);
+/* Test aid, never needed by a host application: the C/N0 and lock-detector post-pass of tracking (include/Calc_CNo_PLD.m,
+ * tracking.m:411-434) on prompt values of the caller.  prompts: double[4][n_ch][n_epochs] = I_P, Q_P, Pilot_I_P, Pilot_Q_P;
+ * done[ch]: epochs the channel completed (0 .. n_epochs); settings give CNoInterval (>= 2), intTime and the pilot mode.
+ * cno5: double[5][n_ch][n_cno] = DataCNo, DataPLD, PilotCNo, PilotPLD, SigCNo of the intervals that completed, 0 elsewhere.
+ * n_pieces = 0 launches the kernel of bds_track once over the arrays; with a list of piece lengths (each >= 1, adding up to
+ * n_epochs) the kernel of bds_track_advance runs once per piece over that piece's epochs, with a session's carry buffers, and
+ * the intervals each piece completes are put end to end.  The aid does no arithmetic of its own. */
+BDS_API int bds_track_cno(bds_ctx *ctx, const bds_settings *s, int n_ch, int n_epochs, const double *prompts,
+                          const int32_t *done, int n_pieces, const int32_t *pieces, int n_cno, double *cno5);
+/* Test aid, never needed by a host application: the loop update of ONE epoch (discriminators, loop filters, next NCO state:
+ * tracking.m:295-389 and the B1C counterparts) by the tracking update kernel, on channel states and correlator sums of the
+ * caller.  state10: per channel {codeFreq, remCodePhase, carrFreq, carrFreqBasis, remCarrPhase, oldCodeNco, oldCodeError,
+ * d2CarrError, dCarrError, codeFreqBasis} (codeFreq > 0 and remCodePhase < codeLength, both finite: the state must give a
+ * block length); sums18: [n_ch][18] in the order of bds_track_correlate.  The record has no end and is resident, so the epoch
+ * is never a short read.  state10_out: the next state; active[ch]: 1, or 0 when the update stopped the channel; completed[ch];
+ * out21: double[21][n_ch], the epoch's entries of the per-epoch arrays in the order of bds_track_out (absoluteSample ..
+ * remCarrPhase), at the reference's template values where the tracker writes none. */
+BDS_API int bds_track_update(bds_ctx *ctx, const bds_settings *s, int n_ch, const double *state10, const double *sums18,
+                             double *state10_out, int32_t *active, int32_t *completed, double *out21);
 
 /* ---- helpers replacing small host functions on the path ------------------------ */
 /* Common/calcLoopCoef.m:41-45 */

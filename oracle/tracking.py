@@ -112,9 +112,16 @@ def calc_cno_pld(i_p, q_p, pil_i, pil_q, settings, pilot_mode):
             z = i ** 2 + q ** 2
             zm = np.mean(z)
             zv = m_var(z)
-            pav = np.sqrt(zm ** 2 - zv)
-            nv = 0.5 * (zm - pav)
-            lin = np.abs((1 / t) * pav / (2 * nv))
+            d = zm ** 2 - zv
+            if d < 0:
+                # MATLAB's sqrt goes complex: Pav = j sd, Nv = 0.5 (Zm - j sd); the abs() is there for this case and gives
+                # |(1/T) j sd / (Zm - j sd)| = ((1/T) sd) / |Zm - j sd|, a finite number (a real sqrt would give NaN)
+                sd = np.sqrt(-d)
+                lin = ((1 / t) * sd) / np.hypot(zm, sd)
+            else:  # (a NaN d comes here and stays NaN)
+                pav = np.sqrt(d)
+                nv = 0.5 * (zm - pav)
+                lin = np.abs((1 / t) * pav / (2 * nv))
             s = np.sum(i[i > 0]) - np.sum(i[i < 0])
             nbp = s ** 2 + np.sum(q) ** 2
             nbd = s ** 2 - np.sum(q) ** 2
@@ -129,6 +136,76 @@ def calc_cno_pld(i_p, q_p, pil_i, pil_q, settings, pilot_mode):
     with np.errstate(all="ignore"):
         cno[2] = 10 * np.log10(d_lin + p_lin)
     return cno, pld
+
+
+# --- loop update -----------------------------------------------------------------
+def qmboc_composite(p11, p61):
+    """WB_tracking.m:375-380: the QMBOC composite of the pilot BOC(1,1) sums p11 and BOC(6,1) sums p61, each
+    (I_E, Q_E, I_P, Q_P, I_L, Q_L)."""
+    s433, s2933 = np.sqrt(4 / 33), np.sqrt(29 / 33)
+    pI_E, pQ_E, pI_P, pQ_P, pI_L, pQ_L = p11
+    sI_E, sQ_E, sI_P, sQ_P, sI_L, sQ_L = p61
+    return (-s433 * sI_E + s2933 * pQ_E, -s433 * sQ_E - s2933 * pI_E,
+            -s433 * sI_P + s2933 * pQ_P, -s433 * sQ_P - s2933 * pI_P,
+            -s433 * sI_L + s2933 * pQ_L, -s433 * sQ_L - s2933 * pI_L)
+
+
+def loop_update(mode, pilot, data6, pil6, st, co):
+    """The discriminators and loop filters of one epoch (B2a/tracking.m:337-389, NB_tracking.m:345-395, WB_tracking.m:383-430).
+
+    data6 / pil6: (I_E, Q_E, I_P, Q_P, I_L, Q_L) of the data and the pilot correlators (WB: the QMBOC composite; None without pilot).
+    st: d2, d1 (carrier filter), old_nco, old_err (code filter), carr_basis, code_basis.
+    co: pf3, pf2, pf1, tau1, tau2, pdi, spc_el, factor (WB only).
+    Returns a namespace: carr_err, carr_nco, code_err, code_nco, the next carr_freq and code_freq, and the next d2, d1."""
+    b2a = mode == "B2A"
+    two_pi = 2.0 * np.pi
+    I_E, Q_E, I_P, Q_P, I_L, Q_L = data6
+    if pilot:
+        pI_E, pQ_E, pI_P, pQ_P, pI_L, pQ_L = pil6
+    with np.errstate(all="ignore"):
+        carr_err = np.arctan(np.float64(Q_P) / np.float64(I_P)) / two_pi  # :337
+        if pilot:
+            if b2a:
+                qi = (pI_P + 1j * pQ_P) * np.exp(-1j * np.pi / 2)  # :345
+                cq = np.arctan(np.float64(qi.imag) / np.float64(qi.real)) / two_pi  # :348
+                carr_err = (carr_err + cq) / 2  # :352
+            elif mode == "NB":
+                cq = np.arctan(np.float64(-pI_P) / np.float64(pQ_P)) / two_pi  # NB:357
+                carr_err = (carr_err * 11 + cq * 29) / 40  # NB:360
+            else:
+                cq = np.arctan(np.float64(pQ_P) / np.float64(pI_P)) / two_pi  # WB:392
+                carr_err = (carr_err * 1 + cq * 3) / 4  # WB:395
+        d2 = st.d2 + carr_err * co.pf3  # :356
+        d1 = d2 + carr_err * co.pf2 + st.d1  # :357
+        carr_nco = d1 + carr_err * co.pf1  # :358
+        carr_freq = st.carr_basis + carr_nco  # :363
+
+        def env(a, b):
+            return np.sqrt(a * a + b * b)
+
+        e_, l_ = env(I_E, Q_E), env(I_L, Q_L)
+        code_err = (e_ - l_) / (e_ + l_)  # :366
+        if not b2a:
+            code_err = code_err * (1 - co.spc_el)  # WB:409-410
+        if pilot:
+            pe_, pl_ = env(pI_E, pQ_E), env(pI_L, pQ_L)
+            pce = (pe_ - pl_) / (pe_ + pl_)
+            if b2a:
+                code_err = (code_err + pce) / 2  # :377
+            elif mode == "NB":
+                code_err = (code_err * 11 + pce * (1 - co.spc_el) * 29) / 40  # NB:381-384
+            else:
+                code_err = code_err * co.factor + pce * (1 - co.spc_el) * (1 - co.factor)  # WB:418
+        code_nco = st.old_nco + (co.tau2 / co.tau1) * (code_err - st.old_err) + code_err * (co.pdi / co.tau1)  # :381
+        code_freq = st.code_basis - code_nco  # :389
+    return SimpleNamespace(carr_err=carr_err, carr_nco=carr_nco, code_err=code_err, code_nco=code_nco, carr_freq=carr_freq,
+                           code_freq=code_freq, d2=d2, d1=d1)
+
+
+def nco_state_ok(code_freq, rem_code):
+    """The next epoch can take a block from this code NCO state: MATLAB stops in fread otherwise (an epoch of all-zero samples
+    gives atan(0/0) and 0/0 in the DLL).  The epoch's results stand; the channel stops as at a short read."""
+    return bool(np.isfinite(code_freq) and np.isfinite(rem_code) and code_freq > 0)
 
 
 # --- channel allocation ----------------------------------------------------------
@@ -216,7 +293,7 @@ def tracking(fid: RawFile, channel, settings, mode=None, trace=None, correlate=N
     adapt = 1 if settings.fileType == 1 else 2
     fs = settings.samplingFreq
     two_pi = 2.0 * np.pi
-    s433, s2933 = np.sqrt(4 / 33), np.sqrt(29 / 33)
+    coef = SimpleNamespace(pf3=pf3, pf2=pf2, pf1=pf1, tau1=tau1, tau2=tau2, pdi=pdi, spc_el=spc_el, factor=factor)
 
     for c in range(nch):
         ch = channel[c]
@@ -275,12 +352,8 @@ def tracking(fid: RawFile, channel, settings, mode=None, trace=None, correlate=N
                     pI_E, pQ_E, pI_P, pQ_P, pI_L, pQ_L = (float(v) for v in sums[6:12])
                     if mode == "WB":
                         sI_E, sQ_E, sI_P, sQ_P, sI_L, sQ_L = (float(v) for v in sums[12:18])
-                        cI_E = -s433 * sI_E + s2933 * pQ_E  # WB:375-380 QMBOC composite
-                        cQ_E = -s433 * sQ_E - s2933 * pI_E
-                        cI_P = -s433 * sI_P + s2933 * pQ_P
-                        cQ_P = -s433 * sQ_P - s2933 * pI_P
-                        cI_L = -s433 * sI_L + s2933 * pQ_L
-                        cQ_L = -s433 * sQ_L - s2933 * pI_L
+                        cI_E, cQ_E, cI_P, cQ_P, cI_L, cQ_L = qmboc_composite(  # WB:375-380
+                            (pI_E, pQ_E, pI_P, pQ_P, pI_L, pQ_L), (sI_E, sQ_E, sI_P, sQ_P, sI_L, sQ_L))
             else:
                 raw, nread = fid.read(adapt * blk)
                 if adapt == 2:
@@ -341,57 +414,23 @@ def tracking(fid: RawFile, channel, settings, mode=None, trace=None, correlate=N
                         sI_E, sQ_E = np.sum(p6e * i_bb), np.sum(p6e * q_bb)
                         sI_P, sQ_P = np.sum(p6p * i_bb), np.sum(p6p * q_bb)
                         sI_L, sQ_L = np.sum(p6l * i_bb), np.sum(p6l * q_bb)
-                        # WB:375-380 QMBOC composite
-                        cI_E = -s433 * sI_E + s2933 * pQ_E
-                        cQ_E = -s433 * sQ_E - s2933 * pI_E
-                        cI_P = -s433 * sI_P + s2933 * pQ_P
-                        cQ_P = -s433 * sQ_P - s2933 * pI_P
-                        cI_L = -s433 * sI_L + s2933 * pQ_L
-                        cQ_L = -s433 * sQ_L - s2933 * pI_L
+                        cI_E, cQ_E, cI_P, cQ_P, cI_L, cQ_L = qmboc_composite(  # WB:375-380
+                            (pI_E, pQ_E, pI_P, pQ_P, pI_L, pQ_L), (sI_E, sQ_E, sI_P, sQ_P, sI_L, sQ_L))
 
-            with np.errstate(all="ignore"):
-                carr_err = np.arctan(np.float64(Q_P) / np.float64(I_P)) / two_pi  # :337
-                if pilot:
-                    if b2a:
-                        qi = (pI_P + 1j * pQ_P) * np.exp(-1j * np.pi / 2)  # :345
-                        cq = np.arctan(np.float64(qi.imag) / np.float64(qi.real)) / two_pi  # :348
-                        carr_err = (carr_err + cq) / 2  # :352
-                    elif mode == "NB":
-                        cq = np.arctan(np.float64(-pI_P) / np.float64(pQ_P)) / two_pi  # NB:357
-                        carr_err = (carr_err * 11 + cq * 29) / 40  # NB:360
-                    else:
-                        cq = np.arctan(np.float64(cQ_P) / np.float64(cI_P)) / two_pi  # WB:392
-                        carr_err = (carr_err * 1 + cq * 3) / 4  # WB:395
-                d2 = d2 + carr_err * pf3  # :356
-                d1 = d2 + carr_err * pf2 + d1  # :357
-                carr_nco = d1 + carr_err * pf1  # :358
-                r.carrFreq[k - 1] = carr_freq  # :361
-                carr_freq = carr_basis + carr_nco  # :363
-
-                def env(a, b):
-                    return np.sqrt(a * a + b * b)
-
-                e_, l_ = env(I_E, Q_E), env(I_L, Q_L)
-                code_err = (e_ - l_) / (e_ + l_)  # :366
-                if not b2a:
-                    code_err = code_err * (1 - spc_el)  # WB:409-410
-                if pilot:
-                    if mode == "WB":
-                        pe_, pl_ = env(cI_E, cQ_E), env(cI_L, cQ_L)
-                    else:
-                        pe_, pl_ = env(pI_E, pQ_E), env(pI_L, pQ_L)
-                    pce = (pe_ - pl_) / (pe_ + pl_)
-                    if b2a:
-                        code_err = (code_err + pce) / 2  # :377
-                    elif mode == "NB":
-                        code_err = (code_err * 11 + pce * (1 - spc_el) * 29) / 40  # NB:381-384
-                    else:
-                        code_err = code_err * factor + pce * (1 - spc_el) * (1 - factor)  # WB:418
-                code_nco = old_nco + (tau2 / tau1) * (code_err - old_err) + code_err * (pdi / tau1)  # :381
-                old_nco = code_nco
-                old_err = code_err
-                r.codeFreq[k - 1] = code_freq  # :387
-                code_freq = ch.codeFreq - code_nco  # :389
+            data6 = (I_E, Q_E, I_P, Q_P, I_L, Q_L)
+            pil6 = None
+            if pilot:
+                pil6 = (cI_E, cQ_E, cI_P, cQ_P, cI_L, cQ_L) if mode == "WB" else (pI_E, pQ_E, pI_P, pQ_P, pI_L, pQ_L)
+            up = loop_update(mode, pilot, data6, pil6,
+                             SimpleNamespace(d2=d2, d1=d1, old_nco=old_nco, old_err=old_err, carr_basis=carr_basis, code_basis=ch.codeFreq), coef)
+            carr_err, carr_nco, code_err, code_nco = up.carr_err, up.carr_nco, up.code_err, up.code_nco
+            d2, d1 = up.d2, up.d1
+            old_nco = code_nco
+            old_err = code_err
+            r.carrFreq[k - 1] = carr_freq  # :361
+            carr_freq = up.carr_freq  # :363
+            r.codeFreq[k - 1] = code_freq  # :387
+            code_freq = up.code_freq  # :389
 
             r.dllDiscr[k - 1] = code_err
             r.dllDiscrFilt[k - 1] = code_nco
@@ -433,6 +472,9 @@ def tracking(fid: RawFile, channel, settings, mode=None, trace=None, correlate=N
                     getattr(r, "B2a_CNo" if b2a else "B1C_CNo")[cc] = cno_val[2] * 0.5 + tmp_cno[2] * 0.5
                     r.PilotPLD[cc] = pll_det[1]
             tmp_cno = cno_val  # :434
+            if not nco_state_ok(code_freq, rem_code):
+                aborted = True  # the epoch's results stand (NaN discriminators); no block can follow
+                break
 
         if aborted:
             # B2a/tracking.m:250-254: message, fclose(fid), return -- later channels untouched

@@ -138,6 +138,8 @@ def assert_closed_loop_parity(ref, got, mode):
             np.testing.assert_allclose(getattr(g, f), getattr(r, f), rtol=0, atol=tol, err_msg=f)
         cn = "B2a_CNo" if mode == "B2A" else "B1C_CNo"
         for f in ("DataCNo", "PilotCNo", cn):
+            # (assert_allclose takes NaN for equal to NaN: four cases of the suite once matched a NaN C/N0 of the oracle's real sqrt)
+            assert np.all(np.isfinite(getattr(r, f))), f
             np.testing.assert_allclose(getattr(g, f), getattr(r, f), rtol=0, atol=1e-3, err_msg=f)
         for f in ("DataPLD", "PilotPLD"):
             np.testing.assert_allclose(getattr(g, f), getattr(r, f), rtol=0, atol=1e-5, err_msg=f)

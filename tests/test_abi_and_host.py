@@ -170,5 +170,5 @@ def test_context_mirror_has_a_method_per_entry_it_wraps():
     """the ctypes mirror keeps one method per native entry the tests and tools call (an edit that drops one -- timing() once --
     must fail here, on CPU, not on the GPU box)"""
     for m in ("acq_load", "acq_prepare", "acq_run", "acq_grid", "acq_peaks", "acq_candidates", "acq_coherent_sums", "timing",
-              "track", "track_correlate", "track_colon", "reload_tuning", "device_name"):
+              "track", "track_correlate", "track_colon", "track_cno", "track_update", "reload_tuning", "device_name"):
         assert callable(getattr(native.Context, m, None)), m

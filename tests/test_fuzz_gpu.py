@@ -125,4 +125,5 @@ def test_random_tracking_configs(ctx, seed):
                 np.testing.assert_allclose(getattr(g, f), getattr(r, f), rtol=0, atol=1e-4 * p, err_msg=f)
         np.testing.assert_allclose(g.carrFreq, r.carrFreq, rtol=0, atol=1e-3)
         np.testing.assert_allclose(g.codeFreq, r.codeFreq, rtol=0, atol=1e-6)
+        assert np.all(np.isfinite(r.DataCNo))  # (NaN would pass for equal to NaN below)
         np.testing.assert_allclose(g.DataCNo, r.DataCNo, rtol=0, atol=1e-3)
