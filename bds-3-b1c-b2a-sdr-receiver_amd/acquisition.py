@@ -66,8 +66,24 @@ def _as_int8(long_signal, settings):
     return np.ascontiguousarray(a).reshape(-1), is_complex
 
 
+def _device_block(long_signal, settings):
+    """A device array as the block: the record's bytes as settings.fileType lays them out -- 1: real int8 samples, 2: interleaved
+    I/Q int8 pairs, 3: packed uint8 bytes -- under the dtype rule of the host arrays."""
+    ft = int(getattr(settings, "fileType", 1))
+    want = "uint8" if ft == 3 else "int8"
+    a = long_signal
+    name = str(a.dtype).split(".")[-1] if hasattr(a, "dtype") else np.dtype(a.__cuda_array_interface__["typestr"]).name
+    if name != want:
+        raise ValueError(f"longSignal must be a {want} device array when settings.fileType is {ft}, not {name}")
+    return a, 2 if ft == 3 else ft == 2
+
+
 def acquisition(long_signal, settings, device: int = 0, prn_list=None, verbose: bool = True, b2a_npoint=None) -> AcqResults:
     """Parallel code-phase search acquisition on the GPU.
+
+    long_signal: the samples as the reference hands them over (real, or complex for an I/Q record; uint8 packed bytes for
+    settings.fileType 3), or (extension) a device array -- a torch tensor on the GPU holding the record's bytes as
+    settings.fileType lays them out -- which is searched where it lies (bds_acq_load_dev), with the same results.
 
     prn_list (extension): the PRN shard this rank searches; results are zero outside
     the shard so an all-reduce(SUM) over ranks reassembles acqResults.
@@ -77,7 +93,7 @@ def acquisition(long_signal, settings, device: int = 0, prn_list=None, verbose: 
     ctx = get_context(device)
     if b2a_npoint is not None:
         ctx.acq_set_b2a_npoint(b2a_npoint)
-    samples, is_complex = _as_int8(long_signal, settings)
+    samples, is_complex = _device_block(long_signal, settings) if native.is_device_array(long_signal) else _as_int8(long_signal, settings)
     ctx.acq_load(settings, samples, is_complex)
     ctx.acq_prepare(settings)
     carr, cph, pm, det = ctx.acq_run(settings, prn_list)

@@ -698,9 +698,12 @@ static void ext_sums(AcqState &a) {
     a.sums_next = a.n_ext;
 }
 
-extern "C" int bds_acq_load(bds_ctx *ctx, const bds_settings *s_in, const int8_t *samples, size_t n_samples,
-                            int is_complex) {
-    if (!ctx || !s_in || !samples) return BDS_ERR_ARG;
+// bds_acq_load and bds_acq_load_dev: the block is at `samples` in host memory, or (samples == NULL) at `d_samples` in device memory,
+// which the caller has checked (check_device_span).  A device block is copied device to device where a host block is copied host to
+// device, and then brought to the host once, as the packed path always was: everything from there on -- the block statistics, the
+// resampling branch, what acq_run reads -- is the same lines on the same bytes for both sources.
+static int acq_load_block(bds_ctx *ctx, const bds_settings *s_in, const int8_t *samples, const void *d_samples, size_t n_samples,
+                          int is_complex) {
     if (int rc0 = check_settings(ctx, *s_in)) return rc0;  // (the resampling band edges are only visible here)
     bds_settings eff;
     const bds_settings *s = effective(s_in, &eff);
@@ -725,14 +728,23 @@ extern "C" int bds_acq_load(bds_ctx *ctx, const bds_settings *s_in, const int8_t
     if (packed) {
         // The bytes go to the device as they are; the search, and the host's sums below, work on the int8 I/Q block unpacked there
         if ((rc = ensure(ctx, &a.d_packed, &a.packed_cap, npk))) return rc;
-        BDS_HIP(ctx, hipMemcpyAsync(a.d_packed, samples, npk, hipMemcpyHostToDevice, st(ctx)));
+        if (samples)
+            BDS_HIP(ctx, hipMemcpyAsync(a.d_packed, samples, npk, hipMemcpyHostToDevice, st(ctx)));
+        else
+            BDS_HIP(ctx, hipMemcpyAsync(a.d_packed, d_samples, npk, hipMemcpyDeviceToDevice, st(ctx)));
         if ((rc = unpack_cplx_device(ctx, a.d_packed, npk, a.d_sig))) return rc;
         h_unpacked.resize(nb);
         BDS_HIP(ctx, hipMemcpyAsync(h_unpacked.data(), a.d_sig, nb, hipMemcpyDeviceToHost, st(ctx)));
         BDS_HIP(ctx, hipStreamSynchronize(st(ctx)));
         samples = h_unpacked.data();
-    } else {
+    } else if (samples) {
         BDS_HIP(ctx, hipMemcpyAsync(a.d_sig, samples, nb, hipMemcpyHostToDevice, st(ctx)));
+    } else {
+        BDS_HIP(ctx, hipMemcpyAsync(a.d_sig, d_samples, nb, hipMemcpyDeviceToDevice, st(ctx)));
+        h_unpacked.resize(nb);
+        BDS_HIP(ctx, hipMemcpyAsync(h_unpacked.data(), a.d_sig, nb, hipMemcpyDeviceToHost, st(ctx)));
+        BDS_HIP(ctx, hipStreamSynchronize(st(ctx)));  // (the caller's memory has been read; the host sums below work on this copy)
+        samples = h_unpacked.data();
     }
     a.cplx = cplx;
     a.rs = r;
@@ -791,6 +803,22 @@ extern "C" int bds_acq_load(bds_ctx *ctx, const bds_settings *s_in, const int8_t
     ext_sums(a);
     BDS_HIP(ctx, hipStreamSynchronize(st(ctx)));
     return BDS_OK;
+}
+
+extern "C" int bds_acq_load(bds_ctx *ctx, const bds_settings *s_in, const int8_t *samples, size_t n_samples,
+                            int is_complex) {
+    if (!ctx || !s_in || !samples) return BDS_ERR_ARG;
+    return acq_load_block(ctx, s_in, samples, nullptr, n_samples, is_complex);
+}
+
+extern "C" int bds_acq_load_dev(bds_ctx *ctx, const bds_settings *s_in, const void *d_samples, size_t n_samples, int is_complex) {
+    if (!ctx || !s_in) return BDS_ERR_ARG;
+    if (is_complex < 0 || is_complex > 2) return fail(ctx, BDS_ERR_ARG, "is_complex must be 0 (real), 1 (I/Q int8 pairs) or 2 (packed 2+2-bit I/Q)");
+    if (!d_samples) return fail(ctx, BDS_ERR_ARG, "bds_acq_load_dev: d_samples is NULL");
+    if (n_samples > ((size_t)1 << 62)) return fail(ctx, BDS_ERR_ARG, "bds_acq_load_dev: n_samples = %zu", n_samples);
+    const size_t bytes = is_complex == 2 ? (n_samples + 1) / 2 : is_complex == 1 ? 2 * n_samples : n_samples;
+    if (int rc = check_device_span(ctx, "bds_acq_load_dev", "d_samples", d_samples, bytes)) return rc;
+    return acq_load_block(ctx, s_in, nullptr, d_samples, n_samples, is_complex);
 }
 
 // Does an N-point pair apply to a run with these settings, and which?  B1C with both components on N = 53 x 12 x 3125 samples

@@ -27,6 +27,35 @@ int fail(bds_ctx *ctx, int code, const char *fmt, ...) {
     return code;
 }
 
+int check_device_span(bds_ctx *ctx, const char *who, const char *arg, const void *p, size_t bytes) {
+    if (!ctx) return fail(ctx, BDS_ERR_ARG, "%s: ctx is NULL", who);
+    if (!p) return bytes ? fail(ctx, BDS_ERR_ARG, "%s: %s is NULL with %zu bytes to go", who, arg, bytes) : BDS_OK;
+    hipPointerAttribute_t at{};
+    const hipError_t e = hipPointerGetAttributes(&at, p);
+    if (e != hipSuccess || at.type == hipMemoryTypeUnregistered) {  // (a plain host pointer is an error to some runtimes, "unregistered" to others)
+        (void)hipGetLastError();
+        return fail(ctx, BDS_ERR_ARG, "%s: %s = %p is not device memory (a host pointer, or one the HIP runtime does not know)", who, arg, p);
+    }
+    if (at.isManaged || at.type == hipMemoryTypeManaged || at.type == hipMemoryTypeUnified)
+        return fail(ctx, BDS_ERR_ARG, "%s: %s = %p is managed memory; the record must be ordinary device memory (hipMalloc)", who, arg, p);
+    if (at.type != hipMemoryTypeDevice)
+        return fail(ctx, BDS_ERR_ARG, "%s: %s = %p is %s, not device memory", who, arg, p,
+                    at.type == hipMemoryTypeHost ? "pinned or registered host memory" : "memory of another kind");
+    if (at.device != ctx->device)
+        return fail(ctx, BDS_ERR_ARG, "%s: %s = %p is memory of device %d, the context runs on device %d", who, arg, p, at.device, ctx->device);
+    hipDeviceptr_t base = nullptr;
+    size_t size = 0;
+    if (hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)p) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(ctx, BDS_ERR_ARG, "%s: %s = %p: the HIP runtime knows no allocation that holds it", who, arg, p);
+    }
+    const size_t at_off = (size_t)((const char *)p - (const char *)base);
+    if ((const char *)p < (const char *)base || at_off > size || bytes > size - at_off)
+        return fail(ctx, BDS_ERR_ARG, "%s: %s = %p with %zu bytes runs past its allocation (%zu bytes, of which %zu lie behind the pointer)", who,
+                    arg, p, bytes, size, at_off <= size ? size - at_off : (size_t)0);
+    return BDS_OK;
+}
+
 // Environment knobs.  The RELEASE library reads four documented ones (include/bds_mi355x.h lists them):
 //   BDS_ACQ_FP16=0      fp32 storage of the spectra and the inter-pass buffer as well (default: fp16 storage, f64 decisions)
 //   BDS_TRK_PREC=0..5   numerics of the tracking correlator (default 4 = strict, a sin / cos of the reference's own carrier argument per

@@ -124,7 +124,14 @@ struct RoctxRange {
 };
 }
 
-#define BDS_HIP(ctx, expr)                                                                     \
+namespace bds {
+// The pointer rule of the *_dev entries (include/bds_mi355x.h, "records in device memory"): BDS_OK when [p, p + bytes) is ordinary
+// device memory (hipMalloc) of the context's device and lies inside one allocation; otherwise BDS_ERR_ARG with a message that names
+// `who`, the argument `arg` and what was found.  Two driver queries, no launch, no copy.  p == NULL with bytes == 0 passes.
+int check_device_span(bds_ctx *ctx, const char *who, const char *arg, const void *p, size_t bytes);
+}
+
+#define BDS_HIP(ctx, expr)                                                                    \
     do {                                                                                       \
         hipError_t _e = (expr);                                                                \
         if (_e != hipSuccess)                                                                  \

@@ -338,6 +338,65 @@ extern "C" int bds_synth(bds_ctx *ctx, const bds_settings *s, int n_sat, const b
     return BDS_OK;
 }
 
+// The record into the caller's device memory.  The kernels store whole 16-byte units at 16-byte-aligned addresses, so they write in
+// place only the whole units of a 16-byte-aligned d_out; everything else (the last, partial unit; all of a misaligned d_out) is
+// generated into a buffer of the library's and copied device to device, byte-exact, so not one byte outside the record is written.
+extern "C" int bds_synth_dev(bds_ctx *ctx, const bds_settings *s, int n_sat, const bds_synth_sat *sats, const bds_synth_opts *opts,
+                             int64_t first_sample, int64_t n_samples, void *d_out, size_t out_bytes) {
+    Plan pl;
+    if (int rc = make_plan(ctx, "bds_synth_dev", s, n_sat, sats, opts, first_sample, n_samples, pl)) return rc;
+    const size_t need = bytes_of(pl.fmt, n_samples);
+    if (out_bytes < need || (need && !d_out))
+        return fail(ctx, BDS_ERR_ARG, "bds_synth_dev: d_out holds %zu bytes, %lld samples of format %d take %zu", d_out ? out_bytes : (size_t)0, (long long)n_samples, pl.fmt, need);
+    if (!ctx) return fail(ctx, BDS_ERR_ARG, "bds_synth_dev: ctx is NULL");
+    if (int rc = check_device_span(ctx, "bds_synth_dev", "d_out", d_out, out_bytes)) return rc;
+    if (n_samples == 0) return BDS_OK;
+    BDS_HIP(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = (hipStream_t)ctx->stream;
+    const int64_t spu = samples_per_unit(pl.fmt);
+    const int64_t n_direct = ((uintptr_t)d_out % kUnitBytes) == 0 ? (int64_t)(need / kUnitBytes) * spu : 0;  // samples of the units written in place
+    const int64_t n_staged = n_samples - n_direct;
+    const int64_t piece = std::min<int64_t>(n_staged, (piece_of(pl.fmt, 0) + 31) / 32 * 32);  // up to 64 MiB of the record staged at a time
+    void *d_stage = nullptr;
+    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
+    double t_gen = 0, t_copy = 0;
+    int rc = plan_upload(ctx, pl);
+    hipError_t e = hipSuccess;
+    if (!rc && n_staged) e = hipMalloc(&d_stage, (size_t)units_of(pl.fmt, piece) * kUnitBytes);
+    for (int i = 0; i < 3 && !rc && e == hipSuccess; ++i) e = hipEventCreate(&ev[i]);
+    if (!rc && e == hipSuccess && n_direct) {
+        e = hipEventRecord(ev[0], st);
+        if (e == hipSuccess) rc = launch(ctx, pl, st, first_sample, n_direct, d_out);
+        if (!rc && e == hipSuccess) e = hipEventRecord(ev[1], st);
+        if (!rc && e == hipSuccess) e = hipStreamSynchronize(st);
+        float g = 0;
+        if (!rc && e == hipSuccess) e = hipEventElapsedTime(&g, ev[0], ev[1]);
+        t_gen += g;
+    }
+    for (int64_t a = n_direct; a < n_samples && !rc && e == hipSuccess; a += piece) {
+        const int64_t m = std::min(piece, n_samples - a);
+        e = hipEventRecord(ev[0], st);
+        if (e == hipSuccess) rc = launch(ctx, pl, st, first_sample + a, m, d_stage);
+        if (!rc && e == hipSuccess) e = hipEventRecord(ev[1], st);
+        if (!rc && e == hipSuccess) e = hipMemcpyAsync((char *)d_out + bytes_of(pl.fmt, a), d_stage, bytes_of(pl.fmt, m), hipMemcpyDeviceToDevice, st);
+        if (!rc && e == hipSuccess) e = hipEventRecord(ev[2], st);
+        if (!rc && e == hipSuccess) e = hipStreamSynchronize(st);
+        float g = 0, c = 0;
+        if (!rc && e == hipSuccess) e = hipEventElapsedTime(&g, ev[0], ev[1]);
+        if (!rc && e == hipSuccess) e = hipEventElapsedTime(&c, ev[1], ev[2]);
+        t_gen += g, t_copy += c;
+    }
+    (void)hipStreamSynchronize(st);  // nothing of this call may still run when its buffers go
+    for (auto v : ev)
+        if (v) (void)hipEventDestroy(v);
+    if (d_stage) (void)hipFree(d_stage);
+    plan_free(pl);
+    if (rc) return rc;
+    if (e != hipSuccess) return fail(ctx, e == hipErrorOutOfMemory ? BDS_ERR_NOMEM : BDS_ERR_HIP, "bds_synth_dev: %s", hipGetErrorString(e));
+    timing_of(ctx, t_gen + t_copy, t_gen, t_copy);
+    return BDS_OK;
+}
+
 extern "C" int bds_synth_file(bds_ctx *ctx, const bds_settings *s, int n_sat, const bds_synth_sat *sats, const bds_synth_opts *opts,
                               int64_t first_sample, int64_t n_samples, const char *path, int64_t piece_samples) {
     Plan pl;

@@ -2002,7 +2002,8 @@ struct bds_track_session {
     std::vector<long long> epochs_done;
     // the record
     bool feed = false, fed_last = false;
-    const int8_t *mem = nullptr;
+    const int8_t *mem = nullptr;  // the record in memory: the host's, or (mem_dev) the device's
+    bool mem_dev = false;
     FILE *file = nullptr;
     void *pin = nullptr;
     size_t pin_bytes = 0;
@@ -2044,7 +2045,7 @@ int track_session_guard(bds_ctx *ctx, const char *who) {
     if (!ctx || !ctx->trk || !ctx->trk->session) return BDS_OK;
     const bds_track_session *h = ctx->trk->session;
     return fail(ctx, BDS_ERR_ARG, "%s: the context has an open tracking session (%d channels on %s): bds_track_close it first", who, h->n_ch,
-                h->feed ? "a fed record" : h->mem ? "a record in memory" : h->path.c_str());
+                h->feed ? "a fed record" : h->mem_dev ? "a record in device memory" : h->mem ? "a record in memory" : h->path.c_str());
 }
 
 static void session_close(bds_track_session *h) {
@@ -2066,12 +2067,13 @@ static void session_close(bds_track_session *h) {
     delete h;
 }
 
-// kind: 0 file at `path`, 1 `n_bytes` bytes at `mem`, 2 fed by the caller from sample `origin` on
+// kind: 0 file at `path`, 1 `n_bytes` bytes at `mem`, 2 fed by the caller from sample `origin` on, 3 `n_bytes` bytes at `mem` in
+// device memory (the caller has checked the span: check_device_span)
 static bds_track_session *session_open(bds_ctx *ctx, const bds_settings *s, int kind, const char *path, const int8_t *mem,
                                        size_t n_bytes, long long origin, int n_ch, const bds_channel *channel) {
-    const char *who = kind == 0 ? "bds_track_open" : kind == 1 ? "bds_track_open_mem" : "bds_track_open_feed";
+    const char *who = kind == 0 ? "bds_track_open" : kind == 1 ? "bds_track_open_mem" : kind == 2 ? "bds_track_open_feed" : "bds_track_open_dev";
     if (!ctx) return nullptr;
-    if (!s || !channel || n_ch < 1 || (kind == 0 && !path) || (kind == 1 && !mem)) {
+    if (!s || !channel || n_ch < 1 || (kind == 0 && !path) || ((kind == 1 || kind == 3) && !mem)) {
         fail(ctx, BDS_ERR_ARG, "%s: settings, channel table (n_ch >= 1) and the record are required", who);
         return nullptr;
     }
@@ -2083,7 +2085,7 @@ static bds_track_session *session_open(bds_ctx *ctx, const bds_settings *s, int 
     if (!ctx->trk) ctx->trk = new TrackState();
     TrackState &t = *ctx->trk;
     bds_track_session *h = new bds_track_session();
-    h->ctx = ctx, h->s = *s, h->n_ch = n_ch, h->feed = kind == 2, h->mem = kind == 1 ? mem : nullptr;
+    h->ctx = ctx, h->s = *s, h->n_ch = n_ch, h->feed = kind == 2, h->mem = kind == 1 || kind == 3 ? mem : nullptr, h->mem_dev = kind == 3;
     h->epochs_done.assign((size_t)n_ch, 0);
     h->margin = ctx->tune.trk_stream_margin >= 0 ? ctx->tune.trk_stream_margin : 1.0;
     // (not registered yet: every failure below frees it here)
@@ -2131,9 +2133,10 @@ static bds_track_session *session_open(bds_ctx *ctx, const bds_settings *s, int 
                 return fail(ctx, BDS_ERR_NOMEM, "resident span of 2 x %zu bytes of the IF record does not fit in HBM", cap);
             }
         // the record's source
-        if (kind == 1) {
-            h->load = [ctx, mem](size_t off, size_t n, int8_t *dst, hipStream_t stream) -> int {
-                BDS_HIP(ctx, hipMemcpyAsync(dst, mem + off, n, hipMemcpyHostToDevice, stream));
+        if (kind == 1 || kind == 3) {
+            const hipMemcpyKind dir = kind == 3 ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+            h->load = [ctx, mem, dir](size_t off, size_t n, int8_t *dst, hipStream_t stream) -> int {
+                BDS_HIP(ctx, hipMemcpyAsync(dst, mem + off, n, dir, stream));
                 return BDS_OK;
             };
         } else if (kind == 0) {
@@ -2202,6 +2205,17 @@ extern "C" bds_track_session *bds_track_open_mem(bds_ctx *ctx, const bds_setting
     return session_open(ctx, s, 1, nullptr, file_bytes, n_bytes, 0, n_ch, channel);
 }
 
+extern "C" bds_track_session *bds_track_open_dev(bds_ctx *ctx, const bds_settings *s, const void *d_file_bytes, size_t n_bytes, int n_ch,
+                                                 const bds_channel *channel) {
+    if (!ctx) return nullptr;
+    if (!d_file_bytes) {
+        fail(ctx, BDS_ERR_ARG, "bds_track_open_dev: d_file_bytes is NULL");
+        return nullptr;
+    }
+    if (check_device_span(ctx, "bds_track_open_dev", "d_file_bytes", d_file_bytes, n_bytes)) return nullptr;
+    return session_open(ctx, s, 3, nullptr, (const int8_t *)d_file_bytes, n_bytes, 0, n_ch, channel);
+}
+
 extern "C" bds_track_session *bds_track_open_feed(bds_ctx *ctx, const bds_settings *s, long long origin_sample, int n_ch,
                                                   const bds_channel *channel) {
     return session_open(ctx, s, 2, nullptr, nullptr, 0, origin_sample, n_ch, channel);
@@ -2211,15 +2225,20 @@ extern "C" void bds_track_close(bds_track_session *sess) {
     if (bds_track_session *h = live_session(sess)) session_close(h);
 }
 
-extern "C" int bds_track_feed(bds_track_session *sess, const int8_t *bytes, size_t n_bytes, int last) {
+// bds_track_feed (dev = false: `bytes` in host memory) and bds_track_feed_dev (dev = true: in device memory): one body, the copy's
+// direction apart
+static int track_feed(bds_track_session *sess, const int8_t *bytes, size_t n_bytes, int last, bool dev) {
+    const char *who = dev ? "bds_track_feed_dev" : "bds_track_feed";
     bds_track_session *h = live_session(sess);
     if (!h) return BDS_ERR_ARG;
     bds_ctx *ctx = h->ctx;
-    if (!h->feed) return fail(ctx, BDS_ERR_ARG, "bds_track_feed: this session reads its record itself (it was not opened with bds_track_open_feed)");
-    if (h->fed_last) return fail(ctx, BDS_ERR_ARG, "bds_track_feed: the end of the record has been fed already");
-    if (n_bytes && !bytes) return fail(ctx, BDS_ERR_ARG, "bds_track_feed: bytes missing");
+    if (!h->feed) return fail(ctx, BDS_ERR_ARG, "%s: this session reads its record itself (it was not opened with bds_track_open_feed)", who);
+    if (h->fed_last) return fail(ctx, BDS_ERR_ARG, "%s: the end of the record has been fed already", who);
+    if (n_bytes && !bytes) return fail(ctx, BDS_ERR_ARG, "%s: %s missing (NULL with %zu bytes to go)", who, dev ? "d_bytes" : "bytes", n_bytes);
     TrkParams &p = h->u.p;
-    if (p.cplx == kFmtIQ && (n_bytes & 1)) return fail(ctx, BDS_ERR_ARG, "bds_track_feed: an I/Q record takes whole int8 pairs, %zu bytes is an odd count", n_bytes);
+    if (p.cplx == kFmtIQ && (n_bytes & 1)) return fail(ctx, BDS_ERR_ARG, "%s: an I/Q record takes whole int8 pairs, %zu bytes is an odd count", who, n_bytes);
+    if (dev)
+        if (int rc = check_device_span(ctx, who, "d_bytes", bytes, n_bytes)) return rc;
     BDS_HIP(ctx, hipSetDevice(ctx->device));
     TrackState &t = *ctx->trk;
     SpanStream &ss = *h->ss;
@@ -2239,7 +2258,7 @@ extern "C" int bds_track_feed(bds_track_session *sess, const int8_t *bytes, size
     }
     const size_t take = std::min(offered, room()) & ~(size_t)(p.cplx == kFmtIQ ? 1 : 0);
     if (take) {
-        BDS_HIP(ctx, hipMemcpyAsync(ss.cur.buf + ss.nb_of(ss.cur.end - ss.cur.base), bytes, take, hipMemcpyHostToDevice, st(ctx)));
+        BDS_HIP(ctx, hipMemcpyAsync(ss.cur.buf + ss.nb_of(ss.cur.end - ss.cur.base), bytes, take, dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st(ctx)));
         BDS_HIP(ctx, hipStreamSynchronize(st(ctx)));  // the bytes are the caller's again on return
         ss.cur.end += p.cplx == kFmtPacked ? (long long)take * 2 : p.cplx == kFmtIQ ? (long long)take / 2 : (long long)take;
         t.loaded_bytes += take, t.pieces += 1;
@@ -2247,6 +2266,14 @@ extern "C" int bds_track_feed(bds_track_session *sess, const int8_t *bytes, size
     }
     if (last && take == n_bytes) h->fed_last = true, p.n_bytes = ss.cur.end;  // end of file is judged against the fed length from here on
     return (int)take;
+}
+
+extern "C" int bds_track_feed(bds_track_session *sess, const int8_t *bytes, size_t n_bytes, int last) {
+    return track_feed(sess, bytes, n_bytes, last, false);
+}
+
+extern "C" int bds_track_feed_dev(bds_track_session *sess, const void *d_bytes, size_t n_bytes, int last) {
+    return track_feed(sess, (const int8_t *)d_bytes, n_bytes, last, true);
 }
 
 extern "C" int bds_track_session_info(bds_track_session *sess, int32_t *epochs_done, long long *next_sample, long long *fed_end,
@@ -2371,6 +2398,19 @@ extern "C" int bds_track_mem(bds_ctx *ctx, const bds_settings *s, const int8_t *
     if (!ctx || !file_bytes) return BDS_ERR_ARG;
     const RecordLoader load = [&](size_t off, size_t n, int8_t *dst, hipStream_t stream) -> int {
         BDS_HIP(ctx, hipMemcpyAsync(dst, file_bytes + off, n, hipMemcpyHostToDevice, stream));
+        return BDS_OK;
+    };
+    return do_track(ctx, s, load, n_bytes, n_ch, channel, out);
+}
+
+extern "C" int bds_track_dev(bds_ctx *ctx, const bds_settings *s, const void *d_file_bytes, size_t n_bytes, int n_ch,
+                             const bds_channel *channel, bds_track_out *out) {
+    if (!ctx) return BDS_ERR_ARG;
+    if (!d_file_bytes) return fail(ctx, BDS_ERR_ARG, "bds_track_dev: d_file_bytes is NULL");
+    if (int rc = check_device_span(ctx, "bds_track_dev", "d_file_bytes", d_file_bytes, n_bytes)) return rc;
+    const int8_t *mem = (const int8_t *)d_file_bytes;
+    const RecordLoader load = [&](size_t off, size_t n, int8_t *dst, hipStream_t stream) -> int {
+        BDS_HIP(ctx, hipMemcpyAsync(dst, mem + off, n, hipMemcpyDeviceToDevice, stream));
         return BDS_OK;
     };
     return do_track(ctx, s, load, n_bytes, n_ch, channel, out);

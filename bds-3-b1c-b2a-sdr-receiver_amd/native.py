@@ -110,6 +110,8 @@ EXPORTS = [
     "bds_multi_rccl_ranks", "bds_acquire_multi", "bds_shard_jobs", "bds_acq_job_cost",
     "bds_synth", "bds_synth_file", "bds_synth_noise",
 ]
+# the entries marked BDS_DEV_API in the header: their record pointer is device memory (device_span below makes it)
+DEVICE_EXPORTS = ["bds_synth_dev", "bds_acq_load_dev", "bds_track_dev", "bds_track_open_dev", "bds_track_feed_dev"]
 
 _lib = None
 HOOKS_LIB = os.path.join(os.path.dirname(os.path.abspath(__file__)), "libbds_mi355x_hooks.so")
@@ -211,6 +213,13 @@ def lib():
         L.bds_synth.restype, L.bds_synth.argtypes = i32, [vp, SP, i32, YP, OP, i64, i64, vp, sz]
         L.bds_synth_file.restype, L.bds_synth_file.argtypes = i32, [vp, SP, i32, YP, OP, i64, i64, C.c_char_p, i64]
         L.bds_synth_noise.restype, L.bds_synth_noise.argtypes = i32, [vp, C.c_uint64, i64, i64, _DP, _DP]
+    if hasattr(L, "bds_synth_dev"):  # (as above: a build of an older commit takes no record in device memory)
+        L.bds_synth_dev.restype, L.bds_synth_dev.argtypes = i32, [vp, SP, i32, YP, OP, i64, i64, vp, sz]
+        L.bds_acq_load_dev.restype, L.bds_acq_load_dev.argtypes = i32, [vp, SP, vp, sz, i32]
+        L.bds_track_dev.restype = i32
+        L.bds_track_dev.argtypes = [vp, SP, vp, sz, i32, C.POINTER(Channel), C.POINTER(TrackOut)]
+        L.bds_track_open_dev.restype, L.bds_track_open_dev.argtypes = vp, [vp, SP, vp, sz, i32, C.POINTER(Channel)]
+        L.bds_track_feed_dev.restype, L.bds_track_feed_dev.argtypes = i32, [vp, vp, sz, i32]
     L.bds_abi_check.restype, L.bds_abi_check.argtypes = i32, [i32, i32, i32, i32]
     if L.bds_abi_check(C.sizeof(Settings), C.sizeof(Channel), C.sizeof(TrackOut), C.sizeof(Timing)) != 0:
         raise ImportError("ctypes struct layout does not match libbds_mi355x.so (include/bds_mi355x.h changed?)")
@@ -292,6 +301,91 @@ def _i8(a):
     return a, a.ctypes.data_as(C.POINTER(C.c_int8))
 
 
+def is_device_array(x) -> bool:
+    """True for what the *_dev entries take: a torch tensor on a GPU, or any object with __cuda_array_interface__.  Everything
+    else -- NumPy arrays, CPU tensors, paths -- takes the host entries."""
+    if type(x).__module__.split(".")[0] == "torch" and hasattr(x, "data_ptr"):
+        return bool(getattr(x, "is_cuda", False))
+    return hasattr(x, "__cuda_array_interface__")
+
+
+def _device_index(dev):
+    """Device ordinal of a .device attribute (torch.device, an object with .id or .index, an int), or None when it tells none."""
+    if dev is None or isinstance(dev, str):
+        return None
+    if isinstance(dev, (int, np.integer)):
+        return int(dev)
+    for name in ("index", "id"):
+        v = getattr(dev, name, None)
+        if isinstance(v, (int, np.integer)):
+            return int(v)
+    return None
+
+
+def device_span(x, ctx_device, dtypes=("int8", "uint8")):
+    """(pointer, n_bytes, keepalive) of a device array for the *_dev entries: a torch tensor on a GPU or an object with
+    __cuda_array_interface__, contiguous, of one of `dtypes` (NumPy names), on the context's device `ctx_device`.  Anything
+    else raises TypeError / ValueError before any native call.  The ordering rule of include/bds_mi355x.h is kept in here:
+    torch's current stream on that device is synchronised before the span is returned, so that every write to the array
+    enqueued there has completed when the library reads it on its own streams."""
+    ctx_device = int(ctx_device)
+    if type(x).__module__.split(".")[0] == "torch" and hasattr(x, "data_ptr"):
+        if not x.is_cuda:
+            raise TypeError("a torch tensor in host memory is not a device array: pass it as a NumPy array (tensor.numpy()), or move it to the GPU")
+        dev, dtype = x.device.index, str(x.dtype).split(".")[-1]
+        contiguous = bool(x.is_contiguous())
+        ptr, n_bytes = int(x.data_ptr()) if x.numel() else 0, int(x.numel()) * int(x.element_size())
+    elif hasattr(x, "__cuda_array_interface__"):
+        cai = x.__cuda_array_interface__
+        dev, dtype = _device_index(getattr(x, "device", None)), np.dtype(cai["typestr"]).name
+        shape, item = tuple(int(v) for v in cai["shape"]), np.dtype(cai["typestr"]).itemsize
+        strides, want = cai.get("strides"), item
+        contiguous = True
+        if strides is not None:  # C order: the last axis steps by one element, every other by the extent of those behind it
+            for n, st in zip(reversed(shape), reversed(tuple(strides))):
+                contiguous &= n <= 1 or int(st) == want
+                want *= n
+        n_bytes = int(np.prod(shape, dtype=np.int64)) * item if shape else item
+        ptr = int(cai["data"][0] or 0) if n_bytes else 0
+    else:
+        raise TypeError(f"{type(x).__name__} is not a device array (a torch tensor on a GPU, or an object with __cuda_array_interface__)")
+    if dtype not in dtypes:
+        raise TypeError(f"a device array of dtype {dtype}: the record takes {' / '.join(dtypes)}")
+    if not contiguous:
+        raise ValueError("the device array is not contiguous: the record is read as one run of bytes (.contiguous() makes a copy that is)")
+    if dev is not None and dev != ctx_device:
+        raise ValueError(f"the array is on device {dev}, the context runs on device {ctx_device}")
+    _sync_current_stream(ctx_device)
+    return ptr, n_bytes, x
+
+
+def _sync_current_stream(device):
+    """Wait for torch's current stream on `device` (nothing to wait for when torch is absent or has opened no GPU)."""
+    try:
+        import torch
+    except Exception:
+        return
+    if torch.cuda.is_available() and torch.cuda.is_initialized():
+        torch.cuda.current_stream(device).synchronize()
+
+
+def check_feed_span(sess, n_bytes) -> None:
+    """check_feed_bytes for bytes in device memory: the same argument errors, before any native call."""
+    if not sess.get("feed"):
+        raise ValueError("feed on a session that reads its record itself (it was opened on a file or an array, not with origin=)")
+    if sess["fileType"] == 2 and n_bytes % 2:
+        raise ValueError(f"an I/Q record is fed in whole int8 pairs: {n_bytes} bytes is an odd count")
+
+
+def synth_out_torch(fmt, n_samples, device):
+    """synth_out as a torch tensor on GPU `device` (the generator's out="torch")."""
+    import torch
+
+    host = synth_out(fmt, 0)  # (the format check, and the dtype)
+    n = synth_out_count(fmt, n_samples)
+    return torch.empty(n, dtype=getattr(torch, host.dtype.name), device=f"cuda:{int(device)}")
+
+
 def sample_format(is_complex) -> int:
     """is_complex of the C ABI: 0 real int8, 1 (True) interleaved I/Q int8 pairs, 2 packed 2+2-bit I/Q bytes (fileType 3)."""
     f = int(is_complex)
@@ -359,10 +453,17 @@ def synth_out(fmt, n_samples) -> np.ndarray:
     """The array n_samples samples of a format take (0: float64, 1: int8, 2: int8 pairs, 3: packed uint8, two samples a byte)."""
     if fmt not in SYNTH_FORMATS:
         raise ValueError(f"format must be 0 (float64 clean sum), 1 (int8), 2 (I/Q int8 pairs) or 3 (packed 2+2-bit I/Q), not {fmt!r}")
+    return np.empty(synth_out_count(fmt, n_samples), dtype=SYNTH_FORMATS[fmt][0])
+
+
+def synth_out_count(fmt, n_samples) -> int:
+    """Elements of synth_out(fmt, n_samples)."""
+    if fmt not in SYNTH_FORMATS:
+        raise ValueError(f"format must be 0 (float64 clean sum), 1 (int8), 2 (I/Q int8 pairs) or 3 (packed 2+2-bit I/Q), not {fmt!r}")
     dtype, num, den = SYNTH_FORMATS[fmt]
     if int(n_samples) < 0 or int(n_samples) % den:
         raise ValueError(f"n_samples = {n_samples}: a packed record holds two samples per byte" if den > 1 else f"n_samples = {n_samples}")
-    return np.empty(int(n_samples) * num // den, dtype=dtype)
+    return int(n_samples) * num // den
 
 
 def gen_code(signal: str, kind: str, prn: int) -> np.ndarray:
@@ -466,6 +567,7 @@ class Context:
 
     def __init__(self, device: int = 0):
         self._lib = lib()
+        self.device = int(device)
         self._h = self._lib.bds_create(int(device))
         if not self._h:
             raise BdsError(-2, self._lib.bds_last_error(None).decode())
@@ -504,11 +606,22 @@ class Context:
     # -- acquisition -----------------------------------------------------------------
     def acq_load(self, settings, samples, is_complex=False, n_samples=None):
         """is_complex: 0 / False real int8, 1 / True I/Q int8 pairs, 2 packed 2+2-bit I/Q bytes (uint8, fileType 3).
-        n_samples: use only the first n_samples of the array (default: all it holds)."""
+        n_samples: use only the first n_samples of the array (default: all it holds).
+        A device array (is_device_array: a torch tensor on the GPU, int8 / uint8) goes through bds_acq_load_dev, with the same
+        checks and the same results."""
+        if is_device_array(samples):
+            return self.acq_load_dev(settings, samples, is_complex, n_samples)
         cs = pack_settings(settings)
         a, p = _i8(samples)
         n = n_samples_of(a.size, is_complex, n_samples)
         self._check(self._lib.bds_acq_load(self._h, C.byref(cs), p, n, sample_format(is_complex)))
+
+    def acq_load_dev(self, settings, samples, is_complex=False, n_samples=None):
+        """bds_acq_load_dev: acq_load of a block in device memory (int8, uint8 for packed bytes)."""
+        cs = pack_settings(settings)
+        ptr, n_bytes, keep = device_span(samples, self.device)
+        n = n_samples_of(n_bytes, is_complex, n_samples)
+        self._check(self._lib.bds_acq_load_dev(self._h, C.byref(cs), ptr, n, sample_format(is_complex)))
 
     def acq_prepare(self, settings):
         cs = pack_settings(settings)
@@ -559,14 +672,29 @@ class Context:
         return carr, cph, pm, det
 
     # -- synthetic IF records (bds_synth*) -----------------------------------------------
-    def synth(self, settings, sats, first_sample, n_samples, fmt, **opts):
+    def synth(self, settings, sats, first_sample, n_samples, fmt, out=None, **opts):
         """bds_synth: samples first_sample .. + n_samples of the record as float64 (fmt 0), int8 (1), int8 I/Q pairs (2) or packed
-        uint8 (3); opts as pack_synth."""
+        uint8 (3); opts as pack_synth.  out="torch": the record stays in HBM -- a torch tensor on the context's device, made by
+        bds_synth_dev; the default is the NumPy array."""
+        if out == "torch":
+            return self.synth_dev(settings, sats, first_sample, n_samples, fmt, synth_out_torch(fmt, n_samples, self.device), **opts)
+        if out is not None:
+            raise ValueError(f'out must be None (a NumPy array) or "torch" (a tensor on the device), not {out!r}')
         cs = pack_settings(settings)
         arr, o, keep = pack_synth(sats, fmt, **opts)
         out = synth_out(fmt, n_samples)
         self._check(self._lib.bds_synth(self._h, C.byref(cs), len(sats), arr, C.byref(o), int(first_sample), int(n_samples),
                                         out.ctypes.data_as(C.c_void_p), out.nbytes))
+        return out
+
+    def synth_dev(self, settings, sats, first_sample, n_samples, fmt, out, **opts):
+        """bds_synth_dev: the same samples written into the device array `out` (float64 for fmt 0, else int8 / uint8; it may be a
+        slice at any byte offset, and must hold at least the record); returns `out`."""
+        cs = pack_settings(settings)
+        arr, o, keep = pack_synth(sats, fmt, **opts)
+        synth_out_count(fmt, n_samples)
+        ptr, n_bytes, _ = device_span(out, self.device, dtypes=("float64",) if fmt == 0 else ("int8", "uint8"))
+        self._check(self._lib.bds_synth_dev(self._h, C.byref(cs), len(sats), arr, C.byref(o), int(first_sample), int(n_samples), ptr, n_bytes))
         return out
 
     def synth_file(self, settings, sats, first_sample, n_samples, fmt, path, piece_samples=0, **opts):
@@ -654,7 +782,8 @@ class Context:
 
     # -- tracking --------------------------------------------------------------------
     def track(self, settings, source, channels, n_epochs, n_cno, fields):
-        """source: file path (str/bytes) or int8 array of raw file bytes (uint8 for a packed fileType-3 record).
+        """source: file path (str/bytes), int8 array of raw file bytes (uint8 for a packed fileType-3 record), or those bytes as
+        a device array (bds_track_dev).
         Returns dict field -> array [n_ch, n_epochs] (C/N0 fields [n_ch, n_cno])."""
         cs = pack_settings(settings)
         nch = len(channels)
@@ -679,6 +808,9 @@ class Context:
         if isinstance(source, (str, bytes, os.PathLike)):
             path = os.fsencode(source)
             self._check(self._lib.bds_track(self._h, C.byref(cs), path, nch, carr, C.byref(out)))
+        elif is_device_array(source):
+            ptr, n_bytes, keep = device_span(source, self.device)
+            self._check(self._lib.bds_track_dev(self._h, C.byref(cs), ptr, n_bytes, nch, carr, C.byref(out)))
         else:
             a, p = _i8(source)
             self._check(self._lib.bds_track_mem(self._h, C.byref(cs), p, a.size, nch, carr, C.byref(out)))
@@ -705,7 +837,9 @@ class Context:
 
     def track_open(self, settings, path_or_bytes, channel):
         """bds_track_open (a path) / bds_track_open_mem (int8 array of raw file bytes, uint8 for a packed fileType-3 record;
-        the array is kept alive until track_close)."""
+        the array is kept alive until track_close) / bds_track_open_dev (those bytes as a device array)."""
+        if is_device_array(path_or_bytes):
+            return self.track_open_dev(settings, path_or_bytes, channel)
         cs = pack_settings(settings)
         carr = self._channels(channel)
         if isinstance(path_or_bytes, (str, bytes, os.PathLike)):
@@ -714,6 +848,25 @@ class Context:
         a, p = _i8(path_or_bytes)
         h = self._lib.bds_track_open_mem(self._h, C.byref(cs), p, a.size, len(channel), carr)
         return self._session(h, settings, channel, keep=a)
+
+    def track_dev(self, settings, source, channels, n_epochs, n_cno, fields):
+        """bds_track_dev: track() on the raw file bytes in device memory."""
+        device_span(source, self.device)  # (anything but a device array raises here)
+        return self.track(settings, source, channels, n_epochs, n_cno, fields)
+
+    def track_open_dev(self, settings, source, channel):
+        """bds_track_open_dev: the record is the device array `source` (raw file bytes); it is kept alive until track_close and
+        must stay unmodified until then."""
+        cs = pack_settings(settings)
+        ptr, n_bytes, keep = device_span(source, self.device)
+        h = self._lib.bds_track_open_dev(self._h, C.byref(cs), ptr, n_bytes, len(channel), self._channels(channel))
+        return self._session(h, settings, channel, keep=keep)
+
+    def track_feed_dev(self, sess, data, last=False) -> int:
+        """bds_track_feed_dev: track_feed from a device array; the bytes are the caller's again on return."""
+        ptr, n_bytes, keep = device_span(data, self.device)
+        check_feed_span(sess, n_bytes)
+        return self._check(self._lib.bds_track_feed_dev(sess["handle"], ptr, n_bytes, int(bool(last))))
 
     def track_open_feed(self, settings, origin, channel):
         """bds_track_open_feed: the record is what track_feed appends; sample `origin` (a multiple of 32) is the first one fed."""
@@ -725,7 +878,10 @@ class Context:
         return sess
 
     def track_feed(self, sess, data, last=False) -> int:
-        """bds_track_feed: bytes of the settings' fileType; returns how many were taken (fewer than offered: the span is full)."""
+        """bds_track_feed: bytes of the settings' fileType; returns how many were taken (fewer than offered: the span is full).
+        A device array goes through bds_track_feed_dev."""
+        if is_device_array(data):
+            return self.track_feed_dev(sess, data, last)
         a = check_feed_bytes(sess, data)
         return self._check(self._lib.bds_track_feed(sess["handle"], a.ctypes.data_as(C.POINTER(C.c_int8)), a.size, int(bool(last))))
 

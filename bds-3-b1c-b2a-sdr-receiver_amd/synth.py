@@ -133,7 +133,7 @@ def _device_format(iq_sign, clean, packed):
 
 
 def make_if_device(settings, sats, n_samples, seed=3550, sigma=20.0, first_sample=0, iq_sign=0, clean=False, packed=False,
-                   threshold=None, code_doppler=True, pilot61_secondary=False, symbols=None, device=0):
+                   threshold=None, code_doppler=True, pilot61_secondary=False, symbols=None, device=0, out=None):
     """make_if's signal generated on the device (bds_synth): samples first_sample .. first_sample + n_samples of the record, as
     int8[n_samples] (real), int8[2 n_samples] (iq_sign = +1 / -1, as in make_if), float64[n_samples] (clean=True: no noise, not
     quantised) or uint8[n_samples / 2] (packed=True with an iq_sign: the 2+2-bit bytes of fileType 3 -- magnitude 3 where the
@@ -141,13 +141,15 @@ def make_if_device(settings, sats, n_samples, seed=3550, sigma=20.0, first_sampl
     stream is not: noise and symbols are counter-based (Philox4x32-10 keyed by `seed`, include/bds_mi355x.h), so sample n does not
     depend on where a call starts -- a record made in pieces equals the record made at once -- and a seed gives another record
     than make_if's.  symbols: int8 [n_sat, 2, n_sym] of +-1 (data, secondary per satellite entry; code period p reads index
-    (p + 1) mod n_sym) instead of the generated ones.  There is no CPU fallback."""
+    (p + 1) mod n_sym) instead of the generated ones.  out="torch": the record stays in HBM -- a torch tensor on the device
+    (int8, uint8 for packed, float64 for clean; bds_synth_dev), ready for acquisition(), tracking() and TrackSession without a
+    trip through host memory; the default is the NumPy array.  There is no CPU fallback."""
     from .acquisition import get_context
 
     fmt = _device_format(iq_sign, clean, packed)
     return get_context(device).synth(settings, list(sats), first_sample, n_samples, fmt, seed=seed, sigma=sigma, iq_sign=iq_sign,
                                      threshold=threshold, code_doppler=code_doppler, pilot61_secondary=pilot61_secondary,
-                                     symbols=symbols)
+                                     symbols=symbols, out=out)
 
 
 def write_if(path, settings, sats, n_samples, seed=3550, sigma=20.0, first_sample=0, iq_sign=0, clean=False, packed=False,

@@ -4,8 +4,9 @@ BDS-3_B2a/tracking.m:1, BDS-3_B1C/NB_tracking.m:1, BDS-3_B1C/WB_tracking.m:1 and
 
 ``fid`` may be a file path, an open binary file object (its ``.name`` is used: the
 reference seeks absolutely from 'bof', B2a/tracking.m:151-153, so the handle position
-is irrelevant) or an int8 array holding the raw file bytes (uint8 for the packed
-records of ``settings.fileType = 3``).  The result is a list of
+is irrelevant), an int8 array holding the raw file bytes (uint8 for the packed
+records of ``settings.fileType = 3``), or those bytes as a device array (a torch tensor
+on the GPU: the record is read where it lies, with the same results).  The result is a list of
 per-channel structs with exactly the field set the reference variant creates
 (SURVEY.md Appendix D).
 """
@@ -78,6 +79,17 @@ def _resident_limit(ctx, resident_limit):
         ctx.track_set_resident_limit(before)
 
 
+def _device_record(a, settings, field):
+    """A device array as the record's raw bytes, with the dtype rule of the host arrays: uint8 for the packed bytes of
+    settings.fileType 3, int8 otherwise (checked before any native call)."""
+    want = "uint8" if int(settings.fileType) == 3 else "int8"
+    name = str(a.dtype).split(".")[-1] if hasattr(a, "dtype") else np.dtype(a.__cuda_array_interface__["typestr"]).name
+    if name != want:
+        raise ValueError(f"{field} must be a {want} device array when settings.fileType is {int(settings.fileType)}"
+                         + (" (packed bytes: two 2+2-bit I/Q samples per byte)" if want == "uint8" else "") + f", not {name}")
+    return a
+
+
 def tracking(fid, channel, settings, mode=None, device: int = 0, resident_limit=None):
     """resident_limit: bytes of the IF record that may be resident in HBM during this call -- a larger window is streamed
     through in pieces, bit-identical results (bds_track_set_resident_limit; 0 = no limit).  None leaves the context's
@@ -89,6 +101,8 @@ def tracking(fid, channel, settings, mode=None, device: int = 0, resident_limit=
     n, m, ep, cn, pilot = field_set(settings, mode)
     if isinstance(fid, (str, bytes, os.PathLike)):
         source = fid
+    elif native.is_device_array(fid):
+        source = _device_record(fid, settings, "fid")
     elif hasattr(fid, "name") and not isinstance(fid, np.ndarray):
         source = fid.name
     elif int(settings.fileType) == 3:  # packed bytes: never through a conversion to int8 values
@@ -142,9 +156,22 @@ def acquire_track(long_signal, path, settings, device: int = 0, resident_limit=N
     B1C/postProcessing.m:105-143) as ONE native call: bds_acquire_track runs the search, allocates the channels with a
     device kernel (bds_pre_run_device) and tracks the record at `path` with the variant the settings select, without
     returning to the host language in between.  Returns (acqResults, channel, trackResults).
+    `path` may also be the record's raw bytes, in host memory or as a device array, and long_signal a device array (the record's
+    bytes as settings.fileType lays them out): the same three steps then run as three native calls -- the search, bds_pre_run_device,
+    bds_track_mem / bds_track_dev -- with the same results.
     resident_limit: as in tracking()."""
     mode = _mode(settings, None)
     n, m, ep, cn, pilot = field_set(settings, mode)
+    if native.is_device_array(long_signal) or not isinstance(path, (str, bytes, os.PathLike)):
+        from .acquisition import acquisition
+
+        ctx = get_context(device)
+        acq = acquisition(long_signal, settings, device=device, verbose=False)
+        ch = ctx.pre_run_device(settings, acq.carrFreq, acq.codePhase, acq.peakMetric)
+        channel = [SimpleNamespace(PRN=int(c.PRN), acquiredFreq=float(c.acquiredFreq), codePhase=float(c.codePhase),
+                                   codeFreq=float(c.codeFreq), status=chr(c.status)) for c in ch]
+        results, _ = tracking(path, channel, settings, device=device, resident_limit=resident_limit)
+        return acq, channel, results
     x = np.asarray(long_signal)
     is_complex = np.iscomplexobj(x)
     if int(settings.fileType) == 3:  # packed bytes, in the block as in the file
@@ -168,7 +195,8 @@ class TrackSession:
     ``tracking()`` call over the same epochs returns (settings.msToProcess is not read: a session has no preset end, and every
     channel stops at its own short read).
 
-    source: a file path, an open binary file (its ``.name``), or the raw file bytes (int8; uint8 for settings.fileType = 3).
+    source: a file path, an open binary file (its ``.name``), or the raw file bytes (int8; uint8 for settings.fileType = 3), in
+    host memory or as a device array (a torch tensor on the GPU; it must stay unmodified until close()).  ``feed`` takes either kind.
     origin=N (a multiple of 32) instead opens a FEED session: pass source=None; the record is what ``feed`` appends, sample N
     of the record first.  resident_limit: bytes of the record resident in HBM (None: the context's limit, else 256 MiB).
     One session may be open per context; tracking() on that context raises until it is closed."""
@@ -198,6 +226,8 @@ class TrackSession:
                 self._sess = self._ctx.track_open_feed(s, origin, self.channel)
             elif isinstance(source, (str, bytes, os.PathLike)):
                 self._sess = self._ctx.track_open(s, source, self.channel)
+            elif native.is_device_array(source):
+                self._sess = self._ctx.track_open(s, _device_record(source, settings, "source"), self.channel)
             elif hasattr(source, "name") and not isinstance(source, np.ndarray):
                 self._sess = self._ctx.track_open(s, source.name, self.channel)
             elif int(settings.fileType) == 3:
@@ -215,6 +245,8 @@ class TrackSession:
         """Append bytes of the settings' fileType to the record; returns how many were taken (fewer than offered when the
         resident span is full: advance, then feed the rest).  last=True marks the end of the record."""
         sess = self._open()
+        if native.is_device_array(data):  # (bds_track_feed_dev; the same argument errors, raised in there before any native call)
+            return self._ctx.track_feed(sess, _device_record(data, self.settings, "data"), last)
         native.check_feed_bytes(sess, data)  # (argument errors raise before any native call)
         return self._ctx.track_feed(sess, data, last)
 

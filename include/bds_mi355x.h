@@ -566,6 +566,52 @@ BDS_API int bds_synth_file(bds_ctx *ctx, const bds_settings *s, int n_sat, const
 /* Test aid: the raw N(0, 1) stream of samples first .. first + n - 1 as the device forms it (either pointer may be NULL). */
 BDS_API int bds_synth_noise(bds_ctx *ctx, uint64_t seed, int64_t first, int64_t n, double *g_i, double *g_q);
 
+/* ---- records in device memory: generate, search and track without the host round trip -------------------------------
+ * A record that is made on the card -- by bds_synth_dev, or by a front end of the caller's (filter, down-converter, channeliser)
+ * -- is searched and tracked from where it lies.  Each entry below does what its host-memory counterpart does with the same
+ * bytes, and every output is bit-identical to that counterpart's: acqResults and what bds_acq_grid / bds_acq_peaks /
+ * bds_acq_candidates / bds_acq_coherent_sums / bds_get_timing report after them, every field of bds_track_out, the pieces of a
+ * session with their C/N0 carry, bds_track_stream_info.  bds_track_loaded_bytes counts the bytes brought into the resident span
+ * whatever their source, so the numbers of a device-sourced run are the host-sourced run's.
+ *   bds_synth_dev       = bds_synth, the record written to d_out (out_bytes as for bds_synth: at least the n_samples samples of the
+ *                         format).  A 16-byte-aligned d_out is written in place, the last partial 16 bytes apart; any other d_out
+ *                         goes through a buffer of the library's and a device-to-device copy.  No byte outside the record is written.
+ *                         bds_get_timing reports as after bds_synth; search_ms is the device-to-device copies (0: none was made).
+ *   bds_acq_load_dev    = bds_acq_load.  The block is copied device to device and brought to the host once: the block statistics
+ *                         (the sums that set the storage scales, the prefix sums of the DC means, the signal power of the B1C
+ *                         decision) stay the host's exact sums, the same lines for both sources.  bds_acq_prepare / bds_acq_run,
+ *                         the resampling branch and the fallbacks work after it exactly as after bds_acq_load.
+ *   bds_track_dev       = bds_track_mem
+ *   bds_track_open_dev  = bds_track_open_mem
+ *   bds_track_feed_dev  = bds_track_feed
+ *                         The one-window load, the pieces of the loader thread, the synchronous reload and the feed append are the
+ *                         same copies, device to device, on the same streams in the same order.  The correlators never run on the
+ *                         caller's buffer in place: their aligned reads assume the library's own allocations.
+ * The pointer rule, checked before any device work: hipPointerGetAttributes must report ordinary device memory
+ *   (hipMemoryTypeDevice: hipMalloc, or a framework's allocator on top of it) of the CONTEXT'S device, and hipMemGetAddressRange
+ *   must show [p, p + bytes) inside one allocation.  A host pointer, pinned or registered host memory, managed memory, memory of
+ *   another device, NULL with a non-zero size, or a range that runs past its allocation returns BDS_ERR_ARG with a message that
+ *   names the argument and what was found; nothing is launched and nothing is copied.  Any byte alignment is accepted.
+ * The ordering rule: the library works on its context's own non-blocking streams, which nothing orders against the caller's.
+ *   The caller guarantees that all writes to the memory are complete when the call is made (synchronise the producing stream
+ *   first).  bds_synth_dev, bds_acq_load_dev, bds_track_dev and bds_track_feed_dev return only after their reads and writes of
+ *   caller memory are complete: the memory is the caller's again.  The record of bds_track_open_dev must stay valid and unmodified
+ *   until bds_track_close, as for bds_track_open_mem: the loader thread reads it while epochs run.
+ * The session rules carry over unchanged, with the same messages: one session per context, origin_sample a multiple of 32,
+ *   whole I/Q pairs, `last`, partial takes when the span is full; bds_track_feed_dev on a session that was not opened with
+ *   bds_track_open_feed, or on a closed one, returns BDS_ERR_ARG.  One feed session may take host and device bytes in turn. */
+/* (these five entries are marked BDS_DEV_API, not BDS_API: the pointer they take for the record is a DEVICE pointer, which a host
+ * language binding must not fill from its own arrays -- a binding generator that walks the BDS_API entries does not see them) */
+#define BDS_DEV_API __attribute__((visibility("default")))
+BDS_DEV_API int bds_synth_dev(bds_ctx *ctx, const bds_settings *s, int n_sat, const bds_synth_sat *sats, const bds_synth_opts *opts,
+                          int64_t first_sample, int64_t n_samples, void *d_out, size_t out_bytes);
+BDS_DEV_API int bds_acq_load_dev(bds_ctx *ctx, const bds_settings *s, const void *d_samples, size_t n_samples, int is_complex);
+BDS_DEV_API int bds_track_dev(bds_ctx *ctx, const bds_settings *s, const void *d_file_bytes, size_t n_bytes, int n_ch,
+                          const bds_channel *channel, bds_track_out *out);
+BDS_DEV_API bds_track_session *bds_track_open_dev(bds_ctx *ctx, const bds_settings *s, const void *d_file_bytes, size_t n_bytes,
+                                              int n_ch, const bds_channel *channel);
+BDS_DEV_API int bds_track_feed_dev(bds_track_session *sess, const void *d_bytes, size_t n_bytes, int last);
+
 #ifdef __cplusplus
 }
 #endif
