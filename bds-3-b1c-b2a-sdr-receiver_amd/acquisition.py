@@ -47,9 +47,12 @@ def packed_bytes(long_signal, field="longSignal"):
 
 
 def _as_int8(long_signal, settings):
+    """The block as the int8 (settings.dataType 'int16': int16) row the native entries take, and is_complex."""
     if int(getattr(settings, "fileType", 1)) == 3:
+        native.record_is_int16(settings, np.asarray(long_signal).dtype.name, "longSignal")  # (int16 settings: uint8 bytes disagree)
         return packed_bytes(long_signal), 2
     a = np.asarray(long_signal)
+    w16 = native.record_is_int16(settings, a.dtype.name, "longSignal")  # dtype against settings.dataType, before any copy
     if np.iscomplexobj(a):
         # fileType 2: data = I + 1i*Q (B2a/postProcessing.m:92-96)
         inter = np.empty(a.size * 2, dtype=np.float64)
@@ -58,6 +61,13 @@ def _as_int8(long_signal, settings):
         a, is_complex = inter, True
     else:
         is_complex = False
+    if w16:
+        if a.dtype != np.int16:
+            r = np.rint(a)
+            if not np.array_equal(r, a) or r.min() < -32768 or r.max() > 32767:
+                raise ValueError("longSignal must hold int16 values (fread(...,'int16'))")
+            a = r.astype(np.int16)
+        return np.ascontiguousarray(a).reshape(-1), is_complex
     if a.dtype != np.int8:
         r = np.rint(a)
         if not np.array_equal(r, a) or r.min() < -128 or r.max() > 127:
@@ -68,11 +78,12 @@ def _as_int8(long_signal, settings):
 
 def _device_block(long_signal, settings):
     """A device array as the block: the record's bytes as settings.fileType lays them out -- 1: real int8 samples, 2: interleaved
-    I/Q int8 pairs, 3: packed uint8 bytes -- under the dtype rule of the host arrays."""
+    I/Q int8 pairs, 3: packed uint8 bytes -- under the dtype rule of the host arrays (int16 with settings.dataType 'int16')."""
     ft = int(getattr(settings, "fileType", 1))
-    want = "uint8" if ft == 3 else "int8"
     a = long_signal
-    name = str(a.dtype).split(".")[-1] if hasattr(a, "dtype") else np.dtype(a.__cuda_array_interface__["typestr"]).name
+    name = native.device_dtype_name(a)
+    w16 = native.record_is_int16(settings, name, "longSignal")
+    want = "int16" if w16 else "uint8" if ft == 3 else "int8"
     if name != want:
         raise ValueError(f"longSignal must be a {want} device array when settings.fileType is {ft}, not {name}")
     return a, 2 if ft == 3 else ft == 2

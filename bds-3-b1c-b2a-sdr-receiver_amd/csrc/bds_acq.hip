@@ -96,6 +96,7 @@ struct AcqState {
     double *d_ffa = nullptr, *d_ffb = nullptr, *d_fir = nullptr;  // filtfilt work buffers, fir1 taps
     size_t ffa_cap = 0, ffb_cap = 0, fir_cap = 0;
     int skind = kS8;                // what the search reads: SampleKind
+    bool w16 = false;               // the block was loaded as int16 samples (settings.dataType 1): d_sig holds its bytes, the search reads d_sig64
     long n_samples = 0;             // samples of the block the search sees (after resampling, if any)
     ResamplePlan rs;                // resampling branch of the loaded block
     // Host view of that block.  An int8 record is kept as the bytes it came in (interleaved I/Q for a complex one) with its
@@ -229,8 +230,8 @@ void acq_state_invalidate(AcqState *a) {
 static int check_settings(bds_ctx *ctx, const bds_settings &s) {
     if (s.signal != BDS_SIGNAL_B1C && s.signal != BDS_SIGNAL_B2A)
         return fail(ctx, BDS_ERR_ARG, "settings.signal must be 1 (B1C) or 2 (B2a)");
-    if (s.dataType != 0)
-        return fail(ctx, BDS_ERR_UNSUPPORTED, "settings.dataType: only 'schar' (int8 samples) is supported");
+    if (s.dataType != 0 && s.dataType != 1)
+        return fail(ctx, BDS_ERR_UNSUPPORTED, "settings.dataType: only 'schar' (0: int8 samples) and 'int16' (1) are supported");
     if (!(s.samplingFreq > 0) || !(s.codeFreqBasis > 0) || s.codeLength != 10230)
         return fail(ctx, BDS_ERR_ARG, "settings.samplingFreq/codeFreqBasis must be positive and codeLength 10230");
     if (!(s.acqStep > 0) || !(s.acqSearchBand >= 0))
@@ -638,7 +639,7 @@ static const bds_settings *effective(const bds_settings *s, bds_settings *tmp) {
 
 // filtfilt(fir1(700, wp), 1, longSignal) + index decimation on the device (acquisition.m:56-112);
 // leaves the conditioned block in a.d_sig64 and its host copy in h_re / h_im.
-template <int NCH>
+template <int NCH, class T>
 static int condition_block(bds_ctx *ctx, AcqState &a, const ResamplePlan &r, long n_in, long *n_out) {
     constexpr int kTaps = 701, kFact = 3 * (kTaps - 1);  // filtfilt: nfact = 3*(nfilt-1)
     if (n_in <= kFact) return fail(ctx, BDS_ERR_ARG, "longSignal (%ld samples) is too short for filtfilt (needs > %d)", n_in, kFact);
@@ -650,7 +651,7 @@ static int condition_block(bds_ctx *ctx, AcqState &a, const ResamplePlan &r, lon
     if ((rc = ensure(ctx, &a.d_ffb, &a.ffb_cap, (size_t)len * NCH))) return rc;
     BDS_HIP(ctx, hipMemcpyAsync(a.d_fir, b.data(), sizeof(double) * kTaps, hipMemcpyHostToDevice, st(ctx)));
     const dim3 grid(2048), blk(256);
-    hipLaunchKernelGGL(k_ff_extend<NCH>, grid, blk, 0, st(ctx), (const int8_t *)a.d_sig, n_in, kFact, a.d_ffa);
+    hipLaunchKernelGGL((k_ff_extend<NCH, T>), grid, blk, 0, st(ctx), (const T *)a.d_sig, n_in, kFact, a.d_ffa);
     hipLaunchKernelGGL(k_ff_fir<NCH>, grid, blk, sizeof(double) * kTaps, st(ctx), (const double *)a.d_ffa, len,
                        (const double *)a.d_fir, kTaps, 0, a.d_ffb);
     hipLaunchKernelGGL(k_ff_fir<NCH>, grid, blk, sizeof(double) * kTaps, st(ctx), (const double *)a.d_ffb, len,
@@ -702,9 +703,13 @@ static void ext_sums(AcqState &a) {
 // which the caller has checked (check_device_span).  A device block is copied device to device where a host block is copied host to
 // device, and then brought to the host once, as the packed path always was: everything from there on -- the block statistics, the
 // resampling branch, what acq_run reads -- is the same lines on the same bytes for both sources.
+// w16: the block holds int16 samples (settings.dataType 1; `samples` then points at int16 values).  They are widened to float64 on
+// the device -- exactly: every int16 is a float64 -- and the search reads that block as it reads the resampling branch's.
 static int acq_load_block(bds_ctx *ctx, const bds_settings *s_in, const int8_t *samples, const void *d_samples, size_t n_samples,
-                          int is_complex) {
+                          int is_complex, bool w16 = false) {
     if (int rc0 = check_settings(ctx, *s_in)) return rc0;  // (the resampling band edges are only visible here)
+    if (w16 && is_complex == 2)
+        return fail(ctx, BDS_ERR_ARG, "is_complex = 2 (packed 2+2-bit I/Q) has no 16-bit form: settings.dataType must be 'schar' (0)");
     bds_settings eff;
     const bds_settings *s = effective(s_in, &eff);
     // n_samples counts complex samples when is_complex: `samples` then holds 2*n_samples int8 (I,Q pairs), or, is_complex == 2,
@@ -721,7 +726,8 @@ static int acq_load_block(bds_ctx *ctx, const bds_settings *s_in, const int8_t *
     AcqState &a = *ctx->acq;
     const ResamplePlan r = resample_plan(*s_in);
     BDS_HIP(ctx, hipSetDevice(ctx->device));
-    const size_t nb = n_samples * (cplx ? 2 : 1);
+    const size_t nv = n_samples * (cplx ? 2 : 1);  // values of the block
+    const size_t nb = w16 ? 2 * nv : nv;           // ... and its bytes as loaded
     const size_t npk = packed ? (n_samples + 1) / 2 : 0;  // packed bytes: each becomes four int8 (the last pair is unused when n_samples is odd)
     if ((rc = ensure(ctx, &a.d_sig, &a.sig_cap, std::max(nb, 4 * npk) + 16))) return rc;  // (+16: k_corr reads whole dwords, bds_acq_corr.h)
     std::vector<int8_t> h_unpacked;
@@ -748,10 +754,27 @@ static int acq_load_block(bds_ctx *ctx, const bds_settings *s_in, const int8_t *
     }
     a.cplx = cplx;
     a.rs = r;
+    a.w16 = w16;
     long n_eff = (long)n_samples;
     if (r.on) {
-        rc = cplx ? condition_block<2>(ctx, a, r, (long)n_samples, &n_eff) : condition_block<1>(ctx, a, r, (long)n_samples, &n_eff);
+        if (w16)
+            rc = cplx ? condition_block<2, int16_t>(ctx, a, r, (long)n_samples, &n_eff) : condition_block<1, int16_t>(ctx, a, r, (long)n_samples, &n_eff);
+        else
+            rc = cplx ? condition_block<2, int8_t>(ctx, a, r, (long)n_samples, &n_eff) : condition_block<1, int8_t>(ctx, a, r, (long)n_samples, &n_eff);
         if (rc) return rc;
+        a.skind = cplx ? kF64C : kF64;
+    } else if (w16) {
+        // the float64 view of the block, on the device for the search and on the host for the sums and the refinement jobs
+        if ((rc = ensure(ctx, &a.d_sig64, &a.sig64_cap, nv + 8))) return rc;  // (+4 samples: k_corr reads whole groups of four, bds_acq_corr.h)
+        hipLaunchKernelGGL(k_widen16, dim3(2048), dim3(256), 0, st(ctx), (const int16_t *)a.d_sig, (long)nv, a.d_sig64);
+        BDS_HIP(ctx, hipGetLastError());
+        const int16_t *h16 = reinterpret_cast<const int16_t *>(samples);
+        a.h_re.resize(n_samples);
+        a.h_im.assign(cplx ? n_samples : 0, 0.0);
+        for (size_t i = 0; i < n_samples; ++i) {
+            a.h_re[i] = (double)h16[cplx ? 2 * i : i];
+            if (cplx) a.h_im[i] = (double)h16[2 * i + 1];
+        }
         a.skind = cplx ? kF64C : kF64;
     } else {
         a.skind = cplx ? kS8C : kS8;
@@ -763,7 +786,7 @@ static int acq_load_block(bds_ctx *ctx, const bds_settings *s_in, const int8_t *
                     n_eff, r.on ? " after resampling" : "", a.N);
     a.n_samples = n_eff;
     a.sigpower_X = 0;
-    if (r.on) {
+    if (a.skind >= kF64) {
         a.h_s8.clear(), a.h_cpre.clear(), a.h_cpre_q.clear();
         a.h_prefix.resize((size_t)n_eff + 1);
         a.h_prefix[0] = 0;
@@ -805,10 +828,26 @@ static int acq_load_block(bds_ctx *ctx, const bds_settings *s_in, const int8_t *
     return BDS_OK;
 }
 
+// the typed entries take the sample type of settings.dataType only
+static int check_entry_type(bds_ctx *ctx, const bds_settings &s, const char *who, bool w16) {
+    if (!w16 && s.dataType != 0)
+        return fail(ctx, BDS_ERR_UNSUPPORTED, "%s takes int8 samples: settings.dataType must be 'schar' (0); an 'int16' (1) block goes to %s16", who, who);
+    if (w16 && s.dataType != 1)
+        return fail(ctx, BDS_ERR_ARG, "%s16 takes int16 samples: settings.dataType must be 'int16' (1), not %d", who, (int)s.dataType);
+    return BDS_OK;
+}
+
 extern "C" int bds_acq_load(bds_ctx *ctx, const bds_settings *s_in, const int8_t *samples, size_t n_samples,
                             int is_complex) {
     if (!ctx || !s_in || !samples) return BDS_ERR_ARG;
+    if (int rc = check_entry_type(ctx, *s_in, "bds_acq_load", false)) return rc;
     return acq_load_block(ctx, s_in, samples, nullptr, n_samples, is_complex);
+}
+
+extern "C" int bds_acq_load16(bds_ctx *ctx, const bds_settings *s_in, const int16_t *samples, size_t n_samples, int is_complex) {
+    if (!ctx || !s_in || !samples) return BDS_ERR_ARG;
+    if (int rc = check_entry_type(ctx, *s_in, "bds_acq_load", true)) return rc;
+    return acq_load_block(ctx, s_in, reinterpret_cast<const int8_t *>(samples), nullptr, n_samples, is_complex, true);
 }
 
 extern "C" int bds_acq_load_dev(bds_ctx *ctx, const bds_settings *s_in, const void *d_samples, size_t n_samples, int is_complex) {
@@ -816,9 +855,12 @@ extern "C" int bds_acq_load_dev(bds_ctx *ctx, const bds_settings *s_in, const vo
     if (is_complex < 0 || is_complex > 2) return fail(ctx, BDS_ERR_ARG, "is_complex must be 0 (real), 1 (I/Q int8 pairs) or 2 (packed 2+2-bit I/Q)");
     if (!d_samples) return fail(ctx, BDS_ERR_ARG, "bds_acq_load_dev: d_samples is NULL");
     if (n_samples > ((size_t)1 << 62)) return fail(ctx, BDS_ERR_ARG, "bds_acq_load_dev: n_samples = %zu", n_samples);
-    const size_t bytes = is_complex == 2 ? (n_samples + 1) / 2 : is_complex == 1 ? 2 * n_samples : n_samples;
+    const bool w16 = s_in->dataType == 1;  // (any other value but 0 is refused by the settings check)
+    if (w16 && is_complex == 2)
+        return fail(ctx, BDS_ERR_ARG, "is_complex = 2 (packed 2+2-bit I/Q) has no 16-bit form: settings.dataType must be 'schar' (0)");
+    const size_t bytes = (is_complex == 2 ? (n_samples + 1) / 2 : is_complex == 1 ? 2 * n_samples : n_samples) * (w16 ? 2 : 1);
     if (int rc = check_device_span(ctx, "bds_acq_load_dev", "d_samples", d_samples, bytes)) return rc;
-    return acq_load_block(ctx, s_in, nullptr, d_samples, n_samples, is_complex);
+    return acq_load_block(ctx, s_in, nullptr, d_samples, n_samples, is_complex, w16);
 }
 
 // Does an N-point pair apply to a run with these settings, and which?  B1C with both components on N = 53 x 12 x 3125 samples
@@ -878,7 +920,7 @@ static PfaPick pfa_pick(const bds_ctx *ctx, const AcqState &a, const bds_setting
     } admitted[] = {{pfa::NP, 1}, {pfa32::NP, 2}};
     PfaPick pk;
     if (a.signal == BDS_SIGNAL_B2A) return pfa6_pick(ctx, a, s);
-    if (!ctx->tune.pfa || !a.half || a.no_fast_search || a.signal != BDS_SIGNAL_B1C || a.ncomp != 2 || a.rs.on) return pk;
+    if (!ctx->tune.pfa || !a.half || a.no_fast_search || a.signal != BDS_SIGNAL_B1C || a.ncomp != 2 || a.rs.on || a.skind >= kF64) return pk;
     int kind = 0;
     for (const auto &ad : admitted)
         if (a.N == ad.N) kind = ad.kind;
@@ -1643,6 +1685,8 @@ int acq_run_once(bds_ctx *ctx, const bds_settings *s_in, const int32_t *prn_list
     if (!a.d_sig || a.n_samples < a.N) return fail(ctx, BDS_ERR_ARG, "bds_acq_run: no IF block loaded (bds_acq_load)");
     if (a.rs.on != resample_plan(*s_in).on || (a.rs.on && a.rs.new_fs != s->samplingFreq))
         return fail(ctx, BDS_ERR_ARG, "bds_acq_run: the loaded block was conditioned for different resampling settings");
+    if (a.w16 != (s_in->dataType == 1))
+        return fail(ctx, BDS_ERR_ARG, "bds_acq_run: settings.dataType = %d, but the block was loaded as %s samples", (int)s_in->dataType, a.w16 ? "int16" : "int8");
     if ((rc = bds_acq_prepare(ctx, s))) return rc;
     AcqRun r(ctx, a, s);
     if (prn_list && n_prn > 0)
@@ -1760,6 +1804,15 @@ extern "C" int bds_acquire(bds_ctx *ctx, const bds_settings *s, const int8_t *sa
                            int is_complex, int max_prn, double *carrFreq, double *codePhase, double *peakMetric,
                            int32_t *detected) {
     int rc = bds_acq_load(ctx, s, samples, n_samples, is_complex);
+    if (rc) return rc;
+    if ((rc = bds_acq_prepare(ctx, s))) return rc;
+    return bds_acq_run(ctx, s, nullptr, 0, max_prn, carrFreq, codePhase, peakMetric, detected);
+}
+
+extern "C" int bds_acquire16(bds_ctx *ctx, const bds_settings *s, const int16_t *samples, size_t n_samples,
+                             int is_complex, int max_prn, double *carrFreq, double *codePhase, double *peakMetric,
+                             int32_t *detected) {
+    int rc = bds_acq_load16(ctx, s, samples, n_samples, is_complex);
     if (rc) return rc;
     if ((rc = bds_acq_prepare(ctx, s))) return rc;
     return bds_acq_run(ctx, s, nullptr, 0, max_prn, carrFreq, codePhase, peakMetric, detected);

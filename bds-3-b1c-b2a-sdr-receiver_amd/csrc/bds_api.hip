@@ -404,6 +404,17 @@ extern "C" int bds_acquire_track(bds_ctx *ctx, const bds_settings *s, const int8
     return bds_track(ctx, s, path, s->numberOfChannels, channel, out);
 }
 
+extern "C" int bds_acquire_track16(bds_ctx *ctx, const bds_settings *s, const int16_t *samples, size_t n_samples, int is_complex,
+                                   int max_prn, double *carrFreq, double *codePhase, double *peakMetric, int32_t *detected,
+                                   const char *path, bds_channel *channel, bds_track_out *out) {
+    if (!ctx || !s || !path || !channel || !out) return BDS_ERR_ARG;
+    if (int g = bds::track_session_guard(ctx, "bds_acquire_track16")) return g;
+    int rc = bds_acquire16(ctx, s, samples, n_samples, is_complex, max_prn, carrFreq, codePhase, peakMetric, detected);
+    if (rc) return rc;
+    if ((rc = bds_pre_run_device(ctx, s, max_prn, carrFreq, codePhase, peakMetric, channel))) return rc;
+    return bds_track(ctx, s, path, s->numberOfChannels, channel, out);
+}
+
 // preRun.m:61-76
 extern "C" int bds_pre_run(const bds_settings *s, int max_prn, const double *carrFreq, const double *codePhase,
                            const double *peakMetric, bds_channel *channel) {

@@ -265,6 +265,8 @@ extern "C" int bds_acquire_multi(bds_multi *m, int n_sig, const bds_acq_job *sig
         const bds_acq_job &g = sig[i];
         if (!g.settings || !g.samples || !g.carrFreq || !g.codePhase || !g.peakMetric || g.max_prn < 1 || g.max_prn > BDS_MAX_PRN)
             return mfail(m, BDS_ERR_ARG, "bds_acquire_multi: signal " + std::to_string(i) + " has a NULL field or max_prn out of 1..63");
+        if (g.settings->dataType != 0)  // (bds_acq_job::samples is int8: 16-bit blocks go to bds_acquire16, one device at a time)
+            return mfail(m, BDS_ERR_UNSUPPORTED, "bds_acquire_multi: signal " + std::to_string(i) + ": settings.dataType must be 'schar' (0), the jobs take int8 samples only");
         const double c = bds_acq_job_cost(g.settings);
         std::vector<int> seen;
         for (int k = 0; k < g.settings->n_acq; ++k) {

@@ -91,9 +91,9 @@ inline std::vector<double> fir1_bandpass(int n_taps, double wp1, double wp2) {
 
 // ---- kernels ----------------------------------------------------------------------------------
 // xt = [2*x(1)-x(nfact+1:-1:2); x; 2*x(end)-x(end-1:-1:end-nfact)]  (filtfilt's edge extension);
-// NCH = 1 real, 2 interleaved complex; the int8 record is widened to f64 here.
-template <int NCH>
-__global__ __launch_bounds__(256) void k_ff_extend(const int8_t *__restrict__ x, long n, int nfact,
+// NCH = 1 real, 2 interleaved complex; the int8 (T = int16_t: int16) record is widened to f64 here.
+template <int NCH, class T>
+__global__ __launch_bounds__(256) void k_ff_extend(const T *__restrict__ x, long n, int nfact,
                                                    double *__restrict__ e) {
     const long tot = n + 2L * nfact;
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < tot; i += (long)gridDim.x * blockDim.x) {
@@ -109,6 +109,11 @@ __global__ __launch_bounds__(256) void k_ff_extend(const int8_t *__restrict__ x,
             e[i * NCH + c] = v;
         }
     }
+}
+
+// A 16-bit block (settings.dataType 1) as the float64 block the search reads (SampleKind kF64 / kF64C): exact, value by value.
+__global__ __launch_bounds__(256) void k_widen16(const int16_t *__restrict__ x, long n, double *__restrict__ out) {
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) out[i] = (double)x[i];
 }
 
 // One direction of filtfilt: y = filter(b, 1, u, zi*u(1)) with the steady-state initial condition,

@@ -69,7 +69,7 @@ struct TrkParams {
     int mode;        // BDS_TRACK_*
     int pilot;       // pilot correlators on
     int cplx;        // sample format (kFmt*): fileType 2, the record is interleaved I/Q int8 pairs (tracking.m:132-136,242-246);
-                     // fileType 3, two 2+2-bit I/Q samples per byte (unpack_cplx.m:18-30)
+                     // fileType 3, two 2+2-bit I/Q samples per byte (unpack_cplx.m:18-30); dataType 1, int16 samples or pairs
     int chunk;       // samples per correlate workgroup
     int runs;        // 1: run-based correlator (correlate_runs), chunk = kTrkThreads * 8 or * 16
     int prec;        // numerics of the run-based correlator's carrier wipe-off and prefix sums (Tuning::trk_prec)
@@ -86,10 +86,17 @@ struct TrkParams {
 
 // Sample formats of the IF record.  Packed (the input of B2a/include/unpack_cplx.m:18-30): complex sample n is nibble n & 1 of
 // byte n >> 1, low nibble first; per nibble bit 0 / 1 = I / Q negative, bit 2 / 3 = |I| / |Q| is 3 (else 1).
-enum : int { kFmtReal = 0, kFmtIQ = 1, kFmtPacked = 2 };
+// 16-bit records (settings.dataType 1): little-endian int16 samples (fileType 1) or interleaved I, Q int16 pairs (fileType 2).
+enum : int { kFmtReal = 0, kFmtIQ = 1, kFmtPacked = 2, kFmtReal16 = 3, kFmtIQ16 = 4 };
 __host__ __device__ constexpr int fmt_align(int fmt) { return fmt == kFmtPacked ? 32 : 16; }  // samples: 16 bytes at least
+// bytes of one sample of an unpacked format
+__host__ __device__ constexpr int fmt_bps(int fmt) { return fmt == kFmtIQ16 ? 4 : fmt == kFmtIQ || fmt == kFmtReal16 ? 2 : 1; }
+__host__ __device__ constexpr bool fmt_complex(int fmt) { return fmt == kFmtIQ || fmt == kFmtPacked || fmt == kFmtIQ16; }
+__host__ __device__ constexpr bool fmt_16bit(int fmt) { return fmt == kFmtReal16 || fmt == kFmtIQ16; }
 // bytes of n samples (packed: n even -- window and span bounds are kept even, the file itself holds whole bytes)
-__host__ __device__ constexpr long long fmt_bytes(int fmt, long long n) { return fmt == kFmtPacked ? n / 2 : fmt == kFmtIQ ? n * 2 : n; }
+__host__ __device__ constexpr long long fmt_bytes(int fmt, long long n) { return fmt == kFmtPacked ? n / 2 : n * fmt_bps(fmt); }
+// samples in n bytes (whole ones: a trailing part of a sample or pair does not count)
+__host__ __device__ constexpr long long fmt_samples(int fmt, long long n) { return fmt == kFmtPacked ? n * 2 : n / fmt_bps(fmt); }
 // one packed byte -> the int8 quadruple (I1, Q1, I2, Q2) unpack_cplx writes for it, without a branch: magnitudes 1 | 2 bit,
 // then two's complement in every byte whose sign bit is set ((m ^ 0xff) + 1 never carries out of a byte for m = 1, 3)
 __device__ __forceinline__ uint32_t iq_of_packed(uint32_t b) {
@@ -204,7 +211,7 @@ __device__ __forceinline__ void correlate_slice(const int8_t *__restrict__ data,
     }
     int it = 0;
     // data[] starts at sample p.base of the record (packed: p.base is even)
-    const int8_t *__restrict__ dwin = p.cplx == kFmtPacked ? data - (p.base >> 1) : data - (p.base * (p.cplx ? 2 : 1));
+    const int8_t *__restrict__ dwin = p.cplx == kFmtPacked ? data - (p.base >> 1) : data - (p.base * fmt_bps(p.cplx));
     // chunk k0 .. k0+chunk of the block, then (only when blksize outgrew the grid the call was sized for:
     // a code rate more than 2 % below the slowest channel's initial one) every k_stride-th chunk after it
     for (long k0 = k0_first; k0 < g.blk; k0 += k_stride) {
@@ -217,6 +224,12 @@ __device__ __forceinline__ void correlate_slice(const int8_t *__restrict__ data,
             const uint32_t v = iq_of_packed(((uint32_t)(uint8_t)dwin[n >> 1] >> (4 * (int)(n & 1))) & 15u);
             raw = (float)(int8_t)(v & 0xffu);
             raw_q = (float)(int8_t)(v >> 8);
+        } else if (p.cplx == kFmtReal16) {  // fread(fid, blksize, 'int16')
+            raw = (float)reinterpret_cast<const short *>(dwin)[g.pos + k];
+        } else if (p.cplx == kFmtIQ16) {
+            const short2 v = reinterpret_cast<const short2 *>(dwin)[g.pos + k];
+            raw = (float)v.x;
+            raw_q = (float)v.y;
         } else if (p.cplx) {  // rawSignal = data(1:2:end) + 1i*data(2:2:end)  (tracking.m:242-246)
             const char2 v = reinterpret_cast<const char2 *>(dwin)[g.pos + k];
             raw = (float)v.x;
@@ -400,10 +413,13 @@ __device__ __forceinline__ void correlate_runs(const int8_t *__restrict__ data, 
     epoch_colons<(MODE != BDS_TRACK_B2A)>(g.rem, g.step, p.spacing, g.blk, cv3);
     const double two_pi = 6.283185307179586476925286766559;
     const double cyc0 = g.remCarr / two_pi;
-    constexpr bool CPLX = FMT != kFmtReal;
-    constexpr int coeff = CPLX ? 2 : 1;
-    constexpr int nwd = CPLX ? 2 * NWD : NWD;  // dwords of a segment
+    constexpr bool CPLX = fmt_complex(FMT);
+    constexpr bool W16 = fmt_16bit(FMT);  // int16 samples: two per dword, an I/Q pair is one dword
+    constexpr int coeff = FMT == kFmtPacked ? 2 : fmt_bps(FMT);  // bytes of a sample (packed: of the pair it decodes to)
+    constexpr int nwd = NWD * coeff;  // dwords of a segment
     constexpr int nrd = FMT == kFmtPacked ? SEG / 8 : nwd;  // ... as the record holds it (packed: SEG / 2 bytes)
+    // dwords fetched: one more than the segment's, for the funnel shift -- except int16 pairs, which start on a dword
+    constexpr int nfd = FMT == kFmtIQ16 ? nrd : nrd + 1;
     const int8_t *__restrict__ dwin = FMT == kFmtPacked ? data - (p.base >> 1) : data - p.base * coeff;  // (packed: p.base is even)
     // address of the byte that holds sample pos + kb
     auto seg_addr = [&](long kb) {
@@ -434,7 +450,7 @@ __device__ __forceinline__ void correlate_runs(const int8_t *__restrict__ data, 
             const uintptr_t a = seg_addr(kb);
             const uint32_t *__restrict__ q = reinterpret_cast<const uint32_t *>(a & ~(uintptr_t)3);
 #pragma unroll
-            for (int i = 0; i <= nrd; ++i) raw[i] = q[i];
+            for (int i = 0; i < nfd; ++i) raw[i] = q[i];
         }
     };
     const long kw_first = k0_first + (long)wave * WCH;
@@ -490,7 +506,11 @@ __device__ __forceinline__ void correlate_runs(const int8_t *__restrict__ data, 
 #pragma unroll
                     for (int b = 0; b < 4; ++b) wr[4 * i + b] = iq_of_packed((w >> (8 * b)) & 0xffu);
                 }
-            } else {
+            } else if constexpr (FMT == kFmtIQ16) {
+                BDS_DASSERT((seg_addr(kb) & 3) == 0);  // (buffers are dword-aligned, a pair is 4 bytes)
+#pragma unroll
+                for (int i = 0; i < nwd; ++i) wr[i] = raw[i];
+            } else {  // (int16 samples: byte offset 0 or 2)
                 const uint32_t sh = (uint32_t)(seg_addr(kb) & 3);
 #pragma unroll
                 for (int i = 0; i < nwd; ++i) wr[i] = __builtin_amdgcn_alignbyte(raw[i + 1], raw[i], sh);
@@ -508,7 +528,13 @@ __device__ __forceinline__ void correlate_runs(const int8_t *__restrict__ data, 
             // (PREC 0, 1) or f64 (PREC 2); PREC 3: sin / cos of the reference's own trigarg(k)
             auto wiped = [&](int j, CT &ib, CT &qb) {
                 CT rw, rw_q = 0;
-                if (CPLX) {  // rawSignal = data(1:2:end) + 1i*data(2:2:end)  (tracking.m:242-246)
+                if constexpr (FMT == kFmtIQ16) {  // one dword: I in the low half, Q in the high half
+                    const uint32_t w = wr[j];
+                    rw = (CT)(int)(int16_t)w;
+                    rw_q = (CT)(int)(int16_t)(w >> 16);
+                } else if constexpr (W16) {
+                    rw = (CT)(int)(int16_t)(wr[j >> 1] >> ((j & 1) * 16));
+                } else if (CPLX) {  // rawSignal = data(1:2:end) + 1i*data(2:2:end)  (tracking.m:242-246)
                     const uint32_t w = wr[j >> 1];
                     rw = (CT)(int)(int8_t)(w >> ((j & 1) * 16));
                     rw_q = (CT)(int)(int8_t)(w >> ((j & 1) * 16 + 8));
@@ -841,7 +867,13 @@ __global__ __launch_bounds__(kTrkThreads) void k_trk_correlate_open(const int8_t
         };                                                                                                  \
         auto go = [&](auto mode_c, auto prec_c) {                                                           \
             constexpr int M = decltype(mode_c)::value, PR = decltype(prec_c)::value;                        \
-            if (p.runs == 16 && p.cplx == kFmtReal) fire(KERN<M, 16, kFmtReal, PR>);                        \
+            /* 16-bit records: the default numerics only (fill_params refuses the rest) */                  \
+            if (fmt_16bit(p.cplx) && p.runs) {                                                              \
+                if (p.runs == 16 && p.cplx == kFmtReal16) fire(KERN<M, 16, kFmtReal16, 4>);                 \
+                else if (p.runs == 16) fire(KERN<M, 16, kFmtIQ16, 4>);                                      \
+                else if (p.cplx == kFmtReal16) fire(KERN<M, 8, kFmtReal16, 4>);                             \
+                else fire(KERN<M, 8, kFmtIQ16, 4>);                                                         \
+            } else if (p.runs == 16 && p.cplx == kFmtReal) fire(KERN<M, 16, kFmtReal, PR>);                 \
             else if (p.runs == 16 && p.cplx == kFmtIQ) fire(KERN<M, 16, kFmtIQ, PR>);                       \
             else if (p.runs == 16) fire(KERN<M, 16, kFmtPacked, PR>);                                       \
             else if (p.runs == 8 && p.cplx == kFmtReal) fire(KERN<M, 8, kFmtReal, PR>);                     \
@@ -1158,8 +1190,10 @@ static int fill_params(bds_ctx *ctx, const bds_settings &s, TrkParams &p, int n_
     if (s.signal != BDS_SIGNAL_B1C && s.signal != BDS_SIGNAL_B2A) return fail(ctx, BDS_ERR_ARG, "settings.signal invalid");
     if (s.fileType != 1 && s.fileType != 2 && s.fileType != 3)
         return fail(ctx, BDS_ERR_ARG, "settings.fileType must be 1 (real), 2 (I/Q) or 3 (packed 2+2-bit I/Q)");
-    if (s.dataType != 0)  // fread(fid, ..., settings.dataType), tracking.m:237-238
-        return fail(ctx, BDS_ERR_UNSUPPORTED, "settings.dataType: only 'schar' (int8 samples) is supported");
+    if (s.dataType != 0 && s.dataType != 1)  // fread(fid, ..., settings.dataType), tracking.m:237-238
+        return fail(ctx, BDS_ERR_UNSUPPORTED, "settings.dataType: only 'schar' (0: int8 samples) and 'int16' (1) are supported");
+    if (s.dataType == 1 && s.fileType == 3)
+        return fail(ctx, BDS_ERR_ARG, "settings.fileType 3 (packed 2+2-bit I/Q) has no 16-bit form: settings.dataType must be 'schar' (0)");
     if (s.codeLength != 10230 || !(s.samplingFreq > 0) || !(s.intTime > 0))
         return fail(ctx, BDS_ERR_ARG, "settings.codeLength/samplingFreq/intTime invalid");
     p.mode = track_mode(s);
@@ -1173,7 +1207,7 @@ static int fill_params(bds_ctx *ctx, const bds_settings &s, TrkParams &p, int n_
     bds_calc_loop_coef_carr(&s, &p.pf3, &p.pf2, &p.pf1);                                 // :116
     p.pdi = s.intTime;                                                                   // :107
     p.factor = p.mode == BDS_TRACK_WB ? bds_calc_weighing_factor(&s) : 0.0;              // WB_tracking.m:138
-    p.cplx = s.fileType == 3 ? kFmtPacked : s.fileType == 2 ? kFmtIQ : kFmtReal;
+    p.cplx = s.fileType == 3 ? kFmtPacked : s.dataType == 1 ? (s.fileType == 2 ? kFmtIQ16 : kFmtReal16) : s.fileType == 2 ? kFmtIQ : kFmtReal;
     if (ctx->tune.trk_persample) {  // per-sample correlator (the round-1 kernel; A/B and cross-check)
         p.chunk = s.signal == BDS_SIGNAL_B2A ? 2048 : 8192;
         if (ctx->tune.trk_chunk > 0) p.chunk = std::max(256, ctx->tune.trk_chunk);
@@ -1186,8 +1220,17 @@ static int fill_params(bds_ctx *ctx, const bds_settings &s, TrkParams &p, int n_
         p.prec = std::max(0, std::min(5, ctx->tune.trk_prec));
         if (ctx->tune.trk_seg == 8 || ctx->tune.trk_seg == 16) p.runs = ctx->tune.trk_seg, p.chunk = kTrkThreads * p.runs;
     }
+    if (fmt_16bit(p.cplx)) {
+        // the run-based correlator is built for 16-bit records in the default numerics only (the per-sample one decodes at run time)
+        if (p.runs && p.prec != 4)
+            return fail(ctx, BDS_ERR_UNSUPPORTED, "BDS_TRK_PREC=%d with settings.dataType 'int16': the tracking kernels for 16-bit records are "
+                        "built for the default numerics (BDS_TRK_PREC=4) only", p.prec);
+        if (n_bytes % (size_t)fmt_bps(p.cplx))
+            return fail(ctx, BDS_ERR_ARG, "settings.dataType 'int16': the record's %zu bytes are not a whole number of %s", n_bytes,
+                        p.cplx == kFmtIQ16 ? "I/Q int16 pairs (4 bytes each)" : "int16 samples (2 bytes each)");
+    }
     // whole samples an fread can deliver
-    p.n_bytes = p.cplx == kFmtPacked ? (long long)n_bytes * 2 : (long long)(n_bytes / (p.cplx ? 2 : 1));
+    p.n_bytes = fmt_samples(p.cplx, (long long)n_bytes);
     return BDS_OK;
 }
 
@@ -1823,7 +1866,7 @@ static int do_track(bds_ctx *ctx, const bds_settings *s, const RecordLoader &loa
                             "one block, in each of the two span buffers, needs at least %zu bytes%s", limit, min_limit,
                             packed ? " of the packed record" : "");
             }
-            span_n = (packed ? (long long)(limit / 2) * 2 : (long long)(limit / (size_t)(2 * (fmt == kFmtIQ ? 2 : 1)))) & ~(al - 1);
+            span_n = fmt_samples(fmt, (long long)(limit / 2)) & ~(al - 1);
             const size_t cap = (size_t)nb_of(span_n);
             if (t.span_cap != cap || !t.d_span[0] || !t.d_span[1]) {
                 for (int8_t *&q : t.d_span)
@@ -2122,7 +2165,7 @@ static bds_track_session *session_open(bds_ctx *ctx, const bds_settings *s, int 
             return fail(ctx, BDS_ERR_ARG, "resident limit of %zu bytes is too small for these channels: the spread of their positions plus "
                         "one block, in each of the two span buffers, needs at least %zu bytes%s", limit, min_limit,
                         fmt == kFmtPacked ? " of the packed record" : "");
-        long long span_n = (fmt == kFmtPacked ? (long long)(limit / 2) * 2 : (long long)(limit / (size_t)(2 * (fmt == kFmtIQ ? 2 : 1)))) & ~(al - 1);
+        long long span_n = fmt_samples(fmt, (long long)(limit / 2)) & ~(al - 1);
         if (kind != 2)  // no more than the record from the first channel on
             span_n = std::min(span_n, std::max(min_half, (std::max(0LL, p.n_bytes - base0) + al - 1) & ~(al - 1)));
         const size_t cap = (size_t)fmt_bytes(fmt, span_n);
@@ -2237,6 +2280,12 @@ static int track_feed(bds_track_session *sess, const int8_t *bytes, size_t n_byt
     if (n_bytes && !bytes) return fail(ctx, BDS_ERR_ARG, "%s: %s missing (NULL with %zu bytes to go)", who, dev ? "d_bytes" : "bytes", n_bytes);
     TrkParams &p = h->u.p;
     if (p.cplx == kFmtIQ && (n_bytes & 1)) return fail(ctx, BDS_ERR_ARG, "%s: an I/Q record takes whole int8 pairs, %zu bytes is an odd count", who, n_bytes);
+    // a 16-bit record: a call takes whole samples (or pairs) and leaves the rest of what it was offered to the caller; the END
+    // of the record cannot lie inside one
+    const size_t unit = fmt_16bit(p.cplx) ? (size_t)fmt_bps(p.cplx) : p.cplx == kFmtIQ ? 2 : 1;
+    if (fmt_16bit(p.cplx) && last && n_bytes % unit)
+        return fail(ctx, BDS_ERR_ARG, "%s: settings.dataType 'int16': the last %zu bytes of the record are not a whole number of %s", who, n_bytes,
+                    p.cplx == kFmtIQ16 ? "I/Q int16 pairs (4 bytes each)" : "int16 samples (2 bytes each)");
     if (dev)
         if (int rc = check_device_span(ctx, who, "d_bytes", bytes, n_bytes)) return rc;
     BDS_HIP(ctx, hipSetDevice(ctx->device));
@@ -2256,11 +2305,11 @@ static int track_feed(bds_track_session *sess, const int8_t *bytes, size_t n_byt
             if (rc) return rc;
         }
     }
-    const size_t take = std::min(offered, room()) & ~(size_t)(p.cplx == kFmtIQ ? 1 : 0);
+    const size_t take = std::min(offered, room()) & ~(unit - 1);
     if (take) {
         BDS_HIP(ctx, hipMemcpyAsync(ss.cur.buf + ss.nb_of(ss.cur.end - ss.cur.base), bytes, take, dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st(ctx)));
         BDS_HIP(ctx, hipStreamSynchronize(st(ctx)));  // the bytes are the caller's again on return
-        ss.cur.end += p.cplx == kFmtPacked ? (long long)take * 2 : p.cplx == kFmtIQ ? (long long)take / 2 : (long long)take;
+        ss.cur.end += fmt_samples(p.cplx, (long long)take);
         t.loaded_bytes += take, t.pieces += 1;
         t.resident_max = std::max(t.resident_max, (size_t)ss.nb_of(ss.cur.end - ss.cur.base));
     }

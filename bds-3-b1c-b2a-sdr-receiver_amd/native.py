@@ -102,6 +102,7 @@ UPDATE_STATE = ["codeFreq", "remCodePhase", "carrFreq", "carrFreqBasis", "remCar
 EXPORTS = [
     "bds_create", "bds_destroy", "bds_reload_tuning", "bds_last_error", "bds_device_name", "bds_abi_check", "bds_build_flags", "bds_gen_code", "bds_acquire",
     "bds_acq_load", "bds_acq_prepare", "bds_acq_run", "bds_acq_set_pair_budget_gb", "bds_acq_set_b2a_npoint", "bds_resample_plan", "bds_fir1_bandpass", "bds_frame_sync", "bds_sync_pattern", "bds_unpack_cplx", "bds_unpack_cplx_file", "bds_acq_grid", "bds_acq_peaks", "bds_acq_candidates", "bds_acq_coherent_sums", "bds_get_timing",
+    "bds_acquire16", "bds_acq_load16", "bds_acquire_track16",
     "bds_track", "bds_track_mem", "bds_track_loaded_bytes", "bds_track_set_resident_limit", "bds_track_stream_info", "bds_track_correlate", "bds_track_colon", "bds_track_cno", "bds_track_update",
     "bds_track_open", "bds_track_open_mem", "bds_track_open_feed", "bds_track_feed", "bds_track_advance", "bds_track_session_info", "bds_track_close",
     "bds_calc_loop_coef", "bds_calc_loop_coef_carr",
@@ -160,6 +161,12 @@ def lib():
     L.bds_acquire.restype = i32
     L.bds_acquire.argtypes = [vp, SP, i8p, sz, i32, i32, _DP, _DP, _DP, _IP]
     L.bds_acq_load.restype, L.bds_acq_load.argtypes = i32, [vp, SP, i8p, sz, i32]
+    if hasattr(L, "bds_acquire16"):  # (a build of an older commit, loaded through BDS_LIB_PATH for an A/B run, takes int8 blocks only)
+        i16p = C.POINTER(C.c_int16)
+        L.bds_acquire16.restype, L.bds_acquire16.argtypes = i32, [vp, SP, i16p, sz, i32, i32, _DP, _DP, _DP, _IP]
+        L.bds_acq_load16.restype, L.bds_acq_load16.argtypes = i32, [vp, SP, i16p, sz, i32]
+        L.bds_acquire_track16.restype = i32
+        L.bds_acquire_track16.argtypes = [vp, SP, i16p, sz, i32, i32, _DP, _DP, _DP, _IP, C.c_char_p, C.POINTER(Channel), C.POINTER(TrackOut)]
     L.bds_acq_prepare.restype, L.bds_acq_prepare.argtypes = i32, [vp, SP]
     L.bds_acq_run.restype = i32
     L.bds_acq_run.argtypes = [vp, SP, _IP, i32, i32, _DP, _DP, _DP, _IP]
@@ -251,8 +258,9 @@ def pack_settings(s) -> Settings:
             raise AttributeError(f"settings.{name} is missing")
         return getattr(s, name)
 
-    # the library rejects anything but int8 samples (BDS_ERR_UNSUPPORTED names the field)
-    cs.dataType = 0 if str(need("dataType")) in ("schar", "int8") else 1
+    # 'schar' / 'int8' -> 0, 'int16' / 'short' -> 1; every other type ('float32', ...) -> a value the library refuses
+    # (BDS_ERR_UNSUPPORTED names the field), so that such a file is never read as int16
+    cs.dataType = data_type_code(need("dataType"))
     cs.fileType = int(need("fileType"))
     cs.samplingFreq = float(need("samplingFreq"))
     cs.IF = float(need("IF"))
@@ -291,6 +299,66 @@ def pack_settings(s) -> Settings:
     cs.pllNoiseBandwidth = float(need("pllNoiseBandwidth"))
     cs.CNoInterval = int(need("CNoInterval"))
     return cs
+
+
+DATA_TYPES = {"schar": 0, "int8": 0, "int16": 1, "short": 1}  # settings.dataType -> bds_settings.dataType
+DATA_TYPE_REFUSED = 2  # what every other fread type maps to
+
+
+def data_type_code(name) -> int:
+    """bds_settings.dataType of a settings.dataType string."""
+    return DATA_TYPES.get(str(name), DATA_TYPE_REFUSED)
+
+
+def record_is_int16(settings, dtype_name, what="the record") -> bool:
+    """The routing rule of every array that carries samples or raw record bytes: an int16 array goes with settings.dataType
+    'int16' / 'short', an int8 array (uint8: raw bytes of a packed record) with 'schar' / 'int8'.  A disagreement raises BdsError
+    naming dataType, before any copy or native call; arrays of other dtypes carry VALUES and are converted by the caller.
+    Returns True when the settings say 16 bits.  dtype_name: NumPy's name of the array's dtype."""
+    name = str(getattr(settings, "dataType", "schar"))
+    code = data_type_code(name)
+    if dtype_name == "int16" and code != 1:
+        raise BdsError(-1, f"settings.dataType is {name!r} but {what} is an int16 array: int16 samples go with dataType 'int16'")
+    if dtype_name in ("int8", "uint8") and code == 1:
+        raise BdsError(-1, f"settings.dataType is {name!r} but {what} is an {dtype_name} array: a 16-bit record is passed as an int16 array "
+                           "(little-endian samples; I, Q pairs for fileType 2)")
+    return code == 1
+
+
+def _i16(a, what="the record"):
+    """Values as a contiguous little-endian int16 row (an int16 array as it is: no copy when contiguous)."""
+    a = np.asarray(a)
+    if a.dtype != np.dtype("<i2"):
+        if a.dtype.kind not in "iuf":
+            raise ValueError(f"{what} must hold int16 values, not {a.dtype}")
+        r = np.rint(a)
+        if not np.array_equal(r, a) or (r.size and (r.min() < -32768 or r.max() > 32767)):
+            raise ValueError(f"{what} must hold int16 values (fread(..., 'int16'))")
+        a = r.astype("<i2")
+    return np.ascontiguousarray(a).reshape(-1)
+
+
+def record_bytes(settings, data, what="the record"):
+    """(int8 view of the record's raw bytes, 16-bit?) of a host array under the routing rule (record_is_int16)."""
+    a = np.asarray(data)
+    if record_is_int16(settings, a.dtype.name, what):
+        return _i16(a, what).view(np.int8), True
+    return _i8(a)[0].reshape(-1), False
+
+
+def device_dtype_name(x) -> str:
+    """NumPy's dtype name of a device array (a torch tensor, or an object with __cuda_array_interface__)."""
+    if hasattr(x, "__cuda_array_interface__") and not (type(x).__module__.split(".")[0] == "torch"):
+        return np.dtype(x.__cuda_array_interface__["typestr"]).name
+    return str(x.dtype).split(".")[-1]
+
+
+def device_record(settings, x, ctx_device, what="the record"):
+    """device_span of a device array that carries a record or a block, under the routing rule: int16 with settings.dataType
+    'int16', int8 / uint8 otherwise.  Returns (pointer, n_bytes, keepalive, 16-bit?)."""
+    w16 = record_is_int16(settings, device_dtype_name(x), what)
+    ptr, n_bytes, keep = device_span(x, ctx_device, dtypes=("int16",) if w16 else ("int8", "uint8"))
+    return ptr, n_bytes, keep, w16
 
 
 def _i8(a):
@@ -373,7 +441,7 @@ def check_feed_span(sess, n_bytes) -> None:
     """check_feed_bytes for bytes in device memory: the same argument errors, before any native call."""
     if not sess.get("feed"):
         raise ValueError("feed on a session that reads its record itself (it was opened on a file or an array, not with origin=)")
-    if sess["fileType"] == 2 and n_bytes % 2:
+    if sess["fileType"] == 2 and n_bytes % 2 and not sess.get("w16"):
         raise ValueError(f"an I/Q record is fed in whole int8 pairs: {n_bytes} bytes is an odd count")
 
 
@@ -420,6 +488,14 @@ def check_feed_bytes(sess, data) -> np.ndarray:
     if not sess.get("feed"):
         raise ValueError("feed on a session that reads its record itself (it was opened on a file or an array, not with origin=)")
     a = np.asarray(data)
+    if sess.get("w16"):  # a 16-bit record: int16 samples, or raw bytes (uint8) in pieces of any size -- a call takes whole samples
+        if a.dtype == np.uint8:
+            return np.ascontiguousarray(a).reshape(-1).view(np.int8)
+        if a.dtype == np.int8:
+            raise BdsError(-1, "settings.dataType is 'int16' but the bytes fed are an int8 array: feed int16 samples, or raw bytes as uint8")
+        return _i16(a, "the samples fed").view(np.int8)
+    if a.dtype == np.int16:
+        raise BdsError(-1, "settings.dataType is 'schar' but the samples fed are an int16 array: int16 samples go with dataType 'int16'")
     if a.dtype == np.uint8:
         a = a.view(np.int8)
     a = np.ascontiguousarray(a, dtype=np.int8).reshape(-1)
@@ -539,6 +615,7 @@ class MultiContext:
         keep, outs = [], []
         for i, (settings, samples, is_complex) in enumerate(jobs):
             cs = pack_settings(settings)
+            record_is_int16(settings, np.asarray(samples).dtype.name, f"the block of signal {i}")  # (16-bit settings: refused by the library)
             a, p = _i8(samples)
             max_prn = max(int(q) for q in np.atleast_1d(settings.acqSatelliteList))
             carr, cph, pm = np.zeros(max_prn), np.zeros(max_prn), np.zeros(max_prn)
@@ -612,15 +689,20 @@ class Context:
         if is_device_array(samples):
             return self.acq_load_dev(settings, samples, is_complex, n_samples)
         cs = pack_settings(settings)
+        if record_is_int16(settings, np.asarray(samples).dtype.name, "the block"):  # int16 values: bds_acq_load16
+            a = _i16(samples, "the block")
+            n = n_samples_of(a.size, is_complex, n_samples)
+            self._check(self._lib.bds_acq_load16(self._h, C.byref(cs), a.ctypes.data_as(C.POINTER(C.c_int16)), n, sample_format(is_complex)))
+            return
         a, p = _i8(samples)
         n = n_samples_of(a.size, is_complex, n_samples)
         self._check(self._lib.bds_acq_load(self._h, C.byref(cs), p, n, sample_format(is_complex)))
 
     def acq_load_dev(self, settings, samples, is_complex=False, n_samples=None):
-        """bds_acq_load_dev: acq_load of a block in device memory (int8, uint8 for packed bytes)."""
+        """bds_acq_load_dev: acq_load of a block in device memory (int8, uint8 for packed bytes; int16 with settings.dataType 'int16')."""
         cs = pack_settings(settings)
-        ptr, n_bytes, keep = device_span(samples, self.device)
-        n = n_samples_of(n_bytes, is_complex, n_samples)
+        ptr, n_bytes, keep, w16 = device_record(settings, samples, self.device, "the block")
+        n = n_samples_of(n_bytes // 2 if w16 else n_bytes, is_complex, n_samples)
         self._check(self._lib.bds_acq_load_dev(self._h, C.byref(cs), ptr, n, sample_format(is_complex)))
 
     def acq_prepare(self, settings):
@@ -659,16 +741,22 @@ class Context:
 
     def acquire(self, settings, samples, is_complex=False, n_samples=None):
         cs = pack_settings(settings)
-        a, p = _i8(samples)
+        w16 = record_is_int16(settings, np.asarray(samples).dtype.name, "the block")
+        if w16:  # bds_acquire16
+            a = _i16(samples, "the block")
+            p = a.ctypes.data_as(C.POINTER(C.c_int16))
+        else:
+            a, p = _i8(samples)
         n = n_samples_of(a.size, is_complex, n_samples)
+        entry = self._lib.bds_acquire16 if w16 else self._lib.bds_acquire
         max_prn = max(int(q) for q in np.atleast_1d(settings.acqSatelliteList))
         carr = np.zeros(max_prn)
         cph = np.zeros(max_prn)
         pm = np.zeros(max_prn)
         det = np.zeros(max_prn, dtype=np.int32)
-        self._check(self._lib.bds_acquire(self._h, C.byref(cs), p, n, sample_format(is_complex), max_prn,
-                                          carr.ctypes.data_as(_DP), cph.ctypes.data_as(_DP),
-                                          pm.ctypes.data_as(_DP), det.ctypes.data_as(_IP)))
+        self._check(entry(self._h, C.byref(cs), p, n, sample_format(is_complex), max_prn,
+                          carr.ctypes.data_as(_DP), cph.ctypes.data_as(_DP),
+                          pm.ctypes.data_as(_DP), det.ctypes.data_as(_IP)))
         return carr, cph, pm, det
 
     # -- synthetic IF records (bds_synth*) -----------------------------------------------
@@ -782,8 +870,8 @@ class Context:
 
     # -- tracking --------------------------------------------------------------------
     def track(self, settings, source, channels, n_epochs, n_cno, fields):
-        """source: file path (str/bytes), int8 array of raw file bytes (uint8 for a packed fileType-3 record), or those bytes as
-        a device array (bds_track_dev).
+        """source: file path (str/bytes), int8 array of raw file bytes (uint8 for a packed fileType-3 record; an int16 array of
+        samples with settings.dataType 'int16'), or those bytes as a device array (bds_track_dev).
         Returns dict field -> array [n_ch, n_epochs] (C/N0 fields [n_ch, n_cno])."""
         cs = pack_settings(settings)
         nch = len(channels)
@@ -809,11 +897,11 @@ class Context:
             path = os.fsencode(source)
             self._check(self._lib.bds_track(self._h, C.byref(cs), path, nch, carr, C.byref(out)))
         elif is_device_array(source):
-            ptr, n_bytes, keep = device_span(source, self.device)
+            ptr, n_bytes, keep, _ = device_record(settings, source, self.device)
             self._check(self._lib.bds_track_dev(self._h, C.byref(cs), ptr, n_bytes, nch, carr, C.byref(out)))
         else:
-            a, p = _i8(source)
-            self._check(self._lib.bds_track_mem(self._h, C.byref(cs), p, a.size, nch, carr, C.byref(out)))
+            a, _ = record_bytes(settings, source)
+            self._check(self._lib.bds_track_mem(self._h, C.byref(cs), a.ctypes.data_as(C.POINTER(C.c_int8)), a.size, nch, carr, C.byref(out)))
         arrays["completed"] = completed
         arrays["status"] = status
         return arrays
@@ -833,7 +921,8 @@ class Context:
     def _session(self, h, settings, channels, keep=None):
         if not h:
             raise BdsError(-1, self._lib.bds_last_error(self._h).decode())
-        return {"handle": h, "n_ch": len(channels), "fileType": int(settings.fileType), "keep": keep, "feed": False}
+        return {"handle": h, "n_ch": len(channels), "fileType": int(settings.fileType), "keep": keep, "feed": False,
+                "w16": data_type_code(getattr(settings, "dataType", "schar")) == 1}
 
     def track_open(self, settings, path_or_bytes, channel):
         """bds_track_open (a path) / bds_track_open_mem (int8 array of raw file bytes, uint8 for a packed fileType-3 record;
@@ -845,26 +934,32 @@ class Context:
         if isinstance(path_or_bytes, (str, bytes, os.PathLike)):
             h = self._lib.bds_track_open(self._h, C.byref(cs), os.fsencode(path_or_bytes), len(channel), carr)
             return self._session(h, settings, channel)
-        a, p = _i8(path_or_bytes)
-        h = self._lib.bds_track_open_mem(self._h, C.byref(cs), p, a.size, len(channel), carr)
+        a, _ = record_bytes(settings, path_or_bytes)
+        h = self._lib.bds_track_open_mem(self._h, C.byref(cs), a.ctypes.data_as(C.POINTER(C.c_int8)), a.size, len(channel), carr)
         return self._session(h, settings, channel, keep=a)
 
     def track_dev(self, settings, source, channels, n_epochs, n_cno, fields):
         """bds_track_dev: track() on the raw file bytes in device memory."""
-        device_span(source, self.device)  # (anything but a device array raises here)
+        if not is_device_array(source):
+            device_span(source, self.device)  # (anything but a device array raises here)
         return self.track(settings, source, channels, n_epochs, n_cno, fields)
 
     def track_open_dev(self, settings, source, channel):
         """bds_track_open_dev: the record is the device array `source` (raw file bytes); it is kept alive until track_close and
         must stay unmodified until then."""
         cs = pack_settings(settings)
-        ptr, n_bytes, keep = device_span(source, self.device)
+        ptr, n_bytes, keep, _ = device_record(settings, source, self.device)
         h = self._lib.bds_track_open_dev(self._h, C.byref(cs), ptr, n_bytes, len(channel), self._channels(channel))
         return self._session(h, settings, channel, keep=keep)
 
     def track_feed_dev(self, sess, data, last=False) -> int:
         """bds_track_feed_dev: track_feed from a device array; the bytes are the caller's again on return."""
-        ptr, n_bytes, keep = device_span(data, self.device)
+        name = device_dtype_name(data)
+        if sess.get("w16") and name == "int8":
+            raise BdsError(-1, "settings.dataType is 'int16' but the bytes fed are an int8 array: feed int16 samples, or raw bytes as uint8")
+        if not sess.get("w16") and name == "int16":
+            raise BdsError(-1, "settings.dataType is 'schar' but the samples fed are an int16 array: int16 samples go with dataType 'int16'")
+        ptr, n_bytes, keep = device_span(data, self.device, dtypes=("int16", "uint8") if sess.get("w16") else ("int8", "uint8"))
         check_feed_span(sess, n_bytes)
         return self._check(self._lib.bds_track_feed_dev(sess["handle"], ptr, n_bytes, int(bool(last))))
 
@@ -937,15 +1032,21 @@ class Context:
         """bds_acquire_track: acquisition -> device preRun -> tracking of the record at `path` in one native call.
         Returns ((carrFreq, codePhase, peakMetric, detected), channel array, dict of trackResults arrays)."""
         cs = pack_settings(settings)
-        a, p = _i8(samples)
+        w16 = record_is_int16(settings, np.asarray(samples).dtype.name, "the block")
+        if w16:  # bds_acquire_track16
+            a = _i16(samples, "the block")
+            p = a.ctypes.data_as(C.POINTER(C.c_int16))
+        else:
+            a, p = _i8(samples)
         n = n_samples_of(a.size, is_complex)
+        entry = self._lib.bds_acquire_track16 if w16 else self._lib.bds_acquire_track
         max_prn = max(int(q) for q in np.atleast_1d(settings.acqSatelliteList))
         carr, cph, pm = np.zeros(max_prn), np.zeros(max_prn), np.zeros(max_prn)
         det = np.zeros(max_prn, dtype=np.int32)
         nch = int(settings.numberOfChannels)
         ch = (Channel * nch)()
         out, arrays = self._track_out(nch, n_epochs, n_cno, fields)
-        self._check(self._lib.bds_acquire_track(self._h, C.byref(cs), p, n, sample_format(is_complex), max_prn, carr.ctypes.data_as(_DP),
+        self._check(entry(self._h, C.byref(cs), p, n, sample_format(is_complex), max_prn, carr.ctypes.data_as(_DP),
                                                 cph.ctypes.data_as(_DP), pm.ctypes.data_as(_DP), det.ctypes.data_as(_IP),
                                                 os.fsencode(path), ch, C.byref(out)))
         return (carr, cph, pm, det), ch, arrays
@@ -975,7 +1076,8 @@ class Context:
 
     def track_correlate(self, settings, file_bytes, prns, state6):
         cs = pack_settings(settings)
-        a, p = _i8(file_bytes)
+        a, _ = record_bytes(settings, file_bytes)
+        p = a.ctypes.data_as(C.POINTER(C.c_int8))
         prn = np.ascontiguousarray(prns, dtype=np.int32)
         st = np.ascontiguousarray(state6, dtype=np.float64).reshape(prn.size, 6)
         sums = np.zeros((prn.size, 18))

@@ -5,7 +5,8 @@ BDS-3_B2a/tracking.m:1, BDS-3_B1C/NB_tracking.m:1, BDS-3_B1C/WB_tracking.m:1 and
 ``fid`` may be a file path, an open binary file object (its ``.name`` is used: the
 reference seeks absolutely from 'bof', B2a/tracking.m:151-153, so the handle position
 is irrelevant), an int8 array holding the raw file bytes (uint8 for the packed
-records of ``settings.fileType = 3``), or those bytes as a device array (a torch tensor
+records of ``settings.fileType = 3``; an int16 array of samples -- I, Q pairs for
+``fileType = 2`` -- when ``settings.dataType`` is ``'int16'``), or those bytes as a device array (a torch tensor
 on the GPU: the record is read where it lies, with the same results).  The result is a list of
 per-channel structs with exactly the field set the reference variant creates
 (SURVEY.md Appendix D).
@@ -81,9 +82,10 @@ def _resident_limit(ctx, resident_limit):
 
 def _device_record(a, settings, field):
     """A device array as the record's raw bytes, with the dtype rule of the host arrays: uint8 for the packed bytes of
-    settings.fileType 3, int8 otherwise (checked before any native call)."""
-    want = "uint8" if int(settings.fileType) == 3 else "int8"
-    name = str(a.dtype).split(".")[-1] if hasattr(a, "dtype") else np.dtype(a.__cuda_array_interface__["typestr"]).name
+    settings.fileType 3, int16 samples for settings.dataType 'int16', int8 otherwise (checked before any native call)."""
+    name = native.device_dtype_name(a)
+    w16 = native.record_is_int16(settings, name, field)
+    want = "int16" if w16 else "uint8" if int(settings.fileType) == 3 else "int8"
     if name != want:
         raise ValueError(f"{field} must be a {want} device array when settings.fileType is {int(settings.fileType)}"
                          + (" (packed bytes: two 2+2-bit I/Q samples per byte)" if want == "uint8" else "") + f", not {name}")
@@ -108,8 +110,8 @@ def tracking(fid, channel, settings, mode=None, device: int = 0, resident_limit=
     elif int(settings.fileType) == 3:  # packed bytes: never through a conversion to int8 values
         a = np.asarray(fid)
         source = packed_bytes(a.view(np.uint8) if a.dtype == np.int8 else a, field="fid")
-    else:
-        source = np.ascontiguousarray(fid, dtype=np.int8)
+    else:  # (int8 bytes, or int16 samples with settings.dataType 'int16': the dtype is checked against the setting before any copy)
+        source = _host_values(fid, settings, "fid")
     ctx = get_context(device)
     # the native side derives the variant from settings.signal / pilotTRKflag exactly as
     # postProcessing.m does; an explicit NB request on a pilotTRKflag==2 struct is honoured
@@ -176,17 +178,25 @@ def acquire_track(long_signal, path, settings, device: int = 0, resident_limit=N
     is_complex = np.iscomplexobj(x)
     if int(settings.fileType) == 3:  # packed bytes, in the block as in the file
         x, is_complex = packed_bytes(x), 2
-    elif is_complex:  # fileType 2: interleaved int8 pairs, as acquisition() hands them over
-        pairs = np.empty(2 * x.size, dtype=np.int8)
-        pairs[0::2], pairs[1::2] = x.real.astype(np.int8), x.imag.astype(np.int8)
+    elif is_complex:  # fileType 2: interleaved int8 (dataType 'int16': int16) pairs, as acquisition() hands them over
+        pairs = np.empty(2 * x.size, dtype=np.int16 if native.data_type_code(settings.dataType) == 1 else np.int8)
+        pairs[0::2], pairs[1::2] = x.real.astype(pairs.dtype), x.imag.astype(pairs.dtype)
         x = pairs
     ctx = get_context(device)
     with _resident_limit(ctx, resident_limit):
-        (carr, cph, pm, det), ch, arr = ctx.acquire_track(settings, x if is_complex == 2 else np.ascontiguousarray(x, dtype=np.int8), is_complex, path, n, m, ep + cn)
+        (carr, cph, pm, det), ch, arr = ctx.acquire_track(settings, x if is_complex == 2 else _host_values(x, settings, "longSignal"), is_complex, path, n, m, ep + cn)
     acq = SimpleNamespace(carrFreq=carr, codePhase=cph, peakMetric=pm)
     channel = [SimpleNamespace(PRN=int(c.PRN), acquiredFreq=float(c.acquiredFreq), codePhase=float(c.codePhase),
                                codeFreq=float(c.codeFreq), status=chr(c.status)) for c in ch]
     return acq, channel, _results(arr, [c.PRN for c in channel], len(channel), ep, cn, mode)
+
+
+def _host_values(x, settings, field):
+    """A host array of samples (or of a record's raw bytes) as the int8 row the native calls take, or, with settings.dataType
+    'int16', the int16 row; the array's dtype is checked against the setting before any copy (native.record_is_int16)."""
+    if native.record_is_int16(settings, np.asarray(x).dtype.name, field):
+        return native._i16(x, field)
+    return np.ascontiguousarray(x, dtype=np.int8)
 
 
 class TrackSession:
@@ -195,7 +205,8 @@ class TrackSession:
     ``tracking()`` call over the same epochs returns (settings.msToProcess is not read: a session has no preset end, and every
     channel stops at its own short read).
 
-    source: a file path, an open binary file (its ``.name``), or the raw file bytes (int8; uint8 for settings.fileType = 3), in
+    source: a file path, an open binary file (its ``.name``), or the raw file bytes (int8; uint8 for settings.fileType = 3; int16
+    samples for settings.dataType = 'int16'), in
     host memory or as a device array (a torch tensor on the GPU; it must stay unmodified until close()).  ``feed`` takes either kind.
     origin=N (a multiple of 32) instead opens a FEED session: pass source=None; the record is what ``feed`` appends, sample N
     of the record first.  resident_limit: bytes of the record resident in HBM (None: the context's limit, else 256 MiB).
@@ -234,7 +245,7 @@ class TrackSession:
                 a = np.asarray(source)
                 self._sess = self._ctx.track_open(s, packed_bytes(a.view(np.uint8) if a.dtype == np.int8 else a, field="source"), self.channel)
             else:
-                self._sess = self._ctx.track_open(s, np.ascontiguousarray(source, dtype=np.int8), self.channel)
+                self._sess = self._ctx.track_open(s, _host_values(source, settings, "source"), self.channel)
 
     def _open(self):
         if self._sess is None:

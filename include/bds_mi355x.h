@@ -57,7 +57,7 @@ enum {
  */
 typedef struct bds_settings {
     int32_t signal; /* BDS_SIGNAL_*: which receiver directory the struct came from */
-    int32_t fileType;              /* 1 = real int8, 2 = interleaved I/Q int8, 3 = packed 2+2-bit I/Q (below) */
+    int32_t fileType;              /* 1 = real, 2 = interleaved I/Q (int8, or int16 with dataType 1), 3 = packed 2+2-bit I/Q (below) */
     double samplingFreq;           /* [Hz] */
     double IF;                     /* [Hz] */
     double codeFreqBasis;          /* [Hz] */
@@ -85,9 +85,10 @@ typedef struct bds_settings {
     double dllNoiseBandwidth;      /* [Hz] */
     double pllNoiseBandwidth;      /* [Hz] */
     int32_t CNoInterval;
-    int32_t dataType;              /* settings.dataType: 0 = 'schar' (int8 samples, the only format the tracking
-                                      scripts' fread(..., dataType) is ever called with here); anything else is
-                                      rejected with BDS_ERR_UNSUPPORTED (B2a/tracking.m:237-238)            */
+    int32_t dataType;              /* settings.dataType of fread(fid, n, settings.dataType) (B2a/tracking.m:237-238):
+                                      0 = 'schar' (int8 samples), 1 = 'int16' ('short': little-endian two's complement,
+                                      full range; "16-bit records" below); with fileType 3 only 0 (else BDS_ERR_ARG);
+                                      anything else is rejected with BDS_ERR_UNSUPPORTED                     */
     double FEBW;                   /* [Hz] B1C WB only (CalcWeighingFactor.m:46)     */
 } bds_settings;
 
@@ -200,6 +201,23 @@ BDS_API int bds_gen_code(int signal, int kind, int prn, int8_t *out, int n);
  *   end of file is judged in samples.  Every output equals, bit for bit, that of the same call with fileType 2 (is_complex 1)
  *   on the int8 pairs bds_unpack_cplx makes of the same bytes; bds_track_loaded_bytes / bds_track_stream_info count real bytes
  *   (a quarter of the fileType-2 record's), and so does the resident limit.
+ * 16-bit records: settings.dataType == 1 means little-endian int16 samples (fileType 1) or interleaved I, Q int16 pairs
+ *   (fileType 2).  Positions count SAMPLES, the rule of the packed format: skipNumberOfBytes, codePhase and absoluteSample are
+ *   sample counts, a channel starts at sample skipNumberOfBytes + codePhase - 1, a file of B bytes holds B / 2 samples (B / 4
+ *   pairs) and end of file is judged in samples.  (The reference's own fseek / ftell arithmetic counts bytes and says so --
+ *   "Assumes sample type is schar (or 1 byte per sample)", B2a/tracking.m:151-153,226 -- so with a 2-byte type it would start
+ *   every channel at half the intended offset; that is not reproduced.)  A sample enters the arithmetic as the same (double)
+ *   value an int8 sample does: a 16-bit record whose values all fit int8 gives every output of the int8 record bit for bit.
+ *   Tracking: bds_track, bds_track_mem, bds_track_open*, bds_track_feed*, the *_dev entries and bds_track_correlate take the
+ *   record's bytes and need no other entry; a byte count that is not a whole number of samples (2 bytes; 4 for a pair) is
+ *   BDS_ERR_ARG; bds_track_loaded_bytes / bds_track_stream_info and the resident limit count real bytes.  The kernels are built
+ *   for the default numerics only: in the test-hooks build any BDS_TRK_PREC but 4 with dataType 1 is BDS_ERR_UNSUPPORTED.
+ *   Acquisition: the entries typed int8_t (bds_acquire, bds_acq_load, bds_acquire_track, bds_acquire_multi) keep refusing
+ *   dataType != 0 (BDS_ERR_UNSUPPORTED); bds_acquire16, bds_acq_load16 and bds_acquire_track16 take int16_t values and need
+ *   dataType == 1 (else BDS_ERR_ARG); bds_acq_load_dev goes by settings.dataType.  is_complex == 2 with 16 bits is BDS_ERR_ARG.
+ *   COST: a 16-bit block is widened on the device to the float64 block the resampling branch leaves (exact), so its search is
+ *   the L-point pair and its refinement the host path (bds_timing.refine_path = 0): the N-point pairs and the device
+ *   refinement chain read int8 blocks only.  resamplingflag = 1 works on a 16-bit block as on an int8 one.
  * carrFreq/codePhase/peakMetric: double[max_prn], max_prn >= max(acqSatelliteList);
  *   zero where not searched / not detected (B2a/acquisition.m:161-165).
  * detected (optional, may be NULL): int32[max_prn], 1 where the PRN passed the
@@ -209,6 +227,10 @@ BDS_API int bds_gen_code(int signal, int kind, int prn, int8_t *out, int n);
 BDS_API int bds_acquire(bds_ctx *ctx, const bds_settings *s, const int8_t *samples,
                         size_t n_samples, int is_complex, int max_prn, double *carrFreq,
                         double *codePhase, double *peakMetric, int32_t *detected);
+/* ... on int16 samples (settings.dataType 1; n_samples samples, or I/Q pairs when is_complex == 1) */
+BDS_API int bds_acquire16(bds_ctx *ctx, const bds_settings *s, const int16_t *samples,
+                          size_t n_samples, int is_complex, int max_prn, double *carrFreq,
+                          double *codePhase, double *peakMetric, int32_t *detected);
 
 /* The same call split in three so that the timed region of a benchmark starts with
  * the IF block resident in HBM and the code spectra cached:
@@ -220,6 +242,8 @@ BDS_API int bds_acquire(bds_ctx *ctx, const bds_settings *s, const int8_t *sampl
  * ranks reassembles acqResults bit-exactly (x + 0). */
 BDS_API int bds_acq_load(bds_ctx *ctx, const bds_settings *s, const int8_t *samples,
                          size_t n_samples, int is_complex);
+BDS_API int bds_acq_load16(bds_ctx *ctx, const bds_settings *s, const int16_t *samples,
+                           size_t n_samples, int is_complex); /* int16 samples (settings.dataType 1) */
 BDS_API int bds_acq_prepare(bds_ctx *ctx, const bds_settings *s);
 BDS_API int bds_acq_run(bds_ctx *ctx, const bds_settings *s, const int32_t *prn_list, int n_prn,
                         int max_prn, double *carrFreq, double *codePhase, double *peakMetric,
@@ -393,7 +417,9 @@ BDS_API int bds_track_stream_info(bds_ctx *ctx, int32_t *pieces, long long *resi
  * origin_sample must be a multiple of 32 samples.  skipNumberOfBytes + codePhase - 1 stays a position in the record (and
  * absoluteSample counts from the record's sample 0); a start position before origin_sample is BDS_ERR_ARG.  Bytes are those of
  * the settings' fileType: an I/Q record takes whole pairs (an odd count is BDS_ERR_ARG), of a packed record every byte is two
- * samples.
+ * samples.  Of a 16-bit record (settings.dataType 1) a call takes whole samples only -- 2 bytes, 4 for an I/Q pair: the count it
+ * returns is a multiple of that, whatever was offered, and the caller offers the rest again with what follows; a `last` call
+ * whose byte count is not a whole number of samples is BDS_ERR_ARG.
  *   bds_track_feed  appends to the resident span and returns how many bytes it took (>= 0) or < 0.  It takes fewer than
  *                offered when the span is full -- it never drops or overwrites samples a live channel still needs; what lies
  *                behind the slowest channel is released first, the rest carried device to device --: the caller then advances
@@ -482,6 +508,11 @@ BDS_API int bds_acquire_track(bds_ctx *ctx, const bds_settings *s, const int8_t 
                               int is_complex, int max_prn, double *carrFreq, double *codePhase,
                               double *peakMetric, int32_t *detected, const char *path,
                               bds_channel *channel, bds_track_out *out);
+/* ... with an int16 block and a 16-bit record at `path` (settings.dataType 1) */
+BDS_API int bds_acquire_track16(bds_ctx *ctx, const bds_settings *s, const int16_t *samples, size_t n_samples,
+                                int is_complex, int max_prn, double *carrFreq, double *codePhase,
+                                double *peakMetric, int32_t *detected, const char *path,
+                                bds_channel *channel, bds_track_out *out);
 /* ---- frame synchronisation correlators (the first consumers of trackResults) -------------
  * B1C/include/BCNAV1decoding.m:66-91: bits = sign(Pilot_I_P) (wide-band tracking) or sign(Pilot_Q_P)
  *   (narrow-band), XcorrResult = second half of xcorr(bits, generate2ndCode(PRN)) (1800 chips),

@@ -1,10 +1,11 @@
 #!/usr/bin/env python3
 """Time bds_acq_run for any settings, with nothing but native.Context and its timing():
-    python tools/time_acq.py [--b2a [--b2a-npoint 1]] [--set name=value ...] [--prns 19,20 | --prns all] [--repeats 5] [--calls 10] [--sieve-error]
+    python tools/time_acq.py [--b2a [--b2a-npoint 1]] [--int16] [--set name=value ...] [--prns 19,20 | --prns all] [--repeats 5] [--calls 10] [--sieve-error]
 The settings start from init_settings_b1c() (53 MS/s, the reference's B1C/initSettings.m), with --b2a from init_settings_b2a() (99.375 MS/s,
 26 bins: `--b2a --prns all` is the grid of BASELINE.json configs[1]); --set overrides fields (numbers are parsed).  --b2a-npoint 1 / 0 sets
 the context's switch for the opt-in N-point search of csrc/bds_acq_pfa6.h (bds_acq_set_b2a_npoint; not given: the library's default, and no
-call of the entry, so that a library of an earlier commit can be timed).
+call of the entry, so that a library of an earlier commit can be timed).  --int16: the block as int16 samples, 256 x the int8 values, under
+settings.dataType 'int16' (bds_acq_load16: the float64 view, the L-point pair and the host refinement path); the time of acq_load is printed too.
 A synthetic 40 ms block (--b2a: 17 ms) is loaded once and stays in HBM, the code spectra are prepared and one warm-up call runs before the clock
 starts.  Per repeat: the mean over --calls calls of the wall time of acq_run and of the library's own total_ms; then the median and
 max - min of the repeats.  BDS_LIB_PATH selects the library (a build of another commit, for instance): run the tool once per library.
@@ -30,6 +31,7 @@ def main():
     ap.add_argument("--sieve-error", action="store_true")
     ap.add_argument("--b2a", action="store_true")
     ap.add_argument("--b2a-npoint", type=int, choices=(0, 1), default=None)
+    ap.add_argument("--int16", action="store_true")
     a = ap.parse_args()
     if a.sieve_error:
         os.environ.setdefault("BDS_LIB_PATH", os.path.join(ROOT, "bds-3-b1c-b2a-sdr-receiver_amd", "libbds_mi355x_hooks.so"))
@@ -51,6 +53,8 @@ def main():
     spc = int(round(s.samplingFreq * (1e-3 if a.b2a else 10e-3)))
     sats = [synth.Sat(prns[0], -1730.0, 0.613 * spc, 0.7, 45.0)] + ([synth.Sat(prns[-1], 2210.0, 0.2 * spc, 2.0, 46.0)] if len(prns) > 2 else [])
     x = synth.make_if(s, sats, (17 if a.b2a else 4) * spc, seed=a.seed)
+    if a.int16:
+        s, x = s.copy(dataType="int16"), x.astype(np.int16) * 256
 
     def context(env):
         os.environ.update(env)
@@ -64,11 +68,17 @@ def main():
         return c
 
     c = context({})
+    loads = []
+    for _ in range(max(a.repeats, 1)):
+        t0 = time.perf_counter()
+        c.acq_load(s, x)
+        loads.append((time.perf_counter() - t0) * 1e3)
+    print(f"# acq_load of {x.size} {x.dtype} samples ({x.nbytes / 1e6:.2f} MB): wall ms median {np.median(loads):.3f}  min {min(loads):.3f}  max {max(loads):.3f}")
     res = c.acq_run(s, prn_list=prns)
     tm = c.timing()
     print(f"# library {os.environ.get('BDS_LIB_PATH', 'libbds_mi355x.so (in-tree release build)')}")
     print(f"# fs {s.samplingFreq / 1e6:g} MS/s, {len(prns)} PRNs x {int(tm['n_bins'])} bins, fft_len {int(tm['fft_len'])}, plan {int(tm['plan_l1'])} x {int(tm['plan_l2'])}, "
-          f"rows_kernel {int(tm['rows_kernel'])}, cols_kernel {int(tm['cols_kernel'])}, detected {[p for p in prns if res[0][p - 1] != 0]}")
+          f"rows_kernel {int(tm['rows_kernel'])}, cols_kernel {int(tm['cols_kernel'])}, refine_path {int(tm.get('refine_path', -1))}, detected {[p for p in prns if res[0][p - 1] != 0]}")
     wall, own = [], []
     for r in range(a.repeats):
         t0 = time.perf_counter()
