@@ -1830,6 +1830,23 @@ extern "C" int bds_acq_grid(bds_ctx *ctx, float *row_max, int32_t *row_arg, int 
     return n;
 }
 
+// Test aid (bds_acq_block): the host copy of the float64 block of the last load, as it is held.
+extern "C" int bds_acq_block(bds_ctx *ctx, double *re, double *im, size_t cap, long long *n) {
+    if (!ctx || !ctx->acq || !re || !n) return BDS_ERR_ARG;
+    const AcqState &a = *ctx->acq;
+    if (a.n_samples <= 0) return fail(ctx, BDS_ERR_ARG, "bds_acq_block: no block loaded (bds_acq_load first)");
+    if (a.skind < kF64) return fail(ctx, BDS_ERR_ARG, "bds_acq_block: the loaded block is an int8 one, there is no float64 block");
+    const size_t len = (size_t)a.n_samples;
+    if (a.h_re.size() != len || (a.cplx && a.h_im.size() != len))
+        return fail(ctx, BDS_ERR_ARG, "bds_acq_block: no block loaded (the last bds_acq_load failed)");
+    if (a.cplx && !im) return fail(ctx, BDS_ERR_ARG, "bds_acq_block: the block is complex, im must not be NULL");
+    if (cap < len) return fail(ctx, BDS_ERR_ARG, "bds_acq_block: capacity %zu < %zu samples", cap, len);
+    std::copy(a.h_re.begin(), a.h_re.end(), re);
+    if (a.cplx) std::copy(a.h_im.begin(), a.h_im.end(), im);
+    *n = (long long)len;
+    return a.cplx ? 1 : 0;
+}
+
 extern "C" int bds_acq_candidates(bds_ctx *ctx, int prn, int32_t *bin, int64_t *lag, int cap) {
     if (!ctx || !ctx->acq) return BDS_ERR_ARG;
     if (ctx->acq->cands_on_device > 0) {  // the device refinement chain keeps its candidates on the device: fetched when asked for

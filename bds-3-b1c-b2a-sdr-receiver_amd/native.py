@@ -101,7 +101,7 @@ UPDATE_STATE = ["codeFreq", "remCodePhase", "carrFreq", "carrFreqBasis", "remCar
 
 EXPORTS = [
     "bds_create", "bds_destroy", "bds_reload_tuning", "bds_last_error", "bds_device_name", "bds_abi_check", "bds_build_flags", "bds_gen_code", "bds_acquire",
-    "bds_acq_load", "bds_acq_prepare", "bds_acq_run", "bds_acq_set_pair_budget_gb", "bds_acq_set_b2a_npoint", "bds_resample_plan", "bds_fir1_bandpass", "bds_frame_sync", "bds_sync_pattern", "bds_unpack_cplx", "bds_unpack_cplx_file", "bds_acq_grid", "bds_acq_peaks", "bds_acq_candidates", "bds_acq_coherent_sums", "bds_get_timing",
+    "bds_acq_load", "bds_acq_prepare", "bds_acq_run", "bds_acq_set_pair_budget_gb", "bds_acq_set_b2a_npoint", "bds_resample_plan", "bds_fir1_bandpass", "bds_frame_sync", "bds_sync_pattern", "bds_unpack_cplx", "bds_unpack_cplx_file", "bds_acq_grid", "bds_acq_peaks", "bds_acq_candidates", "bds_acq_coherent_sums", "bds_acq_block", "bds_get_timing",
     "bds_acquire16", "bds_acq_load16", "bds_acquire_track16",
     "bds_track", "bds_track_mem", "bds_track_loaded_bytes", "bds_track_set_resident_limit", "bds_track_stream_info", "bds_track_correlate", "bds_track_colon", "bds_track_cno", "bds_track_update",
     "bds_track_open", "bds_track_open_mem", "bds_track_open_feed", "bds_track_feed", "bds_track_advance", "bds_track_session_info", "bds_track_close",
@@ -175,6 +175,8 @@ def lib():
     L.bds_acq_peaks.restype, L.bds_acq_peaks.argtypes = i32, [vp, i32, _DP, _DP, _IP]
     L.bds_acq_coherent_sums.restype = i32
     L.bds_acq_coherent_sums.argtypes = [vp, SP, i32, C.c_int64, _DP, i32, i32, _DP, i32]
+    if hasattr(L, "bds_acq_block"):  # (a build of an older commit, loaded through BDS_LIB_PATH for an A/B run, has no block test aid)
+        L.bds_acq_block.restype, L.bds_acq_block.argtypes = i32, [vp, _DP, _DP, sz, C.POINTER(C.c_longlong)]
     L.bds_get_timing.restype, L.bds_get_timing.argtypes = i32, [vp, C.POINTER(Timing)]
     L.bds_track.restype = i32
     L.bds_track.argtypes = [vp, SP, C.c_char_p, i32, C.POINTER(Channel), C.POINTER(TrackOut)]
@@ -704,6 +706,15 @@ class Context:
         ptr, n_bytes, keep, w16 = device_record(settings, samples, self.device, "the block")
         n = n_samples_of(n_bytes // 2 if w16 else n_bytes, is_complex, n_samples)
         self._check(self._lib.bds_acq_load_dev(self._h, C.byref(cs), ptr, n, sample_format(is_complex)))
+
+    def acq_block(self, cap):
+        """Test aid (bds_acq_block): the float64 block the search reads after the last acq_load -- the resampling branch's output or a
+        widened 16-bit block -- copied as the library holds it.  cap: samples the buffers hold (BdsError when the block is longer, is an
+        int8 one, or nothing is loaded).  Returns a float64 array for a real block, a complex128 one for an I/Q block."""
+        re, im = np.full(int(cap), np.nan), np.full(int(cap), np.nan)
+        n = C.c_longlong(-1)
+        cplx = self._check(self._lib.bds_acq_block(self._h, re.ctypes.data_as(_DP), im.ctypes.data_as(_DP), int(cap), C.byref(n)))
+        return re[:n.value] + 1j * im[:n.value] if cplx else re[:n.value]
 
     def acq_prepare(self, settings):
         cs = pack_settings(settings)

@@ -307,6 +307,13 @@ BDS_API int bds_acq_peaks(bds_ctx *ctx, int max_prn, double *peak, double *denom
  *   mode 2  the same sums, one frequency per pass (what mode 1 must agree with to rounding) */
 BDS_API int bds_acq_coherent_sums(bds_ctx *ctx, const bds_settings *s, int prn, int64_t phase, const double *freqs, int nf, int mode,
                                   double *out, int cap); /* cap: (re, im) pairs `out` holds; BDS_ERR_ARG, nothing written, if the call needs more */
+/* Test aid, never needed by a host application: the float64 block the search reads after the last bds_acq_load / bds_acq_load16 /
+ * bds_acq_load_dev -- the output of the resampling branch (fir1 + filtfilt + index decimation, acquisition.m:56-112), or a 16-bit
+ * block widened to float64 -- as the library holds it on the host, copied without any arithmetic.  re[cap], im[cap] (im may be NULL
+ * for a real block); *n receives the number of samples.  Returns 0 for a real block, 1 for a complex one; BDS_ERR_ARG, nothing
+ * written, when the loaded block is an int8 one (no resampling, dataType 'schar'), when nothing is loaded or when cap is smaller than the block.  The
+ * tests hold every sample against a float64 restatement of filtfilt. */
+BDS_API int bds_acq_block(bds_ctx *ctx, double *re, double *im, size_t cap, long long *n);
 BDS_API int bds_get_timing(bds_ctx *ctx, bds_timing *t);
 
 /* ---- multi-device acquisition -------------------------------------------

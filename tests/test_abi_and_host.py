@@ -105,7 +105,8 @@ def test_host_helpers_match_oracle():
 
 def test_resampling_plan_and_fir1_match_oracle():
     """Host side of the resampling branch (acquisition.m:54-124): rate / IF choice and the fir1 taps
-    against the oracle's scipy restatement; the filter itself is checked on the GPU."""
+    against the oracle's scipy restatement; the filter itself is checked on the GPU, every output of every kernel against a
+    long-double reference (tests/test_resample_stages_gpu.py) and the block the library makes of a record (tests/test_resample_block_gpu.py)."""
     import scipy.signal as ssig
 
     from oracle import acquisition as oacq
@@ -169,6 +170,6 @@ def test_settings_fields_are_required_not_defaulted():
 def test_context_mirror_has_a_method_per_entry_it_wraps():
     """the ctypes mirror keeps one method per native entry the tests and tools call (an edit that drops one -- timing() once --
     must fail here, on CPU, not on the GPU box)"""
-    for m in ("acq_load", "acq_prepare", "acq_run", "acq_grid", "acq_peaks", "acq_candidates", "acq_coherent_sums", "timing",
+    for m in ("acq_load", "acq_prepare", "acq_run", "acq_grid", "acq_peaks", "acq_candidates", "acq_coherent_sums", "acq_block", "timing",
               "track", "track_correlate", "track_colon", "track_cno", "track_update", "reload_tuning", "device_name"):
         assert callable(getattr(native.Context, m, None)), m
