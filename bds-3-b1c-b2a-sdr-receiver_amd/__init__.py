@@ -8,6 +8,7 @@ Host-side mirror of the reference's MATLAB call surface
     channel    = pre_run(acqResults, settings)                  include/preRun.m
     trackResults, channel = tracking(fid, channel, settings)    tracking.m / NB_tracking.m / WB_tracking.m
     TrackSession(source, channel, settings)                     the same run advanced in pieces, or fed by the caller
+    probe_data(settings) / probe_data(fileName, settings)       include/probeData.m (the numbers; also arrays and device tensors)
 
 All numeric work happens in ``libbds_mi355x.so`` (HIP kernels for gfx950) through
 the C ABI of ``include/bds_mi355x.h``; there is no CPU fallback.
@@ -17,4 +18,5 @@ from .acquisition import acquisition, GPU_acquisition, AcqResults, get_context, 
 from .tracking import tracking, NB_tracking, WB_tracking, pre_run, acquire_track, TrackResults, TrackSession  # noqa: F401
 from .framesync import frame_sync, unpack_cplx  # noqa: F401
 from .distributed import shard_prns, shard_joint, sharded_acquisition, sharded_acquisition_joint  # noqa: F401
+from .probedata import probe_data, ProbeResult  # noqa: F401
 from . import native, synth  # noqa: F401

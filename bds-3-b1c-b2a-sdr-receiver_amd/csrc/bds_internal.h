@@ -105,6 +105,7 @@ struct bds_ctx {
     bds::Tuning tune;
     std::set<const void *> lds_attr_done;  // kernels whose dynamic-LDS limit has been raised on this device
     int n_cu = 0;                          // compute units of the device
+    long long probe_piece_segments = 0;    // bds_probe_set_piece_segments: segments per piece of bds_probe_data / _file (0 = 256 MiB of the record)
 };
 
 namespace bds {

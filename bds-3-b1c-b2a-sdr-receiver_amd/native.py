@@ -92,6 +92,13 @@ class SynthOpts(C.Structure):
                 ("threshold", C.c_double), ("symbols", C.POINTER(C.c_int8)), ("n_sym", C.c_int64)]
 
 
+class ProbeOut(C.Structure):
+    _fields_ = ([("hist_i", C.POINTER(C.c_int64)), ("hist_q", C.POINTER(C.c_int64))]
+                + [(f"{k}_{c}", C.c_int64) for c in "iq" for k in ("min", "max", "sum", "sumsq")]
+                + [("psd", C.POINTER(C.c_double)), ("cap", C.c_int32), ("n_psd", C.c_int32), ("n_segments", C.c_int64), ("n_samples", C.c_int64),
+                   ("excerpt_re", C.POINTER(C.c_double)), ("excerpt_im", C.POINTER(C.c_double))])
+
+
 SYNTH_FORMATS = {0: (np.float64, 1, 1), 1: (np.int8, 1, 1), 2: (np.int8, 2, 1), 3: (np.uint8, 1, 2)}  # dtype, elements per `den` samples
 
 
@@ -110,9 +117,12 @@ EXPORTS = [
     "bds_multi_create", "bds_multi_destroy", "bds_multi_last_error", "bds_multi_size", "bds_multi_ctx",
     "bds_multi_rccl_ranks", "bds_acquire_multi", "bds_shard_jobs", "bds_acq_job_cost",
     "bds_synth", "bds_synth_file", "bds_synth_noise",
+    "bds_probe_data", "bds_probe_data_file", "bds_probe_set_piece_segments",
 ]
 # the entries marked BDS_DEV_API in the header: their record pointer is device memory (device_span below makes it)
 DEVICE_EXPORTS = ["bds_synth_dev", "bds_acq_load_dev", "bds_track_dev", "bds_track_open_dev", "bds_track_feed_dev"]
+# the entry marked BDS_PROBE_DEV_API: a device pointer as well
+PROBE_DEVICE_EXPORTS = ["bds_probe_data_dev"]
 
 _lib = None
 HOOKS_LIB = os.path.join(os.path.dirname(os.path.abspath(__file__)), "libbds_mi355x_hooks.so")
@@ -229,6 +239,12 @@ def lib():
         L.bds_track_dev.argtypes = [vp, SP, vp, sz, i32, C.POINTER(Channel), C.POINTER(TrackOut)]
         L.bds_track_open_dev.restype, L.bds_track_open_dev.argtypes = vp, [vp, SP, vp, sz, i32, C.POINTER(Channel)]
         L.bds_track_feed_dev.restype, L.bds_track_feed_dev.argtypes = i32, [vp, vp, sz, i32]
+    if hasattr(L, "bds_probe_data"):  # (as above: a build of an older commit has no probeData)
+        PP, i64 = C.POINTER(ProbeOut), C.c_int64
+        L.bds_probe_data.restype, L.bds_probe_data.argtypes = i32, [vp, SP, vp, sz, i64, PP]
+        L.bds_probe_data_file.restype, L.bds_probe_data_file.argtypes = i32, [vp, SP, C.c_char_p, i64, i64, PP]
+        L.bds_probe_data_dev.restype, L.bds_probe_data_dev.argtypes = i32, [vp, SP, vp, sz, i64, PP]
+        L.bds_probe_set_piece_segments.restype, L.bds_probe_set_piece_segments.argtypes = i32, [vp, i64]
     L.bds_abi_check.restype, L.bds_abi_check.argtypes = i32, [i32, i32, i32, i32]
     if L.bds_abi_check(C.sizeof(Settings), C.sizeof(Channel), C.sizeof(TrackOut), C.sizeof(Timing)) != 0:
         raise ImportError("ctypes struct layout does not match libbds_mi355x.so (include/bds_mi355x.h changed?)")
@@ -809,6 +825,38 @@ class Context:
         self._check(self._lib.bds_synth_noise(self._h, int(seed) & (2 ** 64 - 1), int(first), int(n), gi.ctypes.data_as(_DP),
                                               gq.ctypes.data_as(_DP)))
         return gi, gq
+
+    # -- probeData (bds_probe_data*) --------------------------------------------------------
+    def probe_set_piece_segments(self, n):
+        """bds_probe_set_piece_segments: segments per piece of probe_data on host bytes or a file (0: the default)."""
+        self._check(self._lib.bds_probe_set_piece_segments(self._h, int(n)))
+
+    def probe_data(self, settings, source, n_time, n_samples=0):
+        """bds_probe_data (host array of the record's bytes), bds_probe_data_file (a path; n_samples 0: the reference's window,
+        -1: to the end of the file) or bds_probe_data_dev (a device array, read where it lies).  Returns a dict of arrays and
+        integers: hist_i, hist_q, psd, excerpt_re, excerpt_im, the eight statistics, n_segments, n_samples."""
+        cs = pack_settings(settings)
+        cplx = int(settings.fileType) != 1
+        n_time = int(n_time)
+        hi, hq = np.zeros(257, dtype=np.int64), np.zeros(257, dtype=np.int64)
+        psd = np.full(32768 if cplx else 16385, np.nan)
+        ex = np.full((2, max(n_time, 1)), np.nan)
+        o = ProbeOut()
+        I64 = C.POINTER(C.c_int64)
+        o.hist_i, o.hist_q, o.psd, o.cap = hi.ctypes.data_as(I64), hq.ctypes.data_as(I64), psd.ctypes.data_as(_DP), psd.size
+        o.excerpt_re, o.excerpt_im = ex[0].ctypes.data_as(_DP), ex[1].ctypes.data_as(_DP)
+        if isinstance(source, (str, bytes, os.PathLike)):
+            rc = self._lib.bds_probe_data_file(self._h, C.byref(cs), os.fsencode(source), int(n_samples), n_time, C.byref(o))
+        elif is_device_array(source):
+            ptr, n_bytes, keep, _ = device_record(settings, source, self.device)
+            rc = self._lib.bds_probe_data_dev(self._h, C.byref(cs), ptr, n_bytes, n_time, C.byref(o))
+        else:
+            a, _ = record_bytes(settings, source)
+            rc = self._lib.bds_probe_data(self._h, C.byref(cs), a.ctypes.data_as(C.c_void_p), a.size, n_time, C.byref(o))
+        self._check(rc)
+        out = {k: int(getattr(o, k)) for k in ("n_segments", "n_samples", "min_i", "max_i", "sum_i", "sumsq_i", "min_q", "max_q", "sum_q", "sumsq_q")}
+        out.update(hist_i=hi, hist_q=hq if cplx else None, psd=psd[:o.n_psd], excerpt_re=ex[0, :n_time], excerpt_im=ex[1, :n_time] if cplx else None)
+        return out
 
     def frame_sync(self, signal, prns, prompt, cap=64):
         """bds_frame_sync: prompt [n_ch, n] -> (xcorr int32 [n_ch, M], [1-based index arrays])."""

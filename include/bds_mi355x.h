@@ -650,6 +650,61 @@ BDS_DEV_API bds_track_session *bds_track_open_dev(bds_ctx *ctx, const bds_settin
                                               int n_ch, const bds_channel *channel);
 BDS_DEV_API int bds_track_feed_dev(bds_track_session *sess, const void *d_bytes, size_t n_bytes, int last);
 
+/* ---- probeData: histogram, Welch PSD and excerpt of an IF record ------------------------------------------------------------
+ * probeData(settings) / probeData(fileName, settings)     B2a/include/probeData.m:1, B1C/include/probeData.m:1
+ * The numbers behind the reference's figure 100, of a record in any format bds_track reads -- settings.fileType / dataType select
+ * the decoder exactly as there: int8 real, int8 I/Q pairs, packed 2+2-bit I/Q (fileType 3), int16 real, int16 I/Q pairs -- decoded
+ * on the device from the record's own bytes.
+ *   histogram  hist(data, -128:128) (probeData.m:146; :155,:163 for I and Q): 257 bins, bin = clamp(v, -128, 128) + 128, so a
+ *              16-bit value outside +-128 lands in an end bin as with hist.  int64 counts; they add up to n_samples.  A real
+ *              record fills hist_i (hist_q, if given, is zeroed).  min / max / sum / sumsq per component are exact integers
+ *              (sumsq needs n max(v^2) < 2^63).
+ *   psd        pwelch(data, 32768, 2048, 32768, fs) (probeData.m:128; 'twosided' :131): symmetric Hamming window
+ *              w[n] = 0.54 - 0.46 cos(2 pi n / 32767), segment k starts at sample 30720 k, n_segments = fix((n - 2048) / 30720),
+ *              the tail is ignored, no detrending; |FFT(w x)|^2 / (fs sum w^2), averaged over the segments.  Real record: one-sided,
+ *              n_psd = 16385 bins, all doubled except DC and Nyquist.  I/Q record: two-sided, n_psd = 32768 bins in natural order
+ *              0 .. fs (the reordering of probeData.m:132-134 is the caller's).  Always the density per Hz of settings.samplingFreq
+ *              (the fs / 1e6 of probeData.m:128 is an axis matter).  Transforms in fp32; the sum over segments is a left-to-right
+ *              f64 sum per bin in segment order, independent of pieces and batches: every source gives the same bits.
+ *   excerpt    the first n_time samples as double (probeData.m:96-97 plots round(samplesPerCode / 500) of a real record,
+ *              :106-107,:114-115 round(samplesPerCode / 2) of I and Q; the B1C copy round(samplesPerCode / 2) of both).
+ * bds_probe_out is caller-allocated: hist_i[257], hist_q[257] (may be NULL for a real record), psd[cap] with cap >= n_psd,
+ *   excerpt_re[n_time] and, for an I/Q record, excerpt_im[n_time] (both may be NULL when n_time is 0).
+ * bds_probe_data       the record is n_bytes raw file bytes in host memory (the whole array is the window)
+ * bds_probe_data_file  the record is the file at `path` behind settings.skipNumberOfBytes (the fseek of probeData.m:63), counted
+ *                      as bds_track counts it: in samples (bytes for an int8 real record; pairs for I/Q; a packed record may
+ *                      start at a high nibble).  n_samples > 0: that many samples; 0: what the signal's own probeData.m reads --
+ *                      5 samplesPerCode (B2a/include/probeData.m:76), 10 samplesPerCode (B1C/include/probeData.m:76); -1: to the
+ *                      end of the file.
+ * Both pass the window through device memory in pieces whose seams fall on segment starts (a piece carries whole segments and
+ * the 2048 samples its last one shares with the next piece), by default as many segments as 256 MiB of the record hold.
+ * bds_probe_set_piece_segments(ctx, n) sets the segments per piece for the calls that follow on the context (0: the default);
+ * the results do not depend on it, bit for bit.
+ * Errors: BDS_ERR_ARG with a message and nothing written to *out for fewer than 32768 samples (pwelch cannot form one segment),
+ * a byte count that is not a whole number of samples (odd for an I/Q or 16-bit record), cap < n_psd, n_time outside the window,
+ * and a file shorter than the window ("Could not read enough data", probeData.m:81-84); BDS_ERR_IO when the file cannot be opened. */
+typedef struct bds_probe_out {
+    int64_t *hist_i, *hist_q;
+    int64_t min_i, max_i, sum_i, sumsq_i, min_q, max_q, sum_q, sumsq_q;
+    double *psd;
+    int32_t cap, n_psd;
+    int64_t n_segments, n_samples;
+    double *excerpt_re, *excerpt_im;
+} bds_probe_out;
+BDS_API int bds_probe_data(bds_ctx *ctx, const bds_settings *s, const void *bytes, size_t n_bytes, int64_t n_time, bds_probe_out *out);
+BDS_API int bds_probe_data_file(bds_ctx *ctx, const bds_settings *s, const char *path, int64_t n_samples, int64_t n_time,
+                                bds_probe_out *out);
+BDS_API int bds_probe_set_piece_segments(bds_ctx *ctx, int64_t n_segments);
+/* ... of a record in DEVICE memory (probeData.m:63-168 on bytes that never were in a file), read where it lies, without a copy:
+ * the pointer rule and the ordering rule of the device-record entries above hold, and d_bytes must be aligned to the element size
+ * (2 for a 16-bit record; any address for the int8 and packed formats -- the 16-byte loads of the histogram pass cover only the
+ * whole aligned lines inside the record, the ragged ends go byte by byte).  Same bits as bds_probe_data on the same bytes.
+ * The entry carries a device pointer; its marker has the meaning of the one above and a name of its own, because the five
+ * device-record entries are a closed set. */
+#define BDS_PROBE_DEV_API __attribute__((visibility("default")))
+BDS_PROBE_DEV_API int bds_probe_data_dev(bds_ctx *ctx, const bds_settings *s, const void *d_bytes, size_t n_bytes, int64_t n_time,
+                                         bds_probe_out *out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -17,6 +17,11 @@
  *   code = bds_mex('gen_code', signal, kind, prn)
  *   [XcorrResult, index] = bds_mex('frame_sync', signal, PRN, bits)   % one channel: second half of
  *       xcorr(sign(bits), pattern) and find(abs(.) >= 1799.5) (B1C) / find(abs(.) > 115) (B2a)
+ *   out = bds_mex('probe_data', path, settings, signal[, n_samples])   % the numbers of include/probeData.m's figure (mex/probeData.m
+ *       draws it): struct with hist_i, hist_q (1 x 257 counts over -128:128; hist_q empty for fileType 1), psd (column: one-sided
+ *       16385 bins for fileType 1, else two-sided 32768 bins 0 .. fs), excerpt_re, excerpt_im (the samples of the time-domain
+ *       plot), stats (min, max, sum, sum of squares of I, then of Q), n_segments, n_samples.  n_samples: 0 (default) = the
+ *       window probeData.m reads, -1 = the whole file behind skipNumberOfBytes.
  * signal: 1 = B1C, 2 = B2a (the reference keeps one directory per receiver).
  * Acquisition runs on ONE GPU unless BDS_MEX_DEVICES=n (n > 1, or 0 = every visible GPU) opts into the multi-device
  * path of the library (bds_multi_create + RCCL all-reduce): that path has only ever run on one-GPU boxes (with the exchange
@@ -288,6 +293,54 @@ static void do_frame_sync(int nlhs, mxArray *plhs[], int nrhs, const mxArray *pr
     mxFree(idx);
 }
 
+/* include/probeData.m:63-168 of either receiver: everything the figure shows, computed on the device */
+static void do_probe_data(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[]) {
+    bds_settings s;
+    bds_probe_out o;
+    char path[4096];
+    int64_t hist[2][257], n_samples, n_time;
+    double spc, *hi, *hq, *st, *ex_im;
+    int cplx, rc, i, n_psd;
+    mxArray *out;
+    (void)nlhs;
+    if (nrhs != 4 && nrhs != 5) mexErrMsgIdAndTxt("bds:args", "probe_data: (path, settings, signal[, n_samples])");
+    if (mxGetString(prhs[1], path, sizeof(path))) mexErrMsgIdAndTxt("bds:args", "File name must be a string"); /* probeData.m:50 */
+    pack_settings(prhs[2], (int)mxGetScalar(prhs[3]), &s);
+    n_samples = nrhs == 5 ? (int64_t)mxGetScalar(prhs[4]) : 0;
+    cplx = s.fileType != 1;
+    spc = (double)(int64_t)(s.samplingFreq / (s.codeFreqBasis / s.codeLength) + 0.5); /* probeData.m:66-67 */
+    /* B2a/include/probeData.m:96 round(spc / 500) of a real record, :106 round(spc / 2) of I/Q; B1C/include/probeData.m:96,106 spc / 2 */
+    n_time = (int64_t)(spc / ((!cplx && s.signal == BDS_SIGNAL_B2A) ? 500 : 2) + 0.5);
+    if (n_samples > 0 && n_time > n_samples) n_time = n_samples;
+    n_psd = cplx ? 32768 : 16385;
+    memset(&o, 0, sizeof(o));
+    out = mxCreateStructMatrix(1, 1, 0, NULL);
+    hi = out_field(out, "hist_i", 1, 257);
+    hq = out_field(out, "hist_q", 1, cplx ? 257 : 0);
+    o.psd = out_field(out, "psd", n_psd, 1);
+    o.cap = n_psd;
+    o.excerpt_re = out_field(out, "excerpt_re", 1, (int)n_time);
+    ex_im = out_field(out, "excerpt_im", 1, cplx ? (int)n_time : 0);
+    o.excerpt_im = cplx ? ex_im : NULL;
+    st = out_field(out, "stats", 1, 8);
+    o.hist_i = hist[0];
+    o.hist_q = hist[1];
+    rc = bds_probe_data_file(ctx(), &s, path, n_samples, n_time, &o);
+    if (rc) {
+        mxDestroyArray(out);
+        mexErrMsgIdAndTxt("bds:probe_data", "%s", bds_last_error(ctx()));
+    }
+    for (i = 0; i < 257; ++i) {
+        hi[i] = (double)hist[0][i];
+        if (cplx) hq[i] = (double)hist[1][i];
+    }
+    st[0] = (double)o.min_i, st[1] = (double)o.max_i, st[2] = (double)o.sum_i, st[3] = (double)o.sumsq_i;
+    st[4] = (double)o.min_q, st[5] = (double)o.max_q, st[6] = (double)o.sum_q, st[7] = (double)o.sumsq_q;
+    out_field(out, "n_segments", 1, 1)[0] = (double)o.n_segments;
+    out_field(out, "n_samples", 1, 1)[0] = (double)o.n_samples;
+    plhs[0] = out;
+}
+
 void mexFunction(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[]) {
     char cmd[32];
     if (nrhs < 1 || mxGetString(prhs[0], cmd, sizeof(cmd))) mexErrMsgIdAndTxt("bds:args", "first argument: command string");
@@ -299,6 +352,8 @@ void mexFunction(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[]) {
         do_gen_code(nlhs, plhs, nrhs, prhs);
     else if (!strcmp(cmd, "frame_sync"))
         do_frame_sync(nlhs, plhs, nrhs, prhs);
+    else if (!strcmp(cmd, "probe_data"))
+        do_probe_data(nlhs, plhs, nrhs, prhs);
     else
         mexErrMsgIdAndTxt("bds:args", "unknown command %s", cmd);
 }
