@@ -89,7 +89,7 @@ def _device_block(long_signal, settings):
     return a, 2 if ft == 3 else ft == 2
 
 
-def acquisition(long_signal, settings, device: int = 0, prn_list=None, verbose: bool = True, b2a_npoint=None) -> AcqResults:
+def acquisition(long_signal, settings, device: int = 0, prn_list=None, verbose: bool = True, b2a_npoint=None, b1c_npoint=None) -> AcqResults:
     """Parallel code-phase search acquisition on the GPU.
 
     long_signal: the samples as the reference hands them over (real, or complex for an I/Q record; uint8 packed bytes for
@@ -100,10 +100,13 @@ def acquisition(long_signal, settings, device: int = 0, prn_list=None, verbose: 
     the shard so an all-reduce(SUM) over ranks reassembles acqResults.
     b2a_npoint (extension): True / False sets the device context's opt-in N-point search for B2a at 99.375 MS/s
     (Context.acq_set_b2a_npoint; it stays set for later calls), None leaves the context as it is (off unless set).
+    b1c_npoint (extension): the same for the opt-in N-point search for B1C at 30.69 MS/s (Context.acq_set_b1c_npoint).
     """
     ctx = get_context(device)
     if b2a_npoint is not None:
         ctx.acq_set_b2a_npoint(b2a_npoint)
+    if b1c_npoint is not None:
+        ctx.acq_set_b1c_npoint(b1c_npoint)
     samples, is_complex = _device_block(long_signal, settings) if native.is_device_array(long_signal) else _as_int8(long_signal, settings)
     ctx.acq_load(settings, samples, is_complex)
     ctx.acq_prepare(settings)

@@ -37,6 +37,7 @@
 #include "bds_acq_pfa.h"
 #include "bds_acq_pfa32.h"
 #include "bds_acq_pfa6.h"
+#include "bds_acq_pfa31.h"
 #include "bds_internal.h"
 
 namespace bds {
@@ -141,6 +142,7 @@ struct AcqState {
     double pair_gb = 0;              // bds_acq_set_pair_budget_gb (overrides the BDS_ACQ_PAIR_GB of the context's tuning)
     bool pair_gb_set = false;
     bool b2a_npoint = false;         // bds_acq_set_b2a_npoint: the N-point pair of bds_acq_pfa6.h may run (default off)
+    bool b1c_npoint = false;         // bds_acq_set_b1c_npoint: the N-point pair of bds_acq_pfa31.h may run (default off)
     int pb_last = 0;                 // PRNs per launch pair the last run settled on, and what it was decided for: the next run with
     double pb_key[6] = {0};          // the same (P, D, L, element size, components, budget) takes it without asking the driver again
     char *d_mcells = nullptr;        // cell list of the main search of a small grid (all P x D cells in a few launch pairs) ...
@@ -200,10 +202,11 @@ struct AcqState {
     double sum_sq_ext = 0;     // sum x^2 over it: X_rms^2 (Parseval)
     long sums_N = 0, sums_next = 0;  // sizes the two sums above were computed for
     float sX = 1.f, sC = 1.f, sB = 1.f;  // power-of-two storage scales
-    // N-point plan (bds_acq_pfa.h: 1, bds_acq_pfa32.h: 2, bds_acq_pfa6.h: 3; 0: none): the cached code spectra are in its layout (CRT order), the search
+    // N-point plan (bds_acq_pfa.h: 1, bds_acq_pfa32.h: 2, bds_acq_pfa6.h: 3, bds_acq_pfa31.h: 4; 0: none): the cached code spectra are in its layout (CRT order), the search
     // runs its pair
     int cs_pfa = 0;
     uint4 *d_pfa_coef = nullptr;  // B fragments of the 53-point stage (pfa::make_coef_frags)
+    uint4 *d_pfa31_coef = nullptr;  // B fragments of the 31-point stage (pfa31::make_coef_frags)
     long sigpower_X = 0;       // X the cached B1C normaliser was computed for (0: none; reset by bds_acq_load)
     double sigpower = 0;       // sqrt(var(sig(1:X)) * X), B1C/acquisition.m:150
 };
@@ -211,7 +214,7 @@ struct AcqState {
 void acq_state_free(AcqState *a) {
     if (!a) return;
     plan_free(a->plan);
-    for (void *p : {(void *)a->d_sig, (void *)a->d_packed, (void *)a->d_prim, (void *)a->d_Cs, (void *)a->d_Xs, (void *)a->d_Bw, (void *)a->d_pfa_coef,
+    for (void *p : {(void *)a->d_sig, (void *)a->d_packed, (void *)a->d_prim, (void *)a->d_Cs, (void *)a->d_Xs, (void *)a->d_Bw, (void *)a->d_pfa_coef, (void *)a->d_pfa31_coef,
                     (void *)a->d_recs, (void *)a->d_rowmax, (void *)a->d_rowarg, (void *)a->d_jobs, (void *)a->d_codes,
                     (void *)a->d_jobout, (void *)a->d_sig64, (void *)a->d_ffa, (void *)a->d_ffb, (void *)a->d_fir, (void *)a->d_cells, (void *)a->d_mcells,
                     (void *)a->d_extra, (void *)a->d_extra_count, (void *)a->d_cellmax, (void *)a->d_lb, (void *)a->d_ref_zero,
@@ -878,7 +881,7 @@ static size_t fine_pick_lds(const bds_settings &s, int signal, int ncomp) {
     return sizeof(double) * ((size_t)(b1c ? ncomp : 2 * s.fineNoncoh) * nfine + nfine);
 }
 struct PfaPick {
-    int kind = 0;   // 0: the L-point pair, 1: bds_acq_pfa.h, 2: bds_acq_pfa32.h, 3: bds_acq_pfa6.h
+    int kind = 0;   // 0: the L-point pair, 1: bds_acq_pfa.h, 2: bds_acq_pfa32.h, 3: bds_acq_pfa6.h, 4: bds_acq_pfa31.h
     int shift = 0;  // spectrum bins per Doppler step; kind 3: p of acqStep N / fs = p / q in lowest terms
     int q = 1;      // kind 3: signal spectra per call
 };
@@ -917,13 +920,14 @@ static PfaPick pfa_pick(const bds_ctx *ctx, const AcqState &a, const bds_setting
     static const struct {
         long N;
         int kind;
-    } admitted[] = {{pfa::NP, 1}, {pfa32::NP, 2}};
+    } admitted[] = {{pfa::NP, 1}, {pfa32::NP, 2}, {pfa31::NP, 4}};
     PfaPick pk;
     if (a.signal == BDS_SIGNAL_B2A) return pfa6_pick(ctx, a, s);
     if (!ctx->tune.pfa || !a.half || a.no_fast_search || a.signal != BDS_SIGNAL_B1C || a.ncomp != 2 || a.rs.on || a.skind >= kF64) return pk;
     int kind = 0;
     for (const auto &ad : admitted)
         if (a.N == ad.N) kind = ad.kind;
+    if (kind == 4 && !a.b1c_npoint) kind = 0;  // (opt-in: bds_acq_set_b1c_npoint)
     if (!kind) return pk;
     const double sh = s.acqStep * (double)a.N / s.samplingFreq;
     const long D = (long)m_round(s.acqSearchBand * 2 / s.acqStep) + 1;
@@ -932,11 +936,11 @@ static PfaPick pfa_pick(const bds_ctx *ctx, const AcqState &a, const bds_setting
     return pk;
 }
 // sizes of the selected pair
-static long pfa_np(int kind) { return kind == 3 ? pfa6::NP : kind == 2 ? pfa32::NP : pfa::NP; }
-static int pfa_k3(int kind) { return kind == 3 ? pfa6::K3 : kind == 2 ? pfa32::K3 : pfa::K3; }
-static int pfa_rows(int kind) { return kind == 3 ? pfa6::K1 * pfa6::K2 : kind == 2 ? pfa32::K1 * pfa32::K2 : pfa::K1 * pfa::K2; }
-static size_t pfa_cell_elems(int kind) { return kind == 3 ? pfa6::kCellElems : kind == 2 ? pfa32::kCellElems : pfa::kCellElems; }
-static int pfa_rows_wgs(int kind) { return kind == 3 ? pfa6::kRowsWgs : kind == 2 ? pfa32::kRowsWgs : pfa::MP * pfa::K2; }
+static long pfa_np(int kind) { return kind == 4 ? pfa31::NP : kind == 3 ? pfa6::NP : kind == 2 ? pfa32::NP : pfa::NP; }
+static int pfa_k3(int kind) { return kind == 4 ? pfa31::K3 : kind == 3 ? pfa6::K3 : kind == 2 ? pfa32::K3 : pfa::K3; }
+static int pfa_rows(int kind) { return kind == 4 ? pfa31::K1 * pfa31::K2 : kind == 3 ? pfa6::K1 * pfa6::K2 : kind == 2 ? pfa32::K1 * pfa32::K2 : pfa::K1 * pfa::K2; }
+static size_t pfa_cell_elems(int kind) { return kind == 4 ? pfa31::kCellElems : kind == 3 ? pfa6::kCellElems : kind == 2 ? pfa32::kCellElems : pfa::kCellElems; }
+static int pfa_rows_wgs(int kind) { return kind == 4 ? pfa31::kRowsWgs : kind == 3 ? pfa6::kRowsWgs : kind == 2 ? pfa32::kRowsWgs : pfa::MP * pfa::K2; }
 
 extern "C" int bds_acq_prepare(bds_ctx *ctx, const bds_settings *s_in) {
     if (!ctx || !s_in) return BDS_ERR_ARG;
@@ -956,7 +960,13 @@ extern "C" int bds_acq_prepare(bds_ctx *ctx, const bds_settings *s_in) {
         if (want != a.cs_pfa) a.cs_slot.clear();
         a.cs_pfa = want;
         if (a.half) a.sC = (float)std::exp2(std::floor(std::log2(32768.0 * (double)(want ? a.N : pl.L) / (double)a.X)));
-        if (want && !a.d_pfa_coef) {
+        if (want == 4 && !a.d_pfa31_coef) {
+            std::vector<uint16_t> cf(pfa31::kCoefBytes / 2);
+            pfa31::make_coef_frags(cf.data());
+            BDS_HIP(ctx, hipMalloc((void **)&a.d_pfa31_coef, pfa31::kCoefBytes));
+            BDS_HIP(ctx, hipMemcpy(a.d_pfa31_coef, cf.data(), pfa31::kCoefBytes, hipMemcpyHostToDevice));
+        }
+        if (want && want != 4 && !a.d_pfa_coef) {
             std::vector<uint16_t> cf(pfa::kCoefBytes / 2);
             pfa::make_coef_frags(cf.data());
             BDS_HIP(ctx, hipMalloc((void **)&a.d_pfa_coef, pfa::kCoefBytes));
@@ -992,7 +1002,9 @@ extern "C" int bds_acq_prepare(bds_ctx *ctx, const bds_settings *s_in) {
         float2 *cs_dst = a.half ? (float2 *)((__half2 *)a.d_Cs + (size_t)slot * a.ncomp * pl.L)
                                 : a.d_Cs + (size_t)slot * a.ncomp * pl.L;
         if (a.cs_pfa) {  // conj(fft(code)) / N in the CRT layout, [slot][component][53][K2][K3] (the slots keep the L-point stride)
-            if (a.cs_pfa == 3)
+            if (a.cs_pfa == 4)
+                pfa31::forward(st(ctx), ld, a.ncomp, a.d_Bw, (uint32_t *)cs_dst, pfa31::NP, 1, (float)((double)a.sC / (double)a.N), 0);
+            else if (a.cs_pfa == 3)
                 pfa6::forward(st(ctx), ld, a.ncomp, a.d_Bw, (uint32_t *)cs_dst, pfa6::NP, 1, (float)((double)a.sC / (double)a.N), 0);
             else if (a.cs_pfa == 2)
                 pfa32::forward(st(ctx), ld, a.ncomp, a.d_Bw, (uint32_t *)cs_dst, pfa32::NP, 1, (float)((double)a.sC / (double)a.N), 0);
@@ -1143,7 +1155,7 @@ struct AcqRun {
     float w0 = 1.f, w1 = 1.f;
     bool fsearch = false, wcols = false, multiprn = false, overlap = false;
     int pfa = 0;               // > 0: an N-point pair runs; the value = spectrum bins per Doppler step
-    int pfa_kind = 0;          // which: 1 bds_acq_pfa.h, 2 bds_acq_pfa32.h, 3 bds_acq_pfa6.h (pfa = p, pfa_q = q of the step p / q)
+    int pfa_kind = 0;          // which: 1 bds_acq_pfa.h, 2 bds_acq_pfa32.h, 3 bds_acq_pfa6.h, 4 bds_acq_pfa31.h (pfa = p, pfa_q = q of the step p / q)
     int pfa_q = 1;
     size_t cell_elems = 0;     // fp16-complex-sized elements of one cell in the inter-pass buffer (both components)
     bool dev_refined = false;  // the refinement ran as the device chain
@@ -1369,6 +1381,8 @@ int AcqRun::forward_all() {
         SignalLoader ld{a.sview(), a.N, a.n_ext, f0, s->acqStep, 1.0 / a.fs, 0};
         if (pfa_kind == 3)  // q transforms: the bins 0 .. q - 1 (the loader's batch index is the bin)
             pfa6::forward(stream(), ld, pfa_q, a.d_Bw, (uint32_t *)a.d_Xs, (long)pfa6::kSpecElems, 0, a.sX * a.sB, 1);
+        else if (pfa_kind == 4)
+            pfa31::forward(stream(), ld, 1, a.d_Bw, (uint32_t *)a.d_Xs, 0, 0, a.sX * a.sB, 1);
         else if (pfa_kind == 2)
             pfa32::forward(stream(), ld, 1, a.d_Bw, (uint32_t *)a.d_Xs, 0, 0, a.sX * a.sB, 1);
         else
@@ -1463,6 +1477,20 @@ void AcqRun::launch_list(int ncells, Rec *recs, const CellList &cl, int cell0, h
             want_lds(ctx, pfa6::k_pfa6_cols<false>, pfa6::kColsLds);
             hipLaunchKernelGGL(pfa6::k_pfa6_cols<false>, dim3(cgrid), dim3(pfa6::kColsThreads), pfa6::kColsLds, s_main, ca);
         }
+        return;
+    }
+    if (pfa_kind == 4) {  // the N-point pair of bds_acq_pfa31.h: the same cell list and sieve outputs, its own grids
+        const int gc = std::max(1, cl.gc), chunks = (ncells + gc - 1) / gc;
+        want_lds(ctx, pfa31::k_pfa31_rows, pfa31::kRowsLds);
+        want_lds(ctx, pfa31::k_pfa31_cols, pfa31::kColsLds);
+        pfa::RowsArgs ra{(const uint32_t *)a.d_Xs, (const uint32_t *)a.d_Cs, (uint32_t *)a.d_Bw, cl.bin, cl.cs, ncells, gc, pfa};
+        hipLaunchKernelGGL(pfa31::k_pfa31_rows, dim3((unsigned)(pfa31::kRowsWgs * chunks)), dim3(pfa31::kRowsThreads), pfa31::kRowsLds, s_main, ra);
+        if (mid) (void)hipEventRecord(mid, s_main);
+        const int qch = ctx->tune.pfa_qchunk > 0 ? ctx->tune.pfa_qchunk : 1;
+        const long items = (long)((pfa31::kTiles + qch - 1) / qch) * qch * ncells;
+        const unsigned cgrid = (unsigned)std::min<long>(items, ctx->tune.pfa_cgrid > 0 ? ctx->tune.pfa_cgrid : std::max<long>(512, std::min<long>(8192, items / 24)));
+        pfa::ColsArgs ca{(const uint32_t *)a.d_Bw, a.d_pfa31_coef, ncells, w0, w1, so1.sieve, qch, nullptr, nullptr, -1, -1};
+        hipLaunchKernelGGL(pfa31::k_pfa31_cols, dim3(cgrid), dim3(pfa31::kColsThreads), pfa31::kColsLds, s_main, ca);
         return;
     }
     if (pfa_kind == 2) {  // the N-point pair of bds_acq_pfa32.h: the same cell list and sieve outputs, its own grids
@@ -1748,6 +1776,18 @@ extern "C" int bds_acq_set_b2a_npoint(bds_ctx *ctx, int on) {
     if (!ctx->acq) ctx->acq = new AcqState();
     if (ctx->acq->b2a_npoint != (on != 0)) {
         ctx->acq->b2a_npoint = on != 0;
+        acq_state_invalidate(ctx->acq);
+    }
+    return BDS_OK;
+}
+
+/* Opt-in N-point search for the B1C grid at 30.69 MS/s (bds_acq_pfa31.h; pfa_pick has the conditions).  Takes effect at the next
+   bds_acq_prepare / bds_acq_run: the cached configuration -- plan, storage mode, layout of the code spectra -- is re-derived. */
+extern "C" int bds_acq_set_b1c_npoint(bds_ctx *ctx, int on) {
+    if (!ctx) return BDS_ERR_ARG;
+    if (!ctx->acq) ctx->acq = new AcqState();
+    if (ctx->acq->b1c_npoint != (on != 0)) {
+        ctx->acq->b1c_npoint = on != 0;
         acq_state_invalidate(ctx->acq);
     }
     return BDS_OK;

@@ -108,7 +108,7 @@ UPDATE_STATE = ["codeFreq", "remCodePhase", "carrFreq", "carrFreqBasis", "remCar
 
 EXPORTS = [
     "bds_create", "bds_destroy", "bds_reload_tuning", "bds_last_error", "bds_device_name", "bds_abi_check", "bds_build_flags", "bds_gen_code", "bds_acquire",
-    "bds_acq_load", "bds_acq_prepare", "bds_acq_run", "bds_acq_set_pair_budget_gb", "bds_acq_set_b2a_npoint", "bds_resample_plan", "bds_fir1_bandpass", "bds_frame_sync", "bds_sync_pattern", "bds_unpack_cplx", "bds_unpack_cplx_file", "bds_acq_grid", "bds_acq_peaks", "bds_acq_candidates", "bds_acq_coherent_sums", "bds_acq_block", "bds_get_timing",
+    "bds_acq_load", "bds_acq_prepare", "bds_acq_run", "bds_acq_set_pair_budget_gb", "bds_acq_set_b2a_npoint", "bds_acq_set_b1c_npoint", "bds_resample_plan", "bds_fir1_bandpass", "bds_frame_sync", "bds_sync_pattern", "bds_unpack_cplx", "bds_unpack_cplx_file", "bds_acq_grid", "bds_acq_peaks", "bds_acq_candidates", "bds_acq_coherent_sums", "bds_acq_block", "bds_get_timing",
     "bds_acquire16", "bds_acq_load16", "bds_acquire_track16",
     "bds_track", "bds_track_mem", "bds_track_loaded_bytes", "bds_track_set_resident_limit", "bds_track_stream_info", "bds_track_correlate", "bds_track_colon", "bds_track_cno", "bds_track_update",
     "bds_track_open", "bds_track_open_mem", "bds_track_open_feed", "bds_track_feed", "bds_track_advance", "bds_track_session_info", "bds_track_close",
@@ -748,6 +748,12 @@ class Context:
         it applies -- everything else runs as with the switch off.  Takes effect at the next acq_prepare / acq_run."""
         self._lib.bds_acq_set_b2a_npoint.restype, self._lib.bds_acq_set_b2a_npoint.argtypes = C.c_int32, [C.c_void_p, C.c_int32]
         self._check(self._lib.bds_acq_set_b2a_npoint(self._h, 1 if on else 0))
+
+    def acq_set_b1c_npoint(self, on):
+        """bds_acq_set_b1c_npoint: opt-in N-point search (N = 613 800 = 31 x 11 x 1800) for B1C at 30.69 MS/s; include/bds_mi355x.h lists when
+        it applies -- everything else runs as with the switch off.  Takes effect at the next acq_prepare / acq_run."""
+        self._lib.bds_acq_set_b1c_npoint.restype, self._lib.bds_acq_set_b1c_npoint.argtypes = C.c_int32, [C.c_void_p, C.c_int32]
+        self._check(self._lib.bds_acq_set_b1c_npoint(self._h, 1 if on else 0))
 
     def acq_run(self, settings, prn_list=None):
         cs = pack_settings(settings)

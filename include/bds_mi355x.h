@@ -142,7 +142,7 @@ typedef struct bds_timing {
     double shader_clock_GHz; /* engine clock the search kernels ran at (sampled workgroups time themselves with the shader
                                 clock against the reference clock); 0 unless BDS_ACQ_CLOCKPROBE=1              */
     int32_t plan_l1, plan_l2; /* two-pass factorisation of fft_len: column length x row length                          */
-    int32_t rows_kernel;    /* row pass of the search: 0 run-time plan (k_rows_inv), 1 k_rows_inv_f, 2 k_rows_wave_f, 3 N-point pair: k_pfa_rows (fft_len 1 987 500 = 53 x 12 x 3125, B1C at 99.375 MS/s), k_pfa32_rows (fft_len 1 060 000 = 53 x 32 x 625, B1C at 53 MS/s) or k_pfa6_rows (fft_len 198 750 = 53 x 6 x 625, B2a at 99.375 MS/s, bds_acq_set_b2a_npoint) */
+    int32_t rows_kernel;    /* row pass of the search: 0 run-time plan (k_rows_inv), 1 k_rows_inv_f, 2 k_rows_wave_f, 3 N-point pair: k_pfa_rows (fft_len 1 987 500 = 53 x 12 x 3125, B1C at 99.375 MS/s), k_pfa32_rows (fft_len 1 060 000 = 53 x 32 x 625, B1C at 53 MS/s), k_pfa6_rows (fft_len 198 750 = 53 x 6 x 625, B2a at 99.375 MS/s, bds_acq_set_b2a_npoint) or k_pfa31_rows (fft_len 613 800 = 31 x 11 x 1800, B1C at 30.69 MS/s, bds_acq_set_b1c_npoint) */
     int32_t cols_kernel;    /* column pass: 0 run-time plan (k_cols_inv_max), 1 tile kernel k_cols_inv_max_f, 2 k_cols_wave_f, 3 k_cols_small_f, 4 k_pfa_cols / k_pfa32_cols / k_pfa6_cols */
     int32_t kernel_flags;   /* bit 0: components interleaved in the inter-pass buffer; bit 1: packed-fp32 butterflies     */
     int32_t refine_path;     /* 1: candidates -> f64 sums -> peak / second peak / fine search as one device chain with a single download (csrc/bds_acq_refine.h); 0: through the host */
@@ -285,6 +285,23 @@ BDS_API int bds_acq_set_pair_budget_gb(bds_ctx *ctx, double gib);
  * numbers either way (they are decided in f64 on the candidates of the search).  Takes effect at the next bds_acq_prepare /
  * bds_acq_run and invalidates the cached configuration as bds_reload_tuning does. */
 BDS_API int bds_acq_set_b2a_npoint(bds_ctx *ctx, int on);
+
+/* Opt-in N-point search for B1C at sizes beyond the two that run by default (99.375 and 53 MS/s), default 0 (off).  One size so far:
+ * 30.69 MS/s (30 samples per chip, the alternative rate of B1C/initSettings.m:57), N = 20 ms = 613 800 = 31 x 11 x 1800 samples
+ * (csrc/bds_acq_pfa31.h): the circular correlation over N instead of the zero-padded L-point pair, all Doppler bins as rotations of ONE
+ * signal spectrum.  With the switch on a run takes this pair when ALL of these hold, and the L-point pair -- exactly as with the switch
+ * off -- otherwise:
+ *   - signal B1C with both components (pilotACQflag 1), N = 613 800 (samplingFreq 30.69e6, acqCohT 10);
+ *   - fp16 storage (the default; BDS_ACQ_FP16=0, BDS_ACQ_PFA=0 and every re-run of a call with fp32 storage or on the run-time-plan
+ *     kernels stay L-point);
+ *   - no resampling;
+ *   - an int8 block, real or I/Q (packed 2+2-bit, int16 and resampled blocks stay L-point);
+ *   - acqStep N / fs an integer >= 1 (50 Hz: 1, 100 Hz: 2; not 25 Hz) with that shift x bins < N.
+ * bds_get_timing then reports rows_kernel 3, cols_kernel 4, fft_len 613800, plan_l1 x plan_l2 = 341 x 1800.  acqResults are the same
+ * numbers either way (they are decided in f64 on the candidates of the search).  99.375 and 53 MS/s keep their own pairs whatever the
+ * switch says.  Takes effect at the next bds_acq_prepare / bds_acq_run and invalidates the cached configuration as bds_reload_tuning
+ * does. */
+BDS_API int bds_acq_set_b1c_npoint(bds_ctx *ctx, int on);
 
 /* Diagnostics of the last bds_acq_run: per searched PRN (in search order) and Doppler
  * bin, the maximum of results(bin,:) (fp32 search value) and its 1-based lag.

@@ -1,10 +1,11 @@
 #!/usr/bin/env python3
 """Time bds_acq_run for any settings, with nothing but native.Context and its timing():
-    python tools/time_acq.py [--b2a [--b2a-npoint 1]] [--int16] [--set name=value ...] [--prns 19,20 | --prns all] [--repeats 5] [--calls 10] [--sieve-error]
+    python tools/time_acq.py [--b2a [--b2a-npoint 1]] [--b1c-npoint 1] [--int16] [--set name=value ...] [--prns 19,20 | --prns all] [--repeats 5] [--calls 10] [--sieve-error]
 The settings start from init_settings_b1c() (53 MS/s, the reference's B1C/initSettings.m), with --b2a from init_settings_b2a() (99.375 MS/s,
 26 bins: `--b2a --prns all` is the grid of BASELINE.json configs[1]); --set overrides fields (numbers are parsed).  --b2a-npoint 1 / 0 sets
 the context's switch for the opt-in N-point search of csrc/bds_acq_pfa6.h (bds_acq_set_b2a_npoint; not given: the library's default, and no
-call of the entry, so that a library of an earlier commit can be timed).  --int16: the block as int16 samples, 256 x the int8 values, under
+call of the entry, so that a library of an earlier commit can be timed); --b1c-npoint 1 / 0 likewise for the opt-in B1C pair of
+csrc/bds_acq_pfa31.h (bds_acq_set_b1c_npoint: `--set samplingFreq=30.69e6 --set IF=7.5e6`).  --int16: the block as int16 samples, 256 x the int8 values, under
 settings.dataType 'int16' (bds_acq_load16: the float64 view, the L-point pair and the host refinement path); the time of acq_load is printed too.
 A synthetic 40 ms block (--b2a: 17 ms) is loaded once and stays in HBM, the code spectra are prepared and one warm-up call runs before the clock
 starts.  Per repeat: the mean over --calls calls of the wall time of acq_run and of the library's own total_ms; then the median and
@@ -31,6 +32,7 @@ def main():
     ap.add_argument("--sieve-error", action="store_true")
     ap.add_argument("--b2a", action="store_true")
     ap.add_argument("--b2a-npoint", type=int, choices=(0, 1), default=None)
+    ap.add_argument("--b1c-npoint", type=int, choices=(0, 1), default=None)
     ap.add_argument("--int16", action="store_true")
     a = ap.parse_args()
     if a.sieve_error:
@@ -63,6 +65,8 @@ def main():
             del os.environ[k]
         if a.b2a_npoint is not None:
             c.acq_set_b2a_npoint(a.b2a_npoint)
+        if a.b1c_npoint is not None:
+            c.acq_set_b1c_npoint(a.b1c_npoint)
         c.acq_load(s, x)
         c.acq_prepare(s)
         return c
