@@ -25,7 +25,9 @@
 #include <cmath>
 #include <cstdarg>
 #include <cstdlib>
+#include <functional>
 #include <map>
+#include <queue>
 #include <set>
 #include <tuple>
 
@@ -149,6 +151,11 @@ struct AcqState {
     size_t mcells_cap = 0;
     std::vector<long> mcells_cs;     // ... and what it holds: uploaded again only when a run's list differs
     std::vector<int> mcells_bin;
+    struct RowsChunks {              // chunk list of a launch pair of the N-point row pass (rows_chunk_plan), planned once per shape
+        int nchunks = 0;
+        int2 *d = nullptr;
+    };
+    std::map<std::tuple<int, int, int>, RowsChunks> rows_chunks;  // (PRNs of the pair, D, slots) -> its list on the device
     std::vector<long> ref_tabs_cs;   // what d_ref_tabs holds (refinement chain: code-spectrum offset and PRN of every searched PRN)
     std::vector<int> ref_tabs_prn;
     Extra *d_extra = nullptr;        // overflow list of the column pass (bds_acq_sieve.h)
@@ -220,6 +227,8 @@ void acq_state_free(AcqState *a) {
                     (void *)a->d_extra, (void *)a->d_extra_count, (void *)a->d_cellmax, (void *)a->d_lb, (void *)a->d_ref_zero,
                     (void *)a->d_ref_cand, (void *)a->d_ref_tabs, (void *)a->d_prefix_c, (void *)a->d_prefix_cq, (void *)a->d_extra2})
         if (p) (void)hipFree(p);
+    for (auto &rc : a->rows_chunks)
+        if (rc.second.d) (void)hipFree(rc.second.d);
     delete a;
 }
 
@@ -443,6 +452,116 @@ static int forward(bds_ctx *ctx, AcqState &a, Loader ld, int nb, float2 *dst, lo
     return BDS_OK;
 }
 
+// Cells one row workgroup walks when a multi-PRN launch pair is cut into UNIFORM chunks: all D bins of its PRN if the launch then still
+// has >= 32 waves of row workgroups for the chip's 512 slots (their tail is what a short launch of long workgroups loses: 8 PRNs per
+// pair in 201-bin workgroups 197.2-197.5 ms per cfg3 call = the lean mode's 197.0, in 67-bin chunks 192.0-192.3; 32 PRNs the same
+// either way, profiles/r05_small_pairs*.txt), else the largest divisor of D that gives them, but no chunk below 32 cells.  A chunk stays
+// inside one PRN's cells, hence a divisor.  list_gc = BDS_ACQ_LIST_GC of the hooks build (> 0: that divisor, -1: D).
+static int rows_uniform_gc(int list_gc, int D, int np, long row_wgs) {
+    int gc = D;
+    if (list_gc > 0 && D % list_gc == 0) {
+        gc = list_gc;
+    } else if (list_gc == 0) {
+        const long want_wgs = 32L * 512;
+        for (int dv = 1; dv <= D; ++dv) {
+            if (D % dv) continue;
+            const int gc_ = D / dv;  // dv chunks per PRN and row
+            if (gc_ < 32 && dv > 1) break;
+            gc = gc_;
+            if (row_wgs * np * dv >= want_wgs) break;
+        }
+    }
+    return gc;
+}
+
+// ---- chunk list of the N-point row pass (bds_acq_pfa.h) ----------------------------------------------------------------------------------
+// A launch of np PRNs x D cells runs MP * K2 workgroups per chunk of cells, every one of them for (cells of the chunk + set-up) cell-times,
+// on `slots` = 2 per CU resident workgroups: the pass ends when the last slot does.  With one chunk size for the whole launch the last round
+// of workgroups runs on a nearly empty chip (13 PRNs in 67-cell chunks: 24.2 rounds cost 25).  The list therefore tapers: whole PRNs in
+// equal chunks first, then one or a few PRNs in chunks that shrink geometrically, all in non-increasing order, so that what is still
+// running when the slots start to drain is small.  No chunk straddles a PRN (a workgroup holds one PRN's code rows).
+// The model: greedy assignment in block order onto the slots -- what the dispatcher does with workgroups of equal resources.
+static constexpr int kRowsWorkWgs = pfa::MP * pfa::K2 - pfa::K2 / 2;  // per chunk: the odd-k2 workgroups of the last row pair return at once
+static constexpr int kRowsSetup8 = 3;                                 // set-up of a workgroup in eighths of a cell (measured 0.29 of a cell: profiles/r16_rows_chunks.txt)
+
+// makespan in eighths of a cell-time of chunks of these sizes, in this order
+static long rows_makespan8(const std::vector<int> &sizes, int slots) {
+    std::priority_queue<long, std::vector<long>, std::greater<long>> free_at;
+    for (int i = 0; i < slots; ++i) free_at.push(0);
+    long end = 0;
+    for (int sz : sizes) {
+        const long d = 8L * sz + kRowsSetup8;
+        for (int w = 0; w < kRowsWorkWgs; ++w) {
+            const long t = free_at.top() + d;
+            free_at.pop();
+            free_at.push(t);
+            end = std::max(end, t);
+        }
+    }
+    return end;
+}
+
+// D cells in k chunks as equal as they come, larger first
+static void rows_split_even(int D, int k, std::vector<int> &out) {
+    for (int i = 0; i < k; ++i) out.push_back(D / k + (i < D % k ? 1 : 0));
+}
+// D cells in chunks of 1 / q of what is left, at most `cap` and at least `least` cells
+static void rows_split_taper(int D, int cap, int q, int least, std::vector<int> &out) {
+    for (int rem = D; rem > 0;) {
+        const int c = std::min(rem, std::max(least, std::min(cap, (rem + q - 1) / q)));
+        out.push_back(c);
+        rem -= c;
+    }
+}
+
+// the chunks (first cell, cells) of a launch of np PRNs x D cells for `slots` resident workgroups; `uniform_gc` = the chunk size the
+// uniform rule would take (always a candidate: the list is never worse than it under the model)
+static std::vector<int2> rows_chunk_plan(int np, int D, int slots, int uniform_gc) {
+    std::vector<int2> best;
+    if (np < 1 || D < 1 || slots < 1) return best;
+    long best_t = -1;
+    std::vector<int> ks;
+    for (int k : {1, 2, 3, 4, 6, (D + std::max(1, uniform_gc) - 1) / std::max(1, uniform_gc)})
+        if (k >= 1 && k <= D && std::find(ks.begin(), ks.end(), k) == ks.end()) ks.push_back(k);
+    std::vector<std::vector<int>> per_prn((size_t)np);
+    auto consider = [&]() {
+        // all chunks of all PRNs, larger first; among equals the order of the cells
+        std::vector<int2> list;
+        for (int p = 0; p < np; ++p) {
+            int c = p * D;
+            for (int sz : per_prn[(size_t)p]) list.push_back(make_int2(c, sz)), c += sz;
+        }
+        std::stable_sort(list.begin(), list.end(), [](const int2 &a, const int2 &b) { return a.y > b.y; });
+        std::vector<int> sizes;
+        for (const int2 &ch : list) sizes.push_back(ch.y);
+        const long t = rows_makespan8(sizes, slots);
+        if (best_t < 0 || t < best_t || (t == best_t && list.size() < best.size())) best_t = t, best = list;
+    };
+    for (int k : ks) {
+        const int cap = (D + k - 1) / k;
+        for (int tapered = 0; tapered <= std::min(np, 3); ++tapered)
+            for (int q : {2, 3, 4})
+                for (int least : {1, 3}) {
+                    if (!tapered && (q != 2 || least != 1)) continue;  // (nothing tapers: one candidate)
+                    for (int p = 0; p < np; ++p) {
+                        per_prn[(size_t)p].clear();
+                        if (p < np - tapered)
+                            rows_split_even(D, k, per_prn[(size_t)p]);
+                        else
+                            rows_split_taper(D, cap, q, least, per_prn[(size_t)p]);
+                    }
+                    consider();
+                }
+    }
+    return best;
+}
+
+int rows_chunk_list(int np, int D, int slots, int *out, int cap) {
+    const std::vector<int2> plan = rows_chunk_plan(np, D, slots, rows_uniform_gc(0, D, np, pfa::MP * pfa::K2));
+    for (int i = 0; i < (int)plan.size() && i < cap; ++i) out[2 * i] = plan[(size_t)i].x, out[2 * i + 1] = plan[(size_t)i].y;
+    return (int)plan.size();
+}
+
 // optional per-cell descriptors (device arrays) for a launch whose cells are not "one PRN, consecutive bins"
 struct CellList {
     const int *bin = nullptr;    // Doppler bin of cell g
@@ -450,6 +569,8 @@ struct CellList {
     const int4 *rng = nullptr;   // searched lag ranges (lo1, hi1, lo2, hi2)
     int gc = 1;                  // consecutive listed cells that share their code spectra (one row workgroup walks them)
     const int *src = nullptr;    // 80 x 4096 plan and bds_acq_pfa6.h only: the rows of listed cell g already lie at cell index src[g] of Bw -- no row pass
+    const int2 *chunks = nullptr;  // bds_acq_pfa.h only: the row pass's chunks (first cell, cells) in place of uniform gc (rows_chunk_plan)
+    int nchunks = 0;
 };
 // where a column pass reports: the sieve (bds_acq_sieve.h); the tile kernel writes per-tile records instead of cellmax / lb (both
 // null then) and uses the list as its overflow list
@@ -1507,10 +1628,10 @@ void AcqRun::launch_list(int ncells, Rec *recs, const CellList &cl, int cell0, h
         return;
     }
     if (pfa) {  // the N-point pair (bds_acq_pfa.h): every lag of the N is searched, the cells come as a list
-        const int gc = std::max(1, cl.gc), chunks = (ncells + gc - 1) / gc;
+        const int gc = std::max(1, cl.gc), chunks = cl.chunks ? cl.nchunks : (ncells + gc - 1) / gc;
         const size_t rows_lds = 2 * 3136 * sizeof(float2);
         want_lds(ctx, pfa::k_pfa_cols<2, false>, pfa::kColsLds);
-        pfa::RowsArgs ra{(const uint32_t *)a.d_Xs, (const uint32_t *)a.d_Cs, (uint32_t *)a.d_Bw, cl.bin, cl.cs, ncells, gc, pfa};
+        pfa::RowsArgs ra{(const uint32_t *)a.d_Xs, (const uint32_t *)a.d_Cs, (uint32_t *)a.d_Bw, cl.bin, cl.cs, ncells, gc, pfa, cl.chunks, cl.nchunks};
         hipLaunchKernelGGL(pfa::k_pfa_rows<2>, dim3((unsigned)(pfa::MP * pfa::K2 * chunks)), dim3(pfa::kRowsThreads), rows_lds, s_main, ra);
         if (mid) (void)hipEventRecord(mid, s_main);
         const int qch = ctx->tune.pfa_qchunk > 0 ? ctx->tune.pfa_qchunk : 1;  // (one tile of a cell, then the same tile of the next cell)
@@ -1582,23 +1703,24 @@ int AcqRun::search() {
             CellList cl;
             cl.bin = d_bin + (size_t)pi0 * D;
             cl.cs = d_cs + (size_t)pi0 * D;
-            // Cells one row workgroup walks: all D bins of its PRN if the launch then still has >= 32 waves of row workgroups for the
-            // chip's 512 slots (their tail is what a short launch of long workgroups loses: 8 PRNs per pair in 201-bin workgroups
-            // 197.2-197.5 ms per cfg3 call = the lean mode's 197.0, in 67-bin chunks 192.0-192.3; 32 PRNs the same either way,
-            // profiles/r05_small_pairs*.txt), else the largest divisor of D that gives them, but no chunk below 32 cells (a
-            // workgroup's set-up: code rows, 60 twiddle registers).  A chunk stays inside one PRN's cells, hence a divisor.
-            cl.gc = D;
-            if (ctx->tune.list_gc > 0 && D % ctx->tune.list_gc == 0) {
-                cl.gc = ctx->tune.list_gc;
-            } else if (ctx->tune.list_gc == 0) {
-                const long want_wgs = 32L * 512;
-                for (int dv = 1; dv <= D; ++dv) {
-                    if (D % dv) continue;
-                    const int gc_ = D / dv;  // dv chunks per PRN and row
-                    if (gc_ < 32 && dv > 1) break;
-                    cl.gc = gc_;
-                    if ((long)(pfa ? pfa_rows_wgs(pfa_kind) : pl.L1) * np_ * dv >= want_wgs) break;
+            // Cells one row workgroup walks: uniform chunks (rows_uniform_gc), or for the pair of bds_acq_pfa.h the tapered list of
+            // rows_chunk_plan -- planned and uploaded when a shape is first seen, looked up on every later call.  BDS_ACQ_LIST_GC of
+            // the hooks build keeps the uniform chunks.
+            cl.gc = rows_uniform_gc(ctx->tune.list_gc, D, np_, pfa ? pfa_rows_wgs(pfa_kind) : pl.L1);
+            if (pfa_kind == 1 && ctx->tune.list_gc == 0) {
+                const int slots = 2 * (ctx->n_cu > 0 ? ctx->n_cu : 256);
+                AcqState::RowsChunks &rc_ = a.rows_chunks[std::make_tuple(np_, D, slots)];
+                if (!rc_.d) {
+                    const std::vector<int2> plan = rows_chunk_plan(np_, D, slots, cl.gc);
+                    int2 *d_plan = nullptr;
+                    BDS_HIP(ctx, hipMalloc((void **)&d_plan, plan.size() * sizeof(int2)));
+                    if (hipMemcpy(d_plan, plan.data(), plan.size() * sizeof(int2), hipMemcpyHostToDevice) != hipSuccess) {
+                        (void)hipFree(d_plan);
+                        BDS_HIP(ctx, hipErrorUnknown);
+                    }
+                    rc_.d = d_plan, rc_.nchunks = (int)plan.size();
                 }
+                cl.chunks = rc_.d, cl.nchunks = rc_.nchunks;
             }
             // (a call is a handful of pairs: all of them are timed, the last, shorter one included -- cell_pair_ms and
             //  cells_per_pair are then the means a kernel trace of the call shows)

@@ -32,6 +32,7 @@
 #include "bds_acq_sieve.h"
 #include "bds_fft_pk.h"
 #include "bds_lds.h"
+#include "bds_tw3125.h"
 
 namespace bds {
 namespace pfa {
@@ -135,6 +136,14 @@ __device__ __forceinline__ v2f unit(int num, int den) {  // exp(+2 pi j num / de
     sincospif(2.0f * (float)num / (float)den, &sn, &cs);
     return (v2f){cs, sn};
 }
+// W3125^n, 0 <= n < 3125, from the table of bds_tw3125.h (correctly rounded, no arithmetic): one 8-byte buffer load per twiddle, the
+// lane's offset the only address arithmetic.  A row pass fetches its stage twiddles once per workgroup.
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t tw3125_rsrc() {
+    return __builtin_amdgcn_make_buffer_rsrc((void *)kTw3125, 0, kTw3125Len * 8, 0x00020000);
+}
+__device__ __forceinline__ v2f tw3125(__amdgpu_buffer_rsrc_t rsrc, int n) {
+    return __builtin_bit_cast(v2f, __builtin_amdgcn_raw_buffer_load_b64(rsrc, n * 8, 0, 0));
+}
 
 // LDS reads of the row pass as single ds_read_b64 (bds_lds.h: the ds_read2_b64 the compiler fuses two reads into is served in groups of
 // 16 lanes at half the rate): y[k] = *(a + BASE + k STEP), byte offsets, one wait per batch
@@ -219,6 +228,10 @@ struct RowsArgs {
     int ncells;          // cells of the launch
     int gc;              // cells a workgroup walks (all of one PRN)
     int shift;           // spectrum bins per Doppler bin (acqStep N / fs)
+    // optional chunk list (k_pfa_rows<2> only; the launch is MP * K2 * nchunks workgroups): chunk i = cells chunks[i].x .. + chunks[i].y
+    // of one PRN.  Absent: uniform chunks of gc cells, chunk i = cells i gc .. i gc + gc - 1.
+    const int2 *chunks = nullptr;
+    int nchunks = 0;
 };
 
 template <int NC>
@@ -230,38 +243,53 @@ __global__ __launch_bounds__(kRowsThreads, 2) void k_pfa_rows(RowsArgs A) {
     const int jj = live ? j : 124;
     const int rp = blockIdx.x % (MP * K2), chunk = blockIdx.x / (MP * K2);
     const int mp = rp / K2, k2 = rp % K2;
-    const int k1 = 2 * mp + half;
-    const bool row_ok = k1 < K1;
-    const int k1c = row_ok ? k1 : K1 - 1;
+    // The two rows of a workgroup, one per half-wave: k1 = 2 mp and 2 mp + 1 of its k2.  The last pair has one row only (k1 = 52; row
+    // 53 is the pad row of the 54 the column pass reads, all zeros): the workgroup of an even k2 takes row 52 of k2 AND of k2 + 1, the one
+    // of the odd k2 has nothing left to do -- no transform runs on a row of zeros.
+    const bool last = mp == MP - 1;
+    if (last && (k2 & 1)) return;
+    const int k1lo = 2 * mp, k1hi = last ? k1lo : k1lo + 1, k2hi = last ? k2 + 1 : k2;  // (half 0: (k1lo, k2), half 1: (k1hi, k2hi))
     float2 *region = reinterpret_cast<float2 *>(pfa_lds) + (size_t)half * 3136;  // 3125 elements per row (+ pad)
-    const int c0 = chunk * A.gc, c1 = min(A.ncells, c0 + A.gc);
+    int c0, c1;
+    if (A.chunks) {
+        if (chunk >= A.nchunks) return;
+        const int2 ch = A.chunks[chunk];
+        c0 = ch.x, c1 = min(A.ncells, ch.x + ch.y);
+    } else {
+        c0 = chunk * A.gc, c1 = min(A.ncells, c0 + A.gc);
+    }
     if (c0 >= c1) return;
 
-    // code rows of this workgroup's PRN (zero for the pad row: its outputs are zeros)
+    // code rows of this workgroup's PRN: one descriptor at the PRN's spectra, one lane offset, component and the 25 strides as scalar /
+    // immediate offsets (as the signal rows below)
     uint32_t cv[NC][25];
     {
-        const uint32_t *crow = A.Cs + A.cs[c0] + ((size_t)k1c * K2 + k2) * K3;
+        const __amdgpu_buffer_rsrc_t cs_rsrc = __builtin_amdgcn_make_buffer_rsrc((void *)(A.Cs + A.cs[c0]), 0, NC * K1 * K2 * K3 * 4, 0x00020000);
+        const int coff = (((half ? k1hi * K2 + k2hi : k1lo * K2 + k2) * K3) + jj) * 4;  // < 2^23 bytes
 #pragma unroll
         for (int c = 0; c < NC; ++c)
 #pragma unroll
-            for (int q = 0; q < 25; ++q) cv[c][q] = row_ok ? crow[(size_t)c * K1 * K2 * K3 + jj + 125 * q] : 0u;
+            for (int q = 0; q < 25; ++q) cv[c][q] = __builtin_amdgcn_raw_buffer_load_b32(cs_rsrc, coff, (c * K1 * K2 * K3 + 125 * q) * 4, 0);
     }
-    // stage twiddles: W3125^(j p) after stage 1, W125^(i u) after stage 2 (thread t = i + 25 pg)
+    // stage twiddles: W3125^(j p) after stage 1, W125^(i u) = W3125^(25 i u) after stage 2 (thread t = i + 25 pg), from the table of
+    // bds_tw3125.h: j <= 124 and p <= 24, i <= 24 and u <= 4, so every index is below 3125 as it stands.
     // (W3125^(j p), p = 5 p0 + p1: the 8 with one of p0, p1 zero are held; of the other 16, kTw1Held are held as well and the rest formed as the
     //  product of two of those 8 -- a product more per component.  All 24 held spilled 43 dwords before the butterflies were fused.)
+    static_assert(124 * 24 < K3 && 25 * 24 * 4 < K3, "table indices need no reduction");
+    const __amdgpu_buffer_rsrc_t tw_rsrc = tw3125_rsrc();
     v2f tw1a[5], tw1b[5], tw2[5];
 #pragma unroll
-    for (int p = 1; p < 5; ++p) tw1a[p] = unit((jj * p) % K3, K3), tw1b[p] = unit((jj * 5 * p) % K3, K3);
+    for (int p = 1; p < 5; ++p) tw1a[p] = tw3125(tw_rsrc, jj * p), tw1b[p] = tw3125(tw_rsrc, jj * 5 * p);
     v2f tw1h[kTw1Held];
 #pragma unroll
-    for (int h = 0; h < kTw1Held; ++h) tw1h[h] = unit((jj * (5 * (h % 4 + 1) + h / 4 + 1)) % K3, K3);  // slot p0 + 5 p1 = (h % 4 + 1) + 5 (h / 4 + 1)
+    for (int h = 0; h < kTw1Held; ++h) tw1h[h] = tw3125(tw_rsrc, jj * (5 * (h % 4 + 1) + h / 4 + 1));  // slot p0 + 5 p1 = (h % 4 + 1) + 5 (h / 4 + 1)
     // stage-2 thread t = 5 i + pg: its five reads / in-place writes sit at 25 (i + 25 r) + 5 pg + c = 5 t + (625 r + c) -- stride 5 over
     // the lanes, conflict-free in the 32-lane halves of a ds_read_b64 and the 16-lane groups of a ds_write_b64 (t = i + 25 pg, the
     // first version, was 2-way in every half-wave: SQ_LDS_BANK_CONFLICT 28 % of the LDS cycles, profiles/r06_b1c_pmc_first.txt)
     const int si = jj / 5, spg = jj % 5;
     const unsigned region_b = lds_offset(region);
 #pragma unroll
-    for (int u = 1; u < 5; ++u) tw2[u] = unit((si * u) % 125, 125);
+    for (int u = 1; u < 5; ++u) tw2[u] = tw3125(tw_rsrc, 25 * si * u);
 
     const __amdgpu_buffer_rsrc_t xs_rsrc = __builtin_amdgcn_make_buffer_rsrc((void *)A.Xs, 0, K1 * K2 * 2 * K3 * 4, 0x00020000);
     // The next cell's Doppler bin is requested right behind this cell's signal loads and taken into a scalar in front of this cell's
@@ -269,10 +297,12 @@ __global__ __launch_bounds__(kRowsThreads, 2) void k_pfa_rows(RowsArgs A) {
     int bin_cur = A.bin[c0];
     for (int cell = c0; cell < c1; ++cell) {
         const int s = bin_cur * A.shift;
-        const int k1s = ((k1c - s) % K1 + K1) % K1, k2s = ((k2 - s) % K2 + K2) % K2, o3 = (K3 - s % K3) % K3;
+        // (the rotated rows of the two halves: scalar arithmetic, one select per lane)
+        const int rlo = ((k1lo - s) % K1 + K1) % K1 * K2 + ((k2 - s) % K2 + K2) % K2, rhi = ((k1hi - s) % K1 + K1) % K1 * K2 + ((k2hi - s) % K2 + K2) % K2;
+        const int o3 = (K3 - s % K3) % K3;
         // (buffer loads / stores: one descriptor, one lane offset, the 25 strides as immediates -- per-access 64-bit address arithmetic was
         //  five vector instructions per load: 8 % of the cell loop)
-        const int xoff = ((k1s * K2 + k2s) * (2 * K3) + o3 + jj) * 4;  // < 2^25 bytes
+        const int xoff = ((half ? rhi : rlo) * (2 * K3) + o3 + jj) * 4;  // < 2^25 bytes
         uint32_t xn[25];
 #pragma unroll
         for (int q = 0; q < 25; ++q) xn[q] = __builtin_amdgcn_raw_buffer_load_b32(xs_rsrc, xoff, 500 * q, 0);
@@ -334,29 +364,46 @@ __global__ __launch_bounds__(kRowsThreads, 2) void k_pfa_rows(RowsArgs A) {
         const unsigned long long dst_base = (unsigned long long)(A.Bw + (size_t)cell * kCellElems + bw_piece(mp, k2, 0));
         const v4i dst_words = {(int)(unsigned)dst_base, (int)((unsigned)(dst_base >> 32) & 0xffffu), (int)(unsigned)((kCellElems - bw_piece(mp, k2, 0)) * 4), 0x00020000};
         // the two rows of the pair meet: after the swap half 0 holds (row 0, row 1) of t'' = e, half 1 of t'' = e + 1
+        // (the two kinds of workgroup part ONCE per cell, in front of the 13 swaps and stores, not at each store)
+        auto store_cell = [&](auto last_pair) {
+            constexpr bool kLast = decltype(last_pair)::value;
 #pragma unroll
-        for (int e = 0; e < 25; e += 2) {
-            uint32_t P[2], Q[2];
+            for (int e = 0; e < 25; e += 2) {
+                uint32_t P[2], Q[2];
 #pragma unroll
-            for (int c = 0; c < 2; ++c) {
-                const uint32_t pe = c < NC ? outp[c < NC ? c : 0][e] : 0u, qo = (c < NC && e + 1 < 25) ? outp[c < NC ? c : 0][e + 1 < 25 ? e + 1 : e] : 0u;
-                // v_permlane32_swap: lanes 32-63 of the first <-> lanes 0-31 of the second
-                const auto r = __builtin_amdgcn_permlane32_swap(pe, qo, false, false);
-                P[c] = r[0], Q[c] = r[1];
+                for (int c = 0; c < 2; ++c) {
+                    const uint32_t pe = c < NC ? outp[c < NC ? c : 0][e] : 0u, qo = (c < NC && e + 1 < 25) ? outp[c < NC ? c : 0][e + 1 < 25 ? e + 1 : e] : 0u;
+                    // v_permlane32_swap: lanes 32-63 of the first <-> lanes 0-31 of the second
+                    const auto r = __builtin_amdgcn_permlane32_swap(pe, qo, false, false);
+                    P[c] = r[0], Q[c] = r[1];
+                }
+                const int tq = e + half;
+                if (live && tq < 25) {  // lag t3 = j + 125 tq
+                    typedef uint32_t u4 __attribute__((ext_vector_type(4)));
+                    const int t3s = j + 125 * tq;
+                    // Issued by hand: loads and stores share the vmcnt counter and return out of order relative to each other, so with stores
+                    // the compiler knows of in flight its first wait for a load of the NEXT cell becomes vmcnt(0) -- the whole latency of this
+                    // cell's 13 stores in front of every cell (the row pass with its stores compiled out ran 17 % faster).  Stores it does not
+                    // know of only make its counted waits longer, never shorter: of the k + S operations a wait lets return, at most S are stores.
+                    // Nothing in this kernel reads the buffer; the end of the kernel makes the stores visible.
+                    if constexpr (!kLast) {
+                        asm volatile("buffer_store_dwordx4 %0, %1, %2, 0 offen\n s_nop 0" ::"v"((u4){P[0], Q[0], P[1], Q[1]}), "v"((int)(bw_piece(0, 0, t3s) * 4)), "s"(dst_words)
+                                     : "memory");
+                    } else {
+                        // the last pair: P is row 52 of k2, Q row 52 of k2 + 1 -- each with the zeros of the pad row into its own piece, the
+                        // piece of k2 + 1 one tile row (kTileLags pieces) behind that of k2
+                        static_assert(bw_piece(0, 1, 0) * 4 == 256, "piece of the next k2");
+                        asm volatile("buffer_store_dwordx4 %0, %2, %3, 0 offen\n s_nop 0\n buffer_store_dwordx4 %1, %2, %3, 0 offen offset:256\n s_nop 0" ::"v"((u4){P[0], 0u, P[1], 0u}),
+                                     "v"((u4){Q[0], 0u, Q[1], 0u}), "v"((int)(bw_piece(0, 0, t3s) * 4)), "s"(dst_words)
+                                     : "memory");
+                    }
+                }
             }
-            const int tq = e + half;
-            if (live && tq < 25) {  // lag t3 = j + 125 tq
-                typedef uint32_t u4 __attribute__((ext_vector_type(4)));
-                const int t3s = j + 125 * tq;
-                // Issued by hand: loads and stores share the vmcnt counter and return out of order relative to each other, so with stores
-                // the compiler knows of in flight its first wait for a load of the NEXT cell becomes vmcnt(0) -- the whole latency of this
-                // cell's 13 stores in front of every cell (the row pass with its stores compiled out ran 17 % faster).  Stores it does not
-                // know of only make its counted waits longer, never shorter: of the k + S operations a wait lets return, at most S are stores.
-                // Nothing in this kernel reads the buffer; the end of the kernel makes the stores visible.
-                asm volatile("buffer_store_dwordx4 %0, %1, %2, 0 offen\n s_nop 0" ::"v"((u4){P[0], Q[0], P[1], Q[1]}), "v"((int)(bw_piece(0, 0, t3s) * 4)), "s"(dst_words)
-                             : "memory");
-            }
-        }
+        };
+        if (__builtin_expect(last, 0))  // (6 of the 318 workgroups of a chunk)
+            store_cell(std::true_type{});
+        else
+            store_cell(std::false_type{});
         __syncthreads();  // region free for the next cell
     }
 }

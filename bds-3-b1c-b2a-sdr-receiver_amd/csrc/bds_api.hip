@@ -445,6 +445,14 @@ extern "C" int bds_pre_run(const bds_settings *s, int max_prn, const double *car
     return BDS_OK;
 }
 
+#ifdef BDS_TEST_HOOKS
+// hooks build only (tests/test_pfa_rows_planner.py): the row pass's chunk list of a launch pair, no device needed
+extern "C" __attribute__((visibility("default"))) int bds_test_rows_chunks(int np, int D, int slots, int *out, int cap) {
+    if (np < 1 || D < 1 || slots < 1 || cap < 0 || (cap > 0 && !out)) return BDS_ERR_ARG;
+    return bds::rows_chunk_list(np, D, slots, out, cap);
+}
+#endif
+
 #ifdef BDS_DEBUG
 // debug build only (csrc/bds_debug.h): failed device-side bounds checks since the last call, all translation units
 extern "C" unsigned int bds_debug_failures_acq();

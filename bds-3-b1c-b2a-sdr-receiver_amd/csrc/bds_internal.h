@@ -43,7 +43,7 @@ struct Tuning {
                                      // rows as fit (default 40: 8 PRNs at cfg3); 0 = minimal (one PRN's row per pair on big grids; small grids batch up
                                      // to 8 GiB), < 0 ("auto") = 60 % of the free device memory
     int rows_grid = 0;                  // BDS_ACQ_ROWS_GRID: workgroups of the (then persistent) row pass; 0 = one per item
-    int list_gc = 0;                    // BDS_ACQ_LIST_GC: cells one row workgroup walks in a multi-PRN launch pair (a divisor of D; 0 = chosen by the launch's size, -1 = all D bins of its PRN)
+    int list_gc = 0;                    // BDS_ACQ_LIST_GC: cells one row workgroup walks in a multi-PRN launch pair (a divisor of D; 0 = chosen by the launch's size -- the pair of bds_acq_pfa.h then takes the tapered chunk list of rows_chunk_plan instead --, -1 = all D bins of its PRN)
     bool no_bwreuse = false;            // BDS_ACQ_NO_BWREUSE: the B2a second-peak pass runs its own row pass (A/B, tests)
     bool overlap = false;               // BDS_ACQ_OVERLAP: column pass of group k on a second stream beside the row pass of group k+1
     double kdelta = 0;                  // BDS_ACQ_KDELTA: test hook, sieve tolerance override (0 = per-mode default)
@@ -84,6 +84,9 @@ struct AcqState;    // bds_acq.hip
 struct TrackState;  // bds_track.hip
 void acq_state_free(AcqState *);
 void acq_state_invalidate(AcqState *);  // forget the configuration (plan, storage mode, cached spectra): re-derived by the next prepare
+// The chunk list of the N-point row pass for a launch pair of np PRNs x D cells on `slots` resident workgroups (bds_acq.hip,
+// rows_chunk_plan) as (first cell, cells) pairs: the number of chunks, of which the first min(n, cap) are written to out.
+int rows_chunk_list(int np, int D, int slots, int *out, int cap);
 void track_state_free(TrackState *);
 // BDS_OK, or BDS_ERR_ARG with a message naming the context's open tracking session: `who` (a one-shot tracking call, a
 // second bds_track_open*) cannot run beside it

@@ -1,0 +1,137 @@
+// Row-pass driver of the N-point search pair (csrc/bds_acq_pfa.h) for tests/test_pfa_rows_chunks_gpu.py: launches k_pfa_rows<2> once with
+// a chunk table (RowsArgs::chunks, as csrc/bds_acq.hip launches a multi-PRN pair) and once on the uniform path (gc cells per chunk, no
+// table) for the same cells, each into a buffer of its own, and writes both buffers with their guards.  No arithmetic of its own: inputs
+// and float64 references are tests/pfa_cases.py's.  Any HIP error, a malformed case or a chunk outside the cells ends the program with a
+// non-zero status before anything is launched.
+//   hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=fast -fno-slp-vectorize -I bds-3-b1c-b2a-sdr-receiver_amd/csrc
+//         tools/probe/pfa_rows_chunks.hip -o pfa_rows_chunks && ./pfa_rows_chunks case.bin out.bin
+//
+// File format as tools/probe/pfa_stages.hip (little endian): int64 count, then per array int64 byte length + the bytes (padded to 8).
+// Case: [0] int64 header {magic, 4, ncells, gc, shift, nslots, guard elements};  [1] uint32 Xs[53][12][6250];  [2] uint32 Cs[nslots][2][N];
+//       [3] int32 bin[ncells];  [4] int64 cs[ncells];  [5] int32 chunks[n][2] = (first cell, cells)
+//       -> [0] guard | Bw of the launch with the table (prefilled 0xff) | guard;  [1] the same of the uniform launch
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstdint>
+#include <cstdio>
+#include <cstdlib>
+#include <vector>
+
+#include "bds_acq_pfa.h"
+
+using namespace bds::pfa;
+
+#define CK(x)                                                                                  \
+    do {                                                                                       \
+        hipError_t e_ = (x);                                                                   \
+        if (e_ != hipSuccess) {                                                                \
+            fprintf(stderr, "HIP error %s:%d %s: %s\n", __FILE__, __LINE__, #x, hipGetErrorString(e_)); \
+            exit(2);                                                                           \
+        }                                                                                      \
+    } while (0)
+#define REQUIRE(c)                                                        \
+    do {                                                                  \
+        if (!(c)) {                                                       \
+            fprintf(stderr, "bad case %s:%d: %s\n", __FILE__, __LINE__, #c); \
+            exit(3);                                                      \
+        }                                                                 \
+    } while (0)
+
+constexpr int64_t kMagic = 0x5046415354414745ll;  // "PFASTAGE"
+constexpr uint32_t kGuardWord = 0xA5C31E87u;
+
+typedef std::vector<unsigned char> Bytes;
+
+static std::vector<Bytes> read_arrays(const char *path) {
+    FILE *f = fopen(path, "rb");
+    REQUIRE(f);
+    int64_t n = 0;
+    REQUIRE(fread(&n, 8, 1, f) == 1 && n > 0 && n < 64);
+    std::vector<Bytes> a((size_t)n);
+    for (auto &b : a) {
+        int64_t len = 0;
+        REQUIRE(fread(&len, 8, 1, f) == 1 && len >= 0 && len < (1ll << 32));
+        b.resize((size_t)((len + 7) / 8 * 8));
+        REQUIRE(len == 0 || fread(b.data(), 1, b.size(), f) == b.size());
+        b.resize((size_t)len);
+    }
+    fclose(f);
+    return a;
+}
+
+static void write_array(FILE *f, const void *p, size_t len) {
+    const int64_t l = (int64_t)len;
+    static const unsigned char pad[8] = {0};
+    REQUIRE(fwrite(&l, 8, 1, f) == 1 && fwrite(p, 1, len, f) == len);
+    REQUIRE(len % 8 == 0 || fwrite(pad, 1, 8 - len % 8, f) == 8 - len % 8);
+}
+
+template <class T>
+static T *upload(const Bytes &b) {
+    T *d = nullptr;
+    CK(hipMalloc((void **)&d, b.size() ? b.size() : 8));
+    if (!b.empty()) CK(hipMemcpy(d, b.data(), b.size(), hipMemcpyHostToDevice));
+    return d;
+}
+
+int main(int argc, char **argv) {
+    if (argc != 3) {
+        fprintf(stderr, "usage: pfa_rows_chunks case.bin out.bin\n");
+        return 3;
+    }
+    const std::vector<Bytes> in = read_arrays(argv[1]);
+    REQUIRE(in.size() == 6 && in[0].size() >= 7 * 8);
+    const int64_t *H = (const int64_t *)in[0].data();
+    REQUIRE(H[0] == kMagic && H[1] == 4);
+    const int ncells = (int)H[2], gc = (int)H[3], shift = (int)H[4], nslots = (int)H[5];
+    const size_t guard = (size_t)H[6];
+    REQUIRE(ncells >= 1 && ncells <= 16 && gc >= 1 && shift >= 1 && nslots >= 1 && nslots <= 8 && guard >= 1024 && guard <= (1u << 22));
+    REQUIRE(in[1].size() == (size_t)2 * NP * 4 && in[2].size() == (size_t)nslots * 2 * NP * 4);
+    REQUIRE(in[3].size() == (size_t)ncells * 4 && in[4].size() == (size_t)ncells * 8);
+    const int *bin = (const int *)in[3].data();
+    const int64_t *cs = (const int64_t *)in[4].data();
+    for (int c = 0; c < ncells; ++c) {  // what pfa_shift and the cell lists of csrc/bds_acq.hip guarantee
+        REQUIRE(bin[c] >= 0 && (long)bin[c] * shift < NP);
+        REQUIRE(cs[c] >= 0 && cs[c] % (2 * NP) == 0 && cs[c] / (2 * NP) < nslots);
+    }
+    REQUIRE(in[5].size() >= 8 && in[5].size() % 8 == 0);
+    const int nchunks = (int)(in[5].size() / 8);
+    const int *ch = (const int *)in[5].data();
+    REQUIRE(nchunks <= 16);
+    for (int i = 0; i < nchunks; ++i) {  // inside the cells, and one PRN per chunk (the kernel takes cs[first cell] for all of them)
+        REQUIRE(ch[2 * i] >= 0 && ch[2 * i + 1] >= 1 && ch[2 * i] + ch[2 * i + 1] <= ncells);
+        for (int c = ch[2 * i]; c < ch[2 * i] + ch[2 * i + 1]; ++c) REQUIRE(cs[c] == cs[ch[2 * i]]);
+    }
+    for (int c0 = 0; c0 < ncells; c0 += gc)  // the uniform launch: the same rule
+        for (int c = c0; c < ncells && c < c0 + gc; ++c) REQUIRE(cs[c] == cs[c0]);
+    FILE *f = fopen(argv[2], "wb");
+    REQUIRE(f);
+    const int64_t two = 2;
+    REQUIRE(fwrite(&two, 8, 1, f) == 1);
+
+    uint32_t *d_Xs = upload<uint32_t>(in[1]), *d_Cs = upload<uint32_t>(in[2]), *d_all;
+    int *d_bin = upload<int>(in[3]);
+    long *d_cs = upload<long>(in[4]);
+    int2 *d_chunks = upload<int2>(in[5]);
+    const size_t body = (size_t)ncells * kCellElems, total = body + 2 * guard;
+    CK(hipMalloc((void **)&d_all, total * 4));
+    std::vector<uint32_t> all(total);
+    const size_t rows_lds = 2 * 3136 * sizeof(float2);
+    for (int pass = 0; pass < 2; ++pass) {
+        std::fill(all.begin(), all.end(), kGuardWord);
+        std::fill(all.begin() + guard, all.begin() + guard + body, 0xFFFFFFFFu);
+        CK(hipMemcpy(d_all, all.data(), total * 4, hipMemcpyHostToDevice));
+        RowsArgs ra{d_Xs, d_Cs, d_all + guard, d_bin, d_cs, ncells, gc, shift};
+        int chunks = (ncells + gc - 1) / gc;
+        if (pass == 0) ra.chunks = d_chunks, ra.nchunks = nchunks, chunks = nchunks;
+        hipLaunchKernelGGL(k_pfa_rows<2>, dim3((unsigned)(MP * K2 * chunks)), dim3(kRowsThreads), rows_lds, 0, ra);
+        CK(hipGetLastError());
+        CK(hipDeviceSynchronize());
+        CK(hipMemcpy(all.data(), d_all, total * 4, hipMemcpyDeviceToHost));
+        write_array(f, all.data(), total * 4);
+    }
+    REQUIRE(fclose(f) == 0);
+    printf("ok\n");
+    return 0;
+}
