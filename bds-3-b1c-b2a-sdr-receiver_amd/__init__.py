@@ -19,4 +19,5 @@ from .tracking import tracking, NB_tracking, WB_tracking, pre_run, acquire_track
 from .framesync import frame_sync, unpack_cplx  # noqa: F401
 from .distributed import shard_prns, shard_joint, sharded_acquisition, sharded_acquisition_joint  # noqa: F401
 from .probedata import probe_data, ProbeResult  # noqa: F401
+from .corrfn import corr_function, track_states  # noqa: F401
 from . import native, synth  # noqa: F401

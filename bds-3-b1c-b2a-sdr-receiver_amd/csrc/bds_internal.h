@@ -88,6 +88,15 @@ void acq_state_invalidate(AcqState *);  // forget the configuration (plan, stora
 // rows_chunk_plan) as (first cell, cells) pairs: the number of chunks, of which the first min(n, cap) are written to out.
 int rows_chunk_list(int np, int D, int slots, int *out, int cap);
 void track_state_free(TrackState *);
+// bds_track.hip, for bds_corrfn.hip: what an open-loop replay shares with the trackers
+struct TrkOpenLoop {
+    int mode, pilot, fmt, code_len;  // BDS_TRACK_*, pilot correlators on, kFmt* (bds_trk_replica.h), 10230
+    double fs, inv_fs;
+    long long n_samples;             // whole samples in the record
+    const int8_t *d_prim;            // the per-PRN code tables on the device (bds_trk_replica.h: kTabPad, kTabStride)
+    size_t resident_limit;           // bds_track_set_resident_limit (0: none)
+};
+int track_open_loop_setup(bds_ctx *ctx, const bds_settings &s, size_t n_bytes, TrkOpenLoop &o);
 // BDS_OK, or BDS_ERR_ARG with a message naming the context's open tracking session: `who` (a one-shot tracking call, a
 // second bds_track_open*) cannot run beside it
 int track_session_guard(bds_ctx *ctx, const char *who);

@@ -38,6 +38,7 @@
 #include "bds_debug.h"
 #include "bds_internal.h"
 #include "bds_strict_math.h"
+#include "bds_trk_replica.h"
 
 namespace bds {
 
@@ -45,7 +46,6 @@ namespace bds {
 // 1-ms B2a epochs (measured on 12 channels at 99.375 MS/s, us per epoch: B1C WB 148 / 93 / 84 / 82 and
 // B2a 23.3 / 20.2 / 21.7 / 29.7 at 1024 / 2048 / 4096 / 8192)
 static constexpr int kTrkThreads = 256;
-static constexpr size_t kDataSlack = 256;  // bytes past the record a segment's aligned dword reads may touch
 static constexpr int kNSums = 18;      // I_E,Q_E,I_P,Q_P,I_L,Q_L x {data, pilot BOC11 / B2a pilot, pilot BOC61}
 
 struct ChanState {
@@ -84,26 +84,7 @@ struct TrkParams {
     long long win_end;  // one past the last sample held
 };
 
-// Sample formats of the IF record.  Packed (the input of B2a/include/unpack_cplx.m:18-30): complex sample n is nibble n & 1 of
-// byte n >> 1, low nibble first; per nibble bit 0 / 1 = I / Q negative, bit 2 / 3 = |I| / |Q| is 3 (else 1).
-// 16-bit records (settings.dataType 1): little-endian int16 samples (fileType 1) or interleaved I, Q int16 pairs (fileType 2).
-enum : int { kFmtReal = 0, kFmtIQ = 1, kFmtPacked = 2, kFmtReal16 = 3, kFmtIQ16 = 4 };
-__host__ __device__ constexpr int fmt_align(int fmt) { return fmt == kFmtPacked ? 32 : 16; }  // samples: 16 bytes at least
-// bytes of one sample of an unpacked format
-__host__ __device__ constexpr int fmt_bps(int fmt) { return fmt == kFmtIQ16 ? 4 : fmt == kFmtIQ || fmt == kFmtReal16 ? 2 : 1; }
-__host__ __device__ constexpr bool fmt_complex(int fmt) { return fmt == kFmtIQ || fmt == kFmtPacked || fmt == kFmtIQ16; }
-__host__ __device__ constexpr bool fmt_16bit(int fmt) { return fmt == kFmtReal16 || fmt == kFmtIQ16; }
-// bytes of n samples (packed: n even -- window and span bounds are kept even, the file itself holds whole bytes)
-__host__ __device__ constexpr long long fmt_bytes(int fmt, long long n) { return fmt == kFmtPacked ? n / 2 : n * fmt_bps(fmt); }
-// samples in n bytes (whole ones: a trailing part of a sample or pair does not count)
-__host__ __device__ constexpr long long fmt_samples(int fmt, long long n) { return fmt == kFmtPacked ? n * 2 : n / fmt_bps(fmt); }
-// one packed byte -> the int8 quadruple (I1, Q1, I2, Q2) unpack_cplx writes for it, without a branch: magnitudes 1 | 2 bit,
-// then two's complement in every byte whose sign bit is set ((m ^ 0xff) + 1 never carries out of a byte for m = 1, 3)
-__device__ __forceinline__ uint32_t iq_of_packed(uint32_t b) {
-    const uint32_t sg = (b & 1u) | ((b & 2u) << 7) | ((b & 0x10u) << 12) | ((b & 0x20u) << 19);
-    const uint32_t mg = 0x01010101u | ((b & 4u) >> 1) | ((b & 8u) << 6) | ((b & 0x40u) << 11) | ((b & 0x80u) << 18);
-    return (mg ^ (sg * 0xffu)) + sg;
-}
+// (the sample formats kFmt*, fmt_* and iq_of_packed: bds_trk_replica.h)
 
 struct TrkOut {  // device arrays [n_ch][n_epochs]
     double *absoluteSample, *codeFreq, *carrFreq, *I_P, *I_E, *I_L, *Q_E, *Q_P, *Q_L;
@@ -118,9 +99,7 @@ struct TrkOut {  // device arrays [n_ch][n_epochs]
 //   BOC(6,1): twelfths (-1)^ii c, ii = 1..12 (generatePilotBOC61.m:89-96)
 // with kTabPad wrapped entries on both sides, so a look-up is one clamped index and one byte load
 // (deriving chip, sub-chip sign and wrap from the index cost ~11 instructions per look-up, nine
-// look-ups per sample in wide-band mode).
-static constexpr int kTabPad = 32;
-static constexpr long kTabStride = 122880;  // >= 12 * 10230 + 2 * kTabPad, multiple of 64
+// look-ups per sample in wide-band mode).  (kTabPad, kTabStride: bds_trk_replica.h)
 __device__ __forceinline__ float tab_at(const int8_t *__restrict__ tab, int n_units, int i1) {
     int j = i1 + (kTabPad - 2);  // unit index i1 - 2, shifted by the left padding
     BDS_DASSERT(j >= 0 && j <= n_units + 2 * kTabPad - 1);  // (the clamp below is a guard, never the intended look-up)
@@ -135,33 +114,7 @@ __device__ __forceinline__ char2 tab2_at(const int8_t *__restrict__ tab, int n_u
     return reinterpret_cast<const char2 *>(tab)[j];
 }
 
-// The reference's replica index vectors are MATLAB colon vectors,
-//     tcode = (rem -+ spc)[*2] : step[*2] : ((blksize-1)*step + rem -+ spc)[*2]     (tracking.m:260-286, NB_tracking.m:271-297,
-//                                                                                      WB_tracking.m:289-317),
-// and MATLAB does not build a:d:b as a + k d throughout (MathWorks' published colonop.m, Technical Solution 1-4FLI96): with
-// n = round((b-a)/d) intervals (one less if a + n d overshoots b by more than tol = 2 eps max(|a|,|b|)) and the right end
-// c = a + n d snapped to b within tol, elements 0 .. floor(n/2) are a + k d, the elements after them c - (n-k) d -- generated from
-// the RIGHT end --, and the mid-point of an even n is (a+c)/2.  The second half differs from a + k d by 0-2 ulp of tcode, which
-// moves ceil() for a sample that sits on a chip boundary to rounding (round 6; oracle/matlab.py m_colon is the checker's copy).
-struct ColonVec {
-    double a, d, c;
-    int n, h;
-    bool even;
-};
-__device__ __forceinline__ ColonVec colon_vec(double a, double d, double b) {
-    ColonVec v;
-    const double tol = 2.0 * 2.220446049250313e-16 * fmax(fabs(a), fabs(b));
-    long n = (long)floor((b - a) / d + 0.5);  // MATLAB round() of a non-negative quotient (the tcode vectors ascend)
-    if (a + (double)n * d - b > tol) n -= 1;
-    double c = a + (double)n * d;
-    if (c - b > -tol) c = b;
-    v.a = a, v.d = d, v.c = c, v.n = (int)n, v.h = (int)(n / 2), v.even = (n & 1) == 0;
-    return v;
-}
-__device__ __forceinline__ double colon_at(const ColonVec &v, int k) {
-    const double fwd = v.a + (double)k * v.d, bwd = v.c - (double)(v.n - k) * v.d;
-    return k > v.h ? bwd : (v.even && k == v.h) ? (v.a + v.c) / 2 : fwd;
-}
+// (the reference's replica index vectors -- ColonVec, colon_vec, colon_at --: bds_trk_replica.h)
 // the three replica vectors of an epoch: E, P, L
 template <int SCALE2>
 __device__ __forceinline__ void epoch_colons(double rem, double step, double spacing, long blk, ColonVec cv[3]) {
@@ -326,24 +279,7 @@ __device__ __forceinline__ void correlate_slice(const int8_t *__restrict__ data,
 //   phase 2  the index steps of the six (E/P/L x {code, BOC(6,1)}) sequences are spread over the
 //            threads; each finds its k_u, reads S(k_u) = base + local prefix and adds its term in f64
 static constexpr int kCap1 = 256, kCap6 = 1280;  // code / BOC(6,1) table entries of a wave's pass staged in LDS
-template <int R6>
-__device__ __forceinline__ double code_arg(const ColonVec &v, int k) {
-    double t = colon_at(v, k);  // element k of the reference's colon vector (-ffp-contract=off: one rounding per operation)
-    if (R6) t = t * 6;
-    return t;
-}
-
-// first k in (k_lo, k_hi] with ceil(arg(k)) >= u, given ceil(arg(k_lo)) < u <= ceil(arg(k_hi))
-template <int R6>
-__device__ __forceinline__ int first_sample_of(const ColonVec &v, double inv_inc, int u, int k_lo, int k_hi) {
-    const double thr = (double)(u - 1);  // ceil(t) >= u  <=>  t > u - 1
-    const double tgt = R6 ? thr * (1.0 / 6.0) : thr;  // a prediction only: confirmed below with the exact expression
-    int kc = (int)floor((tgt - v.a) * inv_inc) + 1;
-    kc = max(k_lo + 1, min(kc, k_hi));
-    while (kc > k_lo + 1 && code_arg<R6>(v, kc - 1) > thr) --kc;
-    while (kc < k_hi && !(code_arg<R6>(v, kc) > thr)) ++kc;
-    return kc;
-}
+// (code_arg, first_sample_of -- the exact search of an index step's first sample --: bds_trk_replica.h)
 
 // LDS of one wave of correlate_runs<., SEG>: prefix sums, segment bases, rotation table, code-table slices
 // (prec: TrkParams::prec -- 0 fp32 carrier + fp32 local prefix sums, 1 f64 prefix sums, 2 f64 carrier too, 3 the
@@ -354,33 +290,7 @@ __host__ __device__ constexpr size_t runs_wave_lds(int seg, int prec) {
 static inline size_t runs_lds_bytes(int seg, int prec) {
     return std::max<size_t>(runs_wave_lds(seg, prec) * (kTrkThreads / 64), sizeof(double) * (kTrkThreads / 64) * kNSums);
 }
-__device__ __forceinline__ void wave_sync() {  // LDS written by this wave is read by other lanes of this wave
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-// 64-lane inclusive f64 add-scan on the DPP network (row shifts inside the 16-lane rows, then the row
-// broadcasts): 3 instructions per step instead of two LDS-pipe permutes; lane 63 ends up with the total
-template <int CTRL, int ROW_MASK, bool BOUND>
-__device__ __forceinline__ double dpp_f64(double v) {
-    int lo = __double2loint(v), hi = __double2hiint(v);
-    lo = __builtin_amdgcn_update_dpp(0, lo, CTRL, ROW_MASK, 0xf, BOUND);
-    hi = __builtin_amdgcn_update_dpp(0, hi, CTRL, ROW_MASK, 0xf, BOUND);
-    return __hiloint2double(hi, lo);
-}
-__device__ __forceinline__ double wave_scan_incl(double v) {
-    v += dpp_f64<0x111, 0xf, true>(v);   // row_shr:1
-    v += dpp_f64<0x112, 0xf, true>(v);   // row_shr:2
-    v += dpp_f64<0x114, 0xf, true>(v);   // row_shr:4
-    v += dpp_f64<0x118, 0xf, true>(v);   // row_shr:8
-    v += dpp_f64<0x142, 0xa, false>(v);  // row_bcast:15 into rows 1, 3
-    v += dpp_f64<0x143, 0xc, false>(v);  // row_bcast:31 into rows 2, 3
-    return v;
-}
-__device__ __forceinline__ double lane_f64(double v, int l) {  // broadcast of lane l (compile-time constant)
-    return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), l), __builtin_amdgcn_readlane(__double2loint(v), l));
-}
+// (wave_sync, the 64-lane f64 add-scan wave_scan_incl and lane_f64: bds_trk_replica.h)
 
 // The waves of a workgroup work independently (wave w on samples k0 + w 64 SEG .. of each chunk, its own LDS
 // slice, no workgroup barrier before the final reduction): the kernel is bound by latency -- HBM reads,
@@ -2522,6 +2432,23 @@ extern "C" int bds_track_stream_info(bds_ctx *ctx, int32_t *pieces, long long *r
     return BDS_OK;
 }
 
+namespace bds {
+// What bds_corrfn.hip takes over from the trackers for a record of n_bytes: mode, pilot, sample format and sample count as
+// fill_params derives them (with its argument errors), the device's code tables, the resident limit of the context.
+int track_open_loop_setup(bds_ctx *ctx, const bds_settings &s, size_t n_bytes, TrkOpenLoop &o) {
+    if (!ctx->trk) ctx->trk = new TrackState();
+    TrackState &t = *ctx->trk;
+    TrkParams p{};
+    if (int rc = fill_params(ctx, s, p, 1, n_bytes)) return rc;
+    if (int rc = ensure_prim(ctx, t, s.signal)) return rc;
+    o.mode = p.mode, o.pilot = p.pilot, o.fmt = p.cplx, o.code_len = p.code_len;
+    o.fs = p.fs, o.inv_fs = p.inv_fs, o.n_samples = p.n_bytes;
+    o.d_prim = t.d_prim;
+    o.resident_limit = t.resident_limit;
+    return BDS_OK;
+}
+}  // namespace bds
+
 extern "C" int bds_track_correlate(bds_ctx *ctx, const bds_settings *s, const int8_t *file_bytes, size_t n_bytes,
                                    int n_ch, const int32_t *prn, const double *state6, double *sums18) {
     if (!ctx || !s || !file_bytes || !prn || !state6 || !sums18 || n_ch < 1) return BDS_ERR_ARG;
@@ -2558,12 +2485,29 @@ extern "C" int bds_track_correlate(bds_ctx *ctx, const bds_settings *s, const in
     BDS_HIP(ctx, hipMemcpyAsync(d_prn, prn, sizeof(int) * n_ch, hipMemcpyHostToDevice, st(ctx)));
     BDS_HIP(ctx, hipMemcpyAsync(d_s6, state6, sizeof(double) * 6 * n_ch, hipMemcpyHostToDevice, st(ctx)));
     dim3 gc(nblocks, n_ch);
+    // bds_get_timing after this call: search_ms = the two kernels alone (the upload and the download stand outside the events)
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    struct Events {
+        hipEvent_t *e;
+        ~Events() {
+            for (int i = 0; i < 2; ++i)
+                if (e[i]) (void)hipEventDestroy(e[i]);
+        }
+    } ev_scope{ev};
+    BDS_HIP(ctx, hipEventCreate(&ev[0]));
+    BDS_HIP(ctx, hipEventCreate(&ev[1]));
+    BDS_HIP(ctx, hipEventRecord(ev[0], st(ctx)));
     BDS_TRK_LAUNCH(k_trk_correlate_open, gc, (p.runs ? runs_lds_bytes(p.runs, p.prec) : 0), st(ctx), (const int8_t *)d_data, (const int8_t *)t.d_prim, p,
                    (const int *)d_prn, (const double *)d_s6, d_part, nblocks);
     hipLaunchKernelGGL(k_trk_reduce_open, dim3(n_ch), dim3(64), 0, st(ctx), (const double *)d_part, nblocks, d_sums);
     BDS_HIP(ctx, hipGetLastError());
+    BDS_HIP(ctx, hipEventRecord(ev[1], st(ctx)));
     BDS_HIP(ctx, hipMemcpyAsync(sums18, d_sums, sizeof(double) * (size_t)n_ch * kNSums, hipMemcpyDeviceToHost, st(ctx)));
     BDS_HIP(ctx, hipStreamSynchronize(st(ctx)));
+    float ms = 0.f;
+    BDS_HIP(ctx, hipEventElapsedTime(&ms, ev[0], ev[1]));
+    ctx->timing = bds_timing{};
+    ctx->timing.search_ms = ms;
     return BDS_OK;
 }
 

@@ -118,11 +118,14 @@ EXPORTS = [
     "bds_multi_rccl_ranks", "bds_acquire_multi", "bds_shard_jobs", "bds_acq_job_cost",
     "bds_synth", "bds_synth_file", "bds_synth_noise",
     "bds_probe_data", "bds_probe_data_file", "bds_probe_set_piece_segments",
+    "bds_corr_function", "bds_corr_function_mem",
 ]
 # the entries marked BDS_DEV_API in the header: their record pointer is device memory (device_span below makes it)
 DEVICE_EXPORTS = ["bds_synth_dev", "bds_acq_load_dev", "bds_track_dev", "bds_track_open_dev", "bds_track_feed_dev"]
 # the entry marked BDS_PROBE_DEV_API: a device pointer as well
 PROBE_DEVICE_EXPORTS = ["bds_probe_data_dev"]
+# the entry marked BDS_CORR_DEV_API: a device pointer as well
+CORR_DEVICE_EXPORTS = ["bds_corr_function_dev"]
 
 _lib = None
 HOOKS_LIB = os.path.join(os.path.dirname(os.path.abspath(__file__)), "libbds_mi355x_hooks.so")
@@ -245,6 +248,11 @@ def lib():
         L.bds_probe_data_file.restype, L.bds_probe_data_file.argtypes = i32, [vp, SP, C.c_char_p, i64, i64, PP]
         L.bds_probe_data_dev.restype, L.bds_probe_data_dev.argtypes = i32, [vp, SP, vp, sz, i64, PP]
         L.bds_probe_set_piece_segments.restype, L.bds_probe_set_piece_segments.argtypes = i32, [vp, i64]
+    if hasattr(L, "bds_corr_function"):  # (as above: a build of an older commit has no correlation function)
+        tail = [i32, _IP, _DP, i32, _DP, _DP, _IP]  # n_items, prn, state6, n_taps, taps, out, n_comp
+        L.bds_corr_function.restype, L.bds_corr_function.argtypes = i32, [vp, SP, C.c_char_p] + tail
+        L.bds_corr_function_mem.restype, L.bds_corr_function_mem.argtypes = i32, [vp, SP, i8p, sz] + tail
+        L.bds_corr_function_dev.restype, L.bds_corr_function_dev.argtypes = i32, [vp, SP, vp, sz] + tail
     L.bds_abi_check.restype, L.bds_abi_check.argtypes = i32, [i32, i32, i32, i32]
     if L.bds_abi_check(C.sizeof(Settings), C.sizeof(Channel), C.sizeof(TrackOut), C.sizeof(Timing)) != 0:
         raise ImportError("ctypes struct layout does not match libbds_mi355x.so (include/bds_mi355x.h changed?)")
@@ -1150,6 +1158,33 @@ class Context:
                                                   prn.ctypes.data_as(_IP), st.ctypes.data_as(_DP),
                                                   sums.ctypes.data_as(_DP)))
         return sums
+
+    def corr_function(self, settings, source, prns, state6, taps):
+        """bds_corr_function / _mem / _dev: the correlation function of the items (prns[i], state6[i]) -- one epoch of one channel
+        each, as track_correlate takes them -- at the tap offsets `taps` (primary-code chips).  source: a path, the record's raw
+        bytes as track() takes them, or those bytes as a device array.  Returns complex128 [n_items, n_comp, n_taps], I + jQ of the
+        raw sums; comp 0 data, 1 the pilot (when on), 2 the pilot BOC(6,1) (wide-band mode)."""
+        cs = pack_settings(settings)
+        prn = np.ascontiguousarray(prns, dtype=np.int32).reshape(-1)
+        st = np.ascontiguousarray(state6, dtype=np.float64).reshape(-1, 6)
+        if st.shape[0] != prn.size:
+            raise ValueError(f"corr_function: {prn.size} PRNs for {st.shape[0]} states")
+        tp = np.ascontiguousarray(taps, dtype=np.float64).reshape(-1)
+        out = np.zeros((max(prn.size, 1), 3, max(tp.size, 1), 2))  # room for three components; n_comp tells how many came back
+        n_comp = C.c_int32(0)
+        tail = (prn.size, prn.ctypes.data_as(_IP), st.ctypes.data_as(_DP), tp.size, tp.ctypes.data_as(_DP), out.ctypes.data_as(_DP),
+                C.byref(n_comp))
+        if isinstance(source, (str, bytes, os.PathLike)):
+            self._check(self._lib.bds_corr_function(self._h, C.byref(cs), os.fsencode(source), *tail))
+        elif is_device_array(source):
+            ptr, n_bytes, keep, _ = device_record(settings, source, self.device)
+            self._check(self._lib.bds_corr_function_dev(self._h, C.byref(cs), ptr, n_bytes, *tail))
+        else:
+            a, _ = record_bytes(settings, source)
+            self._check(self._lib.bds_corr_function_mem(self._h, C.byref(cs), a.ctypes.data_as(C.POINTER(C.c_int8)), a.size, *tail))
+        nc = int(n_comp.value)
+        z = out.reshape(-1)[: prn.size * nc * tp.size * 2].reshape(prn.size, nc, tp.size, 2)
+        return z[..., 0] + 1j * z[..., 1]
 
     def track_colon(self, a, d, b, k):
         """Test aid: element k[i] of the colon vector a[i]:d[i]:b[i] as the tracking kernels form it, evaluated on the device.

@@ -46,13 +46,13 @@ compile() {  # source, object, extra flags...
             # the search: FMA contraction on; SLP packing off (v_pk_* f32 runs at the scalar rate on
             # gfx950 and costs register shuffles: measured -4.6 % on the cell pair)
             [ "$f" = bds_acq.hip ] && contract="fast -fno-slp-vectorize"
-            [ "$f" = bds_track.hip ] && contract="off -fno-slp-vectorize"
+            { [ "$f" = bds_track.hip ] || [ "$f" = bds_corrfn.hip ]; } && contract="off -fno-slp-vectorize"
             "$HIPCC" "${FLAGS[@]}" -ffp-contract=$contract -c "$SRC/$f" -o "$o" ${BDS_HIPCC_EXTRA:-} "$@"
         fi
     fi
 }
 objs=(); hobjs=(); pids=()
-for f in bds_acq.hip bds_track.hip bds_codes.cpp bds_api.hip bds_sync.hip bds_multi.hip bds_synth.hip bds_probedata.hip; do
+for f in bds_acq.hip bds_track.hip bds_corrfn.hip bds_codes.cpp bds_api.hip bds_sync.hip bds_multi.hip bds_synth.hip bds_probedata.hip; do
     o="$BLD/${f%.*}.o"
     compile "$f" "$o" & pids+=($!)
     objs+=("$o")

@@ -508,6 +508,54 @@ BDS_API int bds_track_cno(bds_ctx *ctx, const bds_settings *s, int n_ch, int n_e
 BDS_API int bds_track_update(bds_ctx *ctx, const bds_settings *s, int n_ch, const double *state10, const double *sums18,
                              double *state10_out, int32_t *active, int32_t *completed, double *out21);
 
+/* ---- correlation function along a tracked channel -------------------------------
+ * Open-loop replay of tracked epochs at ANY set of tap offsets: the shape of the correlation function (the BOC(1,1) side peaks,
+ * the BOC(6,1) ripple, what a multipath ray does to the S-curve), where the trackers return the three sums at
+ * -+dllCorrelatorSpacing only.  Beyond the reference: tau outside -+dllCorrelatorSpacing has no counterpart there.
+ *
+ * An item is one epoch of one channel, given as bds_track_correlate takes it: prn[i] and state6[i] = {sample offset (0-based),
+ * blksize, remCodePhase, codeFreq, remCarrPhase, carrFreq} -- what bds_track returns for the epoch: absoluteSample, remCodePhase,
+ * remCarrPhase, codeFreq and carrFreq of epoch e (the two rates are stored before the loop filters replace them,
+ * WB_tracking.m:404-406,428-430, so entry e is what epoch e ran on), blksize = ceil((codeLength - remCodePhase) / (codeFreq / fs)).
+ * taps: n_taps offsets tau in primary-code chips, the unit of dllCorrelatorSpacing.  Limits: 1 <= n_taps <= 128, every tau
+ * finite and |tau| <= 16; anything else is BDS_ERR_ARG.
+ *
+ * Index rule (B2a/tracking.m:260-316, B1C/WB_tracking.m:289-324, with tau in the place of -+earlyLateSpc): the replica index
+ * vector of tap tau is the MATLAB colon vector
+ *     t = (rem + tau)*sc : step*sc : (((blk-1)*step + rem) + tau)*sc,       sc = 1 (B2a), 2 (B1C),  step = codeFreq / fs,
+ * the code unit of sample k is u = ceil(t(k)), and u6 = ceil(6 t(k)) for the pilot BOC(6,1) in wide-band mode.  The replica is
+ * the PERIODIC extension of the code: unit u reads c[((u - 1) mod U) + 1] (non-negative mod; U = 10230 chips for B2a, 20460
+ * half-chips for BOC(1,1), 122760 twelfths for BOC(6,1)).  For tau in {-spacing, 0, +spacing} this is index for index what the
+ * trackers read through the reference's padded table [c(L) c(1..L) c(1)].  A tap whose colon vector does not have blksize elements
+ * (MATLAB itself would stop there) makes the call return BDS_ERR_ARG, naming the item and the tap, before anything is launched.
+ * Carrier: the reference's argument (carrFreq*2*pi)*(k/fs) + remCarrPhase at the trackers' default numerics, with their I/Q
+ * conventions -- B2a exp(+j th), i = imag, q = real; B1C exp(-j th), i = real, q = imag.
+ *
+ * Output: out[item][comp][tap][2] = (I, Q) raw sums, double; comp 0 data, comp 1 the pilot (B2a pilot / pilot BOC(1,1)) when the
+ * pilot is on, comp 2 the pilot BOC(6,1) in wide-band mode only -- the order of sums18's components; *n_comp receives the count.
+ * The QMBOC composite (WB_tracking.m:375-380) is formed by the caller from comps 1 and 2.
+ *
+ * Determinism: an item's result depends on the item, the tap list and the settings only -- bit for bit the same whichever other
+ * items are in the call, however the call is batched, and whichever of the three entries supplies the record.
+ *
+ * Record: all five formats the trackers take (fileType 1 / 2 / 3, dataType 0 / 1).  Only the span the items touch is loaded: items
+ * are sorted by position and run in batches whose span of the record fits the resident limit (bds_track_set_resident_limit when
+ * set, else 256 MiB); results come back in the caller's order.  One item that does not fit the limit is BDS_ERR_ARG with the
+ * needed bytes in the message; an item that reaches past the end of the record is BDS_ERR_ARG and names the item.  On any error
+ * nothing is written to out.  Like the one-shot tracking calls, the entries are BDS_ERR_ARG, naming the session, while the context
+ * has an open tracking session (they share its code tables).  bds_get_timing afterwards: total_ms the call's stream time, search_ms its kernels alone, n_pairs the
+ * number of batches, n_comp.  (After bds_track_correlate, search_ms is that call's kernels alone.) */
+BDS_API int bds_corr_function(bds_ctx *ctx, const bds_settings *s, const char *path, int n_items, const int32_t *prn,
+                              const double *state6, int n_taps, const double *taps, double *out, int32_t *n_comp);
+BDS_API int bds_corr_function_mem(bds_ctx *ctx, const bds_settings *s, const int8_t *file_bytes, size_t n_bytes, int n_items,
+                                  const int32_t *prn, const double *state6, int n_taps, const double *taps, double *out,
+                                  int32_t *n_comp);
+/* the record in device memory, under the pointer rule of the *_dev entries ("records in device memory" below) */
+#define BDS_CORR_DEV_API __attribute__((visibility("default")))
+BDS_CORR_DEV_API int bds_corr_function_dev(bds_ctx *ctx, const bds_settings *s, const void *d_file_bytes, size_t n_bytes,
+                                           int n_items, const int32_t *prn, const double *state6, int n_taps, const double *taps,
+                                           double *out, int32_t *n_comp);
+
 /* ---- helpers replacing small host functions on the path ------------------------ */
 /* Common/calcLoopCoef.m:41-45 */
 BDS_API void bds_calc_loop_coef(double lbw, double zeta, double k, double *tau1, double *tau2);

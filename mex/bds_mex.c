@@ -22,6 +22,11 @@
  *       16385 bins for fileType 1, else two-sided 32768 bins 0 .. fs), excerpt_re, excerpt_im (the samples of the time-domain
  *       plot), stats (min, max, sum, sum of squares of I, then of Q), n_segments, n_samples.  n_samples: 0 (default) = the
  *       window probeData.m reads, -1 = the whole file behind skipNumberOfBytes.
+ *   out = bds_mex('corr_function', path, settings, prn, state6, taps)   % the correlation function of tracked epochs (mex/corrFunction.m
+ *       builds prn and state6 from trackResults): prn 1 x n, state6 6 x n = {sample offset; blksize; remCodePhase; codeFreq;
+ *       remCarrPhase; carrFreq} per item, taps in chips (at most 128, |tau| <= 16).  struct with I, Q ([numel(taps) * n_comp x n],
+ *       tap fastest, then component: data, pilot, pilot BOC(6,1)) and n_comp.  The receiver is told from the settings (only
+ *       B1C/initSettings.m defines acqCohT).
  * signal: 1 = B1C, 2 = B2a (the reference keeps one directory per receiver).
  * Acquisition runs on ONE GPU unless BDS_MEX_DEVICES=n (n > 1, or 0 = every visible GPU) opts into the multi-device
  * path of the library (bds_multi_create + RCCL all-reduce): that path has only ever run on one-GPU boxes (with the exchange
@@ -341,6 +346,53 @@ static void do_probe_data(int nlhs, mxArray *plhs[], int nrhs, const mxArray *pr
     plhs[0] = out;
 }
 
+/* bds_corr_function: the correlation function of tracked epochs at the caller's taps (mex/corrFunction.m builds the states) */
+static void do_corr_function(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[]) {
+    bds_settings s;
+    char path[4096];
+    size_t n_items, n_taps, i, n;
+    int32_t *prn, n_comp = 0;
+    double *buf, *pi, *pq;
+    const double *p;
+    int rc, signal;
+    mxArray *res, *a;
+    (void)nlhs;
+    if (nrhs != 6 || !mxIsDouble(prhs[3]) || !mxIsDouble(prhs[4]) || !mxIsDouble(prhs[5]))
+        mexErrMsgIdAndTxt("bds:args", "corr_function: (path, settings, prn, state6, taps)");
+    if (mxGetString(prhs[1], path, sizeof(path))) mexErrMsgIdAndTxt("bds:args", "File name must be a string");
+    if (!mxIsStruct(prhs[2])) mexErrMsgIdAndTxt("bds:settings", "settings must be a struct");
+    signal = mxGetField(prhs[2], 0, "acqCohT") ? BDS_SIGNAL_B1C : BDS_SIGNAL_B2A; /* only B1C/initSettings.m defines acqCohT */
+    pack_settings(prhs[2], signal, &s);
+    n_items = mxGetNumberOfElements(prhs[3]);
+    n_taps = mxGetNumberOfElements(prhs[5]);
+    if (n_items < 1 || mxGetNumberOfElements(prhs[4]) != 6 * n_items)
+        mexErrMsgIdAndTxt("bds:args", "corr_function: state6 must be 6 x numel(prn), one column per item");
+    if (n_taps < 1 || n_taps > 128) mexErrMsgIdAndTxt("bds:args", "corr_function: 1 .. 128 taps");
+    prn = (int32_t *)mxCalloc(n_items, sizeof(int32_t));
+    p = mxGetDoubles(prhs[3]);
+    for (i = 0; i < n_items; ++i) prn[i] = (int32_t)p[i];
+    buf = (double *)mxCalloc(n_items * 3 * n_taps * 2, sizeof(double)); /* [item][comp][tap][2], three components at most */
+    /* a 6 x n matrix is, column-major, the C array [n][6] */
+    rc = bds_corr_function(ctx(), &s, path, (int)n_items, prn, mxGetDoubles(prhs[4]), (int)n_taps, mxGetDoubles(prhs[5]), buf, &n_comp);
+    mxFree(prn);
+    if (rc) {
+        mxFree(buf);
+        mexErrMsgIdAndTxt("bds:corr_function", "%s", bds_last_error(ctx()));
+    }
+    /* I, Q: [n_taps * n_comp x n_items], tap fastest: reshape(I, n_taps, n_comp, []) in the wrapper */
+    res = mxCreateStructMatrix(1, 1, 0, NULL);
+    n = n_taps * (size_t)n_comp;
+    pi = out_field(res, "I", (int)n, (int)n_items);
+    pq = out_field(res, "Q", (int)n, (int)n_items);
+    for (i = 0; i < n * n_items; ++i) pi[i] = buf[2 * i], pq[i] = buf[2 * i + 1];
+    mxFree(buf);
+    a = mxCreateDoubleMatrix(1, 1, mxREAL);
+    mxGetDoubles(a)[0] = (double)n_comp;
+    mxAddField(res, "n_comp");
+    mxSetField(res, 0, "n_comp", a);
+    plhs[0] = res;
+}
+
 void mexFunction(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[]) {
     char cmd[32];
     if (nrhs < 1 || mxGetString(prhs[0], cmd, sizeof(cmd))) mexErrMsgIdAndTxt("bds:args", "first argument: command string");
@@ -354,6 +406,8 @@ void mexFunction(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[]) {
         do_frame_sync(nlhs, plhs, nrhs, prhs);
     else if (!strcmp(cmd, "probe_data"))
         do_probe_data(nlhs, plhs, nrhs, prhs);
+    else if (!strcmp(cmd, "corr_function"))
+        do_corr_function(nlhs, plhs, nrhs, prhs);
     else
         mexErrMsgIdAndTxt("bds:args", "unknown command %s", cmd);
 }
