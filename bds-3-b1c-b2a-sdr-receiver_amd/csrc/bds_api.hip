@@ -373,15 +373,9 @@ extern "C" int bds_pre_run_device(bds_ctx *ctx, const bds_settings *s, int max_p
     hipStream_t st = (hipStream_t)ctx->stream;
     double *d_in = nullptr;
     bds_channel *d_ch = nullptr;
-    struct Scope {
-        void **a, **b;
-        ~Scope() {
-            if (*a) (void)hipFree(*a);
-            if (*b) (void)hipFree(*b);
-        }
-    } scope{(void **)&d_in, (void **)&d_ch};
-    BDS_HIP(ctx, hipMalloc((void **)&d_in, sizeof(double) * 3 * max_prn));
-    BDS_HIP(ctx, hipMalloc((void **)&d_ch, sizeof(bds_channel) * nch));
+    bds::DevScope scope;
+    BDS_HIP(ctx, scope.alloc(&d_in, sizeof(double) * 3 * max_prn));
+    BDS_HIP(ctx, scope.alloc(&d_ch, sizeof(bds_channel) * nch));
     BDS_HIP(ctx, hipMemcpyAsync(d_in, carrFreq, sizeof(double) * max_prn, hipMemcpyHostToDevice, st));
     BDS_HIP(ctx, hipMemcpyAsync(d_in + max_prn, codePhase, sizeof(double) * max_prn, hipMemcpyHostToDevice, st));
     BDS_HIP(ctx, hipMemcpyAsync(d_in + 2 * max_prn, peakMetric, sizeof(double) * max_prn, hipMemcpyHostToDevice, st));

@@ -24,11 +24,11 @@
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
-#include <functional>
 #include <numeric>
 #include <vector>
 
 #include "bds_internal.h"
+#include "bds_record.h"
 #include "bds_strict_math.h"
 #include "bds_trk_replica.h"
 
@@ -46,6 +46,7 @@ static constexpr int kCfPre = kCfChunk + kCfChunk / kCfSeg + 1;  // prefix sums:
 static constexpr size_t kCfLds = (size_t)kCfPre * 16 + kCfWaves * 16 + kCfMaxTaps * 8 + (size_t)kCfCap1 * 2 + kCfCap6;
 static constexpr size_t kCfResident = (size_t)256 << 20;  // resident limit when the context has none
 static constexpr size_t kCfPartBytes = (size_t)64 << 20;  // partial sums of one launch (items per launch follow from it)
+static constexpr size_t kCfStage = (size_t)64 << 20;      // pinned staging of a record read from a file, at the most
 
 struct CfParams {
     int pilot, n_comp, n_taps, code_len, max_chunks;
@@ -248,8 +249,6 @@ __global__ __launch_bounds__(256) void k_corrfn_reduce(const double *__restrict_
     out[(long)item * V + v] = acc;
 }
 
-using CfLoader = std::function<int(size_t off, size_t n, int8_t *dst, hipStream_t stream)>;
-
 template <int MODE>
 static void cf_launch_fmt(bds_ctx *ctx, int fmt, dim3 grid, hipStream_t stream, const int8_t *data, const int8_t *prim, const CfParams &p,
                           const int *prn, const double *s6, const double *taps, double *part) {
@@ -269,8 +268,8 @@ static void cf_launch_fmt(bds_ctx *ctx, int fmt, dim3 grid, hipStream_t stream, 
 
 static bool cf_whole(double v) { return std::isfinite(v) && v == std::floor(v); }
 
-// The three entries: `load` copies bytes [off, off + n) of the record to device memory.
-static int corr_function_run(bds_ctx *ctx, const char *who, const bds_settings *s, const CfLoader &load, size_t n_bytes, int n_items,
+// The three entries differ in where the record lies (bds_record.h).
+static int corr_function_run(bds_ctx *ctx, const char *who, const bds_settings *s, const RecordSource &src, int n_items,
                              const int32_t *prn, const double *state6, int n_taps, const double *taps, double *out, int32_t *n_comp_out) {
     if (!s || !prn || !state6 || !taps || !out) return fail(ctx, BDS_ERR_ARG, "%s: NULL argument", who);
     if (n_items < 1) return fail(ctx, BDS_ERR_ARG, "%s: n_items = %d (at least one item)", who, n_items);
@@ -282,6 +281,7 @@ static int corr_function_run(bds_ctx *ctx, const char *who, const bds_settings *
         tau_min = std::min(tau_min, taps[i]), tau_max = std::max(tau_max, taps[i]);
     }
     if (int rc = track_session_guard(ctx, who)) return rc;  // (the code tables are the open session's: another signal would replace them)
+    const size_t n_bytes = src.size();
     BDS_HIP(ctx, hipSetDevice(ctx->device));
     TrkOpenLoop o{};
     if (int rc = track_open_loop_setup(ctx, *s, n_bytes, o)) return rc;
@@ -362,20 +362,11 @@ static int corr_function_run(bds_ctx *ctx, const char *who, const bds_settings *
     int8_t *d_data = nullptr;
     int *d_prn = nullptr;
     double *d_s6 = nullptr, *d_taps = nullptr, *d_part = nullptr, *d_out = nullptr;
-    std::vector<hipEvent_t> events;
-    struct Scope {
-        void **p[6];
-        std::vector<hipEvent_t> &ev;
-        ~Scope() {
-            for (void **q : p)
-                if (*q) (void)hipFree(*q);
-            for (hipEvent_t e : ev) (void)hipEventDestroy(e);
-        }
-    } scope{{(void **)&d_data, (void **)&d_prn, (void **)&d_s6, (void **)&d_taps, (void **)&d_part, (void **)&d_out}, events};
+    DevScope scope;
     hipStream_t stream = (hipStream_t)ctx->stream;
-    if (hipMalloc((void **)&d_data, max_bytes + kDataSlack) != hipSuccess || hipMalloc((void **)&d_prn, sizeof(int) * n_items) != hipSuccess ||
-        hipMalloc((void **)&d_s6, sizeof(double) * 6 * n_items) != hipSuccess || hipMalloc((void **)&d_taps, sizeof(double) * n_taps) != hipSuccess ||
-        hipMalloc((void **)&d_part, item_part * per_launch) != hipSuccess || hipMalloc((void **)&d_out, sizeof(double) * (size_t)n_items * V) != hipSuccess) {
+    if (scope.alloc(&d_data, max_bytes + kDataSlack) != hipSuccess || scope.alloc(&d_prn, sizeof(int) * n_items) != hipSuccess ||
+        scope.alloc(&d_s6, sizeof(double) * 6 * n_items) != hipSuccess || scope.alloc(&d_taps, sizeof(double) * n_taps) != hipSuccess ||
+        scope.alloc(&d_part, item_part * per_launch) != hipSuccess || scope.alloc(&d_out, sizeof(double) * (size_t)n_items * V) != hipSuccess) {
         (void)hipGetLastError();
         return fail(ctx, BDS_ERR_NOMEM, "%s: device buffers (%zu bytes of the record, %zu of partial sums)", who, max_bytes, item_part * per_launch);
     }
@@ -387,8 +378,7 @@ static int corr_function_run(bds_ctx *ctx, const char *who, const bds_settings *
     }
     auto mark = [&]() -> hipEvent_t {
         hipEvent_t e = nullptr;
-        if (hipEventCreate(&e) != hipSuccess) return nullptr;
-        events.push_back(e);
+        if (scope.event(&e) != hipSuccess) return nullptr;
         (void)hipEventRecord(e, stream);
         return e;
     };
@@ -401,7 +391,7 @@ static int corr_function_run(bds_ctx *ctx, const char *who, const bds_settings *
     p.fs = o.fs, p.inv_fs = o.inv_fs, p.tau_min = tau_min, p.tau_max = tau_max;
     std::vector<std::pair<hipEvent_t, hipEvent_t>> kernel_spans;
     for (const Batch &b : batches) {
-        if (int rc = load(b.off, b.bytes, d_data, stream)) return rc;
+        if (int rc = src.load(b.off, b.bytes, d_data, stream)) return rc;
         p.base = b.base;
         p.win_end = b.base + fmt_samples(fmt, (long long)b.bytes);
         for (int i0 = 0; i0 < b.count; i0 += per_launch) {
@@ -446,11 +436,9 @@ extern "C" int bds_corr_function_mem(bds_ctx *ctx, const bds_settings *s, const 
                                      int32_t *n_comp) {
     if (!ctx) return BDS_ERR_ARG;
     if (!file_bytes) return fail(ctx, BDS_ERR_ARG, "bds_corr_function_mem: file_bytes is NULL");
-    const CfLoader load = [&](size_t off, size_t n, int8_t *dst, hipStream_t stream) -> int {
-        BDS_HIP(ctx, hipMemcpyAsync(dst, file_bytes + off, n, hipMemcpyHostToDevice, stream));
-        return BDS_OK;
-    };
-    return corr_function_run(ctx, "bds_corr_function_mem", s, load, n_bytes, n_items, prn, state6, n_taps, taps, out, n_comp);
+    RecordSource src;
+    src.set_host(ctx, file_bytes, n_bytes);
+    return corr_function_run(ctx, "bds_corr_function_mem", s, src, n_items, prn, state6, n_taps, taps, out, n_comp);
 }
 
 extern "C" int bds_corr_function_dev(bds_ctx *ctx, const bds_settings *s, const void *d_file_bytes, size_t n_bytes, int n_items,
@@ -459,36 +447,16 @@ extern "C" int bds_corr_function_dev(bds_ctx *ctx, const bds_settings *s, const 
     if (!ctx) return BDS_ERR_ARG;
     if (!d_file_bytes) return fail(ctx, BDS_ERR_ARG, "bds_corr_function_dev: d_file_bytes is NULL");
     if (int rc = check_device_span(ctx, "bds_corr_function_dev", "d_file_bytes", d_file_bytes, n_bytes)) return rc;
-    const int8_t *mem = (const int8_t *)d_file_bytes;
-    const CfLoader load = [&](size_t off, size_t n, int8_t *dst, hipStream_t stream) -> int {
-        BDS_HIP(ctx, hipMemcpyAsync(dst, mem + off, n, hipMemcpyDeviceToDevice, stream));
-        return BDS_OK;
-    };
-    return corr_function_run(ctx, "bds_corr_function_dev", s, load, n_bytes, n_items, prn, state6, n_taps, taps, out, n_comp);
+    RecordSource src;
+    src.set_device(ctx, d_file_bytes, n_bytes);
+    return corr_function_run(ctx, "bds_corr_function_dev", s, src, n_items, prn, state6, n_taps, taps, out, n_comp);
 }
 
 extern "C" int bds_corr_function(bds_ctx *ctx, const bds_settings *s, const char *path, int n_items, const int32_t *prn,
                                  const double *state6, int n_taps, const double *taps, double *out, int32_t *n_comp) {
     if (!ctx) return BDS_ERR_ARG;
     if (!path) return fail(ctx, BDS_ERR_ARG, "bds_corr_function: path is NULL");
-    FILE *f = fopen(path, "rb");
-    if (!f) return fail(ctx, BDS_ERR_IO, "Unable to read file %s", path);
-    struct Closer {
-        FILE *f;
-        ~Closer() { fclose(f); }
-    } guard{f};
-    fseeko(f, 0, SEEK_END);
-    const long long sz = ftello(f);
-    if (sz <= 0) return fail(ctx, BDS_ERR_IO, "file %s is empty", path);
-    std::vector<int8_t> stage;
-    const CfLoader load = [&](size_t off, size_t n, int8_t *dst, hipStream_t stream) -> int {
-        if (fseeko(f, (off_t)off, SEEK_SET)) return fail(ctx, BDS_ERR_IO, "seek in %s failed", path);
-        stage.resize(n);
-        if (fread(stage.data(), 1, n, f) != n) return fail(ctx, BDS_ERR_IO, "short read on %s", path);
-        hipError_t e = hipMemcpyAsync(dst, stage.data(), n, hipMemcpyHostToDevice, stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(stream);  // the staging buffer is filled again by the next batch
-        if (e != hipSuccess) return fail(ctx, BDS_ERR_HIP, "H2D copy: %s", hipGetErrorString(e));
-        return BDS_OK;
-    };
-    return corr_function_run(ctx, "bds_corr_function", s, load, (size_t)sz, n_items, prn, state6, n_taps, taps, out, n_comp);
+    RecordSource src;
+    if (int rc = src.open_file(ctx, path, kCfStage)) return rc;
+    return corr_function_run(ctx, "bds_corr_function", s, src, n_items, prn, state6, n_taps, taps, out, n_comp);
 }

@@ -151,3 +151,35 @@ int check_device_span(bds_ctx *ctx, const char *who, const char *arg, const void
             return bds::fail((ctx), BDS_ERR_HIP, "%s failed: %s (%s:%d)", #expr,               \
                              hipGetErrorString(_e), __FILE__, __LINE__);                       \
     } while (0)
+
+#ifdef __HIPCC__  // (bds_codes.cpp is plain C++ and sees no HIP runtime)
+namespace bds {
+// Device allocations and events of one call, released on every exit path (or earlier, by release()).
+struct DevScope {
+    std::vector<void *> mem;
+    std::vector<hipEvent_t> ev;
+    DevScope() = default;
+    DevScope(const DevScope &) = delete;
+    DevScope &operator=(const DevScope &) = delete;
+    template <class T>
+    hipError_t alloc(T **q, size_t bytes) {  // at least 8 bytes: an empty shape still gets a pointer a kernel may be handed
+        *q = nullptr;
+        const hipError_t e = hipMalloc((void **)q, bytes < 8 ? 8 : bytes);
+        if (e == hipSuccess) mem.push_back(*q);
+        return e;
+    }
+    hipError_t event(hipEvent_t *e) {
+        const hipError_t r = hipEventCreate(e);
+        if (r == hipSuccess) ev.push_back(*e);
+        return r;
+    }
+    void release() {
+        for (void *q : mem) (void)hipFree(q);
+        for (hipEvent_t e : ev) (void)hipEventDestroy(e);
+        mem.clear();
+        ev.clear();
+    }
+    ~DevScope() { release(); }
+};
+}  // namespace bds
+#endif

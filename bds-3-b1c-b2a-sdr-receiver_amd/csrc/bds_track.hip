@@ -26,7 +26,6 @@
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
-#include <functional>
 #include <initializer_list>
 #include <memory>
 #include <mutex>
@@ -37,6 +36,7 @@
 
 #include "bds_debug.h"
 #include "bds_internal.h"
+#include "bds_record.h"
 #include "bds_strict_math.h"
 #include "bds_trk_replica.h"
 
@@ -1018,15 +1018,39 @@ __global__ __launch_bounds__(kUpdThreads) void k_trk_update(TrkParams p, ChanSta
     if (threadIdx.x == 0) st[ch] = s;
 }
 
+// The two buffers the resident span of a streamed record slides through, `cap` bytes each (+ kDataSlack).  Owned by the context's
+// TrackState (the one-shot call: kept from call to call while the size stays) or by a session.
+struct SpanPair {
+    int8_t *buf[2] = {nullptr, nullptr};
+    size_t cap = 0;
+    void release() {
+        for (int8_t *&q : buf)
+            if (q) (void)hipFree(q), q = nullptr;
+        cap = 0;
+    }
+    int ensure(bds_ctx *ctx, size_t bytes) {
+        if (cap == bytes && buf[0] && buf[1]) return BDS_OK;
+        release();
+        for (int8_t *&q : buf) {
+            const hipError_t e = hipMalloc((void **)&q, bytes + kDataSlack);
+            if (e != hipSuccess) {
+                (void)hipGetLastError();
+                q = nullptr;
+                return fail(ctx, BDS_ERR_NOMEM, "resident span of 2 x %zu bytes of the IF record does not fit in HBM: %s", bytes, hipGetErrorString(e));
+            }
+        }
+        cap = bytes;
+        return BDS_OK;
+    }
+};
+
 struct TrackState {
     int8_t *d_data = nullptr;
     size_t data_cap = 0;
     size_t loaded_bytes = 0;  // bytes of the record the last call copied host-to-device (diagnostics)
     int8_t *d_prim = nullptr;
     int prim_signal = 0;
-    // streamed mode: the resident span of the record slides through two buffers of span_cap bytes each
-    int8_t *d_span[2] = {nullptr, nullptr};
-    size_t span_cap = 0;
+    SpanPair span;              // streamed mode
     size_t resident_limit = 0;  // bds_track_set_resident_limit (0: none)
     // bds_track_stream_info of the last call
     int pieces = 0;           // loads of a part of the record (1: one window)
@@ -1043,8 +1067,7 @@ void track_state_free(TrackState *t) {
     if (!t) return;
     if (t->session) session_close(t->session);
     if (t->d_data) (void)hipFree(t->d_data);
-    for (int8_t *q : t->d_span)
-        if (q) (void)hipFree(q);
+    t->span.release();
     if (t->d_prim) (void)hipFree(t->d_prim);
     delete t;
 }
@@ -1314,7 +1337,7 @@ __global__ __launch_bounds__(256) void k_trk_cno_seg(TrkOut o, const ChanState *
     }
 }
 
-// the result arrays of a session's advance, one block of n_fields x n doubles, back to the reference's template values
+// the result arrays of a call, one block of n_fields x n doubles, back to the reference's template values
 // (tracking.m:48-82): Inf where bit f of inf_mask is set, else 0
 __global__ void k_trk_fill_out(double *__restrict__ a, size_t n, int n_fields, uint32_t inf_mask) {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -1322,9 +1345,100 @@ __global__ void k_trk_fill_out(double *__restrict__ a, size_t n, int n_fields, u
     a[i] = ((inf_mask >> (int)(i / n)) & 1u) ? INFINITY : 0.0;
 }
 
-// Source of the IF record: copies bytes [off, off + n) of the file into device memory at dst, ordered on `stream`.
-// (Streamed tracking calls it from its loader thread, with the context's second stream, while a batch of epochs runs.)
-using RecordLoader = std::function<int(size_t off, size_t n, int8_t *dst, hipStream_t stream)>;
+// The 21 result arrays of a tracking call on the device: one block [21][n_ch][row] in the order of for_each_field, the table of
+// its arrays for the kernels (by value: d; in device memory: d_out) and the fields whose template value is Inf.  A session keeps
+// one for its lifetime, the one-shot call makes one per call.
+struct TrkResults {
+    static constexpr int kFields = sizeof(TrkOut) / sizeof(double *);
+    double *d_fields = nullptr;
+    size_t cap = 0;  // doubles at d_fields
+    TrkOut d{};
+    TrkOut *d_out = nullptr;
+    int n_ch = 0, row = 0;  // the shape the table was made for
+    uint32_t inf_mask = 0;
+    std::vector<double> h;  // host copy of the block (fetch)
+
+    TrkResults() = default;
+    TrkResults(const TrkResults &) = delete;
+    TrkResults &operator=(const TrkResults &) = delete;
+    ~TrkResults() { release(); }
+    void release() {
+        if (d_fields) (void)hipFree(d_fields), d_fields = nullptr;
+        if (d_out) (void)hipFree(d_out), d_out = nullptr;
+        cap = 0, row = 0;
+    }
+    size_t n() const { return (size_t)n_ch * row; }
+    // arrays of nc x r doubles at the template values, enqueued on the context's stream: the block grows when it has to, the
+    // table is made again when the shape changes
+    int prepare(bds_ctx *ctx, int nc, int r) {
+        hipStream_t stream = (hipStream_t)ctx->stream;
+        const size_t want = (size_t)nc * r * kFields;
+        if (cap < want) {
+            if (d_fields) (void)hipFree(d_fields), d_fields = nullptr, cap = 0;
+            row = 0;
+            const hipError_t e = hipMalloc((void **)&d_fields, sizeof(double) * want);
+            if (e != hipSuccess) {
+                (void)hipGetLastError();
+                d_fields = nullptr;
+                return fail(ctx, BDS_ERR_NOMEM, "hipMalloc track output: %s", hipGetErrorString(e));
+            }
+            cap = want;
+        }
+        if (!d_out) BDS_HIP(ctx, hipMalloc((void **)&d_out, sizeof(TrkOut)));
+        if (row != r || n_ch != nc) {
+            n_ch = nc, row = r, inf_mask = 0;
+            int f = 0;
+            bds_track_out unused{};
+            for_each_field(&unused, &d, [&](double *, double *&dev, double v0) {
+                dev = d_fields + (size_t)f * n();
+                if (v0 != 0.0) inf_mask |= 1u << f;
+                ++f;
+            });
+            BDS_HIP(ctx, hipMemcpyAsync(d_out, &d, sizeof(TrkOut), hipMemcpyHostToDevice, stream));
+            BDS_HIP(ctx, hipStreamSynchronize(stream));  // (d may not change while the copy reads it)
+        }
+        hipLaunchKernelGGL(k_trk_fill_out, dim3((unsigned)((want + 255) / 256)), dim3(256), 0, stream, d_fields, n(), kFields, inf_mask);
+        return BDS_OK;
+    }
+    // the block to the host in one copy, then each array the caller supplied
+    int fetch(bds_ctx *ctx, bds_track_out *out) {
+        hipStream_t stream = (hipStream_t)ctx->stream;
+        h.resize(n() * kFields);
+        BDS_HIP(ctx, hipMemcpyAsync(h.data(), d_fields, sizeof(double) * h.size(), hipMemcpyDeviceToHost, stream));
+        BDS_HIP(ctx, hipStreamSynchronize(stream));
+        int f = 0;
+        TrkOut unused{};
+        for_each_field(out, &unused, [&](double *host, double *&, double) {
+            if (host) memcpy(host, h.data() + (size_t)f * n(), sizeof(double) * n());
+            ++f;
+        });
+        return BDS_OK;
+    }
+};
+
+// The five C/N0 planes [5][n_ch][nq] at d_cno (k_trk_cno, k_trk_cno_seg; NULL: no interval was evaluated) into those of DataCNo,
+// DataPLD, PilotCNo, PilotPLD, SigCNo the caller supplied (rows of out->n_cno): the first count(c) intervals of channel c, zero
+// behind them and in the pilot planes of a channel tracked without pilot (pm == 0).
+template <class F>
+static int cno_scatter(bds_ctx *ctx, const double *d_cno, int n_ch, int nq, int pm, bds_track_out *out, F count) {
+    hipStream_t stream = (hipStream_t)ctx->stream;
+    std::vector<double> h((size_t)n_ch * nq * 5);
+    if (d_cno) {
+        BDS_HIP(ctx, hipMemcpyAsync(h.data(), d_cno, sizeof(double) * h.size(), hipMemcpyDeviceToHost, stream));
+        BDS_HIP(ctx, hipStreamSynchronize(stream));
+    }
+    double *dst[5] = {out->DataCNo, out->DataPLD, out->PilotCNo, out->PilotPLD, out->SigCNo};
+    const size_t plane = (size_t)n_ch * nq;
+    for (int c = 0; c < n_ch; ++c) {
+        const int nd = d_cno ? std::min(count(c), nq) : 0;
+        for (int f = 0; f < 5; ++f) {
+            if (!dst[f]) continue;
+            for (int q = 0; q < out->n_cno; ++q)
+                dst[f][(size_t)c * out->n_cno + q] = q < nd && (pm || f < 2) ? h[f * plane + (size_t)c * nq + q] : 0.0;
+        }
+    }
+    return BDS_OK;
+}
 
 // Streamed tracking: the resident span of the record and the one being prepared (do_track plans the batches).
 //   cur  the span the epochs of the current batch read, on the context's main stream
@@ -1338,7 +1452,7 @@ using RecordLoader = std::function<int(size_t off, size_t n, int8_t *dst, hipStr
 //     kernels of earlier batches are done: the host synchronises the main stream at every batch end).  The next load writes
 //     into that buffer, so move_to() records ev_carry behind the copy and the loader's stream waits for it before its first byte;
 //   * loads that move_to() issues itself are on the main stream, behind the copy.
-// Between start_load() and join() the loader may set the context's error message (the RecordLoader reports its own failures):
+// Between start_load() and join() the loader may set the context's error message (the RecordSource reports its own failures):
 // the main thread must not call fail() in that interval -- it keeps error codes in locals and reports them after join().
 struct SpanStream {
     struct Span {  // samples [base, end) of the record at buf
@@ -1347,7 +1461,7 @@ struct SpanStream {
     } cur, nxt;
     bds_ctx *ctx;
     TrackState &t;
-    const RecordLoader &load;
+    const RecordSource &src;  // loaded from by one thread at a time: join() comes before every load of the main thread's
     hipStream_t main_stream, ld_stream;
     int fmt;            // sample format (kFmt*): span bounds are multiples of fmt_align(fmt) or even, so they fall on whole bytes
     long long span_n;   // samples a span buffer holds
@@ -1361,8 +1475,8 @@ struct SpanStream {
     int th_rc = BDS_OK;
     hipError_t th_err = hipSuccess;
 
-    SpanStream(bds_ctx *c, TrackState &ts, const RecordLoader &l, hipStream_t ms, hipStream_t ls, int fm, long long sn)
-        : ctx(c), t(ts), load(l), main_stream(ms), ld_stream(ls), fmt(fm), span_n(sn) {}
+    SpanStream(bds_ctx *c, TrackState &ts, const RecordSource &l, hipStream_t ms, hipStream_t ls, int fm, long long sn)
+        : ctx(c), t(ts), src(l), main_stream(ms), ld_stream(ls), fmt(fm), span_n(sn) {}
     SpanStream(const SpanStream &) = delete;
     SpanStream &operator=(const SpanStream &) = delete;
     ~SpanStream() {
@@ -1382,7 +1496,7 @@ struct SpanStream {
         const long long from = carry ? cur.end : nb;
         if (!tail_loaded && hi > from) {
             const size_t nbytes = (size_t)nb_of(hi - from);
-            int r = load((size_t)nb_of(from), nbytes, nxt.buf + nb_of(from - nb), main_stream);
+            int r = src.load((size_t)nb_of(from), nbytes, nxt.buf + nb_of(from - nb), main_stream);
             if (r) return r;
             t.loaded_bytes += nbytes, t.pieces += 1;
         }
@@ -1410,7 +1524,7 @@ struct SpanStream {
             th_err = hipSetDevice(ctx->device);
             if (th_err == hipSuccess && wait_carry) th_err = hipStreamWaitEvent(ld_stream, ev_carry, 0);  // nxt.buf is still being read
             if (th_err != hipSuccess) return;
-            th_rc = load(off, nbytes, dst, ld_stream);
+            th_rc = src.load(off, nbytes, dst, ld_stream);
             if (th_rc == BDS_OK) th_err = hipStreamSynchronize(ld_stream);
         });
     }
@@ -1427,8 +1541,15 @@ struct SpanStream {
 };
 
 // ---- the three parts of a tracking call: set-up, "run one planned batch" (TrkRun::run_batch; run_streamed plans the batches of
-// the resident-span path), finish.  bds_track / bds_track_mem run them in sequence (do_track); a tracking session
-// (bds_track_open*) keeps what the first made and calls the second across bds_track_advance calls.
+// the resident-span path), finish.  bds_track / bds_track_mem / bds_track_dev run them in sequence (do_track); a tracking session
+// (bds_track_open*) keeps what the first made and calls the second across bds_track_advance calls.  Both are built from the
+// same pieces and keep only what really differs between them:
+//   RecordSource (bds_record.h)  where the record lies -- a file, host memory, device memory -- behind one load()
+//   TrkPlanner::span_samples     the span rule: samples a span buffer holds under a resident limit, or why the limit is too small
+//   SpanPair                     the two span buffers (the context's, kept across one-shot calls; a session's)
+//   TrkResults                   the 21 result arrays: one device block, prepare() before the epochs, fetch() after them
+//   cno_scatter                  the five C/N0 planes to the caller's, with the caller's count of finished intervals
+//   DevScope (bds_internal.h)    per-call device buffers and events, released on every exit path
 
 // Set-up: parameters, code tables, the channel states the acquisition's table gives (tracking.m:170-188), the correlate grid.
 // Nothing of it depends on the number of epochs, so a session gets the geometry of the one-shot call on the same channels.
@@ -1540,6 +1661,24 @@ struct TrkPlanner {
             hi_max = std::max(hi_max, B), lo_min = std::min(lo_min, blk_lo(hs[c].codeFreq));
         }
         return (std::max(0LL, need) + std::max(0LL, hi_max - lo_min) + al + al - 1) & ~(al - 1);
+    }
+    // The span rule.  A span must hold, from the (16-sample aligned; packed: 32) smallest position base0, every channel's
+    // position plus one block at a code rate 2 % low, plus what the start of the NEXT span -- predicted at a code rate 2 % high
+    // while this one is in use -- can fall behind the channels in one epoch (min_half).  span_n: samples a span buffer holds
+    // when the two together may take `limit` bytes.  A limit the library chose itself (own) is raised to what the channels
+    // need; the caller's, when it is too small, is BDS_ERR_ARG.
+    int span_samples(bds_ctx *ctx, const std::vector<ChanState> &hs, long long base0, size_t limit, bool own, long long &span_n,
+                     long long &min_half_n) const {
+        const long long al = fmt_align(p.cplx);
+        min_half_n = min_half(hs, base0, al);
+        const size_t min_limit = (size_t)fmt_bytes(p.cplx, 2 * min_half_n);
+        if (own) limit = std::max(limit, min_limit);
+        if (limit < min_limit)
+            return fail(ctx, BDS_ERR_ARG, "resident limit of %zu bytes is too small for these channels: the spread of their positions plus "
+                        "one block, in each of the two span buffers, needs at least %zu bytes%s", limit, min_limit,
+                        packed ? " of the packed record" : "");
+        span_n = fmt_samples(p.cplx, (long long)(limit / 2)) & ~(al - 1);
+        return BDS_OK;
     }
 };
 
@@ -1684,8 +1823,8 @@ static int run_streamed(TrkRun &run, TrkPlanner &pl, SpanStream &ss, std::vector
 }
 
 // whole_file: load every byte (second attempt after a channel's reads left the window of the first)
-static int do_track(bds_ctx *ctx, const bds_settings *s, const RecordLoader &load, size_t n_bytes, int n_ch,
-                    const bds_channel *channel, bds_track_out *out, bool whole_file = false) {
+static int do_track(bds_ctx *ctx, const bds_settings *s, const RecordSource &src, int n_ch, const bds_channel *channel,
+                    bds_track_out *out, bool whole_file = false) {
     if (!ctx || !s || !channel || !out) return BDS_ERR_ARG;
     if (n_ch < 1 || out->n_ch != n_ch || out->n_epochs < 1) return fail(ctx, BDS_ERR_ARG, "bds_track: n_ch / n_epochs mismatch");
     if (!out->completed || !out->status || !out->absoluteSample || !out->I_P || !out->Q_P)
@@ -1697,7 +1836,7 @@ static int do_track(bds_ctx *ctx, const bds_settings *s, const RecordLoader &loa
     const int n_epochs = out->n_epochs;
     for (int c = 0; c < n_ch; ++c) out->completed[c] = 0, out->status[c] = '-';
     TrkSetup u;
-    int rc = track_setup(ctx, t, s, n_epochs, n_bytes, n_ch, channel, u);
+    int rc = track_setup(ctx, t, s, n_epochs, src.size(), n_ch, channel, u);
     if (rc) return rc;
     TrkParams &p = u.p;
     std::vector<ChanState> &hs = u.hs;
@@ -1721,13 +1860,11 @@ static int do_track(bds_ctx *ctx, const bds_settings *s, const RecordLoader &loa
     Span cur, nxt;  // one window: cur is the window; streamed: the two span buffers, handed to a SpanStream below
     long long span_n = 0;  // samples a span buffer holds
     TrkPlanner pl(ctx, s, p, n_ch);
-    auto blk_hi = [&](double f) { return pl.blk_hi(f); };
-    auto need_end = [&](const std::vector<ChanState> &v, int k) { return pl.need_end(v, n_epochs - k); };
     {
         long long first = p.n_bytes, last = 0;
         for (int c = 0; c < n_ch; ++c) {
             if (!hs[c].active) continue;
-            const long blk_c = (long)blk_hi(hs[c].codeFreq);
+            const long blk_c = (long)pl.blk_hi(hs[c].codeFreq);
             first = std::min(first, hs[c].pos);
             last = std::max(last, hs[c].pos + (long long)n_epochs * blk_c);
         }
@@ -1752,118 +1889,54 @@ static int do_track(bds_ctx *ctx, const bds_settings *s, const RecordLoader &loa
             }
         }
         if (!stream) {
-            for (int8_t *&q : t.d_span)
-                if (q) (void)hipFree(q), q = nullptr;
-            t.span_cap = 0;
-            if (wbytes && (rc = load((size_t)nb_of(first), wbytes, t.d_data, st(ctx)))) return rc;
-            t.loaded_bytes = wbytes, t.pieces = 1, t.resident_max = wbytes, t.repeated = 0;
+            t.span.release();
             cur.buf = t.d_data, cur.base = first, cur.end = last;
         } else {
             if (t.d_data) (void)hipFree(t.d_data), t.d_data = nullptr, t.data_cap = 0;  // no stale window beside the span
-            // A span must hold, from the (16-sample aligned; packed: 32) smallest position, every channel's position plus one block
-            // at a code rate 2 % low, plus what the start of the NEXT span -- predicted at a code rate 2 % high while
-            // this one is in use -- can fall behind the channels in one epoch.
-            const long long base0 = pl.live_min_pos(hs) & ~(al - 1);
-            const long long min_half = pl.min_half(hs, base0, al);
-            const size_t min_limit = (size_t)nb_of(2 * min_half);
+            // the limit: the context's when it is what made the call stream, else (the window allocation failed) half of what is free
             size_t limit = t.resident_limit;
-            if (!limit || wbytes <= limit) {  // no limit that applies: the window allocation failed
+            const bool own = !limit || wbytes <= limit;
+            if (own) {
                 size_t fr = 0, tot = 0;
                 (void)hipMemGetInfo(&fr, &tot);
-                limit = std::max(min_limit, std::min<size_t>(fr / 2, (size_t)1 << 30));
-            } else if (limit < min_limit) {
-                return fail(ctx, BDS_ERR_ARG, "resident limit of %zu bytes is too small for these channels: the spread of their positions plus "
-                            "one block, in each of the two span buffers, needs at least %zu bytes%s", limit, min_limit,
-                            packed ? " of the packed record" : "");
+                limit = std::min<size_t>(fr / 2, (size_t)1 << 30);
             }
-            span_n = fmt_samples(fmt, (long long)(limit / 2)) & ~(al - 1);
-            const size_t cap = (size_t)nb_of(span_n);
-            if (t.span_cap != cap || !t.d_span[0] || !t.d_span[1]) {
-                for (int8_t *&q : t.d_span)
-                    if (q) (void)hipFree(q), q = nullptr;
-                t.span_cap = 0;
-                for (int8_t *&q : t.d_span) {
-                    hipError_t e = hipMalloc((void **)&q, cap + kDataSlack);
-                    if (e != hipSuccess) {
-                        (void)hipGetLastError();
-                        q = nullptr;
-                        return fail(ctx, BDS_ERR_NOMEM, "resident span of 2 x %zu bytes of the IF record does not fit in HBM: %s", cap, hipGetErrorString(e));
-                    }
-                }
-                t.span_cap = cap;
-            }
-            cur.buf = t.d_span[0], cur.base = base0, cur.end = base0;
-            nxt.buf = t.d_span[1];
-            cur.end = std::max(cur.base, std::min(cur.base + span_n, need_end(hs, 0)));
-            const size_t nb0 = (size_t)nb_of(cur.end - cur.base);
-            if (nb0 && (rc = load((size_t)nb_of(cur.base), nb0, cur.buf, st(ctx)))) return rc;
-            t.loaded_bytes = nb0, t.pieces = 1, t.resident_max = nb0, t.repeated = 0;
+            const long long base0 = pl.live_min_pos(hs) & ~(al - 1);
+            long long min_half = 0;
+            if ((rc = pl.span_samples(ctx, hs, base0, limit, own, span_n, min_half))) return rc;
+            if ((rc = t.span.ensure(ctx, (size_t)nb_of(span_n)))) return rc;
+            cur.buf = t.span.buf[0], nxt.buf = t.span.buf[1];
+            cur.base = base0, cur.end = std::max(base0, std::min(base0 + span_n, pl.need_end(hs, n_epochs)));
         }
+        // the window, or the first span
+        const size_t nb0 = (size_t)nb_of(cur.end - cur.base);
+        if (nb0 && (rc = src.load((size_t)nb_of(cur.base), nb0, cur.buf, st(ctx)))) return rc;
+        t.loaded_bytes = nb0, t.pieces = 1, t.resident_max = nb0, t.repeated = 0;
     }
-    // per-call device buffers, released on every exit path
-    struct DevScope {
-        std::vector<void *> p;
-        std::vector<hipEvent_t> ev;
-        void add(void *q) { p.push_back(q); }
-        void release() {
-            for (void *q : p)
-                if (q) (void)hipFree(q);
-            for (hipEvent_t e : ev) (void)hipEventDestroy(e);
-            p.clear();
-            ev.clear();
-        }
-        ~DevScope() { release(); }
-    } scope;
+    DevScope scope;  // per-call device buffers and events, released on every exit path
     // state and partial sums ping-pong between two buffers when the loop update rides at the head of the next epoch's
     // correlate launch (default); with BDS_TRK_NOFUSE_UPDATE both halves are the same buffer and the update is its own launch
     const bool fuse = !ctx->tune.trk_nofuse_update;
     ChanState *d_st = nullptr;
     double *d_part = nullptr;
-    BDS_HIP(ctx, hipMalloc((void **)&d_st, sizeof(ChanState) * n_ch * 2));
-    scope.add(d_st);
     const size_t part_n = (size_t)n_ch * nblocks * kNSums;
-    BDS_HIP(ctx, hipMalloc((void **)&d_part, sizeof(double) * part_n * 2));
-    scope.add(d_part);
+    BDS_HIP(ctx, scope.alloc(&d_st, sizeof(ChanState) * n_ch * 2));
+    BDS_HIP(ctx, scope.alloc(&d_part, sizeof(double) * part_n * 2));
     BDS_HIP(ctx, hipMemcpyAsync(d_st, hs.data(), sizeof(ChanState) * n_ch, hipMemcpyHostToDevice, st(ctx)));
-    // device result arrays, initialised like the reference template (tracking.m:48-82)
-    const size_t ne = (size_t)n_ch * n_epochs;
-    TrkOut d{};
-    std::vector<double *> allocs;
-    std::vector<double> init(ne);
-    int err = BDS_OK;
-    for_each_field(out, &d, [&](double *host, double *&dev, double v0) {
-        if (err) return;
-        // arrays the variant does not create still need a device target when the kernel writes them
-        hipError_t e = hipMalloc((void **)&dev, sizeof(double) * ne);
-        if (e != hipSuccess) {
-            err = fail(ctx, BDS_ERR_NOMEM, "hipMalloc track output: %s", hipGetErrorString(e));
-            return;
-        }
-        allocs.push_back(dev);
-        scope.add(dev);
-        std::fill(init.begin(), init.end(), v0);
-        (void)hipMemcpyAsync(dev, init.data(), sizeof(double) * ne, hipMemcpyHostToDevice, st(ctx));
-        (void)hipStreamSynchronize(st(ctx));
-        (void)host;
-    });
-    if (err) return err;
-
-    hipEvent_t ev0, ev1;  // (owned by the scope: every early return below destroys them)
-    BDS_HIP(ctx, hipEventCreate(&ev0));
-    scope.ev.push_back(ev0);
-    BDS_HIP(ctx, hipEventCreate(&ev1));
-    scope.ev.push_back(ev1);
+    // device result arrays, initialised like the reference template (tracking.m:48-82); arrays the variant does not create
+    // still need a device target when the kernel writes them
+    TrkResults res;
+    if ((rc = res.prepare(ctx, n_ch, n_epochs))) return rc;
+    hipEvent_t ev0, ev1;
+    BDS_HIP(ctx, scope.event(&ev0));
+    BDS_HIP(ctx, scope.event(&ev1));
     BDS_HIP(ctx, hipEventRecord(ev0, st(ctx)));
-    TrkOut *d_out = nullptr;  // the table of result arrays, for the correlate launches that carry the previous epoch's update
-    BDS_HIP(ctx, hipMalloc((void **)&d_out, sizeof(TrkOut)));
-    scope.add(d_out);
-    BDS_HIP(ctx, hipMemcpyAsync(d_out, &d, sizeof(TrkOut), hipMemcpyHostToDevice, st(ctx)));
-    TrkRun run{ctx, t, p, d_st, d_part, part_n, d, d_out, nblocks, n_ch, fuse, d_st};
+    TrkRun run{ctx, t, p, d_st, d_part, part_n, res.d, res.d_out, nblocks, n_ch, fuse, d_st};
     RoctxRange rg_epochs("trk.epoch_loop");
     if (!stream) {
         run.run_batch(cur, 0, n_epochs, 0);
     } else {
-        SpanStream ss(ctx, t, load, st(ctx), ctx->stream2 ? (hipStream_t)ctx->stream2 : st(ctx), fmt, span_n);
+        SpanStream ss(ctx, t, src, st(ctx), ctx->stream2 ? (hipStream_t)ctx->stream2 : st(ctx), fmt, span_n);
         ss.cur = cur, ss.nxt = nxt;
         int slot = 0, k = 0;
         if ((rc = run_streamed(run, pl, ss, hs, n_epochs, false, false, slot, k))) return rc;
@@ -1881,8 +1954,8 @@ static int do_track(bds_ctx *ctx, const bds_settings *s, const RecordLoader &loa
     for (int c = 0; c < n_ch; ++c)
         if (hs[c].active == -2) {  // a channel read past the loaded window (code rate > 2 % low): redo with the whole record
             if (whole_file || stream) return fail(ctx, BDS_ERR_HIP, "bds_track: channel %d left the loaded record", c + 1);
-            scope.release();  // the retry allocates its own result arrays: do not hold this attempt's beside them
-            return do_track(ctx, s, load, n_bytes, n_ch, channel, out, true);
+            res.release(), scope.release();  // the retry allocates its own result arrays: do not hold this attempt's beside them
+            return do_track(ctx, s, src, n_ch, channel, out, true);
         }
 
     // The reference tracks channels one after another and returns at the first short read
@@ -1893,13 +1966,14 @@ static int do_track(bds_ctx *ctx, const bds_settings *s, const RecordLoader &loa
             first_abort = c;
             break;
         }
-    for_each_field(out, &d, [&](double *host, double *&dev, double v0) {
+    if ((rc = res.fetch(ctx, out))) return rc;
+    // epochs after the abort stay at the template value (device never wrote them), except absoluteSample of the aborted
+    // epoch which the reference assigns before the read; the channels behind it go back to the template
+    TrkOut unused{};
+    for_each_field(out, &unused, [&](double *host, double *&, double v0) {
         if (!host) return;
-        (void)hipMemcpy(host, dev, sizeof(double) * ne, hipMemcpyDeviceToHost);
         for (int c = first_abort + 1; c < n_ch; ++c)
             std::fill(host + (size_t)c * n_epochs, host + (size_t)(c + 1) * n_epochs, v0);
-        // epochs after the abort stay at the template value (device never wrote them), except
-        // absoluteSample of the aborted epoch which the reference assigns before the read
     });
     for (int c = 0; c < n_ch; ++c) {
         if (hs[c].prn == 0 || c > first_abort) {
@@ -1915,26 +1989,13 @@ static int do_track(bds_ctx *ctx, const bds_settings *s, const RecordLoader &loa
         const int pm = p.pilot ? (p.mode == BDS_TRACK_WB ? 2 : 1) : 0;
         const int nq = out->n_cno;
         double *d_raw = nullptr, *d_cno = nullptr;
-        BDS_HIP(ctx, hipMalloc((void **)&d_raw, sizeof(double) * (size_t)n_ch * nq * 3));
-        scope.add(d_raw);
-        BDS_HIP(ctx, hipMalloc((void **)&d_cno, sizeof(double) * (size_t)n_ch * nq * 5));
-        scope.add(d_cno);
+        BDS_HIP(ctx, scope.alloc(&d_raw, sizeof(double) * (size_t)n_ch * nq * 3));
+        BDS_HIP(ctx, scope.alloc(&d_cno, sizeof(double) * (size_t)n_ch * nq * 5));
         BDS_HIP(ctx, hipMemcpyAsync(d_st, hs.data(), sizeof(ChanState) * n_ch, hipMemcpyHostToDevice, st(ctx)));
-        hipLaunchKernelGGL(k_trk_cno, dim3(n_ch), dim3(256), 0, st(ctx), d, (const ChanState *)d_st, n_epochs, M, nq, pm,
+        hipLaunchKernelGGL(k_trk_cno, dim3(n_ch), dim3(256), 0, st(ctx), res.d, (const ChanState *)d_st, n_epochs, M, nq, pm,
                            s->intTime, d_raw, d_cno);
-        std::vector<double> h((size_t)n_ch * nq * 5);
-        BDS_HIP(ctx, hipMemcpyAsync(h.data(), d_cno, sizeof(double) * h.size(), hipMemcpyDeviceToHost, st(ctx)));
-        BDS_HIP(ctx, hipStreamSynchronize(st(ctx)));
-        double *dst[5] = {out->DataCNo, out->DataPLD, out->PilotCNo, out->PilotPLD, out->SigCNo};
-        const size_t plane = (size_t)n_ch * nq;
-        for (int f = 0; f < 5; ++f) {
-            if (!dst[f]) continue;
-            for (int c = 0; c < n_ch; ++c)
-                for (int q = 0; q < nq; ++q) {
-                    const bool live = out->completed[c] > 0 && (q + 1) * M <= out->completed[c] && (pm || f < 2);
-                    dst[f][(size_t)c * nq + q] = live ? h[f * plane + (size_t)c * nq + q] : 0.0;
-                }
-        }
+        // interval q counts when (q + 1) M <= completed
+        return cno_scatter(ctx, d_cno, n_ch, nq, pm, out, [&](int c) { return out->completed[c] / M; });
     }
     return BDS_OK;
 }
@@ -1955,27 +2016,15 @@ struct bds_track_session {
     std::vector<long long> epochs_done;
     // the record
     bool feed = false, fed_last = false;
-    const int8_t *mem = nullptr;  // the record in memory: the host's, or (mem_dev) the device's
-    bool mem_dev = false;
-    FILE *file = nullptr;
-    void *pin = nullptr;
-    size_t pin_bytes = 0;
-    std::string path;
-    bds::RecordLoader load;
+    bds::RecordSource src;  // (a fed session: none)
     std::unique_ptr<bds::SpanStream> ss;
-    int8_t *span[2] = {nullptr, nullptr};
+    bds::SpanPair span;
     // the epoch loop's device buffers
     bds::ChanState *d_st = nullptr;
     double *d_part = nullptr;
     size_t part_n = 0;
     int slot = 0;
-    bds::TrkOut d{};
-    bds::TrkOut *d_out = nullptr;
-    double *d_fields = nullptr;  // one block [21][n_ch][row]: the result arrays of an advance
-    size_t fields_cap = 0;
-    int row = 0;                 // row length the table at d_out was made for
-    uint32_t inf_mask = 0;
-    std::vector<double> h_fields;
+    bds::TrkResults res;  // the result arrays of an advance
     // C/N0 carry (k_trk_cno_seg)
     double *d_carry = nullptr, *d_prev3 = nullptr, *d_raw = nullptr, *d_cno = nullptr;
     int *d_ncarry = nullptr;
@@ -1985,7 +2034,8 @@ struct bds_track_session {
 namespace bds {
 
 static constexpr size_t kSessionResident = (size_t)256 << 20;  // resident limit of a session when the context has none
-static constexpr long long kFeedOpen = 1LL << 60;              // "samples in the record" while a feed session has not seen `last`
+static constexpr size_t kSessionStage = (size_t)64 << 20;      // pinned staging of a session that reads a file, at the most
+static constexpr long long kFeedOpen = 1LL << 60;             // "samples in the record" while a feed session has not seen `last`
 
 static std::mutex g_sess_mu;
 static std::set<const bds_track_session *> g_sessions;  // handles that are open: anything else is refused unread
@@ -1998,7 +2048,7 @@ int track_session_guard(bds_ctx *ctx, const char *who) {
     if (!ctx || !ctx->trk || !ctx->trk->session) return BDS_OK;
     const bds_track_session *h = ctx->trk->session;
     return fail(ctx, BDS_ERR_ARG, "%s: the context has an open tracking session (%d channels on %s): bds_track_close it first", who, h->n_ch,
-                h->feed ? "a fed record" : h->mem_dev ? "a record in device memory" : h->mem ? "a record in memory" : h->path.c_str());
+                h->src.what());
 }
 
 static void session_close(bds_track_session *h) {
@@ -2011,13 +2061,11 @@ static void session_close(bds_track_session *h) {
     h->ss.reset();  // joins the loader
     (void)hipStreamSynchronize(st(ctx));
     if (ctx->stream2) (void)hipStreamSynchronize((hipStream_t)ctx->stream2);
-    for (void *q : {(void *)h->span[0], (void *)h->span[1], (void *)h->d_st, (void *)h->d_part, (void *)h->d_out, (void *)h->d_fields,
-                    (void *)h->d_carry, (void *)h->d_prev3, (void *)h->d_raw, (void *)h->d_cno, (void *)h->d_ncarry})
+    h->span.release();
+    for (void *q : {(void *)h->d_st, (void *)h->d_part, (void *)h->d_carry, (void *)h->d_prev3, (void *)h->d_raw, (void *)h->d_cno, (void *)h->d_ncarry})
         if (q) (void)hipFree(q);
-    if (h->pin) (void)hipHostFree(h->pin);
-    if (h->file) fclose(h->file);
     if (ctx->trk && ctx->trk->session == h) ctx->trk->session = nullptr;
-    delete h;
+    delete h;  // (the result block, the record's file and its staging buffer go with it)
 }
 
 // kind: 0 file at `path`, 1 `n_bytes` bytes at `mem`, 2 fed by the caller from sample `origin` on, 3 `n_bytes` bytes at `mem` in
@@ -2038,22 +2086,20 @@ static bds_track_session *session_open(bds_ctx *ctx, const bds_settings *s, int 
     if (!ctx->trk) ctx->trk = new TrackState();
     TrackState &t = *ctx->trk;
     bds_track_session *h = new bds_track_session();
-    h->ctx = ctx, h->s = *s, h->n_ch = n_ch, h->feed = kind == 2, h->mem = kind == 1 || kind == 3 ? mem : nullptr, h->mem_dev = kind == 3;
+    h->ctx = ctx, h->s = *s, h->n_ch = n_ch, h->feed = kind == 2;
     h->epochs_done.assign((size_t)n_ch, 0);
     h->margin = ctx->tune.trk_stream_margin >= 0 ? ctx->tune.trk_stream_margin : 1.0;
     // (not registered yet: every failure below frees it here)
     auto body = [&]() -> int {
-        if (kind == 0) {
-            h->path = path;
-            h->file = fopen(path, "rb");
-            if (!h->file) return fail(ctx, BDS_ERR_IO, "Unable to read file %s", path);  // postProcessing.m:152-154
-            fseeko(h->file, 0, SEEK_END);
-            const long long sz = ftello(h->file);
-            if (sz <= 0) return fail(ctx, BDS_ERR_IO, "file %s is empty", path);
-            n_bytes = (size_t)sz;
+        int rc = BDS_OK;
+        switch (kind) {
+        case 0: rc = h->src.open_file(ctx, path, kSessionStage); break;
+        case 1: h->src.set_host(ctx, mem, n_bytes); break;
+        case 3: h->src.set_device(ctx, mem, n_bytes); break;
+        default: h->src.set_none(ctx); break;
         }
-        int rc = track_setup(ctx, t, &h->s, 1, kind == 2 ? 0 : n_bytes, n_ch, channel, h->u);
         if (rc) return rc;
+        if ((rc = track_setup(ctx, t, &h->s, 1, h->src.size(), n_ch, channel, h->u))) return rc;
         TrkParams &p = h->u.p;
         std::vector<ChanState> &hs = h->u.hs;
         const int fmt = p.cplx;
@@ -2068,61 +2114,21 @@ static bds_track_session *session_open(bds_ctx *ctx, const bds_settings *s, int 
         // the resident span: sized like do_track's streamed path, from the context's resident limit or the session's default
         TrkPlanner pl(ctx, &h->s, p, n_ch);
         const long long base0 = kind == 2 ? origin : pl.live_min_pos(hs) & ~(al - 1);
-        const long long min_half = pl.min_half(hs, base0, al);
-        const size_t min_limit = (size_t)fmt_bytes(fmt, 2 * min_half);
-        size_t limit = t.resident_limit ? t.resident_limit : std::max(kSessionResident, min_limit);
-        if (limit < min_limit)
-            return fail(ctx, BDS_ERR_ARG, "resident limit of %zu bytes is too small for these channels: the spread of their positions plus "
-                        "one block, in each of the two span buffers, needs at least %zu bytes%s", limit, min_limit,
-                        fmt == kFmtPacked ? " of the packed record" : "");
-        long long span_n = fmt_samples(fmt, (long long)(limit / 2)) & ~(al - 1);
+        long long span_n = 0, min_half = 0;
+        if ((rc = pl.span_samples(ctx, hs, base0, t.resident_limit ? t.resident_limit : kSessionResident, !t.resident_limit, span_n, min_half)))
+            return rc;
         if (kind != 2)  // no more than the record from the first channel on
             span_n = std::min(span_n, std::max(min_half, (std::max(0LL, p.n_bytes - base0) + al - 1) & ~(al - 1)));
-        const size_t cap = (size_t)fmt_bytes(fmt, span_n);
-        for (int8_t *&q : h->span)
-            if (hipMalloc((void **)&q, cap + kDataSlack) != hipSuccess) {
-                (void)hipGetLastError();
-                q = nullptr;
-                return fail(ctx, BDS_ERR_NOMEM, "resident span of 2 x %zu bytes of the IF record does not fit in HBM", cap);
-            }
-        // the record's source
-        if (kind == 1 || kind == 3) {
-            const hipMemcpyKind dir = kind == 3 ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
-            h->load = [ctx, mem, dir](size_t off, size_t n, int8_t *dst, hipStream_t stream) -> int {
-                BDS_HIP(ctx, hipMemcpyAsync(dst, mem + off, n, dir, stream));
-                return BDS_OK;
-            };
-        } else if (kind == 0) {
-            h->pin_bytes = std::min<size_t>((size_t)64 << 20, n_bytes);
-            BDS_HIP(ctx, hipHostMalloc(&h->pin, h->pin_bytes, 0));
-            h->load = [ctx, h](size_t off, size_t n, int8_t *dst, hipStream_t stream) -> int {
-                if (fseeko(h->file, (off_t)off, SEEK_SET)) return fail(ctx, BDS_ERR_IO, "seek in %s failed", h->path.c_str());
-                size_t done = 0;
-                while (done < n) {
-                    const size_t m = std::min(h->pin_bytes, n - done);
-                    if (fread(h->pin, 1, m, h->file) != m) return fail(ctx, BDS_ERR_IO, "short read on %s", h->path.c_str());
-                    hipError_t e = hipMemcpyAsync(dst + done, h->pin, m, hipMemcpyHostToDevice, stream);
-                    if (e == hipSuccess) e = hipStreamSynchronize(stream);  // the staging buffer is filled again next
-                    if (e != hipSuccess) return fail(ctx, BDS_ERR_HIP, "H2D copy: %s", hipGetErrorString(e));
-                    done += m;
-                }
-                return BDS_OK;
-            };
-        } else {
-            h->load = [ctx](size_t, size_t, int8_t *, hipStream_t) -> int {
-                return fail(ctx, BDS_ERR_ARG, "a feed session has no record to load from");
-            };
-        }
+        if ((rc = h->span.ensure(ctx, (size_t)fmt_bytes(fmt, span_n)))) return rc;
         // (feed: the caller's thread is the loader -- one stream)
-        h->ss.reset(new SpanStream(ctx, t, h->load, st(ctx), kind != 2 && ctx->stream2 ? (hipStream_t)ctx->stream2 : st(ctx), fmt, span_n));
-        h->ss->cur.buf = h->span[0], h->ss->cur.base = h->ss->cur.end = base0;  // (the first advance / feed fills it)
-        h->ss->nxt.buf = h->span[1];
+        h->ss.reset(new SpanStream(ctx, t, h->src, st(ctx), kind != 2 && ctx->stream2 ? (hipStream_t)ctx->stream2 : st(ctx), fmt, span_n));
+        h->ss->cur.buf = h->span.buf[0], h->ss->cur.base = h->ss->cur.end = base0;  // (the first advance / feed fills it)
+        h->ss->nxt.buf = h->span.buf[1];
         t.loaded_bytes = 0, t.pieces = 0, t.resident_max = 0, t.repeated = 0;
         // the epoch loop's buffers; the state starts in half 0
         h->part_n = (size_t)n_ch * h->u.nblocks * kNSums;
         BDS_HIP(ctx, hipMalloc((void **)&h->d_st, sizeof(ChanState) * n_ch * 2));
         BDS_HIP(ctx, hipMalloc((void **)&h->d_part, sizeof(double) * h->part_n * 2));
-        BDS_HIP(ctx, hipMalloc((void **)&h->d_out, sizeof(TrkOut)));
         const int M = h->s.CNoInterval;
         if (M > 1) {
             BDS_HIP(ctx, hipMalloc((void **)&h->d_carry, sizeof(double) * (size_t)n_ch * 4 * M));
@@ -2269,29 +2275,9 @@ extern "C" int bds_track_advance(bds_track_session *sess, int max_epochs, bds_tr
         return fail(ctx, BDS_ERR_ARG, "bds_track_advance: out->n_cno = %d, but %d C/N0 intervals can complete in this call", out->n_cno, need_cno);
     BDS_HIP(ctx, hipSetDevice(ctx->device));
     TrackState &t = *ctx->trk;
-    // the call's result arrays: one device block [21][n_ch][row], row = out->n_epochs, at the reference's template values
+    // the call's result arrays, rows of out->n_epochs, at the reference's template values
     const int row = out->n_epochs;
-    const size_t n = (size_t)n_ch * row;
-    constexpr int kFields = sizeof(TrkOut) / sizeof(double *);
-    if (h->fields_cap < n * kFields) {
-        if (h->d_fields) (void)hipFree(h->d_fields), h->d_fields = nullptr, h->fields_cap = 0;
-        BDS_HIP(ctx, hipMalloc((void **)&h->d_fields, sizeof(double) * n * kFields));
-        h->fields_cap = n * kFields;
-        h->row = 0;
-    }
-    if (h->row != row) {
-        int f = 0;
-        h->inf_mask = 0;
-        for_each_field(out, &h->d, [&](double *, double *&dev, double v0) {
-            dev = h->d_fields + (size_t)f * n;
-            if (v0 != 0.0) h->inf_mask |= 1u << f;
-            ++f;
-        });
-        BDS_HIP(ctx, hipMemcpyAsync(h->d_out, &h->d, sizeof(TrkOut), hipMemcpyHostToDevice, st(ctx)));
-        BDS_HIP(ctx, hipStreamSynchronize(st(ctx)));  // (h->d may not change while the copy reads it)
-        h->row = row;
-    }
-    hipLaunchKernelGGL(k_trk_fill_out, dim3((unsigned)((n * kFields + 255) / 256)), dim3(256), 0, st(ctx), h->d_fields, n, kFields, h->inf_mask);
+    if (int rc = h->res.prepare(ctx, n_ch, row)) return rc;
     const int nq = std::max(need_cno, 1);
     if (M > 1 && h->cno_cap < nq) {
         if (h->d_raw) (void)hipFree(h->d_raw), h->d_raw = nullptr;
@@ -2305,7 +2291,7 @@ extern "C" int bds_track_advance(bds_track_session *sess, int max_epochs, bds_tr
     for (ChanState &c : hs) c.completed = 0;
     BDS_HIP(ctx, hipMemcpyAsync(h->d_st + (size_t)h->slot * n_ch, hs.data(), sizeof(ChanState) * n_ch, hipMemcpyHostToDevice, st(ctx)));
     p.n_epochs = row;
-    TrkRun run{ctx, t, p, h->d_st, h->d_part, h->part_n, h->d, h->d_out, h->u.nblocks, n_ch, !ctx->tune.trk_nofuse_update,
+    TrkRun run{ctx, t, p, h->d_st, h->d_part, h->part_n, h->res.d, h->res.d_out, h->u.nblocks, n_ch, !ctx->tune.trk_nofuse_update,
                h->d_st + (size_t)h->slot * n_ch};
     TrkPlanner pl(ctx, &h->s, p, n_ch);
     pl.margin = h->margin;
@@ -2318,48 +2304,32 @@ extern "C" int bds_track_advance(bds_track_session *sess, int max_epochs, bds_tr
     if (rc) return rc;
     BDS_HIP(ctx, hipGetLastError());
     const int pm = p.pilot ? (p.mode == BDS_TRACK_WB ? 2 : 1) : 0;
-    if (M > 1 && k > 0)
-        hipLaunchKernelGGL(k_trk_cno_seg, dim3(n_ch), dim3(256), 0, st(ctx), h->d, (const ChanState *)(h->d_st + (size_t)h->slot * n_ch), row, M, nq,
+    const bool cno_ran = M > 1 && k > 0;
+    if (cno_ran)
+        hipLaunchKernelGGL(k_trk_cno_seg, dim3(n_ch), dim3(256), 0, st(ctx), h->res.d, (const ChanState *)(h->d_st + (size_t)h->slot * n_ch), row, M, nq,
                            pm, h->s.intTime, h->d_carry, h->d_ncarry, h->d_prev3, h->d_raw, h->d_cno);
-    h->h_fields.resize(n * kFields + (size_t)n_ch * nq * 5);
-    BDS_HIP(ctx, hipMemcpyAsync(h->h_fields.data(), h->d_fields, sizeof(double) * n * kFields, hipMemcpyDeviceToHost, st(ctx)));
-    double *hc = h->h_fields.data() + n * kFields;
-    if (M > 1 && k > 0) BDS_HIP(ctx, hipMemcpyAsync(hc, h->d_cno, sizeof(double) * (size_t)n_ch * nq * 5, hipMemcpyDeviceToHost, st(ctx)));
-    BDS_HIP(ctx, hipStreamSynchronize(st(ctx)));
-    {
-        int f = 0;
-        TrkOut unused{};
-        for_each_field(out, &unused, [&](double *host, double *&, double) {
-            if (host) memcpy(host, h->h_fields.data() + (size_t)f * n, sizeof(double) * n);
-            ++f;
-        });
-    }
-    double *dst[5] = {out->DataCNo, out->DataPLD, out->PilotCNo, out->PilotPLD, out->SigCNo};
+    if ((rc = h->res.fetch(ctx, out))) return rc;
+    // intervals a channel finished in this call: those its epochs of before and of this call complete together
+    std::vector<int> nd((size_t)n_ch, 0);
     for (int c = 0; c < n_ch; ++c) {
         const int done = hs[c].prn ? hs[c].completed : 0;
         const long long e0 = h->epochs_done[c];
-        const int nd = M > 1 ? (int)((e0 + done) / M - e0 / M) : 0;
+        if (M > 1) nd[c] = (int)((e0 + done) / M - e0 / M);
         out->completed[c] = done;
         out->status[c] = hs[c].prn && k > 0 && done == k ? 'T' : '-';
-        if (n_cno_done) n_cno_done[c] = nd;
+        if (n_cno_done) n_cno_done[c] = nd[c];
         h->epochs_done[c] = e0 + done;
-        for (int f = 0; f < 5; ++f) {
-            if (!dst[f] || !out->DataCNo) continue;
-            for (int q = 0; q < out->n_cno; ++q)
-                dst[f][(size_t)c * out->n_cno + q] = q < nd && (pm || f < 2) ? hc[(size_t)f * n_ch * nq + (size_t)c * nq + q] : 0.0;
-        }
     }
+    if (out->DataCNo && (rc = cno_scatter(ctx, cno_ran ? h->d_cno : nullptr, n_ch, nq, pm, out, [&](int c) { return nd[c]; }))) return rc;
     return k;
 }
 
 extern "C" int bds_track_mem(bds_ctx *ctx, const bds_settings *s, const int8_t *file_bytes, size_t n_bytes, int n_ch,
                              const bds_channel *channel, bds_track_out *out) {
     if (!ctx || !file_bytes) return BDS_ERR_ARG;
-    const RecordLoader load = [&](size_t off, size_t n, int8_t *dst, hipStream_t stream) -> int {
-        BDS_HIP(ctx, hipMemcpyAsync(dst, file_bytes + off, n, hipMemcpyHostToDevice, stream));
-        return BDS_OK;
-    };
-    return do_track(ctx, s, load, n_bytes, n_ch, channel, out);
+    RecordSource src;
+    src.set_host(ctx, file_bytes, n_bytes);
+    return do_track(ctx, s, src, n_ch, channel, out);
 }
 
 extern "C" int bds_track_dev(bds_ctx *ctx, const bds_settings *s, const void *d_file_bytes, size_t n_bytes, int n_ch,
@@ -2367,49 +2337,18 @@ extern "C" int bds_track_dev(bds_ctx *ctx, const bds_settings *s, const void *d_
     if (!ctx) return BDS_ERR_ARG;
     if (!d_file_bytes) return fail(ctx, BDS_ERR_ARG, "bds_track_dev: d_file_bytes is NULL");
     if (int rc = check_device_span(ctx, "bds_track_dev", "d_file_bytes", d_file_bytes, n_bytes)) return rc;
-    const int8_t *mem = (const int8_t *)d_file_bytes;
-    const RecordLoader load = [&](size_t off, size_t n, int8_t *dst, hipStream_t stream) -> int {
-        BDS_HIP(ctx, hipMemcpyAsync(dst, mem + off, n, hipMemcpyDeviceToDevice, stream));
-        return BDS_OK;
-    };
-    return do_track(ctx, s, load, n_bytes, n_ch, channel, out);
+    RecordSource src;
+    src.set_device(ctx, d_file_bytes, n_bytes);
+    return do_track(ctx, s, src, n_ch, channel, out);
 }
 
 extern "C" int bds_track(bds_ctx *ctx, const bds_settings *s, const char *path, int n_ch, const bds_channel *channel,
                          bds_track_out *out) {
     if (!ctx || !path) return BDS_ERR_ARG;
-    FILE *f = fopen(path, "rb");
-    if (!f) return fail(ctx, BDS_ERR_IO, "Unable to read file %s", path);  // postProcessing.m:152-154
-    struct Closer {
-        FILE *f;
-        void *pin = nullptr;
-        ~Closer() {
-            fclose(f);
-            if (pin) (void)hipHostFree(pin);
-        }
-    } guard{f};
-    fseeko(f, 0, SEEK_END);
-    const long long sz = ftello(f);
-    if (sz <= 0) return fail(ctx, BDS_ERR_IO, "file %s is empty", path);
-    BDS_HIP(ctx, hipSetDevice(ctx->device));
     // the window of the record the channels can touch, staged through pinned memory in 256 MiB pieces
-    const size_t piece = 256u << 20;
-    const RecordLoader load = [&](size_t off, size_t n, int8_t *dst, hipStream_t stream) -> int {
-        if (!guard.pin && hipHostMalloc(&guard.pin, std::min<size_t>(piece, (size_t)sz), 0) != hipSuccess)
-            return fail(ctx, BDS_ERR_NOMEM, "pinned staging buffer");
-        if (fseeko(f, (off_t)off, SEEK_SET)) return fail(ctx, BDS_ERR_IO, "seek in %s failed", path);
-        size_t done = 0;
-        while (done < n) {
-            const size_t m = std::min(piece, n - done);
-            if (fread(guard.pin, 1, m, f) != m) return fail(ctx, BDS_ERR_IO, "short read on %s", path);
-            hipError_t e = hipMemcpyAsync(dst + done, guard.pin, m, hipMemcpyHostToDevice, stream);
-            if (e == hipSuccess) e = hipStreamSynchronize(stream);  // the staging buffer is filled again next
-            if (e != hipSuccess) return fail(ctx, BDS_ERR_HIP, "H2D copy: %s", hipGetErrorString(e));
-            done += m;
-        }
-        return BDS_OK;
-    };
-    return do_track(ctx, s, load, (size_t)sz, n_ch, channel, out);
+    RecordSource src;
+    if (int rc = src.open_file(ctx, path, (size_t)256 << 20)) return rc;
+    return do_track(ctx, s, src, n_ch, channel, out);
 }
 
 extern "C" long long bds_track_loaded_bytes(bds_ctx *ctx) {
@@ -2469,33 +2408,20 @@ extern "C" int bds_track_correlate(bds_ctx *ctx, const bds_settings *s, const in
     int8_t *d_data = nullptr;
     int *d_prn = nullptr;
     double *d_s6 = nullptr, *d_part = nullptr, *d_sums = nullptr;
-    struct Scope {  // released on every exit path
-        void **p[5];
-        ~Scope() {
-            for (void **q : p)
-                if (*q) (void)hipFree(*q);
-        }
-    } scope{{(void **)&d_data, (void **)&d_prn, (void **)&d_s6, (void **)&d_part, (void **)&d_sums}};
-    BDS_HIP(ctx, hipMalloc((void **)&d_data, n_bytes + kDataSlack));
-    BDS_HIP(ctx, hipMalloc((void **)&d_prn, sizeof(int) * n_ch));
-    BDS_HIP(ctx, hipMalloc((void **)&d_s6, sizeof(double) * 6 * n_ch));
-    BDS_HIP(ctx, hipMalloc((void **)&d_part, sizeof(double) * (size_t)n_ch * nblocks * kNSums));
-    BDS_HIP(ctx, hipMalloc((void **)&d_sums, sizeof(double) * (size_t)n_ch * kNSums));
+    DevScope scope;
+    BDS_HIP(ctx, scope.alloc(&d_data, n_bytes + kDataSlack));
+    BDS_HIP(ctx, scope.alloc(&d_prn, sizeof(int) * n_ch));
+    BDS_HIP(ctx, scope.alloc(&d_s6, sizeof(double) * 6 * n_ch));
+    BDS_HIP(ctx, scope.alloc(&d_part, sizeof(double) * (size_t)n_ch * nblocks * kNSums));
+    BDS_HIP(ctx, scope.alloc(&d_sums, sizeof(double) * (size_t)n_ch * kNSums));
     BDS_HIP(ctx, hipMemcpyAsync(d_data, file_bytes, n_bytes, hipMemcpyHostToDevice, st(ctx)));
     BDS_HIP(ctx, hipMemcpyAsync(d_prn, prn, sizeof(int) * n_ch, hipMemcpyHostToDevice, st(ctx)));
     BDS_HIP(ctx, hipMemcpyAsync(d_s6, state6, sizeof(double) * 6 * n_ch, hipMemcpyHostToDevice, st(ctx)));
     dim3 gc(nblocks, n_ch);
     // bds_get_timing after this call: search_ms = the two kernels alone (the upload and the download stand outside the events)
     hipEvent_t ev[2] = {nullptr, nullptr};
-    struct Events {
-        hipEvent_t *e;
-        ~Events() {
-            for (int i = 0; i < 2; ++i)
-                if (e[i]) (void)hipEventDestroy(e[i]);
-        }
-    } ev_scope{ev};
-    BDS_HIP(ctx, hipEventCreate(&ev[0]));
-    BDS_HIP(ctx, hipEventCreate(&ev[1]));
+    BDS_HIP(ctx, scope.event(&ev[0]));
+    BDS_HIP(ctx, scope.event(&ev[1]));
     BDS_HIP(ctx, hipEventRecord(ev[0], st(ctx)));
     BDS_TRK_LAUNCH(k_trk_correlate_open, gc, (p.runs ? runs_lds_bytes(p.runs, p.prec) : 0), st(ctx), (const int8_t *)d_data, (const int8_t *)t.d_prim, p,
                    (const int *)d_prn, (const double *)d_s6, d_part, nblocks);
@@ -2530,17 +2456,11 @@ extern "C" int bds_track_colon(bds_ctx *ctx, int n, const double *a, const doubl
     const size_t nd = sizeof(double) * (size_t)n, ni = sizeof(int) * (size_t)n;
     double *d_in = nullptr, *d_out = nullptr;  // a, d, b | value, c
     int *d_k = nullptr, *d_n = nullptr;
-    struct Scope {  // released on every exit path
-        void **p[4];
-        ~Scope() {
-            for (void **q : p)
-                if (*q) (void)hipFree(*q);
-        }
-    } scope{{(void **)&d_in, (void **)&d_out, (void **)&d_k, (void **)&d_n}};
-    BDS_HIP(ctx, hipMalloc((void **)&d_in, 3 * nd));
-    BDS_HIP(ctx, hipMalloc((void **)&d_out, 2 * nd));
-    BDS_HIP(ctx, hipMalloc((void **)&d_k, ni));
-    BDS_HIP(ctx, hipMalloc((void **)&d_n, ni));
+    DevScope scope;
+    BDS_HIP(ctx, scope.alloc(&d_in, 3 * nd));
+    BDS_HIP(ctx, scope.alloc(&d_out, 2 * nd));
+    BDS_HIP(ctx, scope.alloc(&d_k, ni));
+    BDS_HIP(ctx, scope.alloc(&d_n, ni));
     BDS_HIP(ctx, hipMemcpyAsync(d_in, a, nd, hipMemcpyHostToDevice, st(ctx)));
     BDS_HIP(ctx, hipMemcpyAsync(d_in + n, d, nd, hipMemcpyHostToDevice, st(ctx)));
     BDS_HIP(ctx, hipMemcpyAsync(d_in + 2 * (size_t)n, b, nd, hipMemcpyHostToDevice, st(ctx)));
@@ -2554,20 +2474,6 @@ extern "C" int bds_track_colon(bds_ctx *ctx, int n, const double *a, const doubl
     BDS_HIP(ctx, hipStreamSynchronize(st(ctx)));
     return BDS_OK;
 }
-
-// device memory of a test aid, released on every exit path
-struct AidScope {
-    std::vector<void *> v;
-    template <class T>
-    hipError_t alloc(T **q, size_t bytes) {
-        const hipError_t e = hipMalloc((void **)q, std::max<size_t>(bytes, 8));
-        if (e == hipSuccess) v.push_back(*q);
-        return e;
-    }
-    ~AidScope() {
-        for (void *q : v) (void)hipFree(q);
-    }
-};
 
 // Test aid (bds_track_cno): k_trk_cno, or k_trk_cno_seg once per piece, on prompt arrays of the caller.  The host side only
 // places the arrays and gathers the intervals of each piece, as do_track / bds_track_advance do.
@@ -2592,7 +2498,7 @@ extern "C" int bds_track_cno(bds_ctx *ctx, const bds_settings *s, int n_ch, int 
     const int pm = pilot_on(*s, mode) ? (mode == BDS_TRACK_WB ? 2 : 1) : 0;
     const size_t ne = (size_t)n_ch * n_epochs;
     const int nq_max = std::max(n_cno, n_epochs / M + 2);  // intervals one launch can report
-    AidScope scope;
+    DevScope scope;
     double *d_p = nullptr, *d_raw = nullptr, *d_cno = nullptr, *d_carry = nullptr, *d_prev3 = nullptr;
     int *d_ncarry = nullptr;
     ChanState *d_st = nullptr;
@@ -2683,39 +2589,21 @@ extern "C" int bds_track_update(bds_ctx *ctx, const bds_settings *s, int n_ch, c
         hs[c].prn = 1, hs[c].active = 1;
     }
     BDS_HIP(ctx, hipSetDevice(ctx->device));
-    constexpr int kFields = sizeof(TrkOut) / sizeof(double *);
-    AidScope scope;
+    DevScope scope;
     ChanState *d_st = nullptr;
-    double *d_part = nullptr, *d_fields = nullptr;
+    double *d_part = nullptr;
     BDS_HIP(ctx, scope.alloc(&d_st, sizeof(ChanState) * n_ch));
     BDS_HIP(ctx, scope.alloc(&d_part, sizeof(double) * (size_t)n_ch * kNSums));
-    BDS_HIP(ctx, scope.alloc(&d_fields, sizeof(double) * (size_t)n_ch * kFields));
-    TrkOut d{};
-    bds_track_out unused{};
-    uint32_t inf_mask = 0;
-    int f = 0;
-    for_each_field(&unused, &d, [&](double *, double *&dev, double v0) {  // [21][n_ch], at the reference's template values
-        dev = d_fields + (size_t)f * n_ch;
-        if (v0 != 0.0) inf_mask |= 1u << f;
-        ++f;
-    });
+    TrkResults res;  // [21][n_ch] (one epoch), at the reference's template values
+    if ((rc = res.prepare(ctx, n_ch, 1))) return rc;
     BDS_HIP(ctx, hipMemcpyAsync(d_st, hs.data(), sizeof(ChanState) * n_ch, hipMemcpyHostToDevice, st(ctx)));
     BDS_HIP(ctx, hipMemcpyAsync(d_part, sums18, sizeof(double) * (size_t)n_ch * kNSums, hipMemcpyHostToDevice, st(ctx)));
-    hipLaunchKernelGGL(k_trk_fill_out, dim3((unsigned)(((size_t)n_ch * kFields + 255) / 256)), dim3(256), 0, st(ctx), d_fields, (size_t)n_ch, kFields, inf_mask);
-    switch (p.mode) {
-        case BDS_TRACK_B2A:
-            hipLaunchKernelGGL(k_trk_update<BDS_TRACK_B2A>, dim3(n_ch), dim3(kUpdThreads), 0, st(ctx), p, d_st, (const double *)d_part, 1, 0, d);
-            break;
-        case BDS_TRACK_NB:
-            hipLaunchKernelGGL(k_trk_update<BDS_TRACK_NB>, dim3(n_ch), dim3(kUpdThreads), 0, st(ctx), p, d_st, (const double *)d_part, 1, 0, d);
-            break;
-        default:
-            hipLaunchKernelGGL(k_trk_update<BDS_TRACK_WB>, dim3(n_ch), dim3(kUpdThreads), 0, st(ctx), p, d_st, (const double *)d_part, 1, 0, d);
-            break;
-    }
+    if (!ctx->trk) ctx->trk = new TrackState();
+    TrkRun run{ctx, *ctx->trk, p, d_st, d_part, (size_t)n_ch * kNSums, res.d, res.d_out, 1, n_ch, false, d_st};
+    run.launch_update(d_st, d_part, 0);
     BDS_HIP(ctx, hipGetLastError());
     BDS_HIP(ctx, hipMemcpyAsync(hs.data(), d_st, sizeof(ChanState) * n_ch, hipMemcpyDeviceToHost, st(ctx)));
-    BDS_HIP(ctx, hipMemcpyAsync(out21, d_fields, sizeof(double) * (size_t)n_ch * kFields, hipMemcpyDeviceToHost, st(ctx)));
+    BDS_HIP(ctx, hipMemcpyAsync(out21, res.d_fields, sizeof(double) * (size_t)n_ch * TrkResults::kFields, hipMemcpyDeviceToHost, st(ctx)));
     BDS_HIP(ctx, hipStreamSynchronize(st(ctx)));
     for (int c = 0; c < n_ch; ++c) {
         memcpy(state10_out + (size_t)c * 10, &hs[c], sizeof(double) * 10);
