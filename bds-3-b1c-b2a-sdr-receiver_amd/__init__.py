@@ -9,6 +9,8 @@ Host-side mirror of the reference's MATLAB call surface
     trackResults, channel = tracking(fid, channel, settings)    tracking.m / NB_tracking.m / WB_tracking.m
     TrackSession(source, channel, settings)                     the same run advanced in pieces, or fed by the caller
     probe_data(settings) / probe_data(fileName, settings)       include/probeData.m (the numbers; also arrays and device tensors)
+    frame_sync(trackResults, settings)                          include/BCNAV?decoding.m, the correlators
+    nav_decode(trackResults, settings)                          include/BCNAV?decoding.m + ephemeris.m: eph, firstSubFrame, TOW
 
 All numeric work happens in ``libbds_mi355x.so`` (HIP kernels for gfx950) through
 the C ABI of ``include/bds_mi355x.h``; there is no CPU fallback.
@@ -20,4 +22,5 @@ from .framesync import frame_sync, unpack_cplx  # noqa: F401
 from .distributed import shard_prns, shard_joint, sharded_acquisition, sharded_acquisition_joint  # noqa: F401
 from .probedata import probe_data, ProbeResult  # noqa: F401
 from .corrfn import corr_function, track_states  # noqa: F401
+from .navdecode import nav_decode, BCNAV1decoding, BCNAV2decoding  # noqa: F401
 from . import native, synth  # noqa: F401

@@ -92,6 +92,29 @@ class SynthOpts(C.Structure):
                 ("threshold", C.c_double), ("symbols", C.POINTER(C.c_int8)), ("n_sym", C.c_int64)]
 
 
+# the doubles of bds_eph, in the order of BDS_EPH_FIELDS (include/bds_mi355x.h)
+EPH_FIELDS = ["PRN", "SOH", "SOW", "WN", "HOW", "IODC", "IODE", "IODC_MSB2", "IODC_LSB8",
+              "t_oe", "deltaA", "ADot", "delta_n_0", "delta_n_0Dot", "M_0", "e", "omega",
+              "omega_0", "i_0", "omegaDot", "i_0Dot", "C_is", "C_ic", "C_rs", "C_rc", "C_us", "C_uc",
+              "t_oc", "a_0", "a_1", "a_2", "T_GDB2ap", "ISC_B1Cd", "T_GDB1Cp",
+              "PageID1", "PageID3", "HS", "DIF", "SIF", "AIF", "SISMAI",
+              "alpha1", "alpha2", "alpha3", "alpha4", "alpha5", "alpha6", "alpha7", "alpha8", "alpha9",
+              "A_0UTC", "A_1UTC", "A_2UTC", "delta_t_LS", "t_ot", "WN_ot", "WN_LSF", "DN", "delta_t_LSF",
+              "GNSS_ID", "WN_0BGTO", "t_0BGTO", "A_0BGTO", "A_1BGTO", "A_2BGTO", "TOW"]
+NAV_SHORT, NAV_BCH1_OK, NAV_BCH2_OK, NAV_CRC1_OK, NAV_CRC2_OK, NAV_ENTERED, NAV_PRN_RANGE = 1, 2, 4, 8, 16, 32, 64
+NAV_BITS = {1: 878, 2: 288}  # by SIGNAL value
+
+
+class NavFrame(C.Structure):
+    _fields_ = [("size", C.c_uint32), ("index", C.c_int32), ("status", C.c_uint32), ("polarity", C.c_int32),
+                ("bch1_max", C.c_int32), ("bch2_max", C.c_int32), ("bits", C.c_uint8 * 112)]
+
+
+class Eph(C.Structure):
+    _fields_ = ([("size", C.c_uint32), ("flag", C.c_int32), ("SatType", C.c_int32), ("n_entered", C.c_int32),
+                 ("idValid", C.c_int32 * 8)] + [(f, C.c_double) for f in EPH_FIELDS])
+
+
 class ProbeOut(C.Structure):
     _fields_ = ([("hist_i", C.POINTER(C.c_int64)), ("hist_q", C.POINTER(C.c_int64))]
                 + [(f"{k}_{c}", C.c_int64) for c in "iq" for k in ("min", "max", "sum", "sumsq")]
@@ -119,6 +142,7 @@ EXPORTS = [
     "bds_synth", "bds_synth_file", "bds_synth_noise",
     "bds_probe_data", "bds_probe_data_file", "bds_probe_set_piece_segments",
     "bds_corr_function", "bds_corr_function_mem",
+    "bds_nav_decode", "bds_nav_fields",
 ]
 # the entries marked BDS_DEV_API in the header: their record pointer is device memory (device_span below makes it)
 DEVICE_EXPORTS = ["bds_synth_dev", "bds_acq_load_dev", "bds_track_dev", "bds_track_open_dev", "bds_track_feed_dev"]
@@ -222,6 +246,9 @@ def lib():
     L.bds_frame_sync.restype = i32
     L.bds_frame_sync.argtypes = [vp, i32, i32, _IP, _DP, i32, _IP, _IP, _IP, i32]
     L.bds_sync_pattern.restype, L.bds_sync_pattern.argtypes = i32, [i32, i32, C.POINTER(C.c_int8), i32]
+    L.bds_nav_decode.restype = i32
+    L.bds_nav_decode.argtypes = [vp, SP, i32, _IP, _DP, _DP, i32, C.POINTER(NavFrame), _IP, i32, C.POINTER(Eph), _DP, _DP]
+    L.bds_nav_fields.restype, L.bds_nav_fields.argtypes = i32, [i32, C.POINTER(C.c_uint8), i32, i32, C.POINTER(Eph)]
     L.bds_unpack_cplx.restype, L.bds_unpack_cplx.argtypes = i32, [vp, C.POINTER(C.c_uint8), C.c_size_t, C.POINTER(C.c_int8)]
     L.bds_unpack_cplx_file.restype, L.bds_unpack_cplx_file.argtypes = i32, [vp, C.c_char_p, C.c_char_p]
     L.bds_resample_plan.restype, L.bds_resample_plan.argtypes = i32, [SP, _DP, _DP, _DP]
@@ -578,6 +605,37 @@ def gen_code(signal: str, kind: str, prn: int) -> np.ndarray:
     return out
 
 
+def eph_dict(e: Eph) -> dict:
+    """One bds_eph as a dict: flag, SatType (0..3), n_entered, idValid (int array) and a float per name of EPH_FIELDS (NaN = [])."""
+    d = {"flag": int(e.flag), "SatType": int(e.SatType), "n_entered": int(e.n_entered), "idValid": np.array(e.idValid, dtype=np.int32)}
+    d.update((f, float(getattr(e, f))) for f in EPH_FIELDS)
+    return d
+
+
+def nav_frame_dict(f: NavFrame, signal) -> dict:
+    """One bds_nav_frame as a dict; `bits` unpacked to uint8 0 / 1 (878 for B1C, 288 for B2a)."""
+    sig = signal if isinstance(signal, int) else SIGNAL[str(signal).upper()]
+    bits = np.unpackbits(np.frombuffer(bytes(f.bits), dtype=np.uint8))[:NAV_BITS[sig]]
+    return {"index": int(f.index), "status": int(f.status), "polarity": int(f.polarity), "bch1_max": int(f.bch1_max),
+            "bch2_max": int(f.bch2_max), "bits": bits}
+
+
+def nav_fields(signal, messages) -> tuple:
+    """bds_nav_fields (no GPU): decoded messages, uint8 0 / 1 of shape [n_msg, 878] (B1C) or [n_msg, 288] (B2a), through the
+    field parser and the merging rules in order -> (eph dict, number of messages that entered)."""
+    sig = SIGNAL[str(signal).upper()]
+    m = np.atleast_2d(np.asarray(messages, dtype=np.uint8))
+    if m.shape[1] != NAV_BITS[sig]:
+        raise ValueError(f"nav_fields: {NAV_BITS[sig]} bits per message, got {m.shape[1]}")
+    packed = np.ascontiguousarray(np.packbits(m, axis=1))
+    e = Eph()
+    e.size = C.sizeof(Eph)
+    rc = lib().bds_nav_fields(sig, packed.ctypes.data_as(C.POINTER(C.c_uint8)), m.shape[0], packed.shape[1], C.byref(e))
+    if rc < 0:
+        raise BdsError(rc, "bds_nav_fields")
+    return eph_dict(e), rc
+
+
 def sync_pattern(signal: str, prn: int = 1) -> np.ndarray:
     """+-1 frame-sync pattern: B1C pilot secondary code of the PRN (1800) or the B2a preamble x NH (120)."""
     out = np.empty(1800, dtype=np.int8)
@@ -888,6 +946,37 @@ class Context:
         if np.any(cnt > cap):
             return self.frame_sync(signal, prns, prompt, cap=int(cnt.max()))
         return xc, [idx[c, :cnt[c]].copy() for c in range(n_ch)]
+
+    def nav_decode(self, settings, prns, sync_prompt, data_prompt=None, cap=8):
+        """bds_nav_decode: prompts [n_ch, n] -> per channel {"frames": [nav_frame_dict, ...] (the first `cap`), "n_frames",
+        "eph": eph_dict, "firstSubFrame", "TOW"} (the last two +inf where nothing decoded)."""
+        cs = pack_settings(settings)
+        sp = np.ascontiguousarray(sync_prompt, dtype=np.float64)
+        if sp.ndim != 2:
+            raise ValueError("nav_decode: sync_prompt is [n_ch, n]")
+        n_ch, n = sp.shape
+        dp = None
+        if data_prompt is not None:
+            dp = np.ascontiguousarray(data_prompt, dtype=np.float64)
+            if dp.shape != sp.shape:
+                raise ValueError(f"nav_decode: data_prompt {dp.shape} and sync_prompt {sp.shape} differ in shape")
+        prn = np.ascontiguousarray(prns, dtype=np.int32)
+        if prn.shape != (n_ch,):
+            raise ValueError(f"nav_decode: {n_ch} channels, {prn.size} PRNs")
+        cap = int(cap)
+        frames = (NavFrame * max(1, n_ch * cap))()
+        eph = (Eph * n_ch)()
+        for e in eph:
+            e.size = C.sizeof(Eph)
+        cnt = np.zeros(n_ch, dtype=np.int32)
+        first = np.zeros(n_ch, dtype=np.float64)
+        tow = np.zeros(n_ch, dtype=np.float64)
+        self._check(self._lib.bds_nav_decode(self._h, C.byref(cs), n_ch, prn.ctypes.data_as(_IP), sp.ctypes.data_as(_DP),
+                                             dp.ctypes.data_as(_DP) if dp is not None else None, n, frames, cnt.ctypes.data_as(_IP),
+                                             cap, eph, first.ctypes.data_as(_DP), tow.ctypes.data_as(_DP)))
+        return [{"frames": [nav_frame_dict(frames[c * cap + k], cs.signal) for k in range(min(cap, int(cnt[c])))],
+                 "n_frames": int(cnt[c]), "eph": eph_dict(eph[c]), "firstSubFrame": float(first[c]), "TOW": float(tow[c])}
+                for c in range(n_ch)]
 
     def unpack_cplx(self, data):
         """bds_unpack_cplx: uint8[n] packed samples -> int8[4n] I/Q pairs (unpack_cplx.m)."""

@@ -163,3 +163,138 @@ def write_if(path, settings, sats, n_samples, seed=3550, sigma=20.0, first_sampl
     get_context(device).synth_file(settings, list(sats), first_sample, n_samples, fmt, path, piece_samples=piece_samples, seed=seed,
                                    sigma=sigma, iq_sign=iq_sign, threshold=threshold, code_doppler=code_doppler,
                                    pilot61_secondary=pilot61_secondary, symbols=symbols)
+
+
+# ---- navigation messages: the inverse of navdecode (plain NumPy; for tests and for users of make_if*) -------------------------
+# Bit positions are the reference's own (B1C/include/ephemeris.m:66-230, B2a/include/ephemeris.m:60-310), 1-based and
+# inclusive, in the 878-bit decodedNav of a B-CNAV1 frame and the 288-bit B-CNAV2 message; values are the raw integers
+# (two's complement for negative ones).  Fields the reference reads from overlapping bits overlap here as well.
+BCNAV1_FIELDS = {
+    "PRN": (1, 6), "SOH": (7, 14), "WN": (15, 27), "HOW": (28, 35), "IODC": (36, 46), "IODE": (46, 53),
+    "t_oe": (54, 64), "SatType": (65, 66), "deltaA": (67, 92), "ADot": (93, 117), "delta_n_0": (118, 134),
+    "delta_n_0Dot": (135, 157), "M_0": (158, 190), "e": (191, 223), "omega": (224, 256),
+    "omega_0": (257, 289), "i_0": (290, 322), "omegaDot": (323, 341), "i_0Dot": (342, 356), "C_is": (357, 372),
+    "C_ic": (373, 388), "C_rs": (389, 412), "C_rc": (413, 436), "C_us": (437, 457), "C_uc": (458, 478),
+    "t_oc": (479, 489), "a_0": (490, 514), "a_1": (515, 536), "a_2": (537, 547),
+    "T_GDB2ap": (548, 559), "ISC_B1Cd": (560, 571), "T_GDB1Cp": (572, 583),
+    "PageID": (615, 620), "HS": (621, 622), "DIF": (623, 623), "SIF": (624, 624), "AIF": (625, 625), "SISMAI": (626, 629),
+    # page 1
+    "alpha1": (657, 666), "alpha2": (667, 674), "alpha3": (675, 682), "alpha4": (683, 690), "alpha5": (691, 698),
+    "alpha6": (699, 706), "alpha7": (707, 714), "alpha8": (715, 722), "alpha9": (723, 730),
+    "A_0UTC": (731, 746), "A_1UTC": (747, 759), "A_2UTC": (760, 766), "delta_t_LS": (767, 774), "t_ot": (775, 790),
+    "WN_ot": (791, 803), "WN_LSF": (804, 816), "DN": (817, 819), "delta_t_LSF": (820, 827),
+    # page 3
+    "GNSS_ID": (773, 775), "WN_0BGTO": (776, 788), "t_0BGTO": (789, 804), "A_0BGTO": (805, 820), "A_1BGTO": (821, 833),
+    "A_2BGTO": (834, 840),
+}
+_B2_CLOCK = {"t_oc": (43, 53), "a_0": (54, 78), "a_1": (79, 100), "a_2": (101, 111), "IODC_MSB2": (112, 113),
+             "IODC_LSB8": (114, 121)}
+BCNAV2_HEAD = {"PRN": (1, 6), "MesType": (7, 12), "SOW": (13, 30)}
+BCNAV2_FIELDS = {
+    10: {"WN": (31, 43), "DIF": (44, 44), "SIF": (45, 45), "AIF": (46, 46), "t_oe": (62, 72), "SatType": (73, 74),
+         "deltaA": (75, 100), "ADot": (101, 125), "delta_n_0": (126, 142), "delta_n_0Dot": (143, 165), "M_0": (166, 198),
+         "e": (199, 231), "omega": (232, 264)},
+    11: {"HS": (31, 32), "DIF": (33, 33), "SIF": (34, 34), "AIF": (36, 36), "omega_0": (43, 75), "i_0": (76, 108),
+         "omegaDot": (109, 127), "i_0Dot": (128, 142), "C_is": (143, 158), "C_ic": (159, 174), "C_rs": (175, 198),
+         "C_rc": (199, 222), "C_us": (223, 243), "C_uc": (244, 264)},
+    30: dict(_B2_CLOCK, alpha1=(146, 155), alpha2=(156, 163), alpha3=(164, 171), alpha4=(172, 179), alpha5=(180, 187),
+             alpha6=(188, 195), alpha7=(196, 203), alpha8=(204, 211), alpha9=(212, 219)),
+    31: dict(_B2_CLOCK),
+    32: dict(_B2_CLOCK),
+    33: dict(_B2_CLOCK, WN_0BGTO=(115, 127), t_0BGTO=(128, 143), A_0BGTO=(144, 159), A_1BGTO=(160, 172), A_2BGTO=(173, 179)),
+    34: {"t_oc": (65, 75), "a_0": (76, 100), "a_1": (101, 122), "a_2": (123, 133), "IODC_MSB2": (134, 135),
+         "IODC_LSB8": (136, 143)},
+}
+BCNAV2_PREAMBLE = np.array([-1, -1, -1, 1, 1, 1, -1, 1, 1, -1, 1, 1, -1, -1, 1, -1, -1, -1, -1, 1, -1, 1, 1, 1], dtype=np.int8)
+BCNAV2_SECOND = np.array([1, 1, 1, -1, 1], dtype=np.int8)
+CRC24Q = 0x1864CFB  # x^24 + x^23 + x^18 + x^17 + x^14 + x^11 + x^10 + x^7 + x^6 + x^5 + x^4 + x^3 + x + 1
+
+
+def _put(bits, first, last, value, name):
+    w = last - first + 1
+    v = int(value)
+    if not -(1 << (w - 1)) <= v < (1 << w):
+        raise ValueError(f"{name} = {value} does not fit {w} bits")
+    v &= (1 << w) - 1
+    bits[first - 1:last] = [(v >> (w - 1 - i)) & 1 for i in range(w)]
+
+
+def crc24q(bits):
+    """CRC-24Q of a 0 / 1 sequence, first bit first, zero initial state, no reflection -> 24 bits (uint8 0 / 1)."""
+    r = 0
+    for b in np.asarray(bits).astype(int).tolist() + [0] * 24:
+        r = (r << 1) | b
+        if r >> 24:
+            r ^= CRC24Q
+    return np.array([(r >> (23 - i)) & 1 for i in range(24)], dtype=np.uint8)
+
+
+def bch_codeword(hyp, k, n, feedback):
+    """The n code symbols (uint8 0 / 1) of the k-bit value `hyp` from the shift register of BCH21_6Decoding.m:65-89 /
+    BCH51_8Decoding.m:63-87: the register starts as the value (most significant bit at the output end), the feedback is the
+    XOR of the 1-based `feedback` positions."""
+    reg = [(int(hyp) >> i) & 1 for i in range(k)]
+    out = np.empty(n, dtype=np.uint8)
+    for s in range(n):
+        out[s] = reg[-1]
+        f = 0
+        for p in feedback:
+            f ^= reg[p - 1]
+        reg = [f] + reg[:-1]
+    return out
+
+
+def pack_bcnav1_fields(**fields):
+    """878 bits (uint8 0 / 1) of a B-CNAV1 frame's decodedNav with the named raw integer fields of BCNAV1_FIELDS set (later
+    names overwrite earlier ones where the reference's ranges overlap); the CRC positions are left to bcnav1_symbols."""
+    bits = np.zeros(878, dtype=np.uint8)
+    for name, value in fields.items():
+        _put(bits, *BCNAV1_FIELDS[name], value, name)
+    return bits
+
+
+def pack_bcnav2_fields(MesType, **fields):
+    """The 264 information bits (uint8 0 / 1) of a B-CNAV2 message of type `MesType` with the named raw integer fields set
+    (PRN, SOW and the type's entries of BCNAV2_FIELDS; any other type carries PRN and SOW alone)."""
+    bits = np.zeros(264, dtype=np.uint8)
+    layout = dict(BCNAV2_HEAD, **BCNAV2_FIELDS.get(int(MesType), {}))
+    _put(bits, *layout["MesType"], MesType, "MesType")
+    for name, value in fields.items():
+        _put(bits, *layout[name], value, name)
+    return bits
+
+
+def bcnav1_symbols(bits878, fill=None):
+    """One B-CNAV1 frame as 1800 symbols (int8 +-1, +1 = bit 1, the sign BCNAV1decoding.m:105 reads): BCH(21,6) of bits 1..6,
+    BCH(51,8) of bits 7..14, sub-frame 2 = bits 15..590 + CRC-24Q + 600 parity symbols, sub-frame 3 = bits 615..854 + CRC-24Q +
+    264 parity symbols, interleaved as the 36 x 48 block of :146-154.  The LDPC parity halves are not computed (nothing reads
+    them): they are `fill` (864 values 0 / 1: 600 for sub-frame 2, then 264) or zeros."""
+    b = np.asarray(bits878, dtype=np.uint8).reshape(-1)
+    if b.size != 878:
+        raise ValueError("bcnav1_symbols: 878 bits")
+    fill = np.zeros(864, dtype=np.uint8) if fill is None else np.asarray(fill, dtype=np.uint8).reshape(-1)
+    if fill.size != 864:
+        raise ValueError("bcnav1_symbols: fill has 600 + 264 values")
+    val = lambda x: int("".join(map(str, x.tolist())), 2)  # noqa: E731
+    s1 = np.concatenate([bch_codeword(val(b[:6]), 6, 21, (2, 4, 5, 6)), bch_codeword(val(b[6:14]), 8, 51, (1, 4, 5, 6, 7, 8))])
+    f2 = np.concatenate([b[14:590], crc24q(b[14:590]), fill[:600]])
+    f3 = np.concatenate([b[614:854], crc24q(b[614:854]), fill[600:]])
+    rows3 = np.arange(2, 35, 3)  # 0-based rows of Frame3Colum = 3:3:35
+    rows2 = np.setdiff1d(np.arange(36), rows3)
+    block = np.empty((36, 48), dtype=np.uint8)
+    block[rows2] = f2.reshape(25, 48)
+    block[rows3] = f3.reshape(11, 48)
+    bits = np.concatenate([s1, block.reshape(-1, order="F")])
+    return (2 * bits.astype(np.int8) - 1).astype(np.int8)
+
+
+def bcnav2_symbols(bits264):
+    """One B-CNAV2 message as 3000 one-millisecond symbols (int8 +-1): the 24-symbol preamble, the 264 bits + CRC-24Q (bit 1 =
+    symbol -1, BCNAV2decoding.m:136), 288 zero parity symbols (not computed, as above), each times the five-chip secondary
+    code [1 1 1 -1 1] (:69)."""
+    b = np.asarray(bits264, dtype=np.uint8).reshape(-1)
+    if b.size != 264:
+        raise ValueError("bcnav2_symbols: 264 bits")
+    msg = np.concatenate([b, crc24q(b), np.zeros(288, dtype=np.uint8)])
+    sym = np.concatenate([BCNAV2_PREAMBLE, (1 - 2 * msg.astype(np.int8)).astype(np.int8)])
+    return np.kron(sym, BCNAV2_SECOND).astype(np.int8)

@@ -52,7 +52,7 @@ compile() {  # source, object, extra flags...
     fi
 }
 objs=(); hobjs=(); pids=()
-for f in bds_acq.hip bds_track.hip bds_corrfn.hip bds_codes.cpp bds_api.hip bds_sync.hip bds_multi.hip bds_synth.hip bds_probedata.hip; do
+for f in bds_acq.hip bds_track.hip bds_corrfn.hip bds_codes.cpp bds_nav.cpp bds_api.hip bds_sync.hip bds_multi.hip bds_synth.hip bds_probedata.hip; do
     o="$BLD/${f%.*}.o"
     compile "$f" "$o" & pids+=($!)
     objs+=("$o")

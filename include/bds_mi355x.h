@@ -600,6 +600,75 @@ BDS_API int bds_frame_sync(bds_ctx *ctx, int signal, int n_ch, const int32_t *pr
                            int n, int32_t *xcorr, int32_t *index, int32_t *n_index, int cap);
 BDS_API int bds_sync_pattern(int signal, int prn, int8_t *out, int cap);
 
+/* ---- navigation decoding: B-CNAV1 / B-CNAV2 frames, ephemeris, TOW ---------------------------------------
+ * The rest of B1C/include/BCNAV1decoding.m (:93-189, with BCH21_6Decoding.m, BCH51_8Decoding.m and B1C/include/ephemeris.m)
+ * and of B2a/include/BCNAV2decoding.m (:99-159, with B2a/include/ephemeris.m): every candidate frame start that
+ * bds_frame_sync's correlator finds is decoded on the device (one workgroup per channel and candidate, one launch), the decoded
+ * frames are merged on the host, in candidate order, into one ephemeris per channel.  As in the reference NO LDPC decoding is
+ * done: the information halves of the LDPC blocks are taken as received and stand or fall with their CRC-24Q.
+ *
+ * One rule is this library's own.  In the reference a CRC-valid frame whose PRN field is outside 1..63 makes ephemeris() return
+ * early, after which `TOW = eph.TOW` (B1C) finds an empty field.  Here such a frame is NOT ENTERED: it changes no field of the
+ * ephemeris and does not set firstSubFrame / TOW (status BDS_NAV_PRN_RANGE). */
+enum {
+    BDS_NAV_SHORT = 1,      /* B2a: fewer than 3000 prompts from the candidate on (BCNAV2decoding.m:105); nothing else is set */
+    BDS_NAV_BCH1_OK = 2,    /* B1C: BCH(21,6) of symbols 1..21 passed, as received or inverted */
+    BDS_NAV_BCH2_OK = 4,    /* B1C: BCH(51,8) of symbols 22..72 passed in the polarity kept; bits[] is written */
+    BDS_NAV_CRC1_OK = 8,    /* CRC-24Q of sub-frame 2's 600 bits (B1C) / of the message's 288 bits (B2a) */
+    BDS_NAV_CRC2_OK = 16,   /* B1C: CRC-24Q of sub-frame 3's 264 bits */
+    BDS_NAV_ENTERED = 32,   /* the frame entered the channel's ephemeris */
+    BDS_NAV_PRN_RANGE = 64  /* all checks passed but the PRN field is outside 1..63: not entered (above) */
+};
+#define BDS_NAV_BITS_B1C 878 /* decodedNav: 6 + 8 + 600 + 264 (BCNAV1decoding.m:94,129,142,161,163) */
+#define BDS_NAV_BITS_B2A 288 /* decodedNavBits (BCNAV2decoding.m:132) */
+typedef struct bds_nav_frame {
+    uint32_t size;     /* sizeof(bds_nav_frame), set by the library */
+    int32_t index;     /* the candidate, 1-based as in the reference's `index` */
+    uint32_t status;   /* BDS_NAV_* flags */
+    int32_t polarity;  /* +1 as received, -1 inverted, 0 not determined (B1C: both BCH(21,6) attempts failed; B2a: short) */
+    int32_t bch1_max;  /* B1C: maxValue of the last BCH(21,6) attempt made (the inverted one when the first failed) */
+    int32_t bch2_max;  /* B1C: maxValue of BCH(51,8) in the polarity kept; 0 when not reached */
+    uint8_t bits[112]; /* the decoded bits, first bit = most significant bit of bits[0]: 878 (B1C) or 288 (B2a), rest zero */
+} bds_nav_frame;
+
+/* One double per numeric field of B1C/include/eph_structure_init.m and B2a/include/eph_structure_init.m (the union of the two;
+ * names as there).  NaN = the reference's []: not decoded, or not a field of this signal. */
+#define BDS_EPH_FIELDS(X)                                                                                                   \
+    X(PRN) X(SOH) X(SOW) X(WN) X(HOW) X(IODC) X(IODE) X(IODC_MSB2) X(IODC_LSB8)                                             \
+    X(t_oe) X(deltaA) X(ADot) X(delta_n_0) X(delta_n_0Dot) X(M_0) X(e) X(omega)                                             \
+    X(omega_0) X(i_0) X(omegaDot) X(i_0Dot) X(C_is) X(C_ic) X(C_rs) X(C_rc) X(C_us) X(C_uc)                                 \
+    X(t_oc) X(a_0) X(a_1) X(a_2) X(T_GDB2ap) X(ISC_B1Cd) X(T_GDB1Cp)                                                        \
+    X(PageID1) X(PageID3) X(HS) X(DIF) X(SIF) X(AIF) X(SISMAI)                                                              \
+    X(alpha1) X(alpha2) X(alpha3) X(alpha4) X(alpha5) X(alpha6) X(alpha7) X(alpha8) X(alpha9)                               \
+    X(A_0UTC) X(A_1UTC) X(A_2UTC) X(delta_t_LS) X(t_ot) X(WN_ot) X(WN_LSF) X(DN) X(delta_t_LSF)                             \
+    X(GNSS_ID) X(WN_0BGTO) X(t_0BGTO) X(A_0BGTO) X(A_1BGTO) X(A_2BGTO) X(TOW)
+typedef struct bds_eph {
+    uint32_t size;       /* sizeof(bds_eph), set by the CALLER (of each array element); checked */
+    int32_t flag;        /* 1 once a frame has entered (B1C: eph.flag), else 0 */
+    int32_t SatType;     /* 0 = [] / code 0, 1 = 'GEO', 2 = 'IGSO', 3 = 'MEO' */
+    int32_t n_entered;   /* frames / messages that entered */
+    int32_t idValid[8];  /* B2a: 10, 11, 30..34 in slots 0..6 once seen, the last other message type in slot 7; B1C: zeros */
+#define BDS_EPH_X(name) double name;
+    BDS_EPH_FIELDS(BDS_EPH_X)
+#undef BDS_EPH_X
+} bds_eph;
+
+/* BCNAV1decoding(trackResults, channelNr, settings) / BCNAV2decoding(I_P_InputBits) for n_ch channels in one call.
+ *   settings:     only .signal is read; which series is the pilot's is the caller's choice by pilotTRKflag, as below.
+ *   sync_prompt:  double[n_ch * n], what bds_frame_sync takes: Pilot_I_P / Pilot_Q_P by pilotTRKflag (B1C), I_P (B2a).
+ *   data_prompt:  double[n_ch * n]: I_P (B1C).  NULL = sync_prompt itself; B2a decodes the series it synchronised on, so it must
+ *                 be NULL (or the same pointer) there.
+ *   frames (optional): bds_nav_frame[n_ch * cap], the first min(cap, n_frames[c]) candidates of channel c in candidate order;
+ *                 n_frames[n_ch] (optional) = candidates per channel (may exceed cap; the ephemeris uses all of them).
+ *   eph:          bds_eph[n_ch], each with .size set.  firstSubFrame, TOW: double[n_ch], +inf where nothing entered.
+ * Returns the number of frames that entered, over all channels, or < 0.
+ * bds_nav_fields (no GPU): the host half alone.  n_msg decoded messages of `stride` bytes each (bits as in bds_nav_frame,
+ * at least 110 / 36 bytes) go, in order, through the field parser and the merging rules into *eph; returns how many entered. */
+BDS_API int bds_nav_decode(bds_ctx *ctx, const bds_settings *settings, int n_ch, const int32_t *prn, const double *sync_prompt,
+                           const double *data_prompt, int n, bds_nav_frame *frames, int32_t *n_frames, int cap, bds_eph *eph,
+                           double *firstSubFrame, double *TOW);
+BDS_API int bds_nav_fields(int signal, const uint8_t *bits, int n_msg, int stride, bds_eph *eph);
+
 /* B2a/include/unpack_cplx.m: converter of packed records (one byte = two complex samples, 2-bit
  * sign/magnitude I and Q each) into the int8 I/Q pairs of a fileType-2 record.
  * out: int8[4 * n_bytes] = I1, Q1, I2, Q2 per input byte.  The file variant mirrors

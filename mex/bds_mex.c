@@ -17,6 +17,11 @@
  *   code = bds_mex('gen_code', signal, kind, prn)
  *   [XcorrResult, index] = bds_mex('frame_sync', signal, PRN, bits)   % one channel: second half of
  *       xcorr(sign(bits), pattern) and find(abs(.) >= 1799.5) (B1C) / find(abs(.) > 115) (B2a)
+ *   out = bds_mex('nav_decode', signal, PRN, sync_bits, data_bits)   % one channel: the rest of BCNAV1decoding.m (:93-189) /
+ *       BCNAV2decoding.m (:99-159).  sync_bits: the prompt series frame_sync takes; data_bits: I_P (B1C), [] for B2a.  struct with
+ *       eph (one field per double of bds_eph, [] where the reference leaves []; SatType 0..3, flag, n_entered, idValid 1 x 8),
+ *       firstSubFrame, TOW (inf where nothing decoded) and, per candidate (the first 64), the columns index, status, polarity.
+ *       mex/B1C/include/BCNAV1decoding.m and mex/B2a/include/BCNAV2decoding.m shape eph like the reference's struct.
  *   out = bds_mex('probe_data', path, settings, signal[, n_samples])   % the numbers of include/probeData.m's figure (mex/probeData.m
  *       draws it): struct with hist_i, hist_q (1 x 257 counts over -128:128; hist_q empty for fileType 1), psd (column: one-sided
  *       16385 bins for fileType 1, else two-sided 32768 bins 0 .. fs), excerpt_re, excerpt_im (the samples of the time-domain
@@ -298,6 +303,64 @@ static void do_frame_sync(int nlhs, mxArray *plhs[], int nrhs, const mxArray *pr
     mxFree(idx);
 }
 
+/* BCNAV1decoding.m:93-189 / BCNAV2decoding.m:99-159 for one channel: candidates, frame decoding, ephemeris, TOW */
+static void eph_field(mxArray *st, const char *name, double v) {
+    double *p = out_field(st, name, v != v ? 0 : 1, v != v ? 0 : 1); /* NaN = the reference's [] */
+    if (v == v) p[0] = v;
+}
+
+static void do_nav_decode(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[]) {
+    enum { CAP = 64 };
+    bds_settings s;
+    bds_nav_frame *fr;
+    bds_eph e;
+    int32_t prn, cnt = 0;
+    double first = 0, tow = 0, *pi, *ps, *pp;
+    const double *data = NULL;
+    int n, rc, i, shown;
+    mxArray *res, *eph;
+    (void)nlhs;
+    if (nrhs != 5 || !mxIsDouble(prhs[3]) || !mxIsDouble(prhs[4])) mexErrMsgIdAndTxt("bds:args", "nav_decode: (signal, PRN, sync_bits, data_bits)");
+    memset(&s, 0, sizeof(s));
+    s.signal = (int)mxGetScalar(prhs[1]);
+    prn = (int32_t)mxGetScalar(prhs[2]);
+    n = (int)mxGetNumberOfElements(prhs[3]);
+    if (mxGetNumberOfElements(prhs[4]) != 0) {
+        if ((int)mxGetNumberOfElements(prhs[4]) != n) mexErrMsgIdAndTxt("bds:args", "nav_decode: sync_bits and data_bits differ in length");
+        data = mxGetDoubles(prhs[4]);
+    }
+    memset(&e, 0, sizeof(e));
+    e.size = sizeof(e);
+    fr = (bds_nav_frame *)mxCalloc(CAP, sizeof(bds_nav_frame));
+    rc = bds_nav_decode(ctx(), &s, 1, &prn, mxGetDoubles(prhs[3]), data, n, fr, &cnt, CAP, &e, &first, &tow);
+    if (rc < 0) {
+        mxFree(fr);
+        mexErrMsgIdAndTxt("bds:nav_decode", "%s", bds_last_error(ctx()));
+    }
+    res = mxCreateStructMatrix(1, 1, 0, NULL);
+    eph = mxCreateStructMatrix(1, 1, 0, NULL);
+#define BDS_EPH_X(name) eph_field(eph, #name, e.name);
+    BDS_EPH_FIELDS(BDS_EPH_X)
+#undef BDS_EPH_X
+    out_field(eph, "SatType", 1, 1)[0] = e.SatType;
+    out_field(eph, "flag", 1, 1)[0] = e.flag;
+    out_field(eph, "n_entered", 1, 1)[0] = e.n_entered;
+    pi = out_field(eph, "idValid", 1, 8);
+    for (i = 0; i < 8; ++i) pi[i] = e.idValid[i];
+    mxAddField(res, "eph");
+    mxSetField(res, 0, "eph", eph);
+    out_field(res, "firstSubFrame", 1, 1)[0] = first;
+    out_field(res, "TOW", 1, 1)[0] = tow;
+    out_field(res, "n_frames", 1, 1)[0] = cnt;
+    shown = cnt < CAP ? cnt : CAP;
+    pi = out_field(res, "index", shown, 1);
+    ps = out_field(res, "status", shown, 1);
+    pp = out_field(res, "polarity", shown, 1);
+    for (i = 0; i < shown; ++i) pi[i] = fr[i].index, ps[i] = fr[i].status, pp[i] = fr[i].polarity;
+    mxFree(fr);
+    plhs[0] = res;
+}
+
 /* include/probeData.m:63-168 of either receiver: everything the figure shows, computed on the device */
 static void do_probe_data(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[]) {
     bds_settings s;
@@ -404,6 +467,8 @@ void mexFunction(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[]) {
         do_gen_code(nlhs, plhs, nrhs, prhs);
     else if (!strcmp(cmd, "frame_sync"))
         do_frame_sync(nlhs, plhs, nrhs, prhs);
+    else if (!strcmp(cmd, "nav_decode"))
+        do_nav_decode(nlhs, plhs, nrhs, prhs);
     else if (!strcmp(cmd, "probe_data"))
         do_probe_data(nlhs, plhs, nrhs, prhs);
     else if (!strcmp(cmd, "corr_function"))
