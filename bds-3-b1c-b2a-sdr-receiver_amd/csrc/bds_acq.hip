@@ -212,8 +212,7 @@ struct AcqState {
     // N-point plan (bds_acq_pfa.h: 1, bds_acq_pfa32.h: 2, bds_acq_pfa6.h: 3, bds_acq_pfa31.h: 4; 0: none): the cached code spectra are in its layout (CRT order), the search
     // runs its pair
     int cs_pfa = 0;
-    uint4 *d_pfa_coef = nullptr;  // B fragments of the 53-point stage (pfa::make_coef_frags)
-    uint4 *d_pfa31_coef = nullptr;  // B fragments of the 31-point stage (pfa31::make_coef_frags)
+    std::map<void (*)(uint16_t *), uint4 *> pfa_coef;  // B fragments of the column passes' first stage: one table per Plan::make_coef_frags
     long sigpower_X = 0;       // X the cached B1C normaliser was computed for (0: none; reset by bds_acq_load)
     double sigpower = 0;       // sqrt(var(sig(1:X)) * X), B1C/acquisition.m:150
 };
@@ -221,7 +220,7 @@ struct AcqState {
 void acq_state_free(AcqState *a) {
     if (!a) return;
     plan_free(a->plan);
-    for (void *p : {(void *)a->d_sig, (void *)a->d_packed, (void *)a->d_prim, (void *)a->d_Cs, (void *)a->d_Xs, (void *)a->d_Bw, (void *)a->d_pfa_coef, (void *)a->d_pfa31_coef,
+    for (void *p : {(void *)a->d_sig, (void *)a->d_packed, (void *)a->d_prim, (void *)a->d_Cs, (void *)a->d_Xs, (void *)a->d_Bw,
                     (void *)a->d_recs, (void *)a->d_rowmax, (void *)a->d_rowarg, (void *)a->d_jobs, (void *)a->d_codes,
                     (void *)a->d_jobout, (void *)a->d_sig64, (void *)a->d_ffa, (void *)a->d_ffb, (void *)a->d_fir, (void *)a->d_cells, (void *)a->d_mcells,
                     (void *)a->d_extra, (void *)a->d_extra_count, (void *)a->d_cellmax, (void *)a->d_lb, (void *)a->d_ref_zero,
@@ -229,6 +228,8 @@ void acq_state_free(AcqState *a) {
         if (p) (void)hipFree(p);
     for (auto &rc : a->rows_chunks)
         if (rc.second.d) (void)hipFree(rc.second.d);
+    for (auto &cf : a->pfa_coef)
+        if (cf.second) (void)hipFree(cf.second);
     delete a;
 }
 
@@ -481,7 +482,7 @@ static int rows_uniform_gc(int list_gc, int D, int np, long row_wgs) {
 // equal chunks first, then one or a few PRNs in chunks that shrink geometrically, all in non-increasing order, so that what is still
 // running when the slots start to drain is small.  No chunk straddles a PRN (a workgroup holds one PRN's code rows).
 // The model: greedy assignment in block order onto the slots -- what the dispatcher does with workgroups of equal resources.
-static constexpr int kRowsWorkWgs = pfa::MP * pfa::K2 - pfa::K2 / 2;  // per chunk: the odd-k2 workgroups of the last row pair return at once
+static constexpr int kRowsWorkWgs = pfa::kRowsWgs - pfa::K2 / 2;      // per chunk: the odd-k2 workgroups of the last row pair return at once
 static constexpr int kRowsSetup8 = 3;                                 // set-up of a workgroup in eighths of a cell (measured 0.29 of a cell: profiles/r16_rows_chunks.txt)
 
 // makespan in eighths of a cell-time of chunks of these sizes, in this order
@@ -557,7 +558,7 @@ static std::vector<int2> rows_chunk_plan(int np, int D, int slots, int uniform_g
 }
 
 int rows_chunk_list(int np, int D, int slots, int *out, int cap) {
-    const std::vector<int2> plan = rows_chunk_plan(np, D, slots, rows_uniform_gc(0, D, np, pfa::MP * pfa::K2));
+    const std::vector<int2> plan = rows_chunk_plan(np, D, slots, rows_uniform_gc(0, D, np, pfa::kRowsWgs));
     for (int i = 0; i < (int)plan.size() && i < cap; ++i) out[2 * i] = plan[(size_t)i].x, out[2 * i + 1] = plan[(size_t)i].y;
     return (int)plan.size();
 }
@@ -1001,10 +1002,41 @@ static size_t fine_pick_lds(const bds_settings &s, int signal, int ncomp) {
     const size_t nfine = b1c ? (size_t)m_round(s.acqStep / 25) * 2 + 1 : (size_t)m_round(s.acqStep / 25) + 1;  // B1C :267, B2a :265
     return sizeof(double) * ((size_t)(b1c ? ncomp : 2 * s.fineNoncoh) * nfine + nfine);
 }
+// ---- the N-point plans: each header's `Plan` describes and launches its pair (bds_acq_pfa.h) ------------------------------------------
+// What the host asks of the selected plan at run time, as plain data
+struct NPointInfo {
+    int kind = 0;  // the number AcqState::cs_pfa keeps.  0: none, the L-point pair
+    long np = 0;   // transform length N = K1 K2 K3
+    int k3 = 0, rows = 0, rows_wgs = 0;             // row length, rows K1 K2, row workgroups per chunk of cells
+    size_t cell_elems = 0, spec_elems = 0;          // 4-byte (fp16 complex) elements of a cell in the inter-pass buffer, of a signal spectrum
+    void (*make_coef_frags)(uint16_t *) = nullptr;  // the column pass's coefficient table (AcqState::pfa_coef) ...
+    size_t coef_bytes = 0;                          // ... and its size
+    bool chunk_list = false;  // the row pass takes the tapered chunk list (rows_chunk_plan)
+    bool masked = false;      // B2a: the second-peak pass is a masked column launch on the main search's cells, so all P x D cells of a run
+                              // are ONE launch pair; the Doppler step is p / q spectrum bins and the run holds q signal spectra
+};
+// The one place that knows which number is which plan: f(Plan{}) of kind 1 .. 4
+template <class F>
+static void with_npoint(int kind, F &&f) {
+    switch (kind) {
+    case 1: f(pfa::Plan{}); break;    // B1C, N = 1 987 500 (the default)
+    case 2: f(pfa32::Plan{}); break;  // B1C at 53 MS/s
+    case 3: f(pfa6::Plan{}); break;   // B2a at 99.375 MS/s, opt-in
+    case 4: f(pfa31::Plan{}); break;  // B1C at 30.69 MS/s, opt-in
+    }
+}
+static NPointInfo npoint_info(int kind) {
+    NPointInfo i;
+    with_npoint(kind, [&](auto plan) {
+        using P = decltype(plan);
+        i = NPointInfo{kind, P::NP, P::K3, P::kRows, P::kRowsWgs, P::kCellElems, P::kSpecElems, P::make_coef_frags, P::kCoefBytes, P::kChunkList, P::kMasked};
+    });
+    return i;
+}
 struct PfaPick {
-    int kind = 0;   // 0: the L-point pair, 1: bds_acq_pfa.h, 2: bds_acq_pfa32.h, 3: bds_acq_pfa6.h, 4: bds_acq_pfa31.h
-    int shift = 0;  // spectrum bins per Doppler step; kind 3: p of acqStep N / fs = p / q in lowest terms
-    int q = 1;      // kind 3: signal spectra per call
+    int kind = 0;   // NPointInfo::kind
+    int shift = 0;  // spectrum bins per Doppler step; a masked plan: p of acqStep N / fs = p / q in lowest terms
+    int q = 1;      // a masked plan: signal spectra per call
 };
 // budget of the inter-pass buffer of one launch pair: the hooks build's BDS_ACQ_PBCAP_GB, else bds_acq_set_pair_budget_gb, else
 // BDS_ACQ_PAIR_GB / its default.  GiB as given (< 0: "auto", 0: minimal), and in bytes for a small grid, where 0 counts as 8 GiB.
@@ -1017,7 +1049,7 @@ static double pair_budget_bytes(const bds_ctx *ctx, const AcqState &a) {
     const double pair_gb = pair_budget_gb(ctx, a);
     return (pair_gb > 0 ? pair_gb : 8.0) * 1073741824.0;
 }
-// Kind 3 (opt-in, bds_acq_set_b2a_npoint): B2a on N = 53 x 6 x 625 samples (99.375 MS/s), both components, fp16 storage on the 80 x 4096
+// bds_acq_pfa6.h (opt-in, bds_acq_set_b2a_npoint): B2a on N = 53 x 6 x 625 samples (99.375 MS/s), both components, fp16 storage on the 80 x 4096
 // plan (whose refinement paths it shares), no resampling, acqStep N / fs = p / q exactly with q <= 5 (B2a/acquisition.m:187-211: bin
 // b = q m + j is spectrum j rotated by p m), every rotation below N, all P x D cells in ONE launch pair within the pair budget (the
 // second-peak pass reads the winning cells out of the main search's buffer), and the refinement as the device chain.
@@ -1038,16 +1070,13 @@ static PfaPick pfa6_pick(const bds_ctx *ctx, const AcqState &a, const bds_settin
     return pk;
 }
 static PfaPick pfa_pick(const bds_ctx *ctx, const AcqState &a, const bds_settings &s) {
-    static const struct {
-        long N;
-        int kind;
-    } admitted[] = {{pfa::NP, 1}, {pfa32::NP, 2}, {pfa31::NP, 4}};
+    static const int admitted[] = {1, 2, 4};  // the B1C plans, each by its N
     PfaPick pk;
     if (a.signal == BDS_SIGNAL_B2A) return pfa6_pick(ctx, a, s);
     if (!ctx->tune.pfa || !a.half || a.no_fast_search || a.signal != BDS_SIGNAL_B1C || a.ncomp != 2 || a.rs.on || a.skind >= kF64) return pk;
     int kind = 0;
-    for (const auto &ad : admitted)
-        if (a.N == ad.N) kind = ad.kind;
+    for (const int k : admitted)
+        if (a.N == npoint_info(k).np) kind = k;
     if (kind == 4 && !a.b1c_npoint) kind = 0;  // (opt-in: bds_acq_set_b1c_npoint)
     if (!kind) return pk;
     const double sh = s.acqStep * (double)a.N / s.samplingFreq;
@@ -1056,12 +1085,6 @@ static PfaPick pfa_pick(const bds_ctx *ctx, const AcqState &a, const bds_setting
     pk.kind = kind, pk.shift = (int)sh;
     return pk;
 }
-// sizes of the selected pair
-static long pfa_np(int kind) { return kind == 4 ? pfa31::NP : kind == 3 ? pfa6::NP : kind == 2 ? pfa32::NP : pfa::NP; }
-static int pfa_k3(int kind) { return kind == 4 ? pfa31::K3 : kind == 3 ? pfa6::K3 : kind == 2 ? pfa32::K3 : pfa::K3; }
-static int pfa_rows(int kind) { return kind == 4 ? pfa31::K1 * pfa31::K2 : kind == 3 ? pfa6::K1 * pfa6::K2 : kind == 2 ? pfa32::K1 * pfa32::K2 : pfa::K1 * pfa::K2; }
-static size_t pfa_cell_elems(int kind) { return kind == 4 ? pfa31::kCellElems : kind == 3 ? pfa6::kCellElems : kind == 2 ? pfa32::kCellElems : pfa::kCellElems; }
-static int pfa_rows_wgs(int kind) { return kind == 4 ? pfa31::kRowsWgs : kind == 3 ? pfa6::kRowsWgs : kind == 2 ? pfa32::kRowsWgs : pfa::MP * pfa::K2; }
 
 extern "C" int bds_acq_prepare(bds_ctx *ctx, const bds_settings *s_in) {
     if (!ctx || !s_in) return BDS_ERR_ARG;
@@ -1077,21 +1100,18 @@ extern "C" int bds_acq_prepare(bds_ctx *ctx, const bds_settings *s_in) {
     pick_group(a, *s);
     if ((rc = ensure(ctx, &a.d_Bw, &a.bw_cap, bw_batches(a, ctx->tune) * (size_t)pl.L))) return rc;
     {   // layout of the cached code spectra: the N-point plan's or the L-point plan's; a change drops the cache
-        const int want = pfa_pick(ctx, a, *s).kind;
-        if (want != a.cs_pfa) a.cs_slot.clear();
-        a.cs_pfa = want;
-        if (a.half) a.sC = (float)std::exp2(std::floor(std::log2(32768.0 * (double)(want ? a.N : pl.L) / (double)a.X)));
-        if (want == 4 && !a.d_pfa31_coef) {
-            std::vector<uint16_t> cf(pfa31::kCoefBytes / 2);
-            pfa31::make_coef_frags(cf.data());
-            BDS_HIP(ctx, hipMalloc((void **)&a.d_pfa31_coef, pfa31::kCoefBytes));
-            BDS_HIP(ctx, hipMemcpy(a.d_pfa31_coef, cf.data(), pfa31::kCoefBytes, hipMemcpyHostToDevice));
-        }
-        if (want && want != 4 && !a.d_pfa_coef) {
-            std::vector<uint16_t> cf(pfa::kCoefBytes / 2);
-            pfa::make_coef_frags(cf.data());
-            BDS_HIP(ctx, hipMalloc((void **)&a.d_pfa_coef, pfa::kCoefBytes));
-            BDS_HIP(ctx, hipMemcpy(a.d_pfa_coef, cf.data(), pfa::kCoefBytes, hipMemcpyHostToDevice));
+        const NPointInfo want = npoint_info(pfa_pick(ctx, a, *s).kind);
+        if (want.kind != a.cs_pfa) a.cs_slot.clear();
+        a.cs_pfa = want.kind;
+        if (a.half) a.sC = (float)std::exp2(std::floor(std::log2(32768.0 * (double)(want.kind ? a.N : pl.L) / (double)a.X)));
+        if (want.kind) {  // its coefficient table (plans with the same first column stage share one)
+            uint4 *&d_coef = a.pfa_coef[want.make_coef_frags];
+            if (!d_coef) {
+                std::vector<uint16_t> cf(want.coef_bytes / 2);
+                want.make_coef_frags(cf.data());
+                BDS_HIP(ctx, hipMalloc((void **)&d_coef, want.coef_bytes));
+                BDS_HIP(ctx, hipMemcpy(d_coef, cf.data(), want.coef_bytes, hipMemcpyHostToDevice));
+            }
         }
     }
     std::vector<int> todo;
@@ -1123,14 +1143,10 @@ extern "C" int bds_acq_prepare(bds_ctx *ctx, const bds_settings *s_in) {
         float2 *cs_dst = a.half ? (float2 *)((__half2 *)a.d_Cs + (size_t)slot * a.ncomp * pl.L)
                                 : a.d_Cs + (size_t)slot * a.ncomp * pl.L;
         if (a.cs_pfa) {  // conj(fft(code)) / N in the CRT layout, [slot][component][53][K2][K3] (the slots keep the L-point stride)
-            if (a.cs_pfa == 4)
-                pfa31::forward(st(ctx), ld, a.ncomp, a.d_Bw, (uint32_t *)cs_dst, pfa31::NP, 1, (float)((double)a.sC / (double)a.N), 0);
-            else if (a.cs_pfa == 3)
-                pfa6::forward(st(ctx), ld, a.ncomp, a.d_Bw, (uint32_t *)cs_dst, pfa6::NP, 1, (float)((double)a.sC / (double)a.N), 0);
-            else if (a.cs_pfa == 2)
-                pfa32::forward(st(ctx), ld, a.ncomp, a.d_Bw, (uint32_t *)cs_dst, pfa32::NP, 1, (float)((double)a.sC / (double)a.N), 0);
-            else
-                pfa::forward(st(ctx), ld, a.ncomp, a.d_Bw, (uint32_t *)cs_dst, pfa::NP, 1, (float)((double)a.sC / (double)a.N), 0);
+            with_npoint(a.cs_pfa, [&](auto plan) {
+                using P = decltype(plan);
+                P::forward(st(ctx), ld, a.ncomp, a.d_Bw, (uint32_t *)cs_dst, P::NP, 1, (float)((double)a.sC / (double)a.N), 0);
+            });
             BDS_HIP(ctx, hipGetLastError());
         } else if ((rc = forward(ctx, a, ld, a.ncomp, cs_dst, pl.L, 1, (float)((double)a.sC / (double)pl.L))))
             return rc;
@@ -1276,8 +1292,9 @@ struct AcqRun {
     float w0 = 1.f, w1 = 1.f;
     bool fsearch = false, wcols = false, multiprn = false, overlap = false;
     int pfa = 0;               // > 0: an N-point pair runs; the value = spectrum bins per Doppler step
-    int pfa_kind = 0;          // which: 1 bds_acq_pfa.h, 2 bds_acq_pfa32.h, 3 bds_acq_pfa6.h, 4 bds_acq_pfa31.h (pfa = p, pfa_q = q of the step p / q)
-    int pfa_q = 1;
+    NPointInfo np;             // which one, and its sizes and properties (kind 0: none)
+    int pfa_q = 1;             // a masked plan: pfa = p, pfa_q = q of the Doppler step of p / q bins
+    const uint4 *pfa_coef = nullptr;  // its coefficient table (bds_acq_prepare uploaded it)
     size_t cell_elems = 0;     // fp16-complex-sized elements of one cell in the inter-pass buffer (both components)
     bool dev_refined = false;  // the refinement ran as the device chain
     size_t elem = 8;  // bytes of one stored complex value
@@ -1339,13 +1356,13 @@ int AcqRun::setup() {
     G = a.group;
     if (a.cs_pfa) {  // (bds_acq_prepare laid the code spectra out for it with these very settings)
         const PfaPick pk = pfa_pick(ctx, a, *s);
-        if (pk.kind == a.cs_pfa) pfa = pk.shift, pfa_kind = pk.kind, pfa_q = pk.q;
-        // (kind 3 was admitted for the settings' PRN list: a run on a part of it has fewer cells, never more)
+        if (a.cs_pfa == pk.kind) pfa = pk.shift, np = npoint_info(pk.kind), pfa_q = pk.q, pfa_coef = a.pfa_coef[np.make_coef_frags];
+        // (a masked plan was admitted for the settings' PRN list: a run on a part of it has fewer cells, never more)
     }
     if (a.cs_pfa && !pfa) return fail(ctx, BDS_ERR_HIP, "internal: code spectra in the N-point layout for a run that cannot use them");
     if ((rc = ensure(ctx, &a.d_Bw, &a.bw_cap, bw_batches(a, ctx->tune) * (size_t)pl.L))) return rc;
     // (N-point pair: ONE signal spectrum, every row stored twice -- 2 N fp16 complex = N float2-sized elements)
-    if ((rc = ensure(ctx, &a.d_Xs, &a.xs_cap, pfa ? (size_t)pfa_q * (size_t)pfa_np(pfa_kind) : (size_t)D * pl.L))) return rc;
+    if ((rc = ensure(ctx, &a.d_Xs, &a.xs_cap, pfa ? (size_t)pfa_q * (size_t)np.np : (size_t)D * pl.L))) return rc;
 
     BDS_HIP(ctx, evp.make(&ev0));
     BDS_HIP(ctx, evp.make(&ev1));
@@ -1367,7 +1384,7 @@ int AcqRun::setup() {
         // inter-pass values: rms = X_rms * C_rms / L * sqrt(L2) (Parseval); allow 64 x rms
         // (N-point pair: transform length N, rows of 3125 points; its row pass has no output scale -- sB rides on the stored signal
         //  spectrum, whose rms stays ~0.2 whatever the block: forward_all)
-        const double b_rms = pfa ? std::sqrt(a.sum_sq_ext) * std::sqrt((double)a.X) / (double)a.N * std::sqrt((double)pfa_k3(pfa_kind))
+        const double b_rms = pfa ? std::sqrt(a.sum_sq_ext) * std::sqrt((double)a.X) / (double)a.N * std::sqrt((double)np.k3)
                                  : std::sqrt(a.sum_sq_ext) * std::sqrt((double)a.X) / (double)pl.L * std::sqrt((double)pl.L2);
         a.sB = (float)std::exp2(std::floor(std::log2(32768.0 / (64.0 * std::max(1e-30, b_rms) * a.sX * a.sC))));
     }
@@ -1427,7 +1444,7 @@ int AcqRun::setup() {
         so.recs = a.d_recs;
     }
     elem = a.half ? 4 : 8;
-    cell_elems = pfa ? pfa_cell_elems(pfa_kind) : (size_t)ncomp * pl.L;  // stored complex values of one cell in the inter-pass buffer
+    cell_elems = pfa ? np.cell_elems : (size_t)ncomp * pl.L;  // stored complex values of one cell in the inter-pass buffer
     // One launch pair carries the whole Doppler rows of SEVERAL PRNs through a cell list: the grids fill the chip, a row workgroup
     // walks all the bins of one PRN (its code rows and twiddles set up once per D cells), the row workgroups of different PRNs
     // read the same spectrum rows at about the same time, and a call is a few long launches instead of many short ones.
@@ -1482,8 +1499,8 @@ int AcqRun::setup() {
     cells_per_pair = G;
     if (multiprn) n_pairs_total = (P + PB - 1) / PB, cells_per_pair = (long)PB * D;
     if (pfa && !multiprn) multiprn = true, PB = 1, n_pairs_total = P, cells_per_pair = D;  // the N-point pair always runs on cell lists
-    // (bds_acq_pfa6.h was admitted because all cells fit one pair: the second-peak pass reads them there)
-    if (pfa_kind == 3) multiprn = true, PB = P, n_pairs_total = 1, cells_per_pair = (long)P * D;
+    // (a masked plan was admitted because all cells fit one pair: the second-peak pass reads them there)
+    if (np.masked) multiprn = true, PB = P, n_pairs_total = 1, cells_per_pair = (long)P * D;
     // Overlapped passes (BDS_ACQ_OVERLAP=1, fp32-arithmetic kernels): group k's column pass runs on a second stream beside
     // group k+1's row pass, the two working in different halves of the inter-pass buffer.
     overlap = fsearch && tune.overlap && !multiprn;
@@ -1500,14 +1517,10 @@ int AcqRun::forward_all() {
     Plan2D &pl = a.plan;
     if (pfa) {  // ONE transform: the spectrum of bin 0; bin b is its rotation by b * pfa bins (bds_acq_pfa.h)
         SignalLoader ld{a.sview(), a.N, a.n_ext, f0, s->acqStep, 1.0 / a.fs, 0};
-        if (pfa_kind == 3)  // q transforms: the bins 0 .. q - 1 (the loader's batch index is the bin)
-            pfa6::forward(stream(), ld, pfa_q, a.d_Bw, (uint32_t *)a.d_Xs, (long)pfa6::kSpecElems, 0, a.sX * a.sB, 1);
-        else if (pfa_kind == 4)
-            pfa31::forward(stream(), ld, 1, a.d_Bw, (uint32_t *)a.d_Xs, 0, 0, a.sX * a.sB, 1);
-        else if (pfa_kind == 2)
-            pfa32::forward(stream(), ld, 1, a.d_Bw, (uint32_t *)a.d_Xs, 0, 0, a.sX * a.sB, 1);
-        else
-            pfa::forward(stream(), ld, 1, a.d_Bw, (uint32_t *)a.d_Xs, 0, 0, a.sX * a.sB, 1);
+        // (a masked plan: q transforms, the bins 0 .. q - 1 -- the loader's batch index is the bin --, one spectrum apart)
+        with_npoint(np.kind, [&](auto plan) {
+            decltype(plan)::forward(stream(), ld, pfa_q, a.d_Bw, (uint32_t *)a.d_Xs, np.masked ? (long)np.spec_elems : 0, 0, a.sX * a.sB, 1);
+        });
         BDS_HIP(ctx, hipGetLastError());
         BDS_HIP(ctx, hipEventRecord(ev1, stream()));
         return BDS_OK;
@@ -1579,67 +1592,27 @@ void AcqRun::launch_list(int ncells, Rec *recs, const CellList &cl, int cell0, h
     so1.mid = mid;
     if (mid) mids = true;
     const int hi1 = cl.rng ? -1 : (int)a.N - 1, lo2 = cl.rng ? 0 : 1, hi2 = cl.rng ? -1 : 0;
-    if (pfa_kind == 3) {  // the N-point pair of bds_acq_pfa6.h.  With lag ranges: the masked column pass alone on the cells cl.src names
-                          // in the main search's buffer, or (no cl.src) behind a row pass of the listed cells
-        const int gc = cl.rng ? 1 : std::max(1, cl.gc), chunks = (ncells + gc - 1) / gc;
-        if (!cl.src) {
-            pfa6::RowsArgs ra{(const uint32_t *)a.d_Xs, (const uint32_t *)a.d_Cs, (uint32_t *)a.d_Bw, cl.bin, cl.cs, ncells, gc, pfa, pfa_q};
-            hipLaunchKernelGGL(pfa6::k_pfa6_rows, dim3((unsigned)(pfa6::kRowsWgs * chunks)), dim3(pfa6::kRowsThreads), pfa6::kRowsLds, s_main, ra);
-        }
-        if (mid) (void)hipEventRecord(mid, s_main);
-        const int qch = ctx->tune.pfa_qchunk > 0 ? ctx->tune.pfa_qchunk : 1;
-        const long items = (long)((pfa6::kTiles + qch - 1) / qch) * qch * ncells;
-        const unsigned cgrid = (unsigned)std::min<long>(items, ctx->tune.pfa_cgrid > 0 ? ctx->tune.pfa_cgrid : std::max<long>(512, std::min<long>(8192, items / 24)));
-        pfa6::ColsArgs ca{(const uint32_t *)a.d_Bw, a.d_pfa_coef, ncells, w0, w1, so1.sieve, qch, nullptr, cl.rng, cl.src};
-        if (cl.rng) {
-            want_lds(ctx, pfa6::k_pfa6_cols<true>, pfa6::kColsLds);
-            hipLaunchKernelGGL(pfa6::k_pfa6_cols<true>, dim3(cgrid), dim3(pfa6::kColsThreads), pfa6::kColsLds, s_main, ca);
-        } else {
-            want_lds(ctx, pfa6::k_pfa6_cols<false>, pfa6::kColsLds);
-            hipLaunchKernelGGL(pfa6::k_pfa6_cols<false>, dim3(cgrid), dim3(pfa6::kColsThreads), pfa6::kColsLds, s_main, ca);
-        }
-        return;
-    }
-    if (pfa_kind == 4) {  // the N-point pair of bds_acq_pfa31.h: the same cell list and sieve outputs, its own grids
-        const int gc = std::max(1, cl.gc), chunks = (ncells + gc - 1) / gc;
-        want_lds(ctx, pfa31::k_pfa31_rows, pfa31::kRowsLds);
-        want_lds(ctx, pfa31::k_pfa31_cols, pfa31::kColsLds);
-        pfa::RowsArgs ra{(const uint32_t *)a.d_Xs, (const uint32_t *)a.d_Cs, (uint32_t *)a.d_Bw, cl.bin, cl.cs, ncells, gc, pfa};
-        hipLaunchKernelGGL(pfa31::k_pfa31_rows, dim3((unsigned)(pfa31::kRowsWgs * chunks)), dim3(pfa31::kRowsThreads), pfa31::kRowsLds, s_main, ra);
-        if (mid) (void)hipEventRecord(mid, s_main);
-        const int qch = ctx->tune.pfa_qchunk > 0 ? ctx->tune.pfa_qchunk : 1;
-        const long items = (long)((pfa31::kTiles + qch - 1) / qch) * qch * ncells;
-        const unsigned cgrid = (unsigned)std::min<long>(items, ctx->tune.pfa_cgrid > 0 ? ctx->tune.pfa_cgrid : std::max<long>(512, std::min<long>(8192, items / 24)));
-        pfa::ColsArgs ca{(const uint32_t *)a.d_Bw, a.d_pfa31_coef, ncells, w0, w1, so1.sieve, qch, nullptr, nullptr, -1, -1};
-        hipLaunchKernelGGL(pfa31::k_pfa31_cols, dim3(cgrid), dim3(pfa31::kColsThreads), pfa31::kColsLds, s_main, ca);
-        return;
-    }
-    if (pfa_kind == 2) {  // the N-point pair of bds_acq_pfa32.h: the same cell list and sieve outputs, its own grids
-        const int gc = std::max(1, cl.gc), chunks = (ncells + gc - 1) / gc;
-        want_lds(ctx, pfa32::k_pfa32_cols, pfa32::kColsLds);
-        pfa::RowsArgs ra{(const uint32_t *)a.d_Xs, (const uint32_t *)a.d_Cs, (uint32_t *)a.d_Bw, cl.bin, cl.cs, ncells, gc, pfa};
-        hipLaunchKernelGGL(pfa32::k_pfa32_rows, dim3((unsigned)(pfa32::kRowsWgs * chunks)), dim3(pfa32::kRowsThreads), pfa32::kRowsLds, s_main, ra);
-        if (mid) (void)hipEventRecord(mid, s_main);
-        const int qch = ctx->tune.pfa_qchunk > 0 ? ctx->tune.pfa_qchunk : 1;
-        const long items = (long)((pfa32::kTiles + qch - 1) / qch) * qch * ncells;
-        const unsigned cgrid = (unsigned)std::min<long>(items, ctx->tune.pfa_cgrid > 0 ? ctx->tune.pfa_cgrid : std::max<long>(512, std::min<long>(8192, items / 24)));
-        pfa::ColsArgs ca{(const uint32_t *)a.d_Bw, a.d_pfa_coef, ncells, w0, w1, so1.sieve, qch, nullptr, nullptr, -1, -1};
-        hipLaunchKernelGGL(pfa32::k_pfa32_cols, dim3(cgrid), dim3(pfa32::kColsThreads), pfa32::kColsLds, s_main, ca);
-        return;
-    }
-    if (pfa) {  // the N-point pair (bds_acq_pfa.h): every lag of the N is searched, the cells come as a list
-        const int gc = std::max(1, cl.gc), chunks = cl.chunks ? cl.nchunks : (ncells + gc - 1) / gc;
-        const size_t rows_lds = 2 * 3136 * sizeof(float2);
-        want_lds(ctx, pfa::k_pfa_cols<2, false>, pfa::kColsLds);
-        pfa::RowsArgs ra{(const uint32_t *)a.d_Xs, (const uint32_t *)a.d_Cs, (uint32_t *)a.d_Bw, cl.bin, cl.cs, ncells, gc, pfa, cl.chunks, cl.nchunks};
-        hipLaunchKernelGGL(pfa::k_pfa_rows<2>, dim3((unsigned)(pfa::MP * pfa::K2 * chunks)), dim3(pfa::kRowsThreads), rows_lds, s_main, ra);
-        if (mid) (void)hipEventRecord(mid, s_main);
-        const int qch = ctx->tune.pfa_qchunk > 0 ? ctx->tune.pfa_qchunk : 1;  // (one tile of a cell, then the same tile of the next cell)
-        const long items = (long)((pfa::kTiles + qch - 1) / qch) * qch * ncells;
-        // (a workgroup loads the 57 KB coefficient table once: at least ~24 items each when the launch is small -- one PRN's row per pair)
-        const unsigned cgrid = (unsigned)std::min<long>(items, ctx->tune.pfa_cgrid > 0 ? ctx->tune.pfa_cgrid : std::max<long>(512, std::min<long>(8192, items / 24)));
-        pfa::ColsArgs ca{(const uint32_t *)a.d_Bw, a.d_pfa_coef, ncells, w0, w1, so1.sieve, qch, nullptr, nullptr, -1, -1};
-        hipLaunchKernelGGL((pfa::k_pfa_cols<2, false>), dim3(cgrid), dim3(pfa::kColsThreads), pfa::kColsLds, s_main, ca);
+    if (pfa) {  // the N-point pair: every lag of the N is searched, the cells come as a list.  With lag ranges (a masked plan): the masked column
+                // pass alone on the cells cl.src names in the main search's buffer, or (no cl.src) behind a row pass of the listed cells
+        with_npoint(np.kind, [&](auto plan) {
+            using P = decltype(plan);
+            const auto lds = [&](auto kern, size_t bytes) { want_lds(ctx, kern, bytes); };
+            const int gc = cl.rng ? 1 : std::max(1, cl.gc);
+            if (!cl.src) {
+                typename P::RowsArgs ra{(const uint32_t *)a.d_Xs, (const uint32_t *)a.d_Cs, (uint32_t *)a.d_Bw, cl.bin, cl.cs, ncells, gc, pfa};
+                if constexpr (P::kMasked) ra.q = pfa_q;
+                if constexpr (P::kChunkList) ra.chunks = cl.chunks, ra.nchunks = cl.nchunks;
+                P::launch_rows(s_main, ra, cl.chunks ? cl.nchunks : (ncells + gc - 1) / gc, lds);
+            }
+            if (mid) (void)hipEventRecord(mid, s_main);
+            typename P::ColsArgs ca{(const uint32_t *)a.d_Bw, pfa_coef, ncells, w0, w1, so1.sieve, 0, nullptr};
+            if constexpr (P::kMasked)
+                ca.rng = cl.rng, ca.src = cl.src;
+            else
+                ca.dbg_cell = ca.dbg_group = -1;
+            const Tuning &tune = ctx->tune;  // (hooks build: tiles per run and workgroups as asked for, at most one workgroup per item)
+            P::launch_cols(s_main, ca, tune.pfa_qchunk, std::min<long>(tune.pfa_cgrid, pfa::cols_items(P::kTiles, tune.pfa_qchunk, ncells)), lds);
+        });
         return;
     }
     if (a.half) {
@@ -1703,11 +1676,11 @@ int AcqRun::search() {
             CellList cl;
             cl.bin = d_bin + (size_t)pi0 * D;
             cl.cs = d_cs + (size_t)pi0 * D;
-            // Cells one row workgroup walks: uniform chunks (rows_uniform_gc), or for the pair of bds_acq_pfa.h the tapered list of
-            // rows_chunk_plan -- planned and uploaded when a shape is first seen, looked up on every later call.  BDS_ACQ_LIST_GC of
-            // the hooks build keeps the uniform chunks.
-            cl.gc = rows_uniform_gc(ctx->tune.list_gc, D, np_, pfa ? pfa_rows_wgs(pfa_kind) : pl.L1);
-            if (pfa_kind == 1 && ctx->tune.list_gc == 0) {
+            // Cells one row workgroup walks: uniform chunks (rows_uniform_gc), or for a plan whose row pass takes it (bds_acq_pfa.h) the
+            // tapered list of rows_chunk_plan -- planned and uploaded when a shape is first seen, looked up on every later call.
+            // BDS_ACQ_LIST_GC of the hooks build keeps the uniform chunks.
+            cl.gc = rows_uniform_gc(ctx->tune.list_gc, D, np_, pfa ? np.rows_wgs : pl.L1);
+            if (np.chunk_list && ctx->tune.list_gc == 0) {
                 const int slots = 2 * (ctx->n_cu > 0 ? ctx->n_cu : 256);
                 AcqState::RowsChunks &rc_ = a.rows_chunks[std::make_tuple(np_, D, slots)];
                 if (!rc_.d) {
@@ -1804,14 +1777,14 @@ int AcqRun::finish() {
     t.cell_pair_ms = nsamp ? acc / nsamp : (n_pairs_total ? t.search_ms / (double)n_pairs_total : 0);
     t.cells_per_pair = samp_cells > 0 && nsamp ? samp_cells / nsamp : (double)cells_per_pair;
     t.n_pairs = n_pairs_total;
-    t.fft_len = pfa ? pfa_np(pfa_kind) : pl.L;
+    t.fft_len = pfa ? np.np : pl.L;
     t.n_circ = a.N;
     t.n_bins = D;
     t.n_prn = P;
     t.n_comp = ncomp;
     t.half_storage = a.half ? 1 : 0;  // 0 fp32; 1 fp16 storage (fp32 arithmetic either way)
-    t.plan_l1 = pfa ? pfa_rows(pfa_kind) : pl.L1;
-    t.plan_l2 = pfa ? pfa_k3(pfa_kind) : pl.L2;
+    t.plan_l1 = pfa ? np.rows : pl.L1;
+    t.plan_l2 = pfa ? np.k3 : pl.L2;
     t.refine_path = dev_refined ? 1 : 0;
     {
         const bool wrows_on = fsearch && a.half && pl.L2 == 4096 && (tune.wrows != 0 || pl.small);

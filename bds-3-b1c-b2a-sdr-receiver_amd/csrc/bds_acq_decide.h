@@ -218,9 +218,9 @@ int AcqRun::second_peak_b2a() {
     // (63 tiny launch pairs were ~1 ms of the 2.7 ms refinement at cfg2)
     const size_t cap_cells = bw_cells();  // cells the work buffer holds
     const bool batched = fsearch && (size_t)P <= cap_cells;
-    // (bds_acq_pfa6.h: its spectra are in the N-point layout, launch_cells() has no kernel for them -- always the list, in pieces of
-    //  cap_cells where the buffer holds fewer than P cells: a run whose pair was halved after a failed allocation)
-    const bool listed = batched || pfa_kind == 3;
+    // (a masked N-point plan, bds_acq_pfa6.h: its spectra are in the N-point layout, launch_cells() has no kernel for them -- always the list,
+    //  in pieces of cap_cells where the buffer holds fewer than P cells: a run whose pair was halved after a failed allocation)
+    const bool listed = batched || np.masked;
     BDS_HIP(ctx, hipMemsetAsync(a.d_extra_count, 0, sizeof(int), stream()));  // overflow list of this pass: cell = PRN index
     std::vector<int> h_bin(P);
     std::vector<long> h_cs(P);
@@ -437,7 +437,7 @@ constexpr int kExtra2Cap = 1 << 20;  // candidate list of the B2a second-peak pa
 
 // (the L-point pair: ncomp x L stored values per cell; bds_acq_pfa6.h: its own cell, 0.63 of that.  bw_cap counts 8-byte elements)
 size_t AcqRun::bw_cells() const {
-    if (pfa_kind == 3) return a.bw_cap * 8 / (cell_elems * (size_t)elem);
+    if (np.masked) return a.bw_cap * 8 / (cell_elems * (size_t)elem);
     return a.bw_cap / (size_t)a.plan.L * 8 / elem / (size_t)ncomp;
 }
 

@@ -27,6 +27,7 @@
 #include <hip/hip_fp16.h>
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <type_traits>
 
 #include "bds_acq_sieve.h"
@@ -51,6 +52,9 @@ __host__ __device__ constexpr size_t bw_piece(int mp, int k2, int t3) {  // elem
     return (((size_t)(t3 / kTileLags) * MP + mp) * K2 + k2) * (kTileLags * 4) + (size_t)(t3 % kTileLags) * 4;
 }  // 4-byte (fp16 complex) elements of a cell in the inter-pass buffer
 constexpr int kRowsThreads = 256, kColsThreads = 256;
+constexpr int kRowsWgs = MP * K2;                        // row workgroups per chunk of cells: one row pair of one k2 each
+constexpr size_t kRowsLds = 2 * 3136 * sizeof(float2);   // k_pfa_rows' two row regions of 3125 elements (+ pad)
+constexpr size_t kSpecElems = (size_t)K1 * K2 * 2 * K3;  // 4-byte elements of the signal spectrum (rows doubled)
 // stage-1 twiddles W3125^(j (5 p0 + p1)), p0, p1 >= 1, that k_pfa_rows holds in registers of their own, in slot order (the other 16 - kTw1Held
 // slots take two products by the factors W3125^(j p1), W3125^(5 j p0)): 14 is what 256 registers hold without scratch (254 used)
 constexpr int kTw1Held = 14;
@@ -833,6 +837,59 @@ inline void forward(hipStream_t st, Loader ld, int nb, float2 *tmp, uint32_t *ds
     hipLaunchKernelGGL(k_pfa_fwd_53, dim3((K2 * K3 + 255) / 256, nb), dim3(256), 0, st, (const float2 *)T, U);
     hipLaunchKernelGGL(k_pfa_fwd_12, dim3((K1 * K3 + 255) / 256, nb), dim3(256), 0, st, (const float2 *)U, dst, dst_batch_stride, conj_flag, scale, doubled);
 }
+
+// ---- the launches of a search pair (host), for this header and its siblings bds_acq_pfa32.h, bds_acq_pfa6.h, bds_acq_pfa31.h -----------
+// Each header ends in a `Plan`: its sizes, its coefficient table, its forward transform and its two launches.  csrc/bds_acq.hip and the
+// stage drivers of tools/probe/ launch through a Plan, so each launch is written once.  `lds(kernel, bytes)` is the caller's way of
+// raising a kernel's dynamic-LDS limit: the library keeps books per context (one process may drive several devices), a driver calls
+// hipFuncSetAttribute.
+// Row pass: `chunks` runs of cells (RowsArgs::gc cells each, or the chunk list's), `wgs` workgroups per run.
+template <class K, class Args, class Lds>
+inline void launch_rows_of(K kern, int wgs, int threads, size_t bytes, hipStream_t st, const Args &A, int chunks, Lds &&lds) {
+    lds(kern, bytes);
+    hipLaunchKernelGGL(kern, dim3((unsigned)(wgs * chunks)), dim3(threads), bytes, st, A);
+}
+// Column pass.  Work items: the tiles of a cell in runs of qchunk (<= 0: 1 -- one tile of a cell, then the same tile of the next cell),
+// cell after cell.
+inline long cols_items(int tiles, int qchunk, int ncells) {
+    const int qch = qchunk > 0 ? qchunk : 1;
+    return (long)((tiles + qch - 1) / qch) * qch * ncells;
+}
+// `grid` workgroups; <= 0: a workgroup loads the 57 KB coefficient table once, so at least ~24 items each when the launch is small (one
+// PRN's row per pair)
+template <class K, class Args, class Lds>
+inline void launch_cols_of(K kern, int tiles, int threads, size_t bytes, hipStream_t st, Args A, int qchunk, long grid, Lds &&lds) {
+    A.qchunk = qchunk > 0 ? qchunk : 1;
+    const long items = cols_items(tiles, qchunk, A.ncells);
+    if (grid <= 0) grid = std::min<long>(items, std::max<long>(512, std::min<long>(8192, items / 24)));
+    lds(kern, bytes);
+    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(threads), bytes, st, A);
+}
+
+struct Plan {
+    using RowsArgs = pfa::RowsArgs;
+    using ColsArgs = pfa::ColsArgs;
+    static constexpr long NP = pfa::NP;
+    static constexpr int K3 = pfa::K3, kRows = K1 * K2, kRowsWgs = pfa::kRowsWgs, kTiles = pfa::kTiles;
+    static constexpr size_t kCellElems = pfa::kCellElems, kSpecElems = pfa::kSpecElems, kCoefBytes = pfa::kCoefBytes;
+    static constexpr void (*make_coef_frags)(uint16_t *) = pfa::make_coef_frags;
+    static constexpr bool kChunkList = true;  // the row pass takes a chunk list in place of uniform runs (RowsArgs::chunks)
+    // (bds_acq_pfa6.h) a masked column pass on per-cell lag ranges; it reads the cells of the main search, so a run is ONE launch pair;
+    // several signal spectra per call
+    static constexpr bool kMasked = false;
+    template <class Loader>
+    static void forward(hipStream_t st, Loader ld, int nb, float2 *tmp, uint32_t *dst, long dst_batch_stride, int conj_flag, float scale, int doubled) {
+        pfa::forward(st, ld, nb, tmp, dst, dst_batch_stride, conj_flag, scale, doubled);
+    }
+    template <class Lds>
+    static void launch_rows(hipStream_t st, const RowsArgs &A, int chunks, Lds &&lds) {
+        launch_rows_of(k_pfa_rows<2>, kRowsWgs, kRowsThreads, kRowsLds, st, A, chunks, lds);
+    }
+    template <bool DBG = false, class Lds>  // (DBG: the timing probe's sampled launch)
+    static void launch_cols(hipStream_t st, const ColsArgs &A, int qchunk, long grid, Lds &&lds) {
+        launch_cols_of(k_pfa_cols<2, DBG>, kTiles, kColsThreads, kColsLds, st, A, qchunk, grid, lds);
+    }
+};
 
 }  // namespace pfa
 }  // namespace bds

@@ -499,5 +499,27 @@ inline void forward(hipStream_t st, Loader ld, int nb, float2 *tmp, uint32_t *ds
     hipLaunchKernelGGL(k_pfa31_fwd_store, grid(NP), dim3(256), 0, st, (const float2 *)U, dst, dst_batch_stride, conj_flag, scale, doubled);
 }
 
+struct Plan {  // (bds_acq_pfa.h: the launches of a search pair)
+    using RowsArgs = pfa::RowsArgs;
+    using ColsArgs = pfa::ColsArgs;
+    static constexpr long NP = pfa31::NP;
+    static constexpr int K3 = pfa31::K3, kRows = K1 * K2, kRowsWgs = pfa31::kRowsWgs, kTiles = pfa31::kTiles;
+    static constexpr size_t kCellElems = pfa31::kCellElems, kSpecElems = pfa31::kSpecElems, kCoefBytes = pfa31::kCoefBytes;
+    static constexpr void (*make_coef_frags)(uint16_t *) = pfa31::make_coef_frags;  // the 31-point stage's own table
+    static constexpr bool kChunkList = false, kMasked = false;
+    template <class Loader>
+    static void forward(hipStream_t st, Loader ld, int nb, float2 *tmp, uint32_t *dst, long dst_batch_stride, int conj_flag, float scale, int doubled) {
+        pfa31::forward(st, ld, nb, tmp, dst, dst_batch_stride, conj_flag, scale, doubled);
+    }
+    template <class Lds>
+    static void launch_rows(hipStream_t st, const RowsArgs &A, int chunks, Lds &&lds) {
+        pfa::launch_rows_of(k_pfa31_rows, kRowsWgs, kRowsThreads, kRowsLds, st, A, chunks, lds);
+    }
+    template <class Lds>
+    static void launch_cols(hipStream_t st, const ColsArgs &A, int qchunk, long grid, Lds &&lds) {
+        pfa::launch_cols_of(k_pfa31_cols, kTiles, kColsThreads, kColsLds, st, A, qchunk, grid, lds);
+    }
+};
+
 }  // namespace pfa31
 }  // namespace bds

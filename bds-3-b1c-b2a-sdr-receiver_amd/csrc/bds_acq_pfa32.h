@@ -49,6 +49,7 @@ constexpr int kRowsThreads = 256, kColsThreads = 256;
 constexpr int kRowsWgs = MP * (K2 / 4);                              // row workgroups per chunk of cells: 4 waves = 4 k2 of one row pair
 constexpr int kRowRegion = 640;                                      // float2 elements of a row's LDS region (625 + pad)
 constexpr size_t kRowsLds = (size_t)4 * 2 * kRowRegion * sizeof(float2);  // 4 waves x 2 rows
+constexpr size_t kSpecElems = (size_t)K1 * K2 * 2 * K3;              // 4-byte elements of the signal spectrum (rows doubled)
 constexpr size_t kCoefBytes = pfa::kCoefBytes;                       // the same 53-point B fragments (pfa::make_coef_frags)
 constexpr size_t kColsLds = kCoefBytes;
 static_assert(pfa::K1 == K1 && pfa::NB == NB && pfa::MP == MP, "the 53-point stage shares its coefficient fragments with bds_acq_pfa.h");
@@ -444,6 +445,28 @@ inline void forward(hipStream_t st, Loader ld, int nb, float2 *tmp, uint32_t *ds
     hipLaunchKernelGGL(k_pfa32_fwd_53<K2>, dim3((K2 * K3 + 255) / 256, nb), dim3(256), 0, st, (const float2 *)T, U);
     hipLaunchKernelGGL(k_pfa32_fwd_32, dim3((K1 * K3 + 255) / 256, nb), dim3(256), 0, st, (const float2 *)U, dst, dst_batch_stride, conj_flag, scale, doubled);
 }
+
+struct Plan {  // (bds_acq_pfa.h: the launches of a search pair)
+    using RowsArgs = pfa::RowsArgs;
+    using ColsArgs = pfa::ColsArgs;
+    static constexpr long NP = pfa32::NP;
+    static constexpr int K3 = pfa32::K3, kRows = K1 * K2, kRowsWgs = pfa32::kRowsWgs, kTiles = pfa32::kTiles;
+    static constexpr size_t kCellElems = pfa32::kCellElems, kSpecElems = pfa32::kSpecElems, kCoefBytes = pfa32::kCoefBytes;
+    static constexpr void (*make_coef_frags)(uint16_t *) = pfa::make_coef_frags;
+    static constexpr bool kChunkList = false, kMasked = false;
+    template <class Loader>
+    static void forward(hipStream_t st, Loader ld, int nb, float2 *tmp, uint32_t *dst, long dst_batch_stride, int conj_flag, float scale, int doubled) {
+        pfa32::forward(st, ld, nb, tmp, dst, dst_batch_stride, conj_flag, scale, doubled);
+    }
+    template <class Lds>
+    static void launch_rows(hipStream_t st, const RowsArgs &A, int chunks, Lds &&lds) {
+        pfa::launch_rows_of(k_pfa32_rows, kRowsWgs, kRowsThreads, kRowsLds, st, A, chunks, lds);
+    }
+    template <class Lds>
+    static void launch_cols(hipStream_t st, const ColsArgs &A, int qchunk, long grid, Lds &&lds) {
+        pfa::launch_cols_of(k_pfa32_cols, kTiles, kColsThreads, kColsLds, st, A, qchunk, grid, lds);
+    }
+};
 
 }  // namespace pfa32
 }  // namespace bds

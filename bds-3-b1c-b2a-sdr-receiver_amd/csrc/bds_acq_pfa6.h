@@ -398,6 +398,31 @@ inline void forward(hipStream_t st, Loader ld, int nb, float2 *tmp, uint32_t *ds
     hipLaunchKernelGGL(k_pfa6_fwd_6, dim3((K1 * K3 + 255) / 256, nb), dim3(256), 0, st, (const float2 *)U, dst, dst_batch_stride, conj_flag, scale, doubled);
 }
 
+struct Plan {  // (bds_acq_pfa.h: the launches of a search pair)
+    using RowsArgs = pfa6::RowsArgs;
+    using ColsArgs = pfa6::ColsArgs;
+    static constexpr long NP = pfa6::NP;
+    static constexpr int K3 = pfa6::K3, kRows = K1 * K2, kRowsWgs = pfa6::kRowsWgs, kTiles = pfa6::kTiles;
+    static constexpr size_t kCellElems = pfa6::kCellElems, kSpecElems = pfa6::kSpecElems, kCoefBytes = pfa6::kCoefBytes;
+    static constexpr void (*make_coef_frags)(uint16_t *) = pfa::make_coef_frags;
+    static constexpr bool kChunkList = false, kMasked = true;
+    template <class Loader>
+    static void forward(hipStream_t st, Loader ld, int nb, float2 *tmp, uint32_t *dst, long dst_batch_stride, int conj_flag, float scale, int doubled) {
+        pfa6::forward(st, ld, nb, tmp, dst, dst_batch_stride, conj_flag, scale, doubled);
+    }
+    template <class Lds>
+    static void launch_rows(hipStream_t st, const RowsArgs &A, int chunks, Lds &&lds) {
+        pfa::launch_rows_of(k_pfa6_rows, kRowsWgs, kRowsThreads, kRowsLds, st, A, chunks, lds);
+    }
+    template <class Lds>  // the masked pass where the launch has lag ranges
+    static void launch_cols(hipStream_t st, const ColsArgs &A, int qchunk, long grid, Lds &&lds) {
+        if (!A.rng)
+            pfa::launch_cols_of(k_pfa6_cols<false>, kTiles, kColsThreads, kColsLds, st, A, qchunk, grid, lds);
+        else
+            pfa::launch_cols_of(k_pfa6_cols<true>, kTiles, kColsThreads, kColsLds, st, A, qchunk, grid, lds);
+    }
+};
+
 // ---- admission: acqStep N / fs = p / q exactly, in lowest terms ------------------------------------------------------------------
 // step and fs are whole numbers of hertz in every admitted setting; the ratio is decided in 64-bit integers (one rounded double would
 // take 410 Hz x 2 ms = 0.82 for whatever fraction lies nearest).  False when either is not a whole number or the product overflows.

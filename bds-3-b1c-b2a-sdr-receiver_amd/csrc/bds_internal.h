@@ -43,7 +43,7 @@ struct Tuning {
                                      // rows as fit (default 40: 8 PRNs at cfg3); 0 = minimal (one PRN's row per pair on big grids; small grids batch up
                                      // to 8 GiB), < 0 ("auto") = 60 % of the free device memory
     int rows_grid = 0;                  // BDS_ACQ_ROWS_GRID: workgroups of the (then persistent) row pass; 0 = one per item
-    int list_gc = 0;                    // BDS_ACQ_LIST_GC: cells one row workgroup walks in a multi-PRN launch pair (a divisor of D; 0 = chosen by the launch's size -- the pair of bds_acq_pfa.h then takes the tapered chunk list of rows_chunk_plan instead --, -1 = all D bins of its PRN)
+    int list_gc = 0;                    // BDS_ACQ_LIST_GC: cells one row workgroup walks in a multi-PRN launch pair (a divisor of D; 0 = chosen by the launch's size -- an N-point plan with Plan::kChunkList then takes the tapered chunk list of rows_chunk_plan instead --, -1 = all D bins of its PRN)
     bool no_bwreuse = false;            // BDS_ACQ_NO_BWREUSE: the B2a second-peak pass runs its own row pass (A/B, tests)
     bool overlap = false;               // BDS_ACQ_OVERLAP: column pass of group k on a second stream beside the row pass of group k+1
     double kdelta = 0;                  // BDS_ACQ_KDELTA: test hook, sieve tolerance override (0 = per-mode default)
@@ -56,8 +56,10 @@ struct Tuning {
     int wrows = -1;                  // BDS_ACQ_WROWS: wave-private 4096-point row pass (bds_acq_wrows.h); -1 = default on, 0 = k_rows_inv_f
     int pfa = 1;                     // BDS_ACQ_PFA (hooks): the N-point search pairs where they apply (B1C, N = 53 x 12 x 3125: bds_acq_pfa.h, N = 53 x 32 x 625:
                                      // bds_acq_pfa32.h; fp16 storage, whole bins per acqStep); 0 = the L-point pair of rounds 3-5 everywhere
-    int pfa_qchunk = 0;              // BDS_ACQ_PFA_QCHUNK (hooks): tiles of a cell (16 lags; bds_acq_pfa32.h: 8) that follow each other in the N-point column passes' work list
-    int pfa_cgrid = 0;               // BDS_ACQ_PFA_CGRID (hooks): workgroups of the N-point column passes
+    int pfa_qchunk = 0;              // BDS_ACQ_PFA_QCHUNK (hooks): tiles of a cell (the plan's kTileLags lags each) that follow each other in the N-point column
+                                     // passes' work list: the qchunk of Plan::launch_cols (0 = 1)
+    int pfa_cgrid = 0;               // BDS_ACQ_PFA_CGRID (hooks): workgroups of the N-point column passes, at most one per work item: the grid of
+                                     // Plan::launch_cols (0 = its default rule, bds_acq_pfa.h)
     int small_plan = 1;              // BDS_ACQ_SMALL: small two-component searches on the 80 x 4096 plan (bds_acq_scols.h); 0 = 256 x 1280 as in rounds 1-3
     bool host_refine = false;        // BDS_ACQ_HOSTREFINE: refinement through the host (lists downloaded, jobs built there: rounds 1-4) instead of the device chain
     int neigh = 0;                   // BDS_ACQ_NEIGH: also refine the +-n bin / lag neighbours of every candidate in f64 (rounds 1-3: 1)

@@ -137,9 +137,10 @@ int main(int argc, char **argv) {
         make_coef_frags(cf.data());
         CK(hipMemcpy(d_coef, cf.data(), kCoefBytes, hipMemcpyHostToDevice));
     }
-    const size_t rows_lds = 2 * 3136 * sizeof(float2);
+    // every launch goes through pfa::Plan, as the library's; the dynamic-LDS limits are raised here, outside the timed launches
     CK(hipFuncSetAttribute((const void *)k_pfa_cols<2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kColsLds));
     CK(hipFuncSetAttribute((const void *)k_pfa_cols<2, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kColsLds));
+    const auto lds_done = [](auto, size_t) {};
 
     // ---------------- correctness: each test cell is its own one-cell chunk (gc = 1: the PRN slot changes from cell to cell)
     for (int i = 0; i < ncell_t; ++i) h_bin[i] = tb[i], h_cs[i] = (long)tslot[i] * 2 * NP;
@@ -147,7 +148,7 @@ int main(int argc, char **argv) {
     CK(hipMemcpy(d_cs, h_cs.data(), ncell_t * sizeof(long), hipMemcpyHostToDevice));
     CK(hipMemset(d_Bw, 0xff, (size_t)ncell_t * kCellElems * 4));  // NaN pattern: every element must be written
     RowsArgs ra{d_Xs, d_Cs, d_Bw, d_bin, d_cs, ncell_t, 1, 1};
-    hipLaunchKernelGGL(k_pfa_rows<2>, dim3(MP * K2 * ncell_t), dim3(kRowsThreads), rows_lds, 0, ra);
+    Plan::launch_rows(0, ra, ncell_t, lds_done);
     CK(hipDeviceSynchronize());
     std::vector<uint32_t> Bw((size_t)ncell_t * kCellElems);
     CK(hipMemcpy(Bw.data(), d_Bw, Bw.size() * 4, hipMemcpyDeviceToHost));
@@ -192,7 +193,7 @@ int main(int argc, char **argv) {
             CK(hipMemset(d_extra_count, 0, sizeof(int)));
             CK(hipMemset(d_dbg, 0, sizeof(float) * 2 * K1 * 12 * 4));
             ColsArgs ca{d_Bw, d_coef, ncell_t, 0.52440442f, 0.85146932f, {d_cellmax, d_lb, 1, d_extra, d_extra_count, extra_cap, 0, 0.996f}, 4, nullptr, d_dbg, cell, grp};
-            hipLaunchKernelGGL((k_pfa_cols<2, true>), dim3(512), dim3(kColsThreads), kColsLds, 0, ca);
+            Plan::launch_cols<true>(0, ca, 4, 512, lds_done);
             CK(hipDeviceSynchronize());
             std::vector<float> dbg(2 * K1 * 12 * 4);
             CK(hipMemcpy(dbg.data(), d_dbg, dbg.size() * 4, hipMemcpyDeviceToHost));
@@ -311,9 +312,9 @@ int main(int argc, char **argv) {
                 CK(hipMemset(d_stats, 0, 4 * sizeof(unsigned long long)));
                 ColsArgs ct{d_Bw, d_coef, ncells, 0.52440442f, 0.85146932f, {d_cellmax, d_lb, D, d_extra, d_extra_count, extra_cap, 0, 0.996f}, qch, counting ? d_stats : nullptr, nullptr, -1, -1};
                 CK(hipEventRecord(e0));
-                hipLaunchKernelGGL(k_pfa_rows<2>, dim3(MP * K2 * chunks), dim3(kRowsThreads), rows_lds, 0, rt);
+                Plan::launch_rows(0, rt, chunks, lds_done);
                 CK(hipEventRecord(e1));
-                hipLaunchKernelGGL((k_pfa_cols<2, false>), dim3(cgrid), dim3(kColsThreads), kColsLds, 0, ct);
+                Plan::launch_cols(0, ct, qch, cgrid, lds_done);
                 CK(hipEventRecord(e2));
                 CK(hipDeviceSynchronize());
                 float mr, mc;
@@ -344,11 +345,11 @@ int main(int argc, char **argv) {
         const int nA = (prns / 2) * D, nB = ncells - nA, gc = 67;
         auto rows = [&](hipStream_t st, int off, int n) {
             RowsArgs r{d_Xs, d_Cs, d_Bw + (size_t)off * kCellElems, d_bin + off, d_cs + off, n, gc, 1};
-            hipLaunchKernelGGL(k_pfa_rows<2>, dim3(MP * K2 * ((n + gc - 1) / gc)), dim3(kRowsThreads), rows_lds, st, r);
+            Plan::launch_rows(st, r, (n + gc - 1) / gc, lds_done);
         };
         auto cols = [&](hipStream_t st, int off, int n) {
             ColsArgs c{d_Bw + (size_t)off * kCellElems, d_coef, n, 0.52440442f, 0.85146932f, {d_cellmax, d_lb, D, d_extra, d_extra_count, extra_cap, off, 0.996f}, 1, nullptr, nullptr, -1, -1};
-            hipLaunchKernelGGL((k_pfa_cols<2, false>), dim3(8192), dim3(kColsThreads), kColsLds, st, c);
+            Plan::launch_cols(st, c, 1, 8192, lds_done);
         };
         float best_seq = 1e9f, best_ovl = 1e9f;
         for (int rep = 0; rep < 2 * reps; ++rep) {

@@ -117,7 +117,6 @@ int main(int argc, char **argv) {
     const size_t body = (size_t)ncells * kCellElems, total = body + 2 * guard;
     CK(hipMalloc((void **)&d_all, total * 4));
     std::vector<uint32_t> all(total);
-    const size_t rows_lds = 2 * 3136 * sizeof(float2);
     for (int pass = 0; pass < 2; ++pass) {
         std::fill(all.begin(), all.end(), kGuardWord);
         std::fill(all.begin() + guard, all.begin() + guard + body, 0xFFFFFFFFu);
@@ -125,7 +124,9 @@ int main(int argc, char **argv) {
         RowsArgs ra{d_Xs, d_Cs, d_all + guard, d_bin, d_cs, ncells, gc, shift};
         int chunks = (ncells + gc - 1) / gc;
         if (pass == 0) ra.chunks = d_chunks, ra.nchunks = nchunks, chunks = nchunks;
-        hipLaunchKernelGGL(k_pfa_rows<2>, dim3((unsigned)(MP * K2 * chunks)), dim3(kRowsThreads), rows_lds, 0, ra);
+        Plan::launch_rows(0, ra, chunks, [](auto kern, size_t bytes) {
+            CK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+        });
         CK(hipGetLastError());
         CK(hipDeviceSynchronize());
         CK(hipMemcpy(all.data(), d_all, total * 4, hipMemcpyDeviceToHost));
