@@ -233,9 +233,8 @@ void acq_state_free(AcqState *a) {
     delete a;
 }
 
-// After the tuning knobs changed: the plan, the storage mode and the element order of the cached spectra all depend on them
-// (spectra_permuted() must agree between the forward transforms and the search), so the next bds_acq_prepare re-derives
-// everything.  The loaded IF block stays.
+// After the tuning knobs changed: the plan, the storage mode and the kernels of the search (kernel_pick(), hence the element order of
+// the cached spectra) all depend on them, so the next bds_acq_prepare re-derives everything.  The loaded IF block stays.
 void acq_state_invalidate(AcqState *a) {
     if (a) a->plan.L = 0;
 }
@@ -361,20 +360,9 @@ static void want_lds(bds_ctx *ctx, K kern, size_t bytes) {
         (void)hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
 }
 
-
-static int set_lds_limits(bds_ctx *ctx) {
-    if (!ctx->lds_attr_done.insert((const void *)k_rows_fwd).second) return BDS_OK;
-    const int maxlds = 160 * 1024 - 4096;  // leave room for the kernels' small static LDS
-    BDS_HIP(ctx, hipFuncSetAttribute((const void *)k_cols_fwd<SignalLoader>, hipFuncAttributeMaxDynamicSharedMemorySize, maxlds));
-    BDS_HIP(ctx, hipFuncSetAttribute((const void *)k_cols_fwd<CodeLoader>, hipFuncAttributeMaxDynamicSharedMemorySize, maxlds));
-    BDS_HIP(ctx, hipFuncSetAttribute((const void *)k_rows_fwd, hipFuncAttributeMaxDynamicSharedMemorySize, maxlds));
-    BDS_HIP(ctx, hipFuncSetAttribute((const void *)k_rows_fwd_st<__half2>, hipFuncAttributeMaxDynamicSharedMemorySize, maxlds));
-    BDS_HIP(ctx, hipFuncSetAttribute((const void *)k_rows_inv<1>, hipFuncAttributeMaxDynamicSharedMemorySize, maxlds));
-    BDS_HIP(ctx, hipFuncSetAttribute((const void *)k_rows_inv<2>, hipFuncAttributeMaxDynamicSharedMemorySize, maxlds));
-    BDS_HIP(ctx, hipFuncSetAttribute((const void *)k_cols_inv_max<1>, hipFuncAttributeMaxDynamicSharedMemorySize, maxlds));
-    BDS_HIP(ctx, hipFuncSetAttribute((const void *)k_cols_inv_max<2>, hipFuncAttributeMaxDynamicSharedMemorySize, maxlds));
-    return BDS_OK;
-}
+// the run-time-plan kernels (bds_acq_kernels.h, k_rows_fwd_st) size their dynamic LDS from the plan: the limit they may be given,
+// leaving room for their small static LDS
+constexpr size_t kPlanLdsMax = 160 * 1024 - 4096;
 
 // forward transform of `nb` batches produced by loader `ld` into dst[b*dst_stride]
 // forward passes on the specialised stages (plans with pl.fast)
@@ -405,20 +393,71 @@ static void launch_rows_fwd_any(bds_ctx *ctx, hipStream_t s_, const Plan2D &pl, 
     }
 }
 
-// The spectra of this configuration are stored in the element order of the wave-private 4096-point row pass (wrows_perm(),
-// bds_acq_fast.h): exactly when launch_rows_f will run k_rows_wave_f on them -- fp16 storage, 4096-point rows, a specialised
-// plan (or the 80 x 4096 one) and the specialised search not switched off.  Every fallback (fp32 storage, run-time-plan
-// kernels) clears a.half and re-runs bds_acq_prepare, which rebuilds the spectra in natural order.
-static bool spectra_permuted(const bds_ctx *ctx, const AcqState &a) {
+// ---- which kernels a configuration's search runs on ----------------------------------------------------------------
+// Decided HERE and nowhere else: kernel_pick() is the only reader of the tuning knobs that select kernels.  The forward transforms
+// (element order of the spectra), AcqRun::setup (what the sieve's output looks like), the launcher of a pair (launch_pair) and the timing
+// record (AcqRun::finish) read the fields.  The enumerators are the numbers bds_timing::rows_kernel / cols_kernel report.
+enum RowsKernel { kRowsPlan = 0, kRowsInvF = 1, kRowsWaveF = 2, kRowsNPoint = 3 };  // run-time plan (k_rows_inv), k_rows_inv_f, k_rows_wave_f, an N-point plan's
+enum ColsKernel { kColsPlan = 0, kColsTile = 1, kColsWave = 2, kColsSmall = 3, kColsNPoint = 4 };  // k_cols_inv_max, k_cols_inv_max_f, k_cols_wave_f, k_cols_small_f (80 x 4096), an N-point plan's
+struct KernelPick {
+    RowsKernel rows = kRowsPlan;
+    ColsKernel cols = kColsPlan;
+    bool permuted = false;  // the spectra are stored in the element order k_rows_wave_f reads (wrows_perm(), bds_acq_fast.h)
+    bool ilv = false;       // an unmasked launch keeps both components of an element side by side in the inter-pass buffer (the 80 x 4096
+                            // pair: every launch); launch_pair adds the per-launch part
+    bool pk_rows = false, pk_cols = false;  // packed-fp32 butterflies (bds_fft_pk.h) in the row / column pass
+    bool fast() const { return rows != kRowsPlan; }        // the fp32-arithmetic specialised kernels (or an N-point pair), not the run-time plan
+    bool per_cell() const { return cols >= kColsWave; }    // the column pass reports packed per-cell maxima and running bounds, not per-tile records
+};
+// npoint = PfaPick::kind of the run (AcqState::cs_pfa; 0: the L-point pair).  Under an N-point pair ilv and pk_rows describe the L-point
+// pair of the same plan, which is what kernel_flags has always reported there.  Every fallback of a run (fp32 storage, run-time-plan
+// kernels) clears a.half / sets a.no_fast_search and re-runs bds_acq_prepare, which rebuilds the spectra for the new pick.
+static KernelPick kernel_pick(const Tuning &tune, const AcqState &a, int npoint) {
     const Plan2D &pl = a.plan;
-    return a.half && pl.L2 == 4096 && (pl.fast || pl.small) && (ctx->tune.wrows != 0 || pl.small) && !a.no_fast_search;
+    KernelPick p;
+    if (!(pl.fast || (pl.small && a.half) || npoint) || a.no_fast_search) return p;
+    // wave-private 4096-point row pass (bds_acq_wrows.h): fp16 storage; the 80 x 4096 plan has no other
+    const bool wave_rows = a.half && pl.L2 == 4096 && (tune.wrows != 0 || pl.small);
+    p.rows = npoint ? kRowsNPoint : wave_rows ? kRowsWaveF : kRowsInvF;
+    // wave-private column pass: the default, but the 256-point plans keep the tile kernel unless forced with BDS_ACQ_WCOLS=1 (a workgroup's
+    // share of such a tile is 8 points per lane and the per-workgroup constants and barriers dominate: cfg2 2.18 vs 1.39 ms per launch)
+    const bool wave_cols = tune.wcols != 0 && (pl.L1 != 256 || tune.wcols > 0);
+    p.cols = npoint ? kColsNPoint : pl.small ? kColsSmall : wave_cols ? kColsWave : kColsTile;
+    p.permuted = p.rows == kRowsWaveF;
+    p.ilv = wave_rows && p.per_cell() && a.ncomp == 2 && ((pl.L1 == 768 && tune.ilv != 0) || pl.small);
+    p.pk_rows = wave_rows && tune.pk != 0;
+    p.pk_cols = p.ilv && p.cols == kColsWave && tune.pk != 0 && tune.pk != 2;  // (BDS_ACQ_PK=2: row pass only; only the interleaved variants have a packed form)
+    return p;
 }
 
+// (half, ncomp) -> f(StoreTag<ST>{}, std::integral_constant<int, NC>{}): the one place that turns the storage mode and the component
+// count into template arguments
+template <class ST>
+struct StoreTag {
+    using type = ST;
+};
+template <class F>
+static void with_storage(bool half, int ncomp, F &&f) {
+    using C1 = std::integral_constant<int, 1>;
+    using C2 = std::integral_constant<int, 2>;
+    if (half)
+        ncomp == 2 ? f(StoreTag<__half2>{}, C2{}) : f(StoreTag<__half2>{}, C1{});
+    else
+        ncomp == 2 ? f(StoreTag<float2>{}, C2{}) : f(StoreTag<float2>{}, C1{});
+}
+
+// perm: KernelPick::permuted of the configuration
 template <class Loader>
 static int forward(bds_ctx *ctx, AcqState &a, Loader ld, int nb, float2 *dst, long dst_stride, int conj_flag,
-                   float scale) {
+                   float scale, bool perm) {
     Plan2D &pl = a.plan;
-    const int perm = spectra_permuted(ctx, a) ? 1 : 0;
+    // rows of a specialised length, stored as the search reads them (dst counts in stored elements)
+    const auto rows_typed = [&]() {
+        with_storage(a.half, a.ncomp, [&](auto st_, auto) {
+            using ST = typename decltype(st_)::type;
+            launch_rows_fwd_any<ST>(ctx, st(ctx), pl, nb, (const float2 *)a.d_Bw, (ST *)dst, dst_stride, conj_flag, scale, perm ? 1 : 0);
+        });
+    };
     if (pl.fast && !ctx->tune.generic_fwd) {
         switch (pl.L1) {
             case 256: launch_cols_fwd_t<256>(ctx, st(ctx), pl, ld, nb, a.d_Bw); break;
@@ -426,29 +465,27 @@ static int forward(bds_ctx *ctx, AcqState &a, Loader ld, int nb, float2 *dst, lo
             case 768: launch_cols_fwd_t<768>(ctx, st(ctx), pl, ld, nb, a.d_Bw); break;
             default: launch_cols_fwd_t<1024>(ctx, st(ctx), pl, ld, nb, a.d_Bw); break;
         }
-        if (a.half)
-            launch_rows_fwd_any<__half2>(ctx, st(ctx), pl, nb, (const float2 *)a.d_Bw, (__half2 *)dst, dst_stride, conj_flag, scale, perm);
-        else
-            launch_rows_fwd_any<float2>(ctx, st(ctx), pl, nb, (const float2 *)a.d_Bw, dst, dst_stride, conj_flag, scale, 0);
+        rows_typed();
         BDS_HIP(ctx, hipGetLastError());
         return BDS_OK;
     }
     dim3 g1(pl.ntiles, nb), g2(pl.L1, nb);
+    want_lds(ctx, k_cols_fwd<Loader>, kPlanLdsMax);
     hipLaunchKernelGGL(k_cols_fwd<Loader>, g1, dim3(pl.nt_cols), pl.lds_cols, st(ctx), pl.p1, pl.twl, pl.L2,
                        pl.logT, pl.Spad, ld, a.d_Bw, pl.L);
     if (fast_rows(pl.L2) && !ctx->tune.generic && !ctx->tune.generic_fwd) {
         // rows of a specialised length under a run-time-plan column pass (the 80 x 4096 plan of cfg2): the compile-time row pass
         // (first stage from global memory, last stage to the typed store; 2 080 rows of cfg2 in ~25 us against 78 on the run-time engine)
-        if (a.half)
-            launch_rows_fwd_any<__half2>(ctx, st(ctx), pl, nb, (const float2 *)a.d_Bw, (__half2 *)dst, dst_stride, conj_flag, scale, perm);
-        else
-            launch_rows_fwd_any<float2>(ctx, st(ctx), pl, nb, (const float2 *)a.d_Bw, dst, dst_stride, conj_flag, scale, 0);
-    } else if (a.half)  // dst counts in stored elements (fp16 complex)
+        rows_typed();
+    } else if (a.half) {  // dst counts in stored elements (fp16 complex)
+        want_lds(ctx, k_rows_fwd_st<__half2>, kPlanLdsMax);
         hipLaunchKernelGGL(k_rows_fwd_st<__half2>, g2, dim3(pl.nt_rows), pl.lds_rows, st(ctx), pl.p2,
-                           (const float2 *)a.d_Bw, pl.L, (__half2 *)dst, dst_stride, conj_flag, scale, perm);
-    else
+                           (const float2 *)a.d_Bw, pl.L, (__half2 *)dst, dst_stride, conj_flag, scale, perm ? 1 : 0);
+    } else {
+        want_lds(ctx, k_rows_fwd, kPlanLdsMax);
         hipLaunchKernelGGL(k_rows_fwd, g2, dim3(pl.nt_rows), pl.lds_rows, st(ctx), pl.p2, (const float2 *)a.d_Bw,
                            pl.L, dst, dst_stride, conj_flag, scale);
+    }
     BDS_HIP(ctx, hipGetLastError());
     return BDS_OK;
 }
@@ -579,15 +616,26 @@ struct SieveOut {
     Rec *recs = nullptr;
     SieveArgs sieve{nullptr, nullptr, 1, nullptr, nullptr, 0, 0, 1.f};
     hipEvent_t mid = nullptr;  // recorded between the two passes of a sampled launch pair (timing)
-    // overlapped passes: the column pass runs on its own stream behind ev_rows and signals ev_cols
-    hipStream_t cols_stream = nullptr;
-    hipEvent_t ev_rows = nullptr, ev_cols = nullptr;
 };
 
-// ---- fp32-arithmetic search kernels (bds_acq_f32.h): dispatch on the compile-time lengths --------------
+// ---- one launch pair of the L-point search: what it works on, and the launchers (dispatch on the compile-time lengths) --------------
+struct PairArgs {
+    const void *Xs = nullptr;  // signal spectra, one per Doppler bin
+    const void *Cs = nullptr;  // code spectra: of the pair's PRN, or with a cell list the base cl.cs counts from
+    void *Bw = nullptr;        // inter-pass buffer
+    int G = 0, bin0 = 0;       // cells; without a cell list they are the bins bin0 .. bin0 + G - 1
+    float out_scale = 1.f;     // of the row pass's stores
+    float w0 = 1.f, w1 = 1.f;  // magnitude weights of the components
+    int lo1 = 0, hi1 = -1, lo2 = 1, hi2 = 0;  // searched lag ranges (inclusive, empty when lo > hi); with cl.rng the list's
+    SieveOut so;
+    CellList cl;
+    bool unmasked() const { return !cl.rng && lo1 == 0 && lo2 > hi2; }  // one lag range from 0
+};
+
 template <int S, int NC, class ST>
-static void launch_rows_f(bds_ctx *ctx, hipStream_t sr, const Plan2D &pl, const void *Xs, int G, int bin0, const void *Cs,
-                          void *Bw, float out_scale, const CellList &cl, bool ilv) {
+static void launch_rows_f(bds_ctx *ctx, hipStream_t sr, const Plan2D &pl, const KernelPick &pick, const PairArgs &pa, bool ilv) {
+    const CellList &cl = pa.cl;
+    const int G = pa.G;
     const size_t lds = sizeof(float2) * (tspan<S>() + f32_tw_span<S, false>());
     want_lds(ctx, k_rows_inv_f<S, NC, ST>, lds);
     // balanced chunks of at most tune.gchunk cells
@@ -595,13 +643,13 @@ static void launch_rows_f(bds_ctx *ctx, hipStream_t sr, const Plan2D &pl, const 
     int gc = (G + nch - 1) / nch;
     if (cl.bin) gc = cl.gc, nch = (G + cl.gc - 1) / cl.gc;  // a workgroup stays inside one PRN's cells
     const int nvb = pl.L1 * nch;  // L1 % 8 == 0 on every specialised plan: virtual workgroup vb sits on XCD vb % 8
-    const RowsFArgs A{pl.d_tw2, pl.twl, Xs, pl.L, pl.L1, G, bin0, Cs, Bw, out_scale, gc, nch, cl.bin, cl.cs, nvb, ctx->tune.clockprobe ? pl.d_clk : nullptr, ilv ? 1 : 0};
+    const RowsFArgs A{pl.d_tw2, pl.twl, pa.Xs, pl.L, pl.L1, G, pa.bin0, pa.Cs, pa.Bw, pa.out_scale, gc, nch, cl.bin, cl.cs, nvb, ctx->tune.clockprobe ? pl.d_clk : nullptr, ilv ? 1 : 0};
     const int grid = ctx->tune.rows_grid > 0 ? std::min(nvb, (ctx->tune.rows_grid + 7) / 8 * 8) : nvb;
     if constexpr (S == 4096 && std::is_same<ST, __half2>::value) {
-        if (ctx->tune.wrows != 0 || pl.small) {  // wave-private row pass (bds_acq_wrows.h): per-lane twiddle constants, 4 barriers per cell
+        if (pick.rows == kRowsWaveF) {  // wave-private row pass (bds_acq_wrows.h): per-lane twiddle constants, 4 barriers per cell
             RowsFArgs B = A;
             B.tw = pl.d_wrtab;
-            const bool pk = ctx->tune.pk != 0;  // packed-fp32 butterflies (bds_fft_pk.h)
+            const bool pk = pick.pk_rows;
             auto go = [&](auto kern) {
                 want_lds(ctx, kern, kWRowsLdsBytes);
                 hipLaunchKernelGGL(kern, dim3(grid), dim3(256), kWRowsLdsBytes, sr, B);
@@ -621,24 +669,23 @@ static void launch_rows_f(bds_ctx *ctx, hipStream_t sr, const Plan2D &pl, const 
     hipLaunchKernelGGL((k_rows_inv_f<S, NC, ST>), dim3(grid), dim3(rows_threads<S>()), lds, sr, A);
 }
 template <int S, int T, int NC, class ST>
-static void launch_cols_ft(bds_ctx *ctx, hipStream_t sc, const Plan2D &pl, int G, const void *Bw, float w0, float w1, int lo1,
-                           int hi1, int lo2, int hi2, const SieveOut &so, const CellList &cl) {
+static void launch_cols_ft(bds_ctx *ctx, hipStream_t sc, const Plan2D &pl, const PairArgs &pa) {
+    const SieveOut &so = pa.so;
     const size_t lds = sizeof(float2) * (T * tspan<S>() + f32_tw_span<S, f32_tab_cols<S>()>());
-    const ColsFArgs A{(const float2 *)(f32_tab_cols<S>() ? pl.d_ftab1 : pl.d_tw1), pl.L2, Bw, pl.L, w0, w1, lo1, hi1, lo2, hi2, so.recs, pl.ntiles, cl.rng,
+    const ColsFArgs A{(const float2 *)(f32_tab_cols<S>() ? pl.d_ftab1 : pl.d_tw1), pl.L2, pa.Bw, pl.L, pa.w0, pa.w1, pa.lo1, pa.hi1, pa.lo2, pa.hi2, so.recs, pl.ntiles, pa.cl.rng,
                       so.sieve.extra, so.sieve.extra_count, so.sieve.extra_cap, so.sieve.cell0, so.sieve.keep};
-    const bool masked = cl.rng || !(lo1 == 0 && lo2 > hi2);  // anything but "one range starting at lag 0"
-    if (masked) {
+    if (!pa.unmasked()) {
         want_lds(ctx, k_cols_inv_max_f<S, T, NC, true, ST>, lds);
-        hipLaunchKernelGGL((k_cols_inv_max_f<S, T, NC, true, ST>), dim3(pl.ntiles, G), dim3(cols_threads<S, T>()), lds, sc, A);
+        hipLaunchKernelGGL((k_cols_inv_max_f<S, T, NC, true, ST>), dim3(pl.ntiles, pa.G), dim3(cols_threads<S, T>()), lds, sc, A);
     } else {
         want_lds(ctx, k_cols_inv_max_f<S, T, NC, false, ST>, lds);
-        hipLaunchKernelGGL((k_cols_inv_max_f<S, T, NC, false, ST>), dim3(pl.ntiles, G), dim3(cols_threads<S, T>()), lds, sc, A);
+        hipLaunchKernelGGL((k_cols_inv_max_f<S, T, NC, false, ST>), dim3(pl.ntiles, pa.G), dim3(cols_threads<S, T>()), lds, sc, A);
     }
 }
 // wave-private column pass: one tile per workgroup, workgroups started by the hardware in list order (see the kernel's
 // note on item order)
 template <int S, int NC, bool MASKED, class ST, int NV, bool ILV = false, bool PK = false>
-static void launch_cols_wm(bds_ctx *ctx, hipStream_t sc, const Plan2D &pl, const WColsArgs &A) {
+static void launch_cols_wm(bds_ctx *ctx, hipStream_t sc, const WColsArgs &A) {
     using W = WCols<S>;
     want_lds(ctx, k_cols_wave_f<S, NC, MASKED, ST, NV, ILV, PK>, W::kLdsBytes);
     WColsArgs B = A;
@@ -649,89 +696,91 @@ static void launch_cols_wm(bds_ctx *ctx, hipStream_t sc, const Plan2D &pl, const
     hipLaunchKernelGGL((k_cols_wave_f<S, NC, MASKED, ST, NV, ILV, PK>), dim3(A.n_items), dim3(W::NT), W::kLdsBytes, sc, B);
 }
 template <int S, int NC, class ST>
-static void launch_cols_w(bds_ctx *ctx, hipStream_t sc, const Plan2D &pl, int G, const void *Bw, float w0, float w1, int lo1,
-                          int hi1, int lo2, int hi2, const SieveOut &so, const CellList &cl, bool ilv) {
+static void launch_cols_w(bds_ctx *ctx, hipStream_t sc, const Plan2D &pl, const KernelPick &pick, const PairArgs &pa, bool ilv) {
     const int ntiles = pl.L2 / WCols<S>::T;  // L2 % 256 == 0 on every specialised plan: ntiles % 32 == 0 (8 XCDs x quads)
-    const WColsArgs A{(const float2 *)pl.d_wtab, pl.L2, ntiles, G, G * ntiles, Bw, pl.L, w0, w1, lo1, hi1, lo2, hi2, cl.rng, so.sieve, 1,
+    const WColsArgs A{(const float2 *)pl.d_wtab, pl.L2, ntiles, pa.G, pa.G * ntiles, pa.Bw, pl.L, pa.w0, pa.w1, pa.lo1, pa.hi1, pa.lo2, pa.hi2, pa.cl.rng, pa.so.sieve, 1,
                       ctx->tune.clockprobe ? pl.d_clk : nullptr};
-    const bool masked = cl.rng || !(lo1 == 0 && lo2 > hi2);  // anything but "one range starting at lag 0"
+    const bool six = pa.hi1 / pl.L2 < 6 * 8 * WCols<S>::R1;  // no searched lag beyond output row 48 R1: outputs v = 6, 7 of the last stage unused
     if constexpr (S == 768 && NC == 2 && std::is_same<ST, __half2>::value) {  // (the plan with 4096-point rows: cfg3)
         if (ilv) {  // k_rows_wave_f<2, true> laid the buffer out [cell][element][component]
-            const bool pk = ctx->tune.pk != 0 && ctx->tune.pk != 2;  // packed-fp32 butterflies (BDS_ACQ_PK=2: row pass only)
-            if (hi1 / pl.L2 < 6 * 8 * WCols<S>::R1) {
-                if (pk) launch_cols_wm<S, NC, false, ST, 6, true, true>(ctx, sc, pl, A);
-                else launch_cols_wm<S, NC, false, ST, 6, true>(ctx, sc, pl, A);
+            if (six) {
+                if (pick.pk_cols) launch_cols_wm<S, NC, false, ST, 6, true, true>(ctx, sc, A);
+                else launch_cols_wm<S, NC, false, ST, 6, true>(ctx, sc, A);
             } else {
-                if (pk) launch_cols_wm<S, NC, false, ST, 8, true, true>(ctx, sc, pl, A);
-                else launch_cols_wm<S, NC, false, ST, 8, true>(ctx, sc, pl, A);
+                if (pick.pk_cols) launch_cols_wm<S, NC, false, ST, 8, true, true>(ctx, sc, A);
+                else launch_cols_wm<S, NC, false, ST, 8, true>(ctx, sc, A);
             }
             return;
         }
     }
-    if (masked)
-        launch_cols_wm<S, NC, true, ST, 8>(ctx, sc, pl, A);
-    else if (hi1 / pl.L2 < 6 * 8 * WCols<S>::R1)  // no searched lag beyond output row 48 R1: outputs v = 6, 7 of the last stage unused
-        launch_cols_wm<S, NC, false, ST, 6>(ctx, sc, pl, A);
+    if (!pa.unmasked())
+        launch_cols_wm<S, NC, true, ST, 8>(ctx, sc, A);
+    else if (six)
+        launch_cols_wm<S, NC, false, ST, 6>(ctx, sc, A);
     else
-        launch_cols_wm<S, NC, false, ST, 8>(ctx, sc, pl, A);
+        launch_cols_wm<S, NC, false, ST, 8>(ctx, sc, A);
 }
-template <int S, int NC, class ST>
-static void launch_cols_f(bds_ctx *ctx, hipStream_t sc, const Plan2D &pl, int G, const void *Bw, float w0, float w1, int lo1,
-                          int hi1, int lo2, int hi2, const SieveOut &so, const CellList &cl, bool ilv) {
-    if (so.sieve.cellmax) return launch_cols_w<S, NC, ST>(ctx, sc, pl, G, Bw, w0, w1, lo1, hi1, lo2, hi2, so, cl, ilv);
-    if (pl.logT == 2)
-        launch_cols_ft<S, 4, NC, ST>(ctx, sc, pl, G, Bw, w0, w1, lo1, hi1, lo2, hi2, so, cl);
-    else
-        launch_cols_ft<S, 8, NC, ST>(ctx, sc, pl, G, Bw, w0, w1, lo1, hi1, lo2, hi2, so, cl);
-}
-// one group of cells: row pass, then column pass, on one stream
+// One group of cells: row pass, then column pass, on one stream, with the kernels of `pick`.  What only a launch knows is applied here:
+//  * a launch that reports per-tile records (pa.so.sieve.cellmax null: the second-peak pass of the host refinement) takes the tile kernel
+//    whatever the main search's column pass is -- the wave-private kernel's running bounds have nothing to run on there;
+//  * components are interleaved (pick.ilv) only in an unmasked launch of the wave-private pair; the 80 x 4096 pair interleaves always.
 template <int NC, class ST>
-static void launch_fast_f(bds_ctx *ctx, hipStream_t st_, const Plan2D &pl, const void *Xs, int G, int bin0, const void *Cs,
-                          void *Bw, float out_scale, float w0, float w1, int lo1, int hi1, int lo2, int hi2, const SieveOut &so,
-                          const CellList &cl = {}) {
-    // both components of an element side by side in the inter-pass buffer: the wave-private pair of the 768 x 4096 plan (cfg3),
-    // unmasked search (one lag range from 0), fp16 storage, two components
+static void launch_pair(bds_ctx *ctx, hipStream_t st_, const Plan2D &pl, const KernelPick &pick, const PairArgs &pa) {
+    const SieveOut &so = pa.so;
+    const int G = pa.G;
+    if (pick.rows == kRowsPlan) {  // run-time-plan kernels: fp32 storage, per-tile records, no lag mask beyond the two ranges
+        want_lds(ctx, k_rows_inv<NC>, kPlanLdsMax);
+        want_lds(ctx, k_cols_inv_max<NC>, kPlanLdsMax);
+        hipLaunchKernelGGL(k_rows_inv<NC>, dim3(pl.L1, G), dim3(pl.nt_rows), pl.lds_rows, st_, pl.p2, pl.twl, (const float2 *)pa.Xs, pl.L, pa.bin0,
+                           (const float2 *)pa.Cs, (float2 *)pa.Bw);
+        hipLaunchKernelGGL(k_cols_inv_max<NC>, dim3(pl.ntiles, G), dim3(pl.nt_cols), pl.lds_cols, st_, pl.p1, pl.L2, pl.logT, pl.Spad,
+                           (const float2 *)pa.Bw, pl.L, pa.w0, pa.w1, pa.lo1, pa.hi1, pa.lo2, pa.hi2, so.recs, pl.ntiles);
+        return;
+    }
     if constexpr (NC == 2 && std::is_same<ST, __half2>::value) {
-        if (pl.small) {  // 80 x 4096: wave-private row pass (components interleaved) + one lane per column and component
-            if (!cl.src) launch_rows_f<4096, NC, ST>(ctx, st_, pl, Xs, G, bin0, Cs, Bw, out_scale, cl, true);
+        if (pick.cols == kColsSmall) {  // 80 x 4096: wave-private row pass (components interleaved) + one lane per column and component
+            if (!pa.cl.src) launch_rows_f<4096, NC, ST>(ctx, st_, pl, pick, pa, true);
             if (so.mid) (void)hipEventRecord(so.mid, st_);
-            const SColsArgs A{(const float2 *)pl.d_tw80, pl.L2, G, Bw, pl.L, w0, w1, lo1, hi1, lo2, hi2, cl.rng, so.sieve, cl.src};
+            const SColsArgs A{(const float2 *)pl.d_tw80, pl.L2, G, pa.Bw, pl.L, pa.w0, pa.w1, pa.lo1, pa.hi1, pa.lo2, pa.hi2, pa.cl.rng, so.sieve, pa.cl.src};
             want_lds(ctx, k_cols_small_f<NC>, kSColsLdsBytes);
             hipLaunchKernelGGL((k_cols_small_f<NC>), dim3((unsigned)(G * (pl.L2 / (kSColsNT / 2)))), dim3(kSColsNT), kSColsLdsBytes, st_, A);
             return;
         }
     }
-    const bool ilv = NC == 2 && std::is_same<ST, __half2>::value && pl.L1 == 768 && pl.L2 == 4096 && ctx->tune.wrows != 0 &&
-                     so.sieve.cellmax && ctx->tune.ilv != 0 && !cl.rng && lo1 == 0 && lo2 > hi2;
+    const bool wave = pick.cols == kColsWave && so.sieve.cellmax;
+    // (the interleaved variants exist for the 768 x 4096 plan, two components, fp16 storage: what pick.ilv holds)
+    const bool ilv = pick.ilv && wave && pa.unmasked();
     switch (pl.L2) {
-        case 1280: launch_rows_f<1280, NC, ST>(ctx, st_, pl, Xs, G, bin0, Cs, Bw, out_scale, cl, false); break;
-        case 2048: launch_rows_f<2048, NC, ST>(ctx, st_, pl, Xs, G, bin0, Cs, Bw, out_scale, cl, false); break;
-        case 3072: launch_rows_f<3072, NC, ST>(ctx, st_, pl, Xs, G, bin0, Cs, Bw, out_scale, cl, false); break;
-        default: launch_rows_f<4096, NC, ST>(ctx, st_, pl, Xs, G, bin0, Cs, Bw, out_scale, cl, ilv); break;
+        case 1280: launch_rows_f<1280, NC, ST>(ctx, st_, pl, pick, pa, false); break;
+        case 2048: launch_rows_f<2048, NC, ST>(ctx, st_, pl, pick, pa, false); break;
+        case 3072: launch_rows_f<3072, NC, ST>(ctx, st_, pl, pick, pa, false); break;
+        default: launch_rows_f<4096, NC, ST>(ctx, st_, pl, pick, pa, ilv); break;
     }
     if (so.mid) (void)hipEventRecord(so.mid, st_);
-    hipStream_t sc = st_;
-    if (so.cols_stream) {
-        sc = so.cols_stream;
-        (void)hipEventRecord(so.ev_rows, st_);
-        (void)hipStreamWaitEvent(sc, so.ev_rows, 0);
-    }
+    const auto cols = [&](auto s_) {
+        constexpr int S = decltype(s_)::value;
+        if (wave)
+            launch_cols_w<S, NC, ST>(ctx, st_, pl, pick, pa, ilv);
+        else if (pl.logT == 2)
+            launch_cols_ft<S, 4, NC, ST>(ctx, st_, pl, pa);
+        else
+            launch_cols_ft<S, 8, NC, ST>(ctx, st_, pl, pa);
+    };
     switch (pl.L1) {
-        case 256: launch_cols_f<256, NC, ST>(ctx, sc, pl, G, Bw, w0, w1, lo1, hi1, lo2, hi2, so, cl, ilv); break;
-        case 512: launch_cols_f<512, NC, ST>(ctx, sc, pl, G, Bw, w0, w1, lo1, hi1, lo2, hi2, so, cl, ilv); break;
-        case 768: launch_cols_f<768, NC, ST>(ctx, sc, pl, G, Bw, w0, w1, lo1, hi1, lo2, hi2, so, cl, ilv); break;
-        default: launch_cols_f<1024, NC, ST>(ctx, sc, pl, G, Bw, w0, w1, lo1, hi1, lo2, hi2, so, cl, ilv); break;
+        case 256: cols(std::integral_constant<int, 256>{}); break;
+        case 512: cols(std::integral_constant<int, 512>{}); break;
+        case 768: cols(std::integral_constant<int, 768>{}); break;
+        default: cols(std::integral_constant<int, 1024>{}); break;
     }
-    if (so.cols_stream) (void)hipEventRecord(so.ev_cols, sc);
 }
 
 // inter-pass work buffer in float2-sized elements per transform length: the `group` cells of one launch pair at the storage type of
-// the search (fp16 complex: half an element) -- which is also what the forward pass of `group` bins needs at fp32 -- , twice that
-// when the column pass runs beside the next group's row pass (BDS_ACQ_OVERLAP).  (Rounds 1-5 kept two fp32-sized halves whatever
-// the mode: 20 GB at cfg3 where 5 are used -- and every GiB a context frees is a GiB the driver clears before the next user gets it.)
-static size_t bw_batches(const AcqState &a, const Tuning &tune) {
+// the search (fp16 complex: half an element) -- which is also what the forward pass of `group` bins needs at fp32.  (Rounds 1-5 kept two
+// fp32-sized halves whatever the mode: 20 GB at cfg3 where 5 are used -- and every GiB a context frees is a GiB the driver clears before
+// the next user gets it.)
+static size_t bw_batches(const AcqState &a) {
     const int per_cell = a.half ? 1 : 2;                                  // float2-sized elements per cell and two components
-    const int search = (a.group * a.ncomp * per_cell + 1) / 2 * (tune.overlap ? 2 : 1);
+    const int search = (a.group * a.ncomp * per_cell + 1) / 2;
     return (size_t)std::max(std::max(search, std::min(a.group, a.D > 0 ? a.D : a.group)), 8);
 }
 
@@ -1095,10 +1144,9 @@ extern "C" int bds_acq_prepare(bds_ctx *ctx, const bds_settings *s_in) {
     if (rc) return rc;
     AcqState &a = *ctx->acq;
     BDS_HIP(ctx, hipSetDevice(ctx->device));
-    if ((rc = set_lds_limits(ctx))) return rc;
     Plan2D &pl = a.plan;
     pick_group(a, *s);
-    if ((rc = ensure(ctx, &a.d_Bw, &a.bw_cap, bw_batches(a, ctx->tune) * (size_t)pl.L))) return rc;
+    if ((rc = ensure(ctx, &a.d_Bw, &a.bw_cap, bw_batches(a) * (size_t)pl.L))) return rc;
     {   // layout of the cached code spectra: the N-point plan's or the L-point plan's; a change drops the cache
         const NPointInfo want = npoint_info(pfa_pick(ctx, a, *s).kind);
         if (want.kind != a.cs_pfa) a.cs_slot.clear();
@@ -1133,12 +1181,11 @@ extern "C" int bds_acq_prepare(bds_ctx *ctx, const bds_settings *s_in) {
         a.cs_cap_slots = need_slots;
     }
     // conj(fft([table zeros]))/L per PRN and component (B2a/acquisition.m:175-184, B1C/acquisition.m:174-187)
-    const int chunk = (int)bw_batches(a, ctx->tune);
+    const bool perm = kernel_pick(ctx->tune, a, a.cs_pfa).permuted;  // (the order the search of this configuration reads them in)
     for (int prn : todo) {
         const int slot = (int)a.cs_slot.size();
         CodeLoader ld{a.tab, (prn - 1) * 2};
         // components of one PRN are adjacent code slots: batch index = component
-        (void)chunk;
         // half storage: the same byte buffer holds 4-byte elements, so offsets count in those
         float2 *cs_dst = a.half ? (float2 *)((__half2 *)a.d_Cs + (size_t)slot * a.ncomp * pl.L)
                                 : a.d_Cs + (size_t)slot * a.ncomp * pl.L;
@@ -1148,7 +1195,7 @@ extern "C" int bds_acq_prepare(bds_ctx *ctx, const bds_settings *s_in) {
                 P::forward(st(ctx), ld, a.ncomp, a.d_Bw, (uint32_t *)cs_dst, P::NP, 1, (float)((double)a.sC / (double)a.N), 0);
             });
             BDS_HIP(ctx, hipGetLastError());
-        } else if ((rc = forward(ctx, a, ld, a.ncomp, cs_dst, pl.L, 1, (float)((double)a.sC / (double)pl.L))))
+        } else if ((rc = forward(ctx, a, ld, a.ncomp, cs_dst, pl.L, 1, (float)((double)a.sC / (double)pl.L), perm)))
             return rc;
         a.cs_slot[prn] = slot;
     }
@@ -1290,7 +1337,9 @@ struct AcqRun {
     int P = 0, D = 0, G = 0, ncomp = 0;
     double f0 = 0, kDelta = 0;
     float w0 = 1.f, w1 = 1.f;
-    bool fsearch = false, wcols = false, multiprn = false, overlap = false;
+    KernelPick pick;           // the kernels of this run (kernel_pick) ...
+    bool fsearch = false, wcols = false;  // ... of which: pick.fast(), pick.per_cell()
+    bool multiprn = false;
     int pfa = 0;               // > 0: an N-point pair runs; the value = spectrum bins per Doppler step
     NPointInfo np;             // which one, and its sizes and properties (kind 0: none)
     int pfa_q = 1;             // a masked plan: pfa = p, pfa_q = q of the Doppler step of p / q bins
@@ -1305,11 +1354,9 @@ struct AcqRun {
     EventPool &evp;
     hipEvent_t ev0 = nullptr, ev1 = nullptr, ev2 = nullptr, ev3 = nullptr;
     hipEvent_t sa[kSamples], sb[kSamples], sm[kSamples];
-    hipEvent_t ev_rows[2] = {nullptr, nullptr}, ev_cols[2] = {nullptr, nullptr};
     int nsamp = 0;
     double samp_cells = 0;  // cells of the sampled multi-PRN pairs
     bool mids = false;  // the sampled pairs carry a mid event (fp32-arithmetic kernels)
-    size_t half_bytes = 0;  // one group of cells in the inter-pass buffer
     // the sieve's output and the decisions made on it
     int n_extra = 0;
     std::vector<Extra> h_extra;
@@ -1327,7 +1374,8 @@ struct AcqRun {
 
     int setup();        // sizes, work buffers, events, storage scales, the sieve's lists
     int forward_all();  // carrier wipe-off + forward transform of every Doppler bin
-    void launch_cells(int prn, int b0, int nb, Rec *recs, int lo1, int hi1, int lo2, int hi2, int cell0, hipEvent_t mid, int buf = -1);
+    void launch(PairArgs pa, Rec *recs, int cell0, hipEvent_t mid);  // one launch pair of the L-point search
+    void launch_cells(int prn, int b0, int nb, Rec *recs, int lo1, int hi1, int lo2, int hi2, int cell0, hipEvent_t mid);
     void launch_list(int ncells, Rec *recs, const CellList &cl, int cell0, hipEvent_t mid);
     int search();          // all (PRN, bin) cells: row pass + column pass per group
     int collect();         // row maxima + list to the host; can the sieve be trusted?
@@ -1360,7 +1408,7 @@ int AcqRun::setup() {
         // (a masked plan was admitted for the settings' PRN list: a run on a part of it has fewer cells, never more)
     }
     if (a.cs_pfa && !pfa) return fail(ctx, BDS_ERR_HIP, "internal: code spectra in the N-point layout for a run that cannot use them");
-    if ((rc = ensure(ctx, &a.d_Bw, &a.bw_cap, bw_batches(a, ctx->tune) * (size_t)pl.L))) return rc;
+    if ((rc = ensure(ctx, &a.d_Bw, &a.bw_cap, bw_batches(a) * (size_t)pl.L))) return rc;
     // (N-point pair: ONE signal spectrum, every row stored twice -- 2 N fp16 complex = N float2-sized elements)
     if ((rc = ensure(ctx, &a.d_Xs, &a.xs_cap, pfa ? (size_t)pfa_q * (size_t)np.np : (size_t)D * pl.L))) return rc;
 
@@ -1400,7 +1448,8 @@ int AcqRun::setup() {
         w0 *= inv;
         w1 *= inv;
     }
-    fsearch = (pl.fast || (pl.small && a.half) || pfa) && !a.no_fast_search;  // fp32-arithmetic specialised kernels (default)
+    pick = kernel_pick(tune, a, np.kind);
+    fsearch = pick.fast();  // fp32-arithmetic specialised kernels (default)
     // sieve tolerance: every lag within kDelta of a PRN's maximum is re-evaluated in f64.  fp32 storage (with the fp32 carrier / twiddle
     // rotations of the forward pass, round 4) errs by 5.3e-7 of the PRN maximum at worst against the f64 oracle (tools/sieve_error.py,
     // profiles/r05_sieve_error_small.txt: 19x inside its kDelta / 2 = 1e-5; checked at run time like the fp16 mode).  fp16 storage: three roundings lie between the exact value and the sieve's (signal spectrum, code spectrum,
@@ -1416,11 +1465,9 @@ int AcqRun::setup() {
         if (!a.d_extra_count) BDS_HIP(ctx, hipMalloc((void **)&a.d_extra_count, sizeof(int)));
         BDS_HIP(ctx, hipMemsetAsync(a.d_extra_count, 0, sizeof(int), stream()));
     }
-    // wave-private column pass (default for the fp32-arithmetic search): per-cell packed maxima and per-PRN running
-    // bounds instead of per-tile records
-    // (the 256-point plans keep the tile kernel unless forced with BDS_ACQ_WCOLS=1: a workgroup's share of such a tile is
-    //  8 points per lane and the per-workgroup constants and barriers dominate -- measured at cfg2 2.18 vs 1.39 ms per launch)
-    wcols = fsearch && (pfa || pl.small || (tune.wcols != 0 && (pl.L1 != 256 || tune.wcols > 0)));
+    // wave-private column pass (default for the fp32-arithmetic search), the 80 x 4096 plan's, an N-point plan's: per-cell packed
+    // maxima and per-PRN running bounds instead of per-tile records
+    wcols = pick.per_cell();
     so = SieveOut{};
     so.sieve.extra = a.d_extra, so.sieve.extra_count = a.d_extra_count, so.sieve.extra_cap = kExtraCap, so.sieve.keep = (float)(1.0 - kDelta);
     if (wcols) {
@@ -1501,15 +1548,6 @@ int AcqRun::setup() {
     if (pfa && !multiprn) multiprn = true, PB = 1, n_pairs_total = P, cells_per_pair = D;  // the N-point pair always runs on cell lists
     // (a masked plan was admitted because all cells fit one pair: the second-peak pass reads them there)
     if (np.masked) multiprn = true, PB = P, n_pairs_total = 1, cells_per_pair = (long)P * D;
-    // Overlapped passes (BDS_ACQ_OVERLAP=1, fp32-arithmetic kernels): group k's column pass runs on a second stream beside
-    // group k+1's row pass, the two working in different halves of the inter-pass buffer.
-    overlap = fsearch && tune.overlap && !multiprn;
-    if (overlap)
-        for (int i = 0; i < 2; ++i) {
-            BDS_HIP(ctx, evp.make(&ev_rows[i], hipEventDisableTiming));
-            BDS_HIP(ctx, evp.make(&ev_cols[i], hipEventDisableTiming));
-        }
-    half_bytes = (size_t)G * ncomp * pl.L * elem;
     return BDS_OK;
 }
 
@@ -1525,75 +1563,49 @@ int AcqRun::forward_all() {
         BDS_HIP(ctx, hipEventRecord(ev1, stream()));
         return BDS_OK;
     }
-    const int chunk = (int)bw_batches(a, ctx->tune);
+    const int chunk = (int)bw_batches(a);
     for (int b0 = 0; b0 < D; b0 += chunk) {
         const int nb = std::min(chunk, D - b0);
         SignalLoader ld{a.sview(), a.N, a.n_ext, f0, s->acqStep, 1.0 / a.fs, b0};
         float2 *xs_dst = a.half ? (float2 *)((__half2 *)a.d_Xs + (size_t)b0 * pl.L) : a.d_Xs + (size_t)b0 * pl.L;
-        if (int rc = forward(ctx, a, ld, nb, xs_dst, pl.L, 0, a.sX)) return rc;
+        if (int rc = forward(ctx, a, ld, nb, xs_dst, pl.L, 0, a.sX, pick.permuted)) return rc;
     }
     BDS_HIP(ctx, hipEventRecord(ev1, stream()));
     return BDS_OK;
 }
 
-// one group of cells of one PRN (consecutive bins b0 .. b0+nb-1, or one bin with lag ranges): both passes on the
-// main stream; cell0 = run-wide index of the first cell (list bookkeeping)
-void AcqRun::launch_cells(int prn, int b0, int nb, Rec *recs, int lo1, int hi1, int lo2, int hi2, int cell0, hipEvent_t mid, int buf) {
-    Plan2D &pl = a.plan;
-    const hipStream_t s_main = stream();
-    const size_t cs_off = (size_t)a.cs_slot[prn] * ncomp * pl.L;
-    SieveOut so1 = so;
-    so1.recs = recs;
-    so1.sieve.cell0 = cell0;
-    so1.mid = mid;
+// One launch pair of the L-point search on the main stream, with the kernels of `pick`: fills in what every pair of the run shares.
+// recs = where a per-tile column pass reports, cell0 = run-wide index of the first cell (list bookkeeping), mid = timing event
+// between the passes (or null)
+void AcqRun::launch(PairArgs pa, Rec *recs, int cell0, hipEvent_t mid) {
+    pa.Xs = a.d_Xs, pa.Bw = a.d_Bw, pa.out_scale = a.sB, pa.w0 = w0, pa.w1 = w1;
+    pa.so = so;
+    pa.so.recs = recs;
+    pa.so.sieve.cell0 = cell0;
+    pa.so.mid = mid;
     if (mid && fsearch) mids = true;
-    void *const Bw_ = buf > 0 ? (void *)((char *)a.d_Bw + half_bytes) : (void *)a.d_Bw;
-    if (buf >= 0) {
-        so1.cols_stream = (hipStream_t)ctx->stream2;
-        so1.ev_rows = ev_rows[buf];
-        so1.ev_cols = ev_cols[buf];
-    }
-    if (fsearch && a.half) {
-        const void *Ch = (const __half2 *)a.d_Cs + cs_off;
-        if (ncomp == 2)
-            launch_fast_f<2, __half2>(ctx, s_main, pl, a.d_Xs, nb, b0, Ch, Bw_, a.sB, w0, w1, lo1, hi1, lo2, hi2, so1);
-        else
-            launch_fast_f<1, __half2>(ctx, s_main, pl, a.d_Xs, nb, b0, Ch, Bw_, a.sB, w0, w1, lo1, hi1, lo2, hi2, so1);
-    } else if (fsearch) {
-        const void *Cf = a.d_Cs + cs_off;
-        if (ncomp == 2)
-            launch_fast_f<2, float2>(ctx, s_main, pl, a.d_Xs, nb, b0, Cf, Bw_, a.sB, w0, w1, lo1, hi1, lo2, hi2, so1);
-        else
-            launch_fast_f<1, float2>(ctx, s_main, pl, a.d_Xs, nb, b0, Cf, Bw_, a.sB, w0, w1, lo1, hi1, lo2, hi2, so1);
-    } else {
-        const float2 *Cs = a.d_Cs + cs_off;
-        dim3 gr(pl.L1, nb), gc(pl.ntiles, nb);
-        if (ncomp == 2) {
-            hipLaunchKernelGGL(k_rows_inv<2>, gr, dim3(pl.nt_rows), pl.lds_rows, s_main, pl.p2, pl.twl,
-                               (const float2 *)a.d_Xs, pl.L, b0, Cs, a.d_Bw);
-            hipLaunchKernelGGL(k_cols_inv_max<2>, gc, dim3(pl.nt_cols), pl.lds_cols, s_main, pl.p1, pl.L2, pl.logT,
-                               pl.Spad, (const float2 *)a.d_Bw, pl.L, w0, w1, lo1, hi1, lo2, hi2, recs, pl.ntiles);
-        } else {
-            hipLaunchKernelGGL(k_rows_inv<1>, gr, dim3(pl.nt_rows), pl.lds_rows, s_main, pl.p2, pl.twl,
-                               (const float2 *)a.d_Xs, pl.L, b0, Cs, a.d_Bw);
-            hipLaunchKernelGGL(k_cols_inv_max<1>, gc, dim3(pl.nt_cols), pl.lds_cols, s_main, pl.p1, pl.L2, pl.logT,
-                               pl.Spad, (const float2 *)a.d_Bw, pl.L, w0, w1, lo1, hi1, lo2, hi2, recs, pl.ntiles);
-        }
-    }
+    with_storage(a.half, ncomp, [&](auto st_, auto nc) {
+        launch_pair<decltype(nc)::value, typename decltype(st_)::type>(ctx, stream(), a.plan, pick, pa);
+    });
+}
+
+// one group of cells of one PRN: consecutive bins b0 .. b0+nb-1, or one bin with lag ranges
+void AcqRun::launch_cells(int prn, int b0, int nb, Rec *recs, int lo1, int hi1, int lo2, int hi2, int cell0, hipEvent_t mid) {
+    PairArgs pa;
+    pa.G = nb, pa.bin0 = b0;
+    pa.Cs = (const char *)a.d_Cs + (size_t)a.cs_slot[prn] * ncomp * a.plan.L * elem;
+    pa.lo1 = lo1, pa.hi1 = hi1, pa.lo2 = lo2, pa.hi2 = hi2;
+    launch(pa, recs, cell0, mid);
 }
 
 // cells described by a list (whole rows of several PRNs, or one (PRN, winning bin) cell per PRN)
 void AcqRun::launch_list(int ncells, Rec *recs, const CellList &cl, int cell0, hipEvent_t mid) {
-    Plan2D &pl = a.plan;
-    const hipStream_t s_main = stream();
-    SieveOut so1 = so;
-    so1.recs = recs;
-    so1.sieve.cell0 = cell0;
-    so1.mid = mid;
-    if (mid) mids = true;
-    const int hi1 = cl.rng ? -1 : (int)a.N - 1, lo2 = cl.rng ? 0 : 1, hi2 = cl.rng ? -1 : 0;
     if (pfa) {  // the N-point pair: every lag of the N is searched, the cells come as a list.  With lag ranges (a masked plan): the masked column
                 // pass alone on the cells cl.src names in the main search's buffer, or (no cl.src) behind a row pass of the listed cells
+        const hipStream_t s_main = stream();
+        SieveOut so1 = so;
+        so1.sieve.cell0 = cell0;
+        if (mid) mids = true;
         with_npoint(np.kind, [&](auto plan) {
             using P = decltype(plan);
             const auto lds = [&](auto kern, size_t bytes) { want_lds(ctx, kern, bytes); };
@@ -1615,17 +1627,11 @@ void AcqRun::launch_list(int ncells, Rec *recs, const CellList &cl, int cell0, h
         });
         return;
     }
-    if (a.half) {
-        if (ncomp == 2)
-            launch_fast_f<2, __half2>(ctx, s_main, pl, a.d_Xs, ncells, 0, a.d_Cs, a.d_Bw, a.sB, w0, w1, 0, hi1, lo2, hi2, so1, cl);
-        else
-            launch_fast_f<1, __half2>(ctx, s_main, pl, a.d_Xs, ncells, 0, a.d_Cs, a.d_Bw, a.sB, w0, w1, 0, hi1, lo2, hi2, so1, cl);
-    } else {
-        if (ncomp == 2)
-            launch_fast_f<2, float2>(ctx, s_main, pl, a.d_Xs, ncells, 0, a.d_Cs, a.d_Bw, a.sB, w0, w1, 0, hi1, lo2, hi2, so1, cl);
-        else
-            launch_fast_f<1, float2>(ctx, s_main, pl, a.d_Xs, ncells, 0, a.d_Cs, a.d_Bw, a.sB, w0, w1, 0, hi1, lo2, hi2, so1, cl);
-    }
+    PairArgs pa;
+    pa.G = ncells, pa.Cs = a.d_Cs, pa.cl = cl;
+    pa.hi1 = (int)a.N - 1;                               // every lag ...
+    if (cl.rng) pa.hi1 = -1, pa.lo2 = 0, pa.hi2 = -1;    // ... or the list's ranges
+    launch(pa, recs, cell0, mid);
 }
 
 int AcqRun::search() {
@@ -1633,8 +1639,8 @@ int AcqRun::search() {
     const hipStream_t s_main = stream();
     int rc;
     const long sample_every = std::max<long>(1, n_pairs_total / kSamples);
-    long pair_idx = 0, group_idx = 0;
-    if (!multiprn && (rc = ensure_fit(ctx, &a.d_Bw, &a.bw_cap, bw_batches(a, ctx->tune) * (size_t)pl.L))) return rc;  // (gives a larger budget's buffer back)
+    long pair_idx = 0;
+    if (!multiprn && (rc = ensure_fit(ctx, &a.d_Bw, &a.bw_cap, bw_batches(a) * (size_t)pl.L))) return rc;  // (gives a larger budget's buffer back)
     if (multiprn) {
         // float2-sized elements the PB*D cells of one launch pair occupy; if the device cannot give that much after all (another
         // process took it since setup() asked), halve the PRNs per pair
@@ -1643,7 +1649,7 @@ int AcqRun::search() {
             // (BDS_ACQ_TEST_PAIR_NOMEM of the hooks build: the first n allocations are taken to have failed)
             if (tries < ctx->tune.test_pair_nomem && PB > 2)
                 rc = BDS_ERR_NOMEM;
-            else if (!(rc = ensure_fit(ctx, &a.d_Bw, &a.bw_cap, std::max(need, bw_batches(a, ctx->tune) * (size_t)pl.L))))
+            else if (!(rc = ensure_fit(ctx, &a.d_Bw, &a.bw_cap, std::max(need, bw_batches(a) * (size_t)pl.L))))
                 break;
             if (PB <= 2) return rc;
             (void)hipGetLastError();  // (the failed hipMalloc is handled here: it must not surface at the end of the search)
@@ -1707,20 +1713,15 @@ int AcqRun::search() {
         }
     } else {
         for (int pi = 0; pi < P; ++pi) {
-            for (int b0 = 0; b0 < D; b0 += G, ++pair_idx, ++group_idx) {
+            for (int b0 = 0; b0 < D; b0 += G, ++pair_idx) {
                 const int nb = std::min(G, D - b0);
-                const int buf = overlap ? (int)(group_idx & 1) : -1;
-                // the row pass of group k re-uses the buffer half the column pass of group k-2 read
-                if (overlap && group_idx >= 2) BDS_HIP(ctx, hipStreamWaitEvent(s_main, ev_cols[buf], 0));
-                const bool sample = !overlap && nb == G && (pair_idx % sample_every) == 0 && nsamp < kSamples;
+                const bool sample = nb == G && (pair_idx % sample_every) == 0 && nsamp < kSamples;
                 if (sample) BDS_HIP(ctx, hipEventRecord(sa[nsamp], s_main));
                 launch_cells(prns[pi], b0, nb, wcols ? nullptr : a.d_recs + ((size_t)pi * D + b0) * pl.ntiles, 0, (int)a.N - 1, 1, 0,
-                             pi * D + b0, sample ? sm[nsamp] : nullptr, buf);
+                             pi * D + b0, sample ? sm[nsamp] : nullptr);
                 if (sample) BDS_HIP(ctx, hipEventRecord(sb[nsamp++], s_main));
             }
         }
-        if (overlap)  // join: everything after this is ordered on the main stream again
-            for (int i = 0; i < 2 && i < group_idx; ++i) BDS_HIP(ctx, hipStreamWaitEvent(s_main, ev_cols[i], 0));
     }
     BDS_HIP(ctx, hipGetLastError());
     if (!wcols)
@@ -1773,7 +1774,7 @@ int AcqRun::finish() {
         BDS_HIP(ctx, hipDeviceGetAttribute(&wall_khz, hipDeviceAttributeWallClockRate, ctx->device));
         if (h[1] + h[3]) t.shader_clock_GHz = (double)(h[0] + h[2]) / (double)(h[1] + h[3]) * wall_khz * 1e-6;
     }
-    // overlapped passes: the average launch-pair duration is the search time over the pair count
+    // (no pair was sampled: the average launch-pair duration is the search time over the pair count)
     t.cell_pair_ms = nsamp ? acc / nsamp : (n_pairs_total ? t.search_ms / (double)n_pairs_total : 0);
     t.cells_per_pair = samp_cells > 0 && nsamp ? samp_cells / nsamp : (double)cells_per_pair;
     t.n_pairs = n_pairs_total;
@@ -1786,13 +1787,10 @@ int AcqRun::finish() {
     t.plan_l1 = pfa ? np.rows : pl.L1;
     t.plan_l2 = pfa ? np.k3 : pl.L2;
     t.refine_path = dev_refined ? 1 : 0;
-    {
-        const bool wrows_on = fsearch && a.half && pl.L2 == 4096 && (tune.wrows != 0 || pl.small);
-        t.rows_kernel = !fsearch ? 0 : pfa ? 3 : wrows_on ? 2 : 1;
-        t.cols_kernel = !fsearch ? 0 : pfa ? 4 : pl.small ? 3 : wcols ? 2 : 1;
-        const bool ilv_on = wrows_on && wcols && ncomp == 2 && ((pl.L1 == 768 && tune.ilv != 0) || pl.small);
-        t.kernel_flags = (ilv_on ? 1 : 0) | (wrows_on && tune.pk != 0 ? 2 : 0);
-    }
+    // what ran: the pick, as the numbers of include/bds_mi355x.h (the enumerators are those numbers)
+    t.rows_kernel = pick.rows;
+    t.cols_kernel = pick.cols;
+    t.kernel_flags = (pick.ilv ? 1 : 0) | (pick.pk_rows ? 2 : 0);
     return BDS_OK;
 }
 

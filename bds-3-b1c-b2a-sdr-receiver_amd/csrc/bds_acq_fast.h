@@ -28,7 +28,8 @@ __device__ __forceinline__ void st_c(__half2 *p, long i, float2 v) { p[i] = __fl
 // its workgroup -- wave w = t / 64, lane (ql = t & 3, bl = (t & 63) >> 2), q' = 4 w + ql -- multiplies the sixteen elements
 // e = 16 bl + q' + 256 bh, bh = 0 .. 15.  Stored at [16 t + bh] they are 64 contiguous bytes per thread and 4 KB per wave:
 // four 16-byte loads per lane and row instead of sixteen 4-byte ones in 16-byte pieces.  The forward row pass writes the rows
-// of the signal and code spectra in this order whenever the search will run that kernel (spectra_permuted() in bds_acq.hip).
+// of the signal and code spectra in this order exactly when the search runs that kernel: KernelPick::permuted, which kernel_pick() in
+// bds_acq.hip derives from its own choice of the row pass.
 __host__ __device__ __forceinline__ constexpr int wrows_perm(int e) {
     const int bh = e >> 8, r = e & 255, bl = r >> 4, qp = r & 15;
     const int t = 64 * (qp >> 2) + 4 * bl + (qp & 3);

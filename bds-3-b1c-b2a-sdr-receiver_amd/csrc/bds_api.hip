@@ -125,7 +125,6 @@ Tuning tuning_from_env() {
     t.pbcells = std::max(0, geti("BDS_ACQ_PBCELLS", 0));
     if (const char *e = std::getenv("BDS_ACQ_PBCAP_GB")) t.pbcap_gb = std::atof(e);
     t.rows_grid = std::max(0, geti("BDS_ACQ_ROWS_GRID", 0));
-    t.overlap = has("BDS_ACQ_OVERLAP");
     t.no_bwreuse = has("BDS_ACQ_NO_BWREUSE");
     t.list_gc = std::max(-1, geti("BDS_ACQ_LIST_GC", 0));
     if (const char *e = std::getenv("BDS_ACQ_KDELTA")) t.kdelta = std::max(0.0, std::min(0.9, std::atof(e)));

@@ -45,7 +45,6 @@ struct Tuning {
     int rows_grid = 0;                  // BDS_ACQ_ROWS_GRID: workgroups of the (then persistent) row pass; 0 = one per item
     int list_gc = 0;                    // BDS_ACQ_LIST_GC: cells one row workgroup walks in a multi-PRN launch pair (a divisor of D; 0 = chosen by the launch's size -- an N-point plan with Plan::kChunkList then takes the tapered chunk list of rows_chunk_plan instead --, -1 = all D bins of its PRN)
     bool no_bwreuse = false;            // BDS_ACQ_NO_BWREUSE: the B2a second-peak pass runs its own row pass (A/B, tests)
-    bool overlap = false;               // BDS_ACQ_OVERLAP: column pass of group k on a second stream beside the row pass of group k+1
     double kdelta = 0;                  // BDS_ACQ_KDELTA: test hook, sieve tolerance override (0 = per-mode default)
     bool no_selfcheck = false;          // BDS_ACQ_NO_SELFCHECK: timing experiments with invalid results (no re-run)
     bool test_force_fallback = false;   // BDS_ACQ_TEST_FORCE_FALLBACK: test hook, take the fp16 -> fp32 storage re-run
@@ -110,7 +109,7 @@ int unpack_cplx_device(bds_ctx *ctx, const uint8_t *d_in, size_t n_bytes, int8_t
 struct bds_ctx {
     int device = 0;
     void *stream = nullptr;   // hipStream_t: everything is ordered on this stream ...
-    void *stream2 = nullptr;  // ... except the search's column pass, which overlaps the next row pass
+    void *stream2 = nullptr;  // ... except what runs beside it: the loader of a streamed tracking span (bds_track.hip), the generator of bds_synth_file (bds_synth.hip)
     std::string err;
     std::string devname;
     bds::AcqState *acq = nullptr;

@@ -264,6 +264,64 @@ def test_both_row_pass_kernels_on_4096_point_rows(ctx, monkeypatch, sig):
         ctx.reload_tuning()
 
 
+# environment -> (rows_kernel, cols_kernel, kernel_flags) of bds_timing on the forced 768 x 4096 plan, B1C with both components
+KERNELS_768x4096 = [
+    ({}, (2, 2, 3)),
+    ({"BDS_ACQ_NOMULTI": "1"}, (2, 2, 3)),  # (one PRN's cells per launch pair, no cell list)
+    ({"BDS_ACQ_PK": "0"}, (2, 2, 1)),
+    ({"BDS_ACQ_PK": "2"}, (2, 2, 3)),       # (packed butterflies in the row pass only: the flag is the row pass's)
+    ({"BDS_ACQ_ILV": "0"}, (2, 2, 2)),
+    ({"BDS_ACQ_PK": "0", "BDS_ACQ_ILV": "0"}, (2, 2, 0)),
+    ({"BDS_ACQ_WROWS": "0"}, (1, 2, 0)),
+    ({"BDS_ACQ_WCOLS": "0"}, (2, 1, 2)),
+    ({"BDS_ACQ_FP16": "0"}, (1, 2, 0)),
+]
+
+
+def test_reported_kernels_on_the_768x4096_plan(ctx, monkeypatch):
+    """The wave-private pair of the 768 x 4096 plan has an interleaved and a packed variant of each pass, chosen by the tuning knobs;
+    at a small grid (3 PRNs x 5 bins on a forced plan) every choice runs against the oracle, and the timing record names the kernels
+    and variants that ran.  The last row is B2a on the same plan: its two components (data and pilot) are interleaved like B1C's."""
+    from helpers import spc_of
+    from bds_amd import synth
+    monkeypatch.setenv("BDS_ACQ_FORCE_L1L2", "768x4096")
+    fs = 10.1e6
+    s1 = bds_amd.init_settings_b1c(samplingFreq=fs, IF=2.5e6, acqSatelliteList=[7, 19, 33], acqSearchBand=200, acqStep=100)
+    s2 = bds_amd.init_settings_b2a(samplingFreq=fs, IF=2.5e6, acqSatelliteList=[7, 19, 33], acqSearchBand=600, acqStep=200,
+                                   fineNoncoh=4)
+    cases = {}
+    for name, s, fn, n_codes in (("b1c", s1, oacq.acquisition_b1c, 3), ("b2a", s2, oacq.acquisition_b2a, 7)):
+        spc = spc_of(s)
+        sats = [synth.Sat(19, 130.0, 0.41 * spc, 0.7, 47.0), synth.Sat(33, -90.0, 0.83 * spc, 2.2, 45.0)]
+        x = synth.make_if(s, sats, n_codes * spc, seed=77)
+        cases[name] = (s, x, fn(x.astype(np.float64), s))
+    try:
+        for sig, env, want in [("b1c", e, w) for e, w in KERNELS_768x4096] + [("b2a", {}, (2, 2, 3))]:
+            s, x, ref = cases[sig]
+            for k, v in env.items():
+                monkeypatch.setenv(k, v)
+            c2 = bds_amd.native.Context(0)
+            try:
+                c2.acq_load(s, x)
+                c2.acq_prepare(s)
+                carr, cph, pm, det = c2.acq_run(s)
+                tm = c2.timing()
+            finally:
+                c2.close()
+            for k in env:
+                monkeypatch.delenv(k)
+            what = f"{sig} {env}"
+            print(what, int(tm["fft_len"]), (int(tm["rows_kernel"]), int(tm["cols_kernel"]), int(tm["kernel_flags"])))
+            assert tm["fft_len"] == 768 * 4096, what
+            np.testing.assert_array_equal(cph, ref.codePhase, err_msg=what)
+            np.testing.assert_array_equal(carr, ref.carrFreq, err_msg=what)
+            np.testing.assert_allclose(pm, ref.peakMetric, rtol=1e-6, atol=0, err_msg=what)
+            assert (tm["rows_kernel"], tm["cols_kernel"], tm["kernel_flags"]) == want, what
+    finally:
+        monkeypatch.delenv("BDS_ACQ_FORCE_L1L2")
+        ctx.reload_tuning()
+
+
 def test_data_type_other_than_schar_is_rejected(ctx):
     """settings.dataType (fread(fid, ..., settings.dataType), B2a/tracking.m:237-238): only int8 records."""
     s, x, _ = cfg1_b2a()
