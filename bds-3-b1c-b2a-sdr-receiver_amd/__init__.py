@@ -11,6 +11,7 @@ Host-side mirror of the reference's MATLAB call surface
     probe_data(settings) / probe_data(fileName, settings)       include/probeData.m (the numbers; also arrays and device tensors)
     frame_sync(trackResults, settings)                          include/BCNAV?decoding.m, the correlators
     nav_decode(trackResults, settings)                          include/BCNAV?decoding.m + ephemeris.m: eph, firstSubFrame, TOW
+    navSolutions, eph = post_navigation(trackResults, settings) postNavigation.m: pseudoranges, satellite and receiver positions
 
 All numeric work happens in ``libbds_mi355x.so`` (HIP kernels for gfx950) through
 the C ABI of ``include/bds_mi355x.h``; there is no CPU fallback.
@@ -23,4 +24,5 @@ from .distributed import shard_prns, shard_joint, sharded_acquisition, sharded_a
 from .probedata import probe_data, ProbeResult  # noqa: F401
 from .corrfn import corr_function, track_states  # noqa: F401
 from .navdecode import nav_decode, BCNAV1decoding, BCNAV2decoding  # noqa: F401
+from .pvt import post_navigation, postNavigation, pvt_plan, pvt_measure, pvt_solve  # noqa: F401
 from . import native, synth  # noqa: F401

@@ -7,6 +7,7 @@ if the library is missing or no GPU is visible the calls raise.
 from __future__ import annotations
 
 import ctypes as C
+import math
 import os
 
 import numpy as np
@@ -115,6 +116,23 @@ class Eph(C.Structure):
                  ("idValid", C.c_int32 * 8)] + [(f, C.c_double) for f in EPH_FIELDS])
 
 
+# bds_pvt_params / bds_pvt_out and the BDS_PVT_* flags of bds_pvt_plan's ready list (include/bds_mi355x.h)
+PVT_READY, PVT_IDLE, PVT_NO_EPH, PVT_NO_SATTYPE, PVT_NO_FRAME = 1, 2, 4, 8, 16
+PVT_SETTINGS = ["navSolPeriod", "elevationMask", "useTropCorr", "c", "startOffset"]
+PVT_CHANNEL_FIELDS = ["PRN", "el", "az", "transmitTime", "satClkCorr", "rawP", "correctedP"]  # [n_ch, n_meas]
+PVT_EPOCH_FIELDS = ["X", "Y", "Z", "dt", "localTime", "currMeasSample", "latitude", "longitude", "height"]  # [n_meas]; DOP is [5, n_meas]
+
+
+class PvtParams(C.Structure):
+    _fields_ = [("size", C.c_uint32), ("useTropCorr", C.c_int32), ("navSolPeriod", C.c_double), ("elevationMask", C.c_double),
+                ("c", C.c_double), ("startOffset", C.c_double)]
+
+
+class PvtOut(C.Structure):
+    _fields_ = ([("size", C.c_uint32), ("cap", C.c_int32)]
+                + [(f, C.POINTER(C.c_double)) for f in PVT_CHANNEL_FIELDS + ["DOP"] + PVT_EPOCH_FIELDS])
+
+
 class ProbeOut(C.Structure):
     _fields_ = ([("hist_i", C.POINTER(C.c_int64)), ("hist_q", C.POINTER(C.c_int64))]
                 + [(f"{k}_{c}", C.c_int64) for c in "iq" for k in ("min", "max", "sum", "sumsq")]
@@ -143,6 +161,7 @@ EXPORTS = [
     "bds_probe_data", "bds_probe_data_file", "bds_probe_set_piece_segments",
     "bds_corr_function", "bds_corr_function_mem",
     "bds_nav_decode", "bds_nav_fields",
+    "bds_pvt_plan", "bds_pvt_measure", "bds_pvt_solve", "bds_post_navigation",
 ]
 # the entries marked BDS_DEV_API in the header: their record pointer is device memory (device_span below makes it)
 DEVICE_EXPORTS = ["bds_synth_dev", "bds_acq_load_dev", "bds_track_dev", "bds_track_open_dev", "bds_track_feed_dev"]
@@ -249,6 +268,14 @@ def lib():
     L.bds_nav_decode.restype = i32
     L.bds_nav_decode.argtypes = [vp, SP, i32, _IP, _DP, _DP, i32, C.POINTER(NavFrame), _IP, i32, C.POINTER(Eph), _DP, _DP]
     L.bds_nav_fields.restype, L.bds_nav_fields.argtypes = i32, [i32, C.POINTER(C.c_uint8), i32, i32, C.POINTER(Eph)]
+    PP, EP, dbl = C.POINTER(PvtParams), C.POINTER(Eph), C.c_double
+    L.bds_pvt_plan.restype, L.bds_pvt_plan.argtypes = i32, [SP, PP, i32, i32, C.c_char_p, _DP, EP, _DP, _DP, _IP, _DP, _DP, _DP]
+    L.bds_pvt_measure.restype = i32
+    L.bds_pvt_measure.argtypes = [vp, SP, i32, i32, _IP, _DP, _DP, _DP, EP, _DP, _DP, dbl, dbl, i32, _DP, _DP, _DP]
+    L.bds_pvt_solve.restype = i32
+    L.bds_pvt_solve.argtypes = [SP, PP, i32, i32, _IP, _IP, dbl, dbl, _DP, _DP, _DP, C.POINTER(PvtOut)]
+    L.bds_post_navigation.restype = i32
+    L.bds_post_navigation.argtypes = [vp, SP, PP, i32, i32, C.c_char_p, _IP, _DP, _DP, _DP, EP, _DP, _DP, _IP, _IP, C.POINTER(PvtOut)]
     L.bds_unpack_cplx.restype, L.bds_unpack_cplx.argtypes = i32, [vp, C.POINTER(C.c_uint8), C.c_size_t, C.POINTER(C.c_int8)]
     L.bds_unpack_cplx_file.restype, L.bds_unpack_cplx_file.argtypes = i32, [vp, C.c_char_p, C.c_char_p]
     L.bds_resample_plan.restype, L.bds_resample_plan.argtypes = i32, [SP, _DP, _DP, _DP]
@@ -610,6 +637,99 @@ def eph_dict(e: Eph) -> dict:
     d = {"flag": int(e.flag), "SatType": int(e.SatType), "n_entered": int(e.n_entered), "idValid": np.array(e.idValid, dtype=np.int32)}
     d.update((f, float(getattr(e, f))) for f in EPH_FIELDS)
     return d
+
+
+def eph_array(ephs):
+    """bds_eph[len(ephs)] from eph dicts (eph_dict's layout; a missing name is NaN, a missing counter 0) or None (nothing decoded)."""
+    arr = (Eph * max(1, len(ephs)))()
+    for e, d in zip(arr, ephs):
+        e.size = C.sizeof(Eph)
+        d = d or {}
+        e.flag, e.SatType, e.n_entered = int(d.get("flag", 0)), int(d.get("SatType", 0)), int(d.get("n_entered", 0))
+        for k, v in enumerate(np.asarray(d.get("idValid", np.zeros(8)), dtype=np.int64)[:8]):
+            e.idValid[k] = int(v)
+        for f in EPH_FIELDS:
+            setattr(e, f, float(d.get(f, math.nan)))
+    return arr
+
+
+def pack_pvt_params(s) -> PvtParams:
+    """The settings postNavigation reads besides bds_settings -> bds_pvt_params; a missing one is an error naming it."""
+    p = PvtParams()
+    p.size = C.sizeof(PvtParams)
+    for name in PVT_SETTINGS:
+        if not hasattr(s, name):
+            raise AttributeError(f"settings.{name} is missing")
+        setattr(p, name, int(getattr(s, name)) if name == "useTropCorr" else float(getattr(s, name)))
+    return p
+
+
+def _status_bytes(status, n_ch):
+    st = "".join(str(x)[:1] or "-" for x in status) if not isinstance(status, (str, bytes)) else status
+    st = st.encode() if isinstance(st, str) else bytes(st)
+    if len(st) != n_ch:
+        raise ValueError(f"pvt: {n_ch} channels, {len(st)} status characters")
+    return st
+
+
+def _series(a, shape, what):
+    a = np.ascontiguousarray(a, dtype=np.float64)
+    if a.shape != shape:
+        raise ValueError(f"pvt: {what} is {a.shape}, not {shape}")
+    return a
+
+
+def _pvt_out(n_ch, cap):
+    """(bds_pvt_out over fresh arrays, the arrays by name)."""
+    arrays = {f: np.zeros((n_ch, cap)) for f in PVT_CHANNEL_FIELDS}
+    arrays["DOP"] = np.zeros((5, cap))
+    arrays.update((f, np.zeros(cap)) for f in PVT_EPOCH_FIELDS)
+    o = PvtOut()
+    o.size, o.cap = C.sizeof(PvtOut), cap
+    for f, a in arrays.items():
+        setattr(o, f, a.ctypes.data_as(_DP))
+    return o, arrays
+
+
+def pvt_plan(settings, status, absolute_sample, ephs, sub_frame_start, tow) -> dict:
+    """bds_pvt_plan (no GPU): status characters [n_ch], absoluteSample [n_ch, n], eph dicts, subFrameStart and TOW [n_ch] ->
+    {"ready" (BDS_PVT_* flags per channel), "sampleStart", "sampleEnd", "measSampleStep", "n_meas"}."""
+    cs, pp = pack_settings(settings), pack_pvt_params(settings)
+    a = np.ascontiguousarray(absolute_sample, dtype=np.float64)
+    if a.ndim != 2:
+        raise ValueError("pvt_plan: absoluteSample is [n_ch, n]")
+    n_ch, n = a.shape
+    sfs, tw = _series(sub_frame_start, (n_ch,), "subFrameStart"), _series(tow, (n_ch,), "TOW")
+    if len(ephs) != n_ch:
+        raise ValueError(f"pvt_plan: {n_ch} channels, {len(ephs)} ephemerides")
+    ready = np.zeros(n_ch, dtype=np.int32)
+    v = np.zeros(3)
+    rc = lib().bds_pvt_plan(C.byref(cs), C.byref(pp), n_ch, n, _status_bytes(status, n_ch), a.ctypes.data_as(_DP), eph_array(ephs),
+                            sfs.ctypes.data_as(_DP), tw.ctypes.data_as(_DP), ready.ctypes.data_as(_IP),
+                            v[0:].ctypes.data_as(_DP), v[1:].ctypes.data_as(_DP), v[2:].ctypes.data_as(_DP))
+    if rc < 0:
+        raise BdsError(rc, "bds_pvt_plan: an argument, the settings, or absoluteSample not strictly increasing on a ready channel")
+    return {"ready": ready, "sampleStart": float(v[0]), "sampleEnd": float(v[1]), "measSampleStep": float(v[2]), "n_meas": rc}
+
+
+def pvt_solve(settings, prns, ready, sample_start, meas_sample_step, transmit_time, sat_pos, sat_clk_corr) -> dict:
+    """bds_pvt_solve (no GPU): the measure stage's arrays ([n_meas, n_ch], [n_meas, n_ch, 3], [n_meas, n_ch]) -> the arrays of
+    navSolutions by name ([n_ch, n_meas], DOP [5, n_meas], [n_meas])."""
+    cs, pp = pack_settings(settings), pack_pvt_params(settings)
+    tt = np.ascontiguousarray(transmit_time, dtype=np.float64)
+    if tt.ndim != 2:
+        raise ValueError("pvt_solve: transmitTime is [n_meas, n_ch]")
+    n_meas, n_ch = tt.shape
+    sp, ck = _series(sat_pos, (n_meas, n_ch, 3), "satPos"), _series(sat_clk_corr, (n_meas, n_ch), "satClkCorr")
+    prn, rd = np.ascontiguousarray(prns, dtype=np.int32), np.ascontiguousarray(ready, dtype=np.int32)
+    if prn.shape != (n_ch,) or rd.shape != (n_ch,):
+        raise ValueError(f"pvt_solve: {n_ch} channels, {prn.size} PRNs, {rd.size} ready flags")
+    o, arrays = _pvt_out(n_ch, n_meas)
+    rc = lib().bds_pvt_solve(C.byref(cs), C.byref(pp), n_ch, n_meas, prn.ctypes.data_as(_IP), rd.ctypes.data_as(_IP), float(sample_start),
+                             float(meas_sample_step), tt.ctypes.data_as(_DP), sp.ctypes.data_as(_DP), ck.ctypes.data_as(_DP), C.byref(o))
+    if rc < 0:
+        raise BdsError(rc, "bds_pvt_solve")
+    return arrays
 
 
 def nav_frame_dict(f: NavFrame, signal) -> dict:
@@ -977,6 +1097,56 @@ class Context:
         return [{"frames": [nav_frame_dict(frames[c * cap + k], cs.signal) for k in range(min(cap, int(cnt[c])))],
                  "n_frames": int(cnt[c]), "eph": eph_dict(eph[c]), "firstSubFrame": float(first[c]), "TOW": float(tow[c])}
                 for c in range(n_ch)]
+
+    def pvt_measure(self, settings, ready, absolute_sample, code_freq, rem_code_phase, ephs, sub_frame_start, tow, sample_start,
+                    meas_sample_step, n_meas):
+        """bds_pvt_measure: the three series [n_ch, n] -> (transmitTime [n_meas, n_ch], satPos [n_meas, n_ch, 3], satClkCorr
+        [n_meas, n_ch]); NaN on a channel that is not ready."""
+        cs = pack_settings(settings)
+        a = np.ascontiguousarray(absolute_sample, dtype=np.float64)
+        if a.ndim != 2:
+            raise ValueError("pvt_measure: absoluteSample is [n_ch, n]")
+        n_ch, n = a.shape
+        cf, rp = _series(code_freq, a.shape, "codeFreq"), _series(rem_code_phase, a.shape, "remCodePhase")
+        sfs, tw = _series(sub_frame_start, (n_ch,), "subFrameStart"), _series(tow, (n_ch,), "TOW")
+        rd = np.ascontiguousarray(ready, dtype=np.int32)
+        if rd.shape != (n_ch,) or len(ephs) != n_ch:
+            raise ValueError(f"pvt_measure: {n_ch} channels, {rd.size} ready flags, {len(ephs)} ephemerides")
+        n_meas = int(n_meas)
+        tt, sp, ck = np.zeros((n_meas, n_ch)), np.zeros((n_meas, n_ch, 3)), np.zeros((n_meas, n_ch))
+        self._check(self._lib.bds_pvt_measure(self._h, C.byref(cs), n_ch, n, rd.ctypes.data_as(_IP), a.ctypes.data_as(_DP),
+                                              cf.ctypes.data_as(_DP), rp.ctypes.data_as(_DP), eph_array(ephs), sfs.ctypes.data_as(_DP),
+                                              tw.ctypes.data_as(_DP), float(sample_start), float(meas_sample_step), n_meas,
+                                              tt.ctypes.data_as(_DP), sp.ctypes.data_as(_DP), ck.ctypes.data_as(_DP)))
+        return tt, sp, ck
+
+    def post_navigation(self, settings, status, prns, absolute_sample, code_freq, rem_code_phase, ephs, sub_frame_start, tow):
+        """bds_post_navigation: plan, measure, solve -> (the arrays of navSolutions by name, or None when there is no solution;
+        the ready flags per channel)."""
+        cs, pp = pack_settings(settings), pack_pvt_params(settings)
+        a = np.ascontiguousarray(absolute_sample, dtype=np.float64)
+        if a.ndim != 2:
+            raise ValueError("post_navigation: absoluteSample is [n_ch, n]")
+        n_ch, n = a.shape
+        cf, rp = _series(code_freq, a.shape, "codeFreq"), _series(rem_code_phase, a.shape, "remCodePhase")
+        sfs, tw = _series(sub_frame_start, (n_ch,), "subFrameStart"), _series(tow, (n_ch,), "TOW")
+        prn = np.ascontiguousarray(prns, dtype=np.int32)
+        if prn.shape != (n_ch,) or len(ephs) != n_ch:
+            raise ValueError(f"post_navigation: {n_ch} channels, {prn.size} PRNs, {len(ephs)} ephemerides")
+        st, eph = _status_bytes(status, n_ch), eph_array(ephs)
+        # the capacity: what the plan can give at most, (last - first sample) / step
+        step = math.trunc(cs.samplingFreq * pp.navSolPeriod / 1000)
+        cap = max(1, int((np.nanmax(a) - np.nanmin(a)) // step) + 1) if step >= 1 and np.isfinite(a).any() else 1
+        o, arrays = _pvt_out(n_ch, cap)
+        ready = np.zeros(n_ch, dtype=np.int32)
+        n_meas = C.c_int32(0)
+        rc = self._lib.bds_post_navigation(self._h, C.byref(cs), C.byref(pp), n_ch, n, st, prn.ctypes.data_as(_IP), a.ctypes.data_as(_DP),
+                                           cf.ctypes.data_as(_DP), rp.ctypes.data_as(_DP), eph, sfs.ctypes.data_as(_DP),
+                                           tw.ctypes.data_as(_DP), ready.ctypes.data_as(_IP), C.byref(n_meas), C.byref(o))
+        self._check(rc)
+        if rc == 0:
+            return None, ready
+        return {f: np.ascontiguousarray(v[..., :rc]) for f, v in arrays.items()}, ready
 
     def unpack_cplx(self, data):
         """bds_unpack_cplx: uint8[n] packed samples -> int8[4n] I/Q pairs (unpack_cplx.m)."""

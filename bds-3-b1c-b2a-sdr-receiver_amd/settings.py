@@ -5,8 +5,10 @@ Field names, meanings and defaults follow
   B2a: BDS-3_B2a/initSettings.m:44-130
 (the reference keeps one ``initSettings.m`` per receiver directory; here the
 extra field ``signal`` ('B1C' | 'B2A') says which receiver the struct belongs
-to).  Only the fields the acquisition/tracking path reads are kept
-(SURVEY.md Appendix D); PVT / plot settings are out of scope.
+to).  The fields the acquisition / tracking path reads
+and the navigation-solution settings that postNavigation reads (navSolPeriod,
+elevationMask, useTropCorr, c, startOffset) are kept; plot settings are out of
+scope.
 """
 from __future__ import annotations
 
@@ -57,6 +59,11 @@ def init_settings_b1c(**overrides) -> Settings:
         pllNoiseBandwidth=12,
         intTime=0.01,
         CNoInterval=50,
+        navSolPeriod=200,
+        elevationMask=5,
+        useTropCorr=1,
+        c=299792458,
+        startOffset=68.802,
     )
     s.__dict__.update(overrides)
     return s
@@ -93,6 +100,11 @@ def init_settings_b2a(**overrides) -> Settings:
         pilotTRKflag=1,
         CNoInterval=200,
         carrFreqBasis=1176.45e6,
+        navSolPeriod=500,
+        elevationMask=5,
+        useTropCorr=1,
+        c=299792458,
+        startOffset=68.802,
     )
     s.__dict__.update(overrides)
     return s

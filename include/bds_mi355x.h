@@ -669,6 +669,87 @@ BDS_API int bds_nav_decode(bds_ctx *ctx, const bds_settings *settings, int n_ch,
                            double *firstSubFrame, double *TOW);
 BDS_API int bds_nav_fields(int signal, const uint8_t *bits, int n_msg, int stride, bds_eph *eph);
 
+/* ---- position fix: postNavigation from trackResults to navSolutions -----------------------------------------
+ * BDS-3_B1C/postNavigation.m:100-298 and BDS-3_B2a/postNavigation.m (the same text from "Set measurement-time point" on), with
+ * Common/calculatePseudoranges.m:63-110, include/satpos.m, include/check_t.m, Common/leastSquarePos.m, Common/e_r_corr.m,
+ * include/topocent.m, Common/togeod.m, Common/tropo.m and Common/cart2geo.m (ellipsoid 5).  Two stages:
+ *   measure  on the device, one lane per (measurement epoch, channel), one launch: index search, transmit time, satpos.  None of
+ *            it depends on an earlier epoch.
+ *   solve    on the host, sequential over the epochs: localTime, the elevation mask, leastSquarePos, DOP, cart2geo.
+ * This is a capability, not a throughput feature: the fix chain is a few microseconds per epoch of host arithmetic.
+ *
+ * Channels are the reference's channel numbers: n_ch = numberOfChannels rows, row c = channel c + 1, idle ones included.
+ *
+ * Rules that are this library's own:
+ *   - B2a T_GDB1Cp.  BDS-3_B2a/include/satpos.m:62,152 reads eph.T_GDB1Cp, which the B2a eph_structure_init.m / ephemeris.m never
+ *     create: the file cannot run as written.  For B2a the term is 0.
+ *   - Empty SatType.  A ready channel whose eph.SatType is empty (0) would leave A_ref undefined (satpos.m:69-73); it is dropped
+ *     from the ready list with BDS_PVT_NO_SATTYPE.
+ *   - A channel that passes the readiness rule but has no finite subFrameStart in [1, n] or no finite TOW (the reference would index
+ *     absoluteSample(inf)) is dropped with BDS_PVT_NO_FRAME.
+ *   - absoluteSample order.  Over [1, n] absoluteSample must be strictly increasing on every ready channel (it is for any channel
+ *     tracked to the end); otherwise BDS_ERR_ARG.  Only then does the binary search equal the reference's scan.
+ *   - Duplicate PRNs.  Two channels with the same PRN are two rows, as in the reference (the fix is then rank deficient when they
+ *     are two of four).
+ *   - A matrix A with a NaN or inf entry, at which MATLAB's rank() stops with an error, takes the rank-failure exit. */
+typedef struct bds_pvt_params {
+    uint32_t size;        /* sizeof(bds_pvt_params), set by the caller; checked */
+    int32_t useTropCorr;  /* settings.useTropCorr: 1 = tropo() in leastSquarePos.m:68-75, anything else = 0 m */
+    double navSolPeriod;  /* [ms] settings.navSolPeriod (postNavigation.m:119) */
+    double elevationMask; /* [deg] settings.elevationMask (:151) */
+    double c;             /* [m/s] settings.c */
+    double startOffset;   /* [ms] settings.startOffset (calculatePseudoranges.m:104) */
+} bds_pvt_params;
+enum {
+    BDS_PVT_READY = 1,       /* on the ready list (readyChnList, postNavigation.m:135) */
+    BDS_PVT_IDLE = 2,        /* status '-' (:69) */
+    BDS_PVT_NO_EPH = 4,      /* readiness rule not met: B1C eph.flag == 1 (:82); B2a idValid(1) == 10 && idValid(2) == 11 &&
+                                any(idValid(3:7) == 30:34) (BDS-3_B2a/postNavigation.m:84-85) */
+    BDS_PVT_NO_SATTYPE = 8,  /* rule met, SatType empty: dropped (above) */
+    BDS_PVT_NO_FRAME = 16    /* rule met, subFrameStart / TOW not usable: dropped (above) */
+};
+/* What the chain stores per epoch (postNavigation.m:155-293).  Every array is the caller's; cap = measurement epochs each holds.
+ * Per channel and epoch, double[n_ch * cap], element [c * cap + m] (MATLAB's navSolutions.x(c + 1, m + 1)):
+ *   PRN 0 where not active; el, az, transmitTime, satClkCorr NaN where not active; rawP -inf where not active (the reference
+ *   computes (localTime - inf) * c); correctedP 0 where not active (MATLAB array growth).
+ * DOP: double[5 * cap], element [k * cap + m] (GDOP, PDOP, HDOP, VDOP, TDOP).  The rest double[cap].
+ * dt is forced to 0 at the first epoch (:218-222); localTime is still corrected with the solved value (:225). */
+typedef struct bds_pvt_out {
+    uint32_t size; /* sizeof(bds_pvt_out), set by the caller; checked */
+    int32_t cap;
+    double *PRN, *el, *az, *transmitTime, *satClkCorr, *rawP, *correctedP;
+    double *DOP;
+    double *X, *Y, *Z, *dt, *localTime, *currMeasSample, *latitude, *longitude, *height;
+} bds_pvt_out;
+
+/* bds_pvt_plan (no GPU): postNavigation.m:69-122 after the decoding.
+ *   status: char[n_ch], trackResults.status ('-' = idle).  absoluteSample: double[n_ch * n].  eph: bds_eph[n_ch] (.size set),
+ *   subFrameStart, TOW: double[n_ch], as bds_nav_decode leaves them (rows of idle channels are not read).
+ *   ready: int32[n_ch], BDS_PVT_* flags.  sampleStart = max(absoluteSample(subFrameStart)) + 1 and sampleEnd =
+ *   min(absoluteSample(end)) - 1 over the ready channels (:106-116), measSampleStep = fix(samplingFreq * navSolPeriod / 1000) (:119).
+ * Returns n_meas = fix((sampleEnd - sampleStart) / measSampleStep) (:122), or 0 -- with the three numbers as far as they exist --
+ * when fewer than 4 channels are ready (:92-98) or that number is <= 0 (the reference would leave navSolutions unassigned), or < 0.
+ * bds_pvt_measure: the device stage.  ready as bds_pvt_plan left it; absoluteSample, codeFreq, remCodePhase: double[n_ch * n],
+ *   uploaded once.  transmitTime, satClkCorr: double[n_meas * n_ch], element [m * n_ch + c]; satPos: double[n_meas * n_ch * 3], x y z
+ *   per element.  A channel that is not ready gets NaN.  bds_get_timing afterwards: search_ms = the kernel alone (hipEvents).
+ * bds_pvt_solve (no GPU): the chain of postNavigation.m:146-298 over those arrays.  prn: int32[n_ch].  Returns n_meas or < 0.
+ * bds_post_navigation: plan, measure, solve.  *n_meas (optional) receives the planned number even when it exceeds out->cap, in which
+ *   case the call returns BDS_ERR_ARG and writes nothing else.  Returns the number of epochs stored (0: no solution, above). */
+BDS_API int bds_pvt_plan(const bds_settings *s, const bds_pvt_params *p, int n_ch, int n, const char *status,
+                         const double *absoluteSample, const bds_eph *eph, const double *subFrameStart, const double *TOW,
+                         int32_t *ready, double *sampleStart, double *sampleEnd, double *measSampleStep);
+BDS_API int bds_pvt_measure(bds_ctx *ctx, const bds_settings *s, int n_ch, int n, const int32_t *ready, const double *absoluteSample,
+                            const double *codeFreq, const double *remCodePhase, const bds_eph *eph, const double *subFrameStart,
+                            const double *TOW, double sampleStart, double measSampleStep, int n_meas, double *transmitTime,
+                            double *satPos, double *satClkCorr);
+BDS_API int bds_pvt_solve(const bds_settings *s, const bds_pvt_params *p, int n_ch, int n_meas, const int32_t *prn,
+                          const int32_t *ready, double sampleStart, double measSampleStep, const double *transmitTime,
+                          const double *satPos, const double *satClkCorr, bds_pvt_out *out);
+BDS_API int bds_post_navigation(bds_ctx *ctx, const bds_settings *s, const bds_pvt_params *p, int n_ch, int n, const char *status,
+                                const int32_t *prn, const double *absoluteSample, const double *codeFreq, const double *remCodePhase,
+                                const bds_eph *eph, const double *subFrameStart, const double *TOW, int32_t *ready, int32_t *n_meas,
+                                bds_pvt_out *out);
+
 /* B2a/include/unpack_cplx.m: converter of packed records (one byte = two complex samples, 2-bit
  * sign/magnitude I and Q each) into the int8 I/Q pairs of a fileType-2 record.
  * out: int8[4 * n_bytes] = I1, Q1, I2, Q2 per input byte.  The file variant mirrors

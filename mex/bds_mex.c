@@ -32,6 +32,13 @@
  *       remCarrPhase; carrFreq} per item, taps in chips (at most 128, |tau| <= 16).  struct with I, Q ([numel(taps) * n_comp x n],
  *       tap fastest, then component: data, pilot, pilot BOC(6,1)) and n_comp.  The receiver is told from the settings (only
  *       B1C/initSettings.m defines acqCohT).
+ *   out = bds_mex('post_navigation', settings, signal, status, PRN, absoluteSample, codeFreq, remCodePhase, eph, subFrameStart, TOW)
+ *       postNavigation.m behind its decoding loop (mex/B1C/postNavigation.m and mex/B2a/postNavigation.m run that loop with
+ *       'nav_decode').  status: char row, one per channel ('-' = idle); PRN, subFrameStart, TOW: double rows; absoluteSample,
+ *       codeFreq, remCodePhase: n x nCh; eph: 1 x nCh struct array of 'nav_decode's eph structs (all fields [] on an idle channel).
+ *       settings also needs navSolPeriod, elevationMask, useTropCorr, c and startOffset.  struct with n_meas (0: fewer than 4
+ *       channels ready, or no measurement epoch fits), ready (1 x nCh, BDS_PVT_* flags), PRN, el, az, transmitTime, satClkCorr,
+ *       rawP, correctedP (nCh x n_meas), DOP (5 x n_meas), X, Y, Z, dt, localTime, currMeasSample, latitude, longitude, height.
  * signal: 1 = B1C, 2 = B2a (the reference keeps one directory per receiver).
  * Acquisition runs on ONE GPU unless BDS_MEX_DEVICES=n (n > 1, or 0 = every visible GPU) opts into the multi-device
  * path of the library (bds_multi_create + RCCL all-reduce): that path has only ever run on one-GPU boxes (with the exchange
@@ -40,6 +47,7 @@
  * declares the MEX API, and tests/test_mex_mock.py builds it against a small stand-in for the MEX runtime
  * (tests/mex_stub/mex_mock.c) and runs every command and every error exit through ctypes.
  */
+#include <math.h>
 #include <stdlib.h>
 #include <string.h>
 
@@ -409,6 +417,125 @@ static void do_probe_data(int nlhs, mxArray *plhs[], int nrhs, const mxArray *pr
     plhs[0] = out;
 }
 
+/* postNavigation.m:100-298 of either receiver behind the decoding loop: readiness, measurement grid, pseudoranges, satellite and
+ * receiver positions (bds_post_navigation).  mex/B1C/postNavigation.m and mex/B2a/postNavigation.m decode the channels with
+ * 'nav_decode' and hand its eph structs back in. */
+static double eph_number(const mxArray *eph, size_t c, const char *name, double empty) {
+    const mxArray *f = mxGetField(eph, c, name);
+    if (!f || mxGetNumberOfElements(f) == 0) return empty; /* [] */
+    if (!mxIsDouble(f)) mexErrMsgIdAndTxt("bds:args", "post_navigation: eph(%d).%s must be a double", (int)c + 1, name);
+    return mxGetDoubles(f)[0];
+}
+
+static void do_post_navigation(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[]) {
+    static const char *per_ch[] = {"PRN", "el", "az", "transmitTime", "satClkCorr", "rawP", "correctedP"};
+    static const char *per_m[] = {"X", "Y", "Z", "dt", "localTime", "currMeasSample", "latitude", "longitude", "height"};
+    bds_settings s;
+    bds_pvt_params p;
+    bds_pvt_out o;
+    bds_eph *eph;
+    char *status;
+    int32_t *prn, *ready, n_meas = 0;
+    double *buf, *q, step;
+    double **ch_slot[7], **m_slot[9];
+    const double *pp, *lo, *hi;
+    const mxArray *f;
+    size_t n_ch, n, c, k, i, cap, per;
+    int rc, signal, m;
+    mxArray *res;
+    (void)nlhs;
+    if (nrhs != 11) mexErrMsgIdAndTxt("bds:args", "post_navigation: (settings, signal, status, PRN, absoluteSample, codeFreq, remCodePhase, eph, subFrameStart, TOW)");
+    signal = (int)mxGetScalar(prhs[2]);
+    pack_settings(prhs[1], signal, &s);
+    memset(&p, 0, sizeof(p));
+    p.size = sizeof(p);
+    p.navSolPeriod = num(prhs[1], "navSolPeriod");
+    p.elevationMask = num(prhs[1], "elevationMask");
+    p.useTropCorr = (int32_t)num(prhs[1], "useTropCorr");
+    p.c = num(prhs[1], "c");
+    p.startOffset = num(prhs[1], "startOffset");
+    n_ch = mxGetNumberOfElements(prhs[4]);
+    if (n_ch < 1 || !mxIsChar(prhs[3]) || mxGetNumberOfElements(prhs[3]) != n_ch || !mxIsDouble(prhs[4]))
+        mexErrMsgIdAndTxt("bds:args", "post_navigation: status is a char row and PRN a double row, one entry per channel");
+    for (i = 5; i <= 7; ++i)
+        if (!mxIsDouble(prhs[i]) || mxGetNumberOfElements(prhs[i]) == 0 || mxGetNumberOfElements(prhs[i]) % n_ch ||
+            mxGetNumberOfElements(prhs[i]) != mxGetNumberOfElements(prhs[5]))
+            mexErrMsgIdAndTxt("bds:args", "post_navigation: absoluteSample, codeFreq and remCodePhase are n x numel(PRN) doubles, one column per channel");
+    n = mxGetNumberOfElements(prhs[5]) / n_ch;
+    if (!mxIsStruct(prhs[8]) || mxGetNumberOfElements(prhs[8]) != n_ch || !mxIsDouble(prhs[9]) || mxGetNumberOfElements(prhs[9]) != n_ch ||
+        !mxIsDouble(prhs[10]) || mxGetNumberOfElements(prhs[10]) != n_ch)
+        mexErrMsgIdAndTxt("bds:args", "post_navigation: eph is a struct array, subFrameStart and TOW double rows, one entry per channel");
+    status = (char *)mxCalloc(n_ch + 1, 1);
+    prn = (int32_t *)mxCalloc(n_ch, sizeof(int32_t));
+    ready = (int32_t *)mxCalloc(n_ch, sizeof(int32_t));
+    eph = (bds_eph *)mxCalloc(n_ch, sizeof(bds_eph));
+    pp = mxGetDoubles(prhs[4]);
+    for (c = 0; c < n_ch; ++c) {
+        status[c] = (char)mxGetChars(prhs[3])[c];
+        prn[c] = (int32_t)pp[c];
+        eph[c].size = sizeof(bds_eph);
+#define BDS_EPH_X(name) eph[c].name = eph_number(prhs[8], c, #name, NAN);
+        BDS_EPH_FIELDS(BDS_EPH_X)
+#undef BDS_EPH_X
+        eph[c].SatType = (int32_t)eph_number(prhs[8], c, "SatType", 0);
+        eph[c].flag = (int32_t)eph_number(prhs[8], c, "flag", 0);
+        eph[c].n_entered = (int32_t)eph_number(prhs[8], c, "n_entered", 0);
+        f = mxGetField(prhs[8], c, "idValid");
+        if (f && mxIsDouble(f))
+            for (k = 0; k < 8 && k < mxGetNumberOfElements(f); ++k) eph[c].idValid[k] = (int32_t)mxGetDoubles(f)[k];
+    }
+    /* the capacity: what the plan can give at most, (last - first sample) / step + 1 */
+    step = (double)(int64_t)(s.samplingFreq * p.navSolPeriod / 1000);
+    lo = hi = mxGetDoubles(prhs[5]);
+    for (i = 0, pp = lo; i < n * n_ch; ++i) {
+        if (pp[i] < *lo) lo = pp + i;
+        if (pp[i] > *hi) hi = pp + i;
+    }
+    cap = step >= 1 && *hi - *lo >= 0 && (*hi - *lo) / step < 1e8 ? (size_t)((*hi - *lo) / step) + 1 : 1;
+    per = 7 * n_ch + 5 + 9;
+    buf = (double *)mxCalloc(per * cap, sizeof(double));
+    memset(&o, 0, sizeof(o));
+    o.size = sizeof(o);
+    o.cap = (int32_t)cap;
+    ch_slot[0] = &o.PRN, ch_slot[1] = &o.el, ch_slot[2] = &o.az, ch_slot[3] = &o.transmitTime, ch_slot[4] = &o.satClkCorr;
+    ch_slot[5] = &o.rawP, ch_slot[6] = &o.correctedP; /* in the order of per_ch / per_m */
+    m_slot[0] = &o.X, m_slot[1] = &o.Y, m_slot[2] = &o.Z, m_slot[3] = &o.dt, m_slot[4] = &o.localTime, m_slot[5] = &o.currMeasSample;
+    m_slot[6] = &o.latitude, m_slot[7] = &o.longitude, m_slot[8] = &o.height;
+    for (i = 0, q = buf; i < 7; ++i, q += n_ch * cap) *ch_slot[i] = q;
+    o.DOP = q, q += 5 * cap;
+    for (i = 0; i < 9; ++i, q += cap) *m_slot[i] = q;
+    /* an n x nCh matrix is, column-major, the C array [nCh][n] */
+    rc = bds_post_navigation(ctx(), &s, &p, (int)n_ch, (int)n, status, prn, mxGetDoubles(prhs[5]), mxGetDoubles(prhs[6]), mxGetDoubles(prhs[7]),
+                             eph, mxGetDoubles(prhs[9]), mxGetDoubles(prhs[10]), ready, &n_meas, &o);
+    mxFree(status);
+    mxFree(prn);
+    mxFree(eph);
+    if (rc < 0) {
+        mxFree(ready);
+        mxFree(buf);
+        mexErrMsgIdAndTxt("bds:post_navigation", "%s", bds_last_error(ctx()));
+    }
+    res = mxCreateStructMatrix(1, 1, 0, NULL);
+    out_field(res, "n_meas", 1, 1)[0] = rc;
+    q = out_field(res, "ready", 1, (int)n_ch);
+    for (c = 0; c < n_ch; ++c) q[c] = ready[c];
+    for (i = 0; i < 7; ++i) { /* [nCh x n_meas], as navSolutions.<name>(channelNr, currMeasNr) */
+        q = out_field(res, per_ch[i], (int)n_ch, rc);
+        for (m = 0; m < rc; ++m)
+            for (c = 0; c < n_ch; ++c) q[(size_t)m * n_ch + c] = (*ch_slot[i])[c * cap + (size_t)m];
+    }
+    q = out_field(res, "DOP", 5, rc);
+    for (m = 0; m < rc; ++m)
+        for (k = 0; k < 5; ++k) q[(size_t)m * 5 + k] = o.DOP[k * cap + (size_t)m];
+    for (i = 0; i < 9; ++i) {
+        q = out_field(res, per_m[i], 1, rc);
+        for (m = 0; m < rc; ++m) q[m] = (*m_slot[i])[m];
+    }
+    mxFree(ready);
+    mxFree(buf);
+    plhs[0] = res;
+}
+
 /* bds_corr_function: the correlation function of tracked epochs at the caller's taps (mex/corrFunction.m builds the states) */
 static void do_corr_function(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[]) {
     bds_settings s;
@@ -473,6 +600,8 @@ void mexFunction(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[]) {
         do_probe_data(nlhs, plhs, nrhs, prhs);
     else if (!strcmp(cmd, "corr_function"))
         do_corr_function(nlhs, plhs, nrhs, prhs);
+    else if (!strcmp(cmd, "post_navigation"))
+        do_post_navigation(nlhs, plhs, nrhs, prhs);
     else
         mexErrMsgIdAndTxt("bds:args", "unknown command %s", cmd);
 }
