@@ -57,5 +57,31 @@ BDS_HD int symbol(uint64_t seed, int64_t period, int prn, int component) {
     return (w[0] & 1u) ? 1 : -1;
 }
 
+// ---- the trajectory path (bds_synth_traj; include/bds_mi355x.h, "driven by an orbit") -------------------------------------------
+// Sample n of a trajectory that starts at sample `first` with segments of 2^seg_log2 samples: the segment index (a shift: no
+// 64-bit division) and the offset inside the segment, an exact integer.
+BDS_HD void traj_index(int64_t n, int64_t first, int seg_log2, int64_t &j, int64_t &u) {
+    const int64_t m = n - first;
+    j = m >> seg_log2;
+    u = m - (j << seg_log2);
+}
+
+// ((a[3] u + a[2]) u + a[1]) u + a[0], six roundings
+BDS_HD double traj_horner(const double a[4], double u) { return ((a[3] * u + a[2]) * u + a[1]) * u + a[0]; }
+
+// Code phase in [0, ncode) chips and the code period of offset u in a segment.
+BDS_HD void traj_code(int64_t period0, const double code[4], double u, double ncode, double &cph, int64_t &period) {
+    const double c = traj_horner(code, u);
+    const double k = floor(c / ncode);
+    cph = c - k * ncode;
+    period = period0 + (int64_t)k;
+}
+
+// Carrier angle [rad] of offset u in a segment: the whole cycles of the polynomial's value are dropped towards zero (fmod(x, 1)).
+BDS_HD double traj_carrier(const double carr[4], double u, double phase) {
+    const double x = traj_horner(carr, u);
+    return 6.283185307179586 * (x - trunc(x)) + phase;
+}
+
 }  // namespace synth
 }  // namespace bds

@@ -93,6 +93,18 @@ class SynthOpts(C.Structure):
                 ("threshold", C.c_double), ("symbols", C.POINTER(C.c_int8)), ("n_sym", C.c_int64)]
 
 
+class SynthSeg(C.Structure):
+    _fields_ = [("period0", C.c_int64), ("code", C.c_double * 4), ("carr", C.c_double * 4)]
+
+
+class SynthTraj(C.Structure):
+    _fields_ = [("size", C.c_int32), ("seg_log2", C.c_int32), ("first", C.c_int64), ("n_seg", C.c_int64), ("seg", C.POINTER(SynthSeg))]
+
+
+# bds_synth_seg as a NumPy structured dtype (72 bytes, no padding): what synth.Trajectory holds
+SYNTH_SEG_DTYPE = np.dtype([("period0", np.int64), ("code", np.float64, 4), ("carr", np.float64, 4)])
+
+
 # the doubles of bds_eph, in the order of BDS_EPH_FIELDS (include/bds_mi355x.h)
 EPH_FIELDS = ["PRN", "SOH", "SOW", "WN", "HOW", "IODC", "IODE", "IODC_MSB2", "IODC_LSB8",
               "t_oe", "deltaA", "ADot", "delta_n_0", "delta_n_0Dot", "M_0", "e", "omega",
@@ -157,7 +169,7 @@ EXPORTS = [
     "bds_calc_weighing_factor", "bds_pre_run", "bds_pre_run_device", "bds_acquire_track",
     "bds_multi_create", "bds_multi_destroy", "bds_multi_last_error", "bds_multi_size", "bds_multi_ctx",
     "bds_multi_rccl_ranks", "bds_acquire_multi", "bds_shard_jobs", "bds_acq_job_cost",
-    "bds_synth", "bds_synth_file", "bds_synth_noise",
+    "bds_synth", "bds_synth_file", "bds_synth_noise", "bds_synth_trajectory", "bds_synth_traj",
     "bds_probe_data", "bds_probe_data_file", "bds_probe_set_piece_segments",
     "bds_corr_function", "bds_corr_function_mem",
     "bds_nav_decode", "bds_nav_fields",
@@ -165,6 +177,8 @@ EXPORTS = [
 ]
 # the entries marked BDS_DEV_API in the header: their record pointer is device memory (device_span below makes it)
 DEVICE_EXPORTS = ["bds_synth_dev", "bds_acq_load_dev", "bds_track_dev", "bds_track_open_dev", "bds_track_feed_dev"]
+# the entry marked BDS_SYNTH_DEV_API: a device pointer as well
+SYNTH_DEVICE_EXPORTS = ["bds_synth_traj_dev"]
 # the entry marked BDS_PROBE_DEV_API: a device pointer as well
 PROBE_DEVICE_EXPORTS = ["bds_probe_data_dev"]
 # the entry marked BDS_CORR_DEV_API: a device pointer as well
@@ -296,6 +310,12 @@ def lib():
         L.bds_track_dev.argtypes = [vp, SP, vp, sz, i32, C.POINTER(Channel), C.POINTER(TrackOut)]
         L.bds_track_open_dev.restype, L.bds_track_open_dev.argtypes = vp, [vp, SP, vp, sz, i32, C.POINTER(Channel)]
         L.bds_track_feed_dev.restype, L.bds_track_feed_dev.argtypes = i32, [vp, vp, sz, i32]
+    if hasattr(L, "bds_synth_traj"):  # (as above: a build of an older commit has no trajectory path)
+        TP = C.POINTER(SynthTraj)
+        L.bds_synth_trajectory.restype = i32
+        L.bds_synth_trajectory.argtypes = [SP, i32, C.POINTER(Eph), _DP, C.c_double, C.c_double, i64, i64, i32, C.POINTER(SynthSeg)]
+        L.bds_synth_traj.restype, L.bds_synth_traj.argtypes = i32, [vp, SP, i32, YP, OP, TP, i64, i64, vp, sz]
+        L.bds_synth_traj_dev.restype, L.bds_synth_traj_dev.argtypes = i32, [vp, SP, i32, YP, OP, TP, i64, i64, vp, sz]
     if hasattr(L, "bds_probe_data"):  # (as above: a build of an older commit has no probeData)
         PP, i64 = C.POINTER(ProbeOut), C.c_int64
         L.bds_probe_data.restype, L.bds_probe_data.argtypes = i32, [vp, SP, vp, sz, i64, PP]
@@ -603,6 +623,34 @@ def pack_synth(sats, fmt, seed=3550, sigma=20.0, iq_sign=0, threshold=None, code
             raise ValueError(f"symbols must have shape [n_sat = {len(sats)}, 2, n_sym >= 1], not {sym.shape}")
         o.symbols, o.n_sym = sym.ctypes.data_as(C.POINTER(C.c_int8)), sym.shape[2]
     return arr, o, sym
+
+
+def pack_traj(segs, first, seg_log2, n_sat):
+    """(bds_synth_traj, the array it points into) from a structured array [n_sat, n_seg] of SYNTH_SEG_DTYPE."""
+    a = np.ascontiguousarray(segs, dtype=SYNTH_SEG_DTYPE)
+    if a.ndim != 2 or a.shape[0] != n_sat or a.shape[1] < 1:
+        raise ValueError(f"the trajectory's segments must have shape [n_sat = {n_sat}, n_seg >= 1], not {a.shape}")
+    t = SynthTraj()
+    t.size, t.seg_log2, t.first, t.n_seg = C.sizeof(SynthTraj), int(seg_log2), int(first), a.shape[1]
+    t.seg = a.ctypes.data_as(C.POINTER(SynthSeg))
+    return t, a
+
+
+def synth_trajectory(settings, ephs, rx, tow, t0, first, n_seg, seg_log2) -> np.ndarray:
+    """bds_synth_trajectory (host only, no GPU): the segments [len(ephs), n_seg] (SYNTH_SEG_DTYPE) of the record whose sample n is
+    taken at system time tow + t0 + n / fs by a receiver at rx [m, Earth-fixed]; ephs: eph dicts (eph_dict's layout)."""
+    cs = pack_settings(settings)
+    arr = eph_array(ephs)
+    r = np.ascontiguousarray(rx, dtype=np.float64).reshape(-1)
+    if r.size != 3:
+        raise ValueError("rx must hold three coordinates")
+    n_seg = int(n_seg)
+    out = np.zeros((len(ephs), max(n_seg, 1)), dtype=SYNTH_SEG_DTYPE)
+    rc = lib().bds_synth_trajectory(C.byref(cs), len(ephs), arr, r.ctypes.data_as(_DP), float(tow), float(t0), int(first), n_seg, int(seg_log2),
+                                    out.ctypes.data_as(C.POINTER(SynthSeg)))
+    if rc < 0:
+        raise BdsError(rc, lib().bds_last_error(None).decode())
+    return out
 
 
 def synth_out(fmt, n_samples) -> np.ndarray:
@@ -979,30 +1027,48 @@ class Context:
         return carr, cph, pm, det
 
     # -- synthetic IF records (bds_synth*) -----------------------------------------------
-    def synth(self, settings, sats, first_sample, n_samples, fmt, out=None, **opts):
+    def synth(self, settings, sats, first_sample, n_samples, fmt, out=None, trajectory=None, **opts):
         """bds_synth: samples first_sample .. + n_samples of the record as float64 (fmt 0), int8 (1), int8 I/Q pairs (2) or packed
         uint8 (3); opts as pack_synth.  out="torch": the record stays in HBM -- a torch tensor on the context's device, made by
-        bds_synth_dev; the default is the NumPy array."""
+        bds_synth_dev; the default is the NumPy array.  trajectory (an object with segs, first, seg_log2: synth.Trajectory):
+        bds_synth_traj / bds_synth_traj_dev, code and carrier phase from its segments."""
         if out == "torch":
-            return self.synth_dev(settings, sats, first_sample, n_samples, fmt, synth_out_torch(fmt, n_samples, self.device), **opts)
+            return self.synth_dev(settings, sats, first_sample, n_samples, fmt, synth_out_torch(fmt, n_samples, self.device),
+                                  trajectory=trajectory, **opts)
         if out is not None:
             raise ValueError(f'out must be None (a NumPy array) or "torch" (a tensor on the device), not {out!r}')
         cs = pack_settings(settings)
         arr, o, keep = pack_synth(sats, fmt, **opts)
         out = synth_out(fmt, n_samples)
-        self._check(self._lib.bds_synth(self._h, C.byref(cs), len(sats), arr, C.byref(o), int(first_sample), int(n_samples),
-                                        out.ctypes.data_as(C.c_void_p), out.nbytes))
+        if trajectory is None:
+            self._check(self._lib.bds_synth(self._h, C.byref(cs), len(sats), arr, C.byref(o), int(first_sample), int(n_samples),
+                                            out.ctypes.data_as(C.c_void_p), out.nbytes))
+        else:
+            t, keep_t = pack_traj(trajectory.segs, trajectory.first, trajectory.seg_log2, len(sats))
+            self._check(self._lib.bds_synth_traj(self._h, C.byref(cs), len(sats), arr, C.byref(o), C.byref(t), int(first_sample),
+                                                 int(n_samples), out.ctypes.data_as(C.c_void_p), out.nbytes))
         return out
 
-    def synth_dev(self, settings, sats, first_sample, n_samples, fmt, out, **opts):
+    def synth_dev(self, settings, sats, first_sample, n_samples, fmt, out, trajectory=None, **opts):
         """bds_synth_dev: the same samples written into the device array `out` (float64 for fmt 0, else int8 / uint8; it may be a
-        slice at any byte offset, and must hold at least the record); returns `out`."""
+        slice at any byte offset, and must hold at least the record); returns `out`.  trajectory: bds_synth_traj_dev."""
         cs = pack_settings(settings)
         arr, o, keep = pack_synth(sats, fmt, **opts)
         synth_out_count(fmt, n_samples)
+        t = keep_t = None
+        if trajectory is not None:
+            t, keep_t = pack_traj(trajectory.segs, trajectory.first, trajectory.seg_log2, len(sats))
         ptr, n_bytes, _ = device_span(out, self.device, dtypes=("float64",) if fmt == 0 else ("int8", "uint8"))
-        self._check(self._lib.bds_synth_dev(self._h, C.byref(cs), len(sats), arr, C.byref(o), int(first_sample), int(n_samples), ptr, n_bytes))
+        if t is None:
+            self._check(self._lib.bds_synth_dev(self._h, C.byref(cs), len(sats), arr, C.byref(o), int(first_sample), int(n_samples), ptr, n_bytes))
+        else:
+            self._check(self._lib.bds_synth_traj_dev(self._h, C.byref(cs), len(sats), arr, C.byref(o), C.byref(t), int(first_sample),
+                                                     int(n_samples), ptr, n_bytes))
         return out
+
+    def synth_traj_dev(self, settings, sats, trajectory, first_sample, n_samples, fmt, out, **opts):
+        """bds_synth_traj_dev: synth_dev with a trajectory."""
+        return self.synth_dev(settings, sats, first_sample, n_samples, fmt, out, trajectory=trajectory, **opts)
 
     def synth_file(self, settings, sats, first_sample, n_samples, fmt, path, piece_samples=0, **opts):
         """bds_synth_file: the same record written to `path`, piece by piece."""

@@ -132,8 +132,62 @@ def _device_format(iq_sign, clean, packed):
     return 2 if iq_sign else 1
 
 
+@dataclass
+class Trajectory:
+    """Code and carrier phase of every satellite of a record as piecewise cubics in the sample index (bds_synth_seg,
+    include/bds_mi355x.h): segs [n_sat, n_seg] of native.SYNTH_SEG_DTYPE, segment j covering samples first + j 2^seg_log2 ..
+    first + (j + 1) 2^seg_log2 - 1; prns, one per row.  trajectory() makes one from a receiver position and ephemerides; one made
+    by hand (any coefficients with code[1] > 0) is as good to make_if_device."""
+    segs: np.ndarray
+    first: int
+    seg_log2: int
+    prns: np.ndarray
+
+    def _at(self, n):
+        n = np.asarray(n, dtype=np.int64)
+        m = n - np.int64(self.first)
+        j = m >> np.int64(self.seg_log2)
+        if ((j < 0) | (j >= self.segs.shape[1])).any():
+            raise ValueError("a sample outside the trajectory")
+        return j, (m - (j << np.int64(self.seg_log2))).astype(np.float64)
+
+    def code_phase(self, n, ncode=10230):
+        """(code phase in [0, ncode) chips, code period) of samples n, [n_sat, ...]: the device's own operations, one rounding each."""
+        j, u = self._at(n)
+        g = self.segs[:, j]
+        a = g["code"]
+        c = ((a[..., 3] * u + a[..., 2]) * u + a[..., 1]) * u + a[..., 0]
+        k = np.floor(c / float(ncode))
+        return c - k * float(ncode), g["period0"] + k.astype(np.int64)
+
+    def carrier_phase(self, n):
+        """Carrier phase [cycles] of samples n, [n_sat, ...]: the polynomial's value (whole cycles of a segment's start left out)."""
+        j, u = self._at(n)
+        a = self.segs[:, j]["carr"]
+        return ((a[..., 3] * u + a[..., 2]) * u + a[..., 1]) * u + a[..., 0]
+
+    def carrier_rate(self, n):
+        """d(carrier phase) / dn [cycles per sample] of samples n, [n_sat, ...]: carr[1] + 2 carr[2] u + 3 carr[3] u^2."""
+        j, u = self._at(n)
+        a = self.segs[:, j]["carr"]
+        return (3.0 * a[..., 3] * u + 2.0 * a[..., 2]) * u + a[..., 1]
+
+
+def trajectory(settings, ephs, rx, n_samples, tow, t0, first_sample=0, seg_log2=17):
+    """The Trajectory of the record whose sample n is taken at system time tow + t0 + n / fs (the receiver clock offset is part
+    of t0) by a receiver at rest at rx [m, Earth-fixed], from the satellites of ephs (eph dicts as navdecode / native.nav_fields
+    give; one row each) -- bds_synth_trajectory, host only: the library's own satpos, the Earth's rotation during the travel time,
+    no atmosphere.  It covers samples first_sample .. first_sample + n_samples and the up to 32 more a device call may evaluate."""
+    from . import native
+
+    ephs = list(ephs)
+    n_seg = -(-(int(n_samples) + 32) >> int(seg_log2)) if 0 <= int(seg_log2) < 63 else 1
+    segs = native.synth_trajectory(settings, ephs, rx, tow, t0, int(first_sample), max(n_seg, 1), int(seg_log2))
+    return Trajectory(segs, int(first_sample), int(seg_log2), np.array([int(e["PRN"]) for e in ephs], dtype=np.int32))
+
+
 def make_if_device(settings, sats, n_samples, seed=3550, sigma=20.0, first_sample=0, iq_sign=0, clean=False, packed=False,
-                   threshold=None, code_doppler=True, pilot61_secondary=False, symbols=None, device=0, out=None):
+                   threshold=None, code_doppler=True, pilot61_secondary=False, symbols=None, device=0, out=None, trajectory=None):
     """make_if's signal generated on the device (bds_synth): samples first_sample .. first_sample + n_samples of the record, as
     int8[n_samples] (real), int8[2 n_samples] (iq_sign = +1 / -1, as in make_if), float64[n_samples] (clean=True: no noise, not
     quantised) or uint8[n_samples / 2] (packed=True with an iq_sign: the 2+2-bit bytes of fileType 3 -- magnitude 3 where the
@@ -143,13 +197,21 @@ def make_if_device(settings, sats, n_samples, seed=3550, sigma=20.0, first_sampl
     than make_if's.  symbols: int8 [n_sat, 2, n_sym] of +-1 (data, secondary per satellite entry; code period p reads index
     (p + 1) mod n_sym) instead of the generated ones.  out="torch": the record stays in HBM -- a torch tensor on the device
     (int8, uint8 for packed, float64 for clean; bds_synth_dev), ready for acquisition(), tracking() and TrackSession without a
-    trip through host memory; the default is the NumPy array.  There is no CPU fallback."""
+    trip through host memory; the default is the NumPy array.  There is no CPU fallback.
+    trajectory: a Trajectory with one row per entry of sats (bds_synth_traj): code and carrier phase of each satellite follow its
+    segments -- Doppler, code Doppler and their rates with them -- in place of one constant Doppler and delay; of a Sat the prn,
+    phase and cn0_dbhz are used, a non-zero doppler or delay is a ValueError, and code_doppler is ignored."""
     from .acquisition import get_context
 
     fmt = _device_format(iq_sign, clean, packed)
-    return get_context(device).synth(settings, list(sats), first_sample, n_samples, fmt, seed=seed, sigma=sigma, iq_sign=iq_sign,
+    sats = list(sats)
+    if trajectory is not None:
+        for k, t in enumerate(sats):
+            if t.doppler != 0 or t.delay != 0:
+                raise ValueError(f"satellite {k + 1}: doppler = {t.doppler}, delay = {t.delay}: with a trajectory, which sets both, they must be 0")
+    return get_context(device).synth(settings, sats, first_sample, n_samples, fmt, seed=seed, sigma=sigma, iq_sign=iq_sign,
                                      threshold=threshold, code_doppler=code_doppler, pilot61_secondary=pilot61_secondary,
-                                     symbols=symbols, out=out)
+                                     symbols=symbols, out=out, trajectory=trajectory)
 
 
 def write_if(path, settings, sats, n_samples, seed=3550, sigma=20.0, first_sample=0, iq_sign=0, clean=False, packed=False,

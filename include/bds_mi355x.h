@@ -819,6 +819,56 @@ BDS_API int bds_synth_file(bds_ctx *ctx, const bds_settings *s, int n_sat, const
 /* Test aid: the raw N(0, 1) stream of samples first .. first + n - 1 as the device forms it (either pointer may be NULL). */
 BDS_API int bds_synth_noise(bds_ctx *ctx, uint64_t seed, int64_t first, int64_t n, double *g_i, double *g_q);
 
+/* ---- synthetic IF records driven by an orbit: a receiver position and ephemerides in, a record out -------------------------
+ * bds_synth gives every satellite one constant Doppler and one constant delay.  On this path code and carrier phase of every
+ * satellite follow a TRAJECTORY instead: piecewise cubics in the sample index, in segments of 2^seg_log2 samples (a power of two,
+ * so the device finds a sample's segment with a shift and no 64-bit division).  Per sample n and satellite, every operation
+ * rounding once (csrc/bds_synth_math.h: traj_index, traj_code, traj_carrier):
+ *   j = (n - traj.first) >> seg_log2;  u = (double)(n - traj.first - (j << seg_log2))            seg = traj.seg[sat][j]
+ *   c = ((code[3] u + code[2]) u + code[1]) u + code[0];  k = floor(c / codeLength);  cph = c - k codeLength;  period = period0 + (int64)k
+ *   x = ((carr[3] u + carr[2]) u + carr[1]) u + carr[0];  th = (2 pi) (x - trunc(x)) + phase
+ * and from cph, period and th on the sample is bds_synth's: chip index, BOC signs, symbols (element (period + 1) mod n_sym of
+ * opts.symbols, or the counter-based stream), amplitude, pilot61_secondary, iq_sign, noise, the formats 0..3, threshold and the
+ * timing report are those of bds_synth, and a record made in pieces, in any order, is the one-call record bit for bit: it depends
+ * on (seed, n, trajectory) alone.  Carrier Doppler, code Doppler and their rates all follow from the one trajectory, so
+ * opts.code_doppler is ignored, and of each bds_synth_sat entry prn, phase and cn0_dbhz are used: a non-zero doppler or delay is
+ * BDS_ERR_ARG.
+ * bds_synth_trajectory (host only, no GPU) fills the segments from the physical model that postNavigation inverts:
+ *   sample n is taken at system time tow + t0 + n / fs (the receiver clock offset is part of t0);
+ *   a signal that leaves satellite k at satellite-clock time tow + rel arrives at tow + rel + delay_k(rel),
+ *   delay_k(rel) = |R3(OmegaE_dot travel) pos - rx| / c - clk, travel = |pos - rx| / c, (pos, clk) = satpos(eph_k, tow + rel)
+ *   (the library's own satpos, csrc/bds_pvt_math.h; OmegaE_dot = 7.292115147e-5 rad/s of e_r_corr.m; c = 299 792 458 m/s; no
+ *   ionosphere, no troposphere, a receiver at rest in the Earth-fixed frame);
+ *   for a sample, rel solves rel = (t0 + n / fs) - delay_k(rel) (the iteration contracts by ~3e-6 per step), and then
+ *   code phase = rel codeFreqBasis chips -- code period P is the one that leaves at tow + P codeLength / codeFreqBasis --
+ *   carrier phase = IF n / fs - carrFreqBasis (n / fs - rel) cycles.
+ * Each segment is the cubic through four of its points, both ends included (u = 0, rint(L / 3), rint(2 L / 3), L = 2^seg_log2), so
+ * neighbours meet at the joint; the large parts stay out of the polynomials: period0 is an integer, code[0] lies in
+ * [0, codeLength), carr[0] in [0, 1).  out: bds_synth_seg[n_sat][n_seg], segment j of satellite k at out[k * n_seg + j].
+ * Argument errors (BDS_ERR_ARG, message in bds_last_error(NULL)): a NULL pointer, seg_log2 outside 10..26, n_sat / n_seg / first
+ * out of range, an ephemeris that is not ready (postNavigation's rule) or has an unknown SatType, a non-finite result, a code rate
+ * that is not positive.
+ * bds_synth_traj / bds_synth_traj_dev check before any device call, besides what bds_synth checks: traj.size, traj.seg, seg_log2,
+ * that every sample the device evaluates -- the call's samples and those that make its last 16-byte unit whole, up to 31 more --
+ * lies inside first .. first + n_seg 2^seg_log2, that every coefficient is finite and code[1] > 0, and the symbol table's period
+ * span (the code period is monotone in n: the first and the last sample bound it). */
+typedef struct bds_synth_seg {   /* one satellite, one segment; u = n - (traj.first + j 2^seg_log2), an exact integer in a double */
+    int64_t period0;             /* code period that code[] counts from */
+    double code[4];              /* chips since the start of period0: ((code[3] u + code[2]) u + code[1]) u + code[0] */
+    double carr[4];              /* carrier phase in cycles, same Horner form */
+} bds_synth_seg;
+/* (a struct tag without a typedef: the entry below carries the same name, as stat() and struct stat do, so the type is always
+ * written `struct bds_synth_traj`) */
+struct bds_synth_traj {
+    int32_t size, seg_log2;      /* sizeof(struct bds_synth_traj); segments of 2^seg_log2 samples, 10 .. 26 */
+    int64_t first, n_seg;        /* segment j covers samples first + j 2^seg_log2 .. first + (j + 1) 2^seg_log2 - 1 */
+    const bds_synth_seg *seg;    /* [n_sat][n_seg] */
+};
+BDS_API int bds_synth_trajectory(const bds_settings *s, int n_sat, const bds_eph *eph, const double rx[3], double tow, double t0,
+                                 int64_t first, int64_t n_seg, int seg_log2, bds_synth_seg *out);
+BDS_API int bds_synth_traj(bds_ctx *ctx, const bds_settings *s, int n_sat, const bds_synth_sat *sats, const bds_synth_opts *opts,
+                           const struct bds_synth_traj *traj, int64_t first_sample, int64_t n_samples, void *out, size_t out_bytes);
+
 /* ---- records in device memory: generate, search and track without the host round trip -------------------------------
  * A record that is made on the card -- by bds_synth_dev, or by a front end of the caller's (filter, down-converter, channeliser)
  * -- is searched and tracked from where it lies.  Each entry below does what its host-memory counterpart does with the same
@@ -864,6 +914,13 @@ BDS_DEV_API int bds_track_dev(bds_ctx *ctx, const bds_settings *s, const void *d
 BDS_DEV_API bds_track_session *bds_track_open_dev(bds_ctx *ctx, const bds_settings *s, const void *d_file_bytes, size_t n_bytes,
                                               int n_ch, const bds_channel *channel);
 BDS_DEV_API int bds_track_feed_dev(bds_track_session *sess, const void *d_bytes, size_t n_bytes, int last);
+/* bds_synth_traj, the record written to device memory: d_out and out_bytes under the pointer rule and the ordering rule above,
+ * written as bds_synth_dev writes (any byte alignment, no byte outside the record); traj and traj->seg are HOST memory.  (Marked
+ * BDS_SYNTH_DEV_API for the reason given above: its record pointer is a device pointer.) */
+#define BDS_SYNTH_DEV_API __attribute__((visibility("default")))
+BDS_SYNTH_DEV_API int bds_synth_traj_dev(bds_ctx *ctx, const bds_settings *s, int n_sat, const bds_synth_sat *sats,
+                                         const bds_synth_opts *opts, const struct bds_synth_traj *traj, int64_t first_sample,
+                                         int64_t n_samples, void *d_out, size_t out_bytes);
 
 /* ---- probeData: histogram, Welch PSD and excerpt of an IF record ------------------------------------------------------------
  * probeData(settings) / probeData(fileName, settings)     B2a/include/probeData.m:1, B1C/include/probeData.m:1
