@@ -152,6 +152,19 @@ class ProbeOut(C.Structure):
                    ("excerpt_re", C.POINTER(C.c_double)), ("excerpt_im", C.POINTER(C.c_double))])
 
 
+class BlankOpts(C.Structure):
+    _fields_ = [("threshold_sq", C.c_uint32), ("pre", C.c_int32), ("post", C.c_int32), ("lead", C.c_int64), ("tail", C.c_int64),
+                ("duty_samples", C.c_int64)]
+
+
+class BlankOut(C.Structure):
+    _fields_ = [("n_samples", C.c_int64), ("n_flagged", C.c_int64), ("n_blanked", C.c_int64), ("n_runs", C.c_int64),
+                ("duty", C.POINTER(C.c_int32)), ("duty_cap", C.c_int64), ("n_duty", C.c_int64)]
+
+
+BLANK_TILE = 16384           # BDS_BLANK_TILE: samples per tile of the blanker's device pass
+BLANK_MAX_WINDOW = 1048576   # BDS_BLANK_MAX_WINDOW: the largest pre / post
+
 SYNTH_FORMATS = {0: (np.float64, 1, 1), 1: (np.int8, 1, 1), 2: (np.int8, 2, 1), 3: (np.uint8, 1, 2)}  # dtype, elements per `den` samples
 
 
@@ -171,6 +184,7 @@ EXPORTS = [
     "bds_multi_rccl_ranks", "bds_acquire_multi", "bds_shard_jobs", "bds_acq_job_cost",
     "bds_synth", "bds_synth_file", "bds_synth_noise", "bds_synth_trajectory", "bds_synth_traj",
     "bds_probe_data", "bds_probe_data_file", "bds_probe_set_piece_segments",
+    "bds_blank", "bds_blank_file",
     "bds_corr_function", "bds_corr_function_mem",
     "bds_nav_decode", "bds_nav_fields",
     "bds_pvt_plan", "bds_pvt_measure", "bds_pvt_solve", "bds_post_navigation",
@@ -181,6 +195,8 @@ DEVICE_EXPORTS = ["bds_synth_dev", "bds_acq_load_dev", "bds_track_dev", "bds_tra
 SYNTH_DEVICE_EXPORTS = ["bds_synth_traj_dev"]
 # the entry marked BDS_PROBE_DEV_API: a device pointer as well
 PROBE_DEVICE_EXPORTS = ["bds_probe_data_dev"]
+# the entry marked BDS_BLANK_DEV_API: device pointers as well (record in, record out)
+BLANK_DEVICE_EXPORTS = ["bds_blank_dev"]
 # the entry marked BDS_CORR_DEV_API: a device pointer as well
 CORR_DEVICE_EXPORTS = ["bds_corr_function_dev"]
 
@@ -322,6 +338,11 @@ def lib():
         L.bds_probe_data_file.restype, L.bds_probe_data_file.argtypes = i32, [vp, SP, C.c_char_p, i64, i64, PP]
         L.bds_probe_data_dev.restype, L.bds_probe_data_dev.argtypes = i32, [vp, SP, vp, sz, i64, PP]
         L.bds_probe_set_piece_segments.restype, L.bds_probe_set_piece_segments.argtypes = i32, [vp, i64]
+    if hasattr(L, "bds_blank"):  # (as above: a build of an older commit has no pulse blanker)
+        BO, BR, i64 = C.POINTER(BlankOpts), C.POINTER(BlankOut), C.c_int64
+        L.bds_blank.restype, L.bds_blank.argtypes = i32, [vp, SP, vp, sz, vp, BO, BR]
+        L.bds_blank_file.restype, L.bds_blank_file.argtypes = i32, [vp, SP, C.c_char_p, C.c_char_p, i64, i64, BO, BR]
+        L.bds_blank_dev.restype, L.bds_blank_dev.argtypes = i32, [vp, SP, vp, sz, vp, BO, BR]
     if hasattr(L, "bds_corr_function"):  # (as above: a build of an older commit has no correlation function)
         tail = [i32, _IP, _DP, i32, _DP, _DP, _IP]  # n_items, prn, state6, n_taps, taps, out, n_comp
         L.bds_corr_function.restype, L.bds_corr_function.argtypes = i32, [vp, SP, C.c_char_p] + tail
@@ -651,6 +672,31 @@ def synth_trajectory(settings, ephs, rx, tow, t0, first, n_seg, seg_log2) -> np.
     if rc < 0:
         raise BdsError(rc, lib().bds_last_error(None).decode())
     return out
+
+
+def blank_sample_bytes(settings) -> int:
+    """Bytes per sample of a record the blanker takes (fileType 1 / 2, 8 or 16 bits); fileType 3 is the library's to refuse."""
+    return (2 if int(settings.fileType) == 2 else 1) * (2 if data_type_code(getattr(settings, "dataType", "schar")) == 1 else 1)
+
+
+def pack_blank(threshold_sq, pre, post, lead=0, tail=0, duty_samples=0):
+    """(bds_blank_opts, bds_blank_out without a duty array, None) of one bds_blank* call."""
+    o, rep = BlankOpts(), BlankOut()
+    ts = int(threshold_sq)
+    if not 0 <= ts <= 2 ** 32 - 1:
+        raise ValueError(f"threshold_sq = {threshold_sq!r} is outside 0 .. 2^32 - 1")
+    o.threshold_sq, o.pre, o.post, o.lead, o.tail, o.duty_samples = ts, int(pre), int(post), int(lead), int(tail), int(duty_samples)
+    return o, rep, None
+
+
+def blank_duty(rep, n, lead, tail, duty_samples):
+    """The duty array of a window of n - lead - tail samples, hung into `rep` (None when no bins are asked for)."""
+    ds = int(duty_samples)
+    if ds <= 0:
+        return None
+    duty = np.zeros(max(-(-max(int(n) - int(lead) - int(tail), 0) // ds), 1), dtype=np.int32)
+    rep.duty, rep.duty_cap = duty.ctypes.data_as(_IP), duty.size
+    return duty
 
 
 def synth_out(fmt, n_samples) -> np.ndarray:
@@ -1115,6 +1161,47 @@ class Context:
         out = {k: int(getattr(o, k)) for k in ("n_segments", "n_samples", "min_i", "max_i", "sum_i", "sumsq_i", "min_q", "max_q", "sum_q", "sumsq_q")}
         out.update(hist_i=hi, hist_q=hq if cplx else None, psd=psd[:o.n_psd], excerpt_re=ex[0, :n_time], excerpt_im=ex[1, :n_time] if cplx else None)
         return out
+
+    # -- pulse blanking (bds_blank*) ---------------------------------------------------------
+    def blank(self, settings, source, threshold_sq, pre, post, out=None, lead=0, tail=0, duty_samples=0, n_samples=-1, piece_samples=0):
+        """bds_blank (host array -> `out`, a host array of the same bytes, or None: a new one), bds_blank_file (path -> the path
+        `out`) or bds_blank_dev (a device array -> `out`, a device array of the same size or the same array; None: in place).
+        Returns (the record written, a dict of n_samples, n_flagged, n_blanked, n_runs and duty: int32 array or None)."""
+        cs = pack_settings(settings)
+        o, rep, duty = pack_blank(threshold_sq, pre, post, lead, tail, duty_samples)
+        if isinstance(source, (str, bytes, os.PathLike)):
+            if not isinstance(out, (str, bytes, os.PathLike)):
+                raise ValueError("blanking a file writes a file: out must be a path")
+            ds = int(duty_samples)
+            if ds > 0:  # the window's length is the file's to tell
+                size, sb = os.path.getsize(source), blank_sample_bytes(settings)
+                n = int(n_samples) if int(n_samples) > 0 else size // sb - int(settings.skipNumberOfBytes)
+                duty = np.zeros(max(-(-max(n - int(lead) - int(tail), 0) // ds), 1), dtype=np.int32)
+                rep.duty, rep.duty_cap = duty.ctypes.data_as(_IP), duty.size
+            rc = self._lib.bds_blank_file(self._h, C.byref(cs), os.fsencode(source), os.fsencode(out), int(n_samples), int(piece_samples), C.byref(o), C.byref(rep))
+            res = out
+        elif is_device_array(source):
+            ptr, n_bytes, keep, _ = device_record(settings, source, self.device)
+            res = source if out is None else out
+            optr, on_bytes, okeep, _ = device_record(settings, res, self.device, "the output record")
+            if on_bytes != n_bytes:
+                raise ValueError(f"the output record holds {on_bytes} bytes, the input {n_bytes}")
+            duty = blank_duty(rep, n_bytes // blank_sample_bytes(settings), lead, tail, duty_samples)
+            rc = self._lib.bds_blank_dev(self._h, C.byref(cs), ptr, n_bytes, optr, C.byref(o), C.byref(rep))
+        else:
+            a, w16 = record_bytes(settings, source)
+            if out is None:
+                res = np.empty(a.size // 2, dtype="<i2") if w16 else np.empty(a.size, dtype=np.asarray(source).dtype if np.asarray(source).dtype == np.uint8 else np.int8)
+            else:
+                res = out
+                if not isinstance(res, np.ndarray) or not res.flags.c_contiguous or res.nbytes != a.size:
+                    raise ValueError(f"out must be a contiguous NumPy array of the record's {a.size} bytes")
+            duty = blank_duty(rep, a.size // blank_sample_bytes(settings), lead, tail, duty_samples)
+            rc = self._lib.bds_blank(self._h, C.byref(cs), a.ctypes.data_as(C.c_void_p), a.size, res.ctypes.data_as(C.c_void_p), C.byref(o), C.byref(rep))
+        self._check(rc)
+        r = {k: int(getattr(rep, k)) for k in ("n_samples", "n_flagged", "n_blanked", "n_runs")}
+        r["duty"] = None if duty is None else duty[:int(rep.n_duty)]
+        return res, r
 
     def frame_sync(self, signal, prns, prompt, cap=64):
         """bds_frame_sync: prompt [n_ch, n] -> (xcorr int32 [n_ch, M], [1-based index arrays])."""

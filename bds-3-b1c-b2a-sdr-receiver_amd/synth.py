@@ -120,6 +120,38 @@ def make_if(settings, sats, n_samples, seed=3550, sigma=20.0, codegen=None, chun
     return out
 
 
+def dme_pulses(settings, n_samples, pairs_per_s, peak, f_offset=0.0, seed=0, iq_sign=0):
+    """DME / TACAN-like pulse interference for n_samples samples at settings.samplingFreq: float64[n_samples], or -- iq_sign
+    = +1 / -1 -- complex128 (the analytic signal or its conjugate, as make_if's iq_sign).  Pulse pairs arrive as a Poisson process
+    of pairs_per_s; a pair is two Gaussian pulses of 3.5 us width at half amplitude, 12 us apart, of amplitude `peak`, on a carrier at
+    IF + f_offset with a random phase per pair.  NumPy only.  The caller adds it to a record's values and quantises again with
+    clip(rint(.), -127, 127)."""
+    rng = np.random.default_rng(seed)
+    fs = float(settings.samplingFreq)
+    span = n_samples / fs
+    sig_t = 3.5e-6 / (2.0 * np.sqrt(2.0 * np.log(2.0)))  # half-amplitude width -> standard deviation
+    reach = 5.0 * sig_t
+    lo = -(12e-6 + reach)  # pairs that begin in front of the record still reach into it
+    n_pairs = int(rng.poisson(pairs_per_s * (span - lo)))
+    t0 = np.sort(rng.uniform(lo, span, n_pairs))
+    phase = rng.uniform(0.0, 2.0 * np.pi, n_pairs)
+    out = np.zeros(n_samples, dtype=np.complex128 if iq_sign else np.float64)
+    f = float(settings.IF) + float(f_offset)
+    for t, ph in zip(t0, phase):
+        for tc in (t, t + 12e-6):
+            a, b = max(int(np.floor((tc - reach) * fs)), 0), min(int(np.ceil((tc + reach) * fs)) + 1, n_samples)
+            if b <= a:
+                continue
+            tt = np.arange(a, b, dtype=np.float64) / fs
+            env = peak * np.exp(-0.5 * ((tt - tc) / sig_t) ** 2)
+            th = 2.0 * np.pi * f * (tt - t) + ph
+            if iq_sign:
+                out[a:b] += env * np.exp((1j if iq_sign > 0 else -1j) * th)
+            else:
+                out[a:b] += env * np.cos(th)
+    return out
+
+
 def _device_format(iq_sign, clean, packed):
     if clean:
         if iq_sign or packed:

@@ -977,6 +977,68 @@ BDS_API int bds_probe_set_piece_segments(bds_ctx *ctx, int64_t n_segments);
 BDS_PROBE_DEV_API int bds_probe_data_dev(bds_ctx *ctx, const bds_settings *s, const void *d_bytes, size_t n_bytes, int64_t n_time,
                                          bds_probe_out *out);
 
+/* ---- pulse blanking of an IF record (DME / TACAN mitigation in front of acquisition and tracking) ---------------------------
+ * B2a lies at 1176.45 MHz inside the aeronautical band; pulse pairs of DME / TACAN beacons reach peak powers tens of dB above the
+ * noise floor.  The blanker zeroes the samples around every strong one, on the record's own bytes: int8 real, int8 I/Q pairs,
+ * int16 real, int16 I/Q pairs (settings.fileType 1 / 2, dataType 0 / 1 as for bds_track).  The packed 2+2-bit format
+ * (fileType 3) has no amplitude to threshold: BDS_ERR_UNSUPPORTED.  A blanked record is an ordinary record of the same format.
+ * The rule, in integers only (csrc/bds_blank_math.h):
+ *   p[n]     = x^2 of a real sample, I^2 + Q^2 of a pair, as uint32 (at most 2 * 32768^2 = 2^31)
+ *   flagged  p[n] > opts.threshold_sq
+ *   blanked  there is a flagged m with m - pre <= n <= m + post: the hold-off window around each hit (the skirts of a Gaussian
+ *            pulse and the zero crossings of its carrier lie under any threshold); pre and post from 0 to BDS_BLANK_MAX_WINDOW
+ *   output   the record with every blanked sample set to 0 (both components of a pair), every other byte unchanged
+ * Context: the first opts.lead and the last opts.tail samples of the buffer are read for flags only; they are neither changed
+ *   nor counted, and out of place they are copied through.  A piece that carries post samples of the record in front of it and
+ *   pre behind gives byte for byte, and in n_flagged and n_blanked count for count, what one call over the whole record gives.
+ * Report (bds_blank_out; every value an exact integer, all of the buffer's samples outside lead / tail):
+ *   n_samples, n_flagged, n_blanked
+ *   n_runs   maximal runs of blanked samples (the pulse count): sample k begins a run when it is blanked and sample k - 1 is
+ *            not; the first sample behind `lead` looks at the blanked state the rule gives the last context sample, so a run that
+ *            crosses a seam is counted once, by the piece in which it begins.  That state needs one more flag than the bytes do:
+ *            the pieces' counts add up to the whole record's when lead is post + 1 (or reaches the record's start); the
+ *            library's own pieces (bds_blank, bds_blank_file) carry post + 1.
+ *   duty[k]  (when opts.duty_samples > 0) the blanked samples among [k duty_samples, (k + 1) duty_samples), counted from the
+ *            first sample behind `lead`; caller-allocated int32[duty_cap], n_duty = ceil(n_samples / duty_samples) bins are
+ *            written; duty_samples at most 2^31 - 1.  (Pieces of a caller's own add their bins up at the offsets they know.)
+ * bds_blank       n_bytes raw record bytes in host memory, through the device in pieces (bds_blank_file's, 64 MiB of the record
+ *                 each); out == in is allowed, a partial overlap is not.
+ * bds_blank_file  path_in -> path_out.  The window starts behind settings.skipNumberOfBytes, counted as bds_probe_data_file counts
+ *                 it (in samples), and runs for n_samples samples (<= 0: to the end of the file); the bytes in front of it and behind
+ *                 it are copied unchanged, so one settings struct reads both files.  Pieces of piece_samples samples (0: 64 MiB of
+ *                 the record) are read from the INPUT file with their context and go through two device buffers and two pinned
+ *                 host buffers on the context's two streams, piece k + 1 read and uploaded while piece k is worked on.  The result
+ *                 does not depend on piece_samples, bit for bit.  piece_samples (when given) below max(pre, post) + 1: BDS_ERR_ARG.
+ * bds_blank_dev   the record in DEVICE memory, read and written where it lies; d_out == d_in (in place) or a disjoint buffer.  The
+ *                 pointer rule and the ordering rule of the device-record entries hold for both pointers; both must be aligned
+ *                 to the element size (2 for a 16-bit record, any address for int8).  The aligned 16-byte lines inside the record
+ *                 move as 16-byte loads and stores, the ragged ends byte by byte (a d_out whose address differs from d_in's
+ *                 modulo 16 is written byte by byte throughout); no byte outside the record is written.  In place only the 16-byte
+ *                 lines that change are written.  Its marker has a name of its own, as BDS_PROBE_DEV_API has.
+ * Errors: BDS_ERR_ARG with a message BEFORE ANY DEVICE CALL (with ctx == NULL the message is bds_last_error(NULL)'s) for pre or
+ * post negative or above BDS_BLANK_MAX_WINDOW, lead + tail above the buffer's samples, a byte count that is not a whole number of
+ * samples (odd for pairs or 16-bit records), duty_cap below n_duty, duty_samples out of range, a partial overlap of in and out,
+ * NULL pointers; BDS_ERR_IO when a file cannot be opened, read or written. */
+#define BDS_BLANK_TILE 16384          /* samples per tile of the device pass (tests place their cases around it) */
+#define BDS_BLANK_MAX_WINDOW 1048576
+typedef struct bds_blank_opts {
+    uint32_t threshold_sq;
+    int32_t pre, post;
+    int64_t lead, tail, duty_samples;
+} bds_blank_opts;
+typedef struct bds_blank_out {
+    int64_t n_samples, n_flagged, n_blanked, n_runs;
+    int32_t *duty;              /* NULL, or caller-allocated [duty_cap] */
+    int64_t duty_cap, n_duty;
+} bds_blank_out;
+BDS_API int bds_blank(bds_ctx *ctx, const bds_settings *s, const void *in, size_t n_bytes, void *out, const bds_blank_opts *opts,
+                      bds_blank_out *report);
+BDS_API int bds_blank_file(bds_ctx *ctx, const bds_settings *s, const char *path_in, const char *path_out, int64_t n_samples,
+                           int64_t piece_samples, const bds_blank_opts *opts, bds_blank_out *report);
+#define BDS_BLANK_DEV_API __attribute__((visibility("default")))
+BDS_BLANK_DEV_API int bds_blank_dev(bds_ctx *ctx, const bds_settings *s, const void *d_in, size_t n_bytes, void *d_out,
+                                    const bds_blank_opts *opts, bds_blank_out *report);
+
 #ifdef __cplusplus
 }
 #endif

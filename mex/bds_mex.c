@@ -27,6 +27,11 @@
  *       16385 bins for fileType 1, else two-sided 32768 bins 0 .. fs), excerpt_re, excerpt_im (the samples of the time-domain
  *       plot), stats (min, max, sum, sum of squares of I, then of Q), n_segments, n_samples.  n_samples: 0 (default) = the
  *       window probeData.m reads, -1 = the whole file behind skipNumberOfBytes.
+ *   out = bds_mex('blank_pulses', path_in, path_out, settings, signal, threshold, pre, post[, duty_samples[, piece_samples]])
+ *       pulse blanking of a record file (mex/blankPulses.m; bds_blank_file): every sample within [m - pre, m + post] of a sample m of
+ *       amplitude above `threshold` (x^2 or I^2 + Q^2 > floor(threshold^2)) is set to 0 in path_out; the bytes in front of
+ *       settings.skipNumberOfBytes are copied.  struct with n_samples, n_flagged, n_blanked, n_runs, threshold_sq and duty (column:
+ *       blanked samples per duty_samples, empty when duty_samples is 0 or absent).  Not for fileType 3.
  *   out = bds_mex('corr_function', path, settings, prn, state6, taps)   % the correlation function of tracked epochs (mex/corrFunction.m
  *       builds prn and state6 from trackResults): prn 1 x n, state6 6 x n = {sample offset; blksize; remCodePhase; codeFreq;
  *       remCarrPhase; carrFreq} per item, taps in chips (at most 128, |tau| <= 16).  struct with I, Q ([numel(taps) * n_comp x n],
@@ -48,6 +53,7 @@
  * (tests/mex_stub/mex_mock.c) and runs every command and every error exit through ctypes.
  */
 #include <math.h>
+#include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 
@@ -417,6 +423,60 @@ static void do_probe_data(int nlhs, mxArray *plhs[], int nrhs, const mxArray *pr
     plhs[0] = out;
 }
 
+/* Pulse blanking of a record file in front of acquisition and tracking (bds_blank_file): file in, file out, the report */
+static void do_blank_pulses(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[]) {
+    bds_settings s;
+    bds_blank_opts o;
+    bds_blank_out r;
+    char path_in[4096], path_out[4096];
+    double thr, *pd;
+    int64_t piece = 0, bins = 0, file_samples, i;
+    int rc, sb;
+    FILE *f;
+    mxArray *rep;
+    (void)nlhs;
+    if (nrhs < 8 || nrhs > 10)
+        mexErrMsgIdAndTxt("bds:args", "blank_pulses: (path_in, path_out, settings, signal, threshold, pre, post[, duty_samples[, piece_samples]])");
+    if (mxGetString(prhs[1], path_in, sizeof(path_in)) || mxGetString(prhs[2], path_out, sizeof(path_out)))
+        mexErrMsgIdAndTxt("bds:args", "File name must be a string");
+    pack_settings(prhs[3], (int)mxGetScalar(prhs[4]), &s);
+    thr = mxGetScalar(prhs[5]);
+    if (!(thr >= 0)) mexErrMsgIdAndTxt("bds:args", "blank_pulses: threshold must be an amplitude >= 0");
+    memset(&o, 0, sizeof(o));
+    memset(&r, 0, sizeof(r));
+    o.threshold_sq = thr * thr >= 4294967295.0 ? 4294967295u : (uint32_t)floor(thr * thr);
+    o.pre = (int32_t)mxGetScalar(prhs[6]);
+    o.post = (int32_t)mxGetScalar(prhs[7]);
+    o.duty_samples = nrhs >= 9 ? (int64_t)mxGetScalar(prhs[8]) : 0;
+    if (nrhs == 10) piece = (int64_t)mxGetScalar(prhs[9]);
+    if (o.duty_samples > 0) { /* the bins of the window behind skipNumberOfBytes: the file's length tells how many */
+        sb = (s.fileType == 2 ? 2 : 1) * (s.dataType == 1 ? 2 : 1);
+        f = fopen(path_in, "rb");
+        if (!f) mexErrMsgIdAndTxt("bds:blank_pulses", "Unable to read file %s", path_in);
+        fseek(f, 0, SEEK_END);
+        file_samples = (int64_t)ftell(f) / sb - s.skipNumberOfBytes;
+        fclose(f);
+        bins = file_samples > 0 ? (file_samples + o.duty_samples - 1) / o.duty_samples : 0;
+        r.duty = (int32_t *)mxCalloc((size_t)(bins > 0 ? bins : 1), sizeof(int32_t));
+        r.duty_cap = bins;
+    }
+    rc = bds_blank_file(ctx(), &s, path_in, path_out, -1, piece, &o, &r);
+    if (rc) {
+        if (r.duty) mxFree(r.duty);
+        mexErrMsgIdAndTxt("bds:blank_pulses", "%s", bds_last_error(ctx()));
+    }
+    rep = mxCreateStructMatrix(1, 1, 0, NULL);
+    out_field(rep, "n_samples", 1, 1)[0] = (double)r.n_samples;
+    out_field(rep, "n_flagged", 1, 1)[0] = (double)r.n_flagged;
+    out_field(rep, "n_blanked", 1, 1)[0] = (double)r.n_blanked;
+    out_field(rep, "n_runs", 1, 1)[0] = (double)r.n_runs;
+    out_field(rep, "threshold_sq", 1, 1)[0] = (double)o.threshold_sq;
+    pd = out_field(rep, "duty", (int)r.n_duty, r.n_duty ? 1 : 0);
+    for (i = 0; i < r.n_duty; ++i) pd[i] = (double)r.duty[i];
+    if (r.duty) mxFree(r.duty);
+    plhs[0] = rep;
+}
+
 /* postNavigation.m:100-298 of either receiver behind the decoding loop: readiness, measurement grid, pseudoranges, satellite and
  * receiver positions (bds_post_navigation).  mex/B1C/postNavigation.m and mex/B2a/postNavigation.m decode the channels with
  * 'nav_decode' and hand its eph structs back in. */
@@ -598,6 +658,8 @@ void mexFunction(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[]) {
         do_nav_decode(nlhs, plhs, nrhs, prhs);
     else if (!strcmp(cmd, "probe_data"))
         do_probe_data(nlhs, plhs, nrhs, prhs);
+    else if (!strcmp(cmd, "blank_pulses"))
+        do_blank_pulses(nlhs, plhs, nrhs, prhs);
     else if (!strcmp(cmd, "corr_function"))
         do_corr_function(nlhs, plhs, nrhs, prhs);
     else if (!strcmp(cmd, "post_navigation"))
