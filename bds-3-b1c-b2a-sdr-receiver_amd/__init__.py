@@ -10,6 +10,7 @@ Host-side mirror of the reference's MATLAB call surface
     TrackSession(source, channel, settings)                     the same run advanced in pieces, or fed by the caller
     probe_data(settings) / probe_data(fileName, settings)       include/probeData.m (the numbers; also arrays and device tensors)
     blank_pulses(source, settings, ...)                         pulse blanking of a record (DME / TACAN), file, array or device tensor
+    notch_tones(source, settings, tones, ...)                   excision of CW / narrow-band interference, block by block, same sources
     frame_sync(trackResults, settings)                          include/BCNAV?decoding.m, the correlators
     nav_decode(trackResults, settings)                          include/BCNAV?decoding.m + ephemeris.m: eph, firstSubFrame, TOW
     navSolutions, eph = post_navigation(trackResults, settings) postNavigation.m: pseudoranges, satellite and receiver positions
@@ -24,6 +25,7 @@ from .framesync import frame_sync, unpack_cplx  # noqa: F401
 from .distributed import shard_prns, shard_joint, sharded_acquisition, sharded_acquisition_joint  # noqa: F401
 from .probedata import probe_data, ProbeResult  # noqa: F401
 from .blank import blank_pulses, blank_threshold, BlankReport  # noqa: F401
+from .notch import notch_tones, notch_step, notch_detect, notch_refine, NotchReport  # noqa: F401
 from .corrfn import corr_function, track_states  # noqa: F401
 from .navdecode import nav_decode, BCNAV1decoding, BCNAV2decoding  # noqa: F401
 from .pvt import post_navigation, postNavigation, pvt_plan, pvt_measure, pvt_solve  # noqa: F401

@@ -162,6 +162,24 @@ class BlankOut(C.Structure):
                 ("duty", C.POINTER(C.c_int32)), ("duty_cap", C.c_int64), ("n_duty", C.c_int64)]
 
 
+class NotchOpts(C.Structure):
+    _fields_ = [("n_tones", C.c_int32), ("block_log2", C.c_int32), ("step", C.c_uint32 * 8), ("first_sample", C.c_int64),
+                ("apply", C.c_int32), ("reserved", C.c_int32)]
+
+
+class NotchOut(C.Structure):
+    _fields_ = [("n_samples", C.c_int64), ("n_blocks", C.c_int64), ("n_saturated", C.c_int64), ("sum_sq_in", C.c_uint64),
+                ("sum_sq_out", C.c_uint64), ("est", C.POINTER(C.c_int32)), ("est_cap", C.c_int64)]
+
+
+NOTCH_MAX_TONES = 8          # BDS_NOTCH_MAX_TONES
+NOTCH_MIN_LOG2 = 8           # BDS_NOTCH_MIN_LOG2
+NOTCH_MAX_LOG2 = 16          # BDS_NOTCH_MAX_LOG2
+NOTCH_PHASE_BITS = 14        # BDS_NOTCH_PHASE_BITS: the LO table holds 2^14 entries
+NOTCH_LO_LOG2 = 14           # BDS_NOTCH_LO_LOG2: its amplitude L = 2^14
+NOTCH_AMP_FRAC = 8           # BDS_NOTCH_AMP_FRAC: estimates in 1 / 256 LSB
+NOTCH_RUN_BYTES = 1048576    # BDS_NOTCH_RUN_BYTES: record bytes per workgroup of the excisor's device passes
+
 BLANK_TILE = 16384           # BDS_BLANK_TILE: samples per tile of the blanker's device pass
 BLANK_MAX_WINDOW = 1048576   # BDS_BLANK_MAX_WINDOW: the largest pre / post
 
@@ -185,6 +203,7 @@ EXPORTS = [
     "bds_synth", "bds_synth_file", "bds_synth_noise", "bds_synth_trajectory", "bds_synth_traj",
     "bds_probe_data", "bds_probe_data_file", "bds_probe_set_piece_segments",
     "bds_blank", "bds_blank_file",
+    "bds_notch", "bds_notch_file", "bds_notch_lo",
     "bds_corr_function", "bds_corr_function_mem",
     "bds_nav_decode", "bds_nav_fields",
     "bds_pvt_plan", "bds_pvt_measure", "bds_pvt_solve", "bds_post_navigation",
@@ -197,6 +216,8 @@ SYNTH_DEVICE_EXPORTS = ["bds_synth_traj_dev"]
 PROBE_DEVICE_EXPORTS = ["bds_probe_data_dev"]
 # the entry marked BDS_BLANK_DEV_API: device pointers as well (record in, record out)
 BLANK_DEVICE_EXPORTS = ["bds_blank_dev"]
+# the entry marked BDS_NOTCH_DEV_API: device pointers as well (record in, record out)
+NOTCH_DEVICE_EXPORTS = ["bds_notch_dev"]
 # the entry marked BDS_CORR_DEV_API: a device pointer as well
 CORR_DEVICE_EXPORTS = ["bds_corr_function_dev"]
 
@@ -343,6 +364,12 @@ def lib():
         L.bds_blank.restype, L.bds_blank.argtypes = i32, [vp, SP, vp, sz, vp, BO, BR]
         L.bds_blank_file.restype, L.bds_blank_file.argtypes = i32, [vp, SP, C.c_char_p, C.c_char_p, i64, i64, BO, BR]
         L.bds_blank_dev.restype, L.bds_blank_dev.argtypes = i32, [vp, SP, vp, sz, vp, BO, BR]
+    if hasattr(L, "bds_notch"):  # (as above: a build of an older commit has no tone excisor)
+        NO, NR, i64 = C.POINTER(NotchOpts), C.POINTER(NotchOut), C.c_int64
+        L.bds_notch.restype, L.bds_notch.argtypes = i32, [vp, SP, vp, sz, vp, NO, NR]
+        L.bds_notch_file.restype, L.bds_notch_file.argtypes = i32, [vp, SP, C.c_char_p, C.c_char_p, i64, i64, NO, NR]
+        L.bds_notch_dev.restype, L.bds_notch_dev.argtypes = i32, [vp, SP, vp, sz, vp, NO, NR]
+        L.bds_notch_lo.restype, L.bds_notch_lo.argtypes = i32, [C.POINTER(C.c_int16)]
     if hasattr(L, "bds_corr_function"):  # (as above: a build of an older commit has no correlation function)
         tail = [i32, _IP, _DP, i32, _DP, _DP, _IP]  # n_items, prn, state6, n_taps, taps, out, n_comp
         L.bds_corr_function.restype, L.bds_corr_function.argtypes = i32, [vp, SP, C.c_char_p] + tail
@@ -697,6 +724,38 @@ def blank_duty(rep, n, lead, tail, duty_samples):
     duty = np.zeros(max(-(-max(int(n) - int(lead) - int(tail), 0) // ds), 1), dtype=np.int32)
     rep.duty, rep.duty_cap = duty.ctypes.data_as(_IP), duty.size
     return duty
+
+
+def pack_notch(steps, block_log2, first_sample=0, apply=True):
+    """(bds_notch_opts, bds_notch_out without an est array) of one bds_notch* call; steps: uint32 phase steps per sample."""
+    o, rep = NotchOpts(), NotchOut()
+    steps = [int(v) for v in steps]
+    if any(not 0 <= v <= 2 ** 32 - 1 for v in steps):
+        raise ValueError(f"steps = {steps!r}: each is a uint32 phase step")
+    o.n_tones, o.block_log2, o.first_sample, o.apply = len(steps), int(block_log2), int(first_sample), 1 if apply else 0
+    for k, v in enumerate(steps[:NOTCH_MAX_TONES]):
+        o.step[k] = v
+    return o, rep
+
+
+def notch_est(rep, n, block_log2, n_tones, want=True):
+    """The int32 [n_blocks, n_tones, 2] estimates of a window of n samples, hung into `rep` (want=False: None, nothing hung)."""
+    if not want:
+        return None
+    nb = -(-max(int(n), 0) // (1 << int(block_log2))) if 0 <= int(block_log2) < 32 else 0
+    est = np.zeros((nb, max(int(n_tones), 0), 2), dtype=np.int32)
+    if est.size:
+        rep.est, rep.est_cap = est.ctypes.data_as(_IP), nb * int(n_tones)
+    return est
+
+
+def notch_lo() -> np.ndarray:
+    """bds_notch_lo (no GPU): the excisor's local-oscillator table, int16 [2, 2^14]: cosines, then sines."""
+    t = np.zeros((2, 1 << NOTCH_PHASE_BITS), dtype=np.int16)
+    rc = lib().bds_notch_lo(t.ctypes.data_as(C.POINTER(C.c_int16)))
+    if rc < 0:
+        raise BdsError(rc, lib().bds_last_error(None).decode())
+    return t
 
 
 def synth_out(fmt, n_samples) -> np.ndarray:
@@ -1201,6 +1260,51 @@ class Context:
         self._check(rc)
         r = {k: int(getattr(rep, k)) for k in ("n_samples", "n_flagged", "n_blanked", "n_runs")}
         r["duty"] = None if duty is None else duty[:int(rep.n_duty)]
+        return res, r
+
+    # -- tone excision (bds_notch*) -----------------------------------------------------------
+    def notch(self, settings, source, steps, block_log2, out=None, first_sample=0, apply=True, n_samples=-1, piece_samples=0, want_est=True):
+        """bds_notch (host array -> `out`, a host array of the same bytes, or None: a new one), bds_notch_file (path -> the path
+        `out`) or bds_notch_dev (a device array -> `out`, a device array of the same size or the same array; None: in place).
+        apply=False estimates only: nothing is written and the record returned is None.  Returns (the record written, a dict of
+        n_samples, n_blocks, n_saturated, sum_sq_in, sum_sq_out and est: int32 [n_blocks, n_tones, 2]; want_est=False leaves the
+        estimates on the device and est None)."""
+        cs = pack_settings(settings)
+        o, rep = pack_notch(steps, block_log2, first_sample, apply)
+        sb = blank_sample_bytes(settings)
+        if isinstance(source, (str, bytes, os.PathLike)):
+            if apply and not isinstance(out, (str, bytes, os.PathLike)):
+                raise ValueError("notching a file writes a file: out must be a path")
+            n = int(n_samples) if int(n_samples) > 0 else os.path.getsize(source) // sb - int(settings.skipNumberOfBytes)
+            est = notch_est(rep, n, block_log2, len(steps), want_est)
+            rc = self._lib.bds_notch_file(self._h, C.byref(cs), os.fsencode(source), os.fsencode(out) if apply else None, int(n_samples),
+                                          int(piece_samples), C.byref(o), C.byref(rep))
+            res = out if apply else None
+        elif is_device_array(source):
+            ptr, n_bytes, keep, _ = device_record(settings, source, self.device)
+            res, optr = None, None
+            if apply:
+                res = source if out is None else out
+                optr, on_bytes, okeep, _ = device_record(settings, res, self.device, "the output record")
+                if on_bytes != n_bytes:
+                    raise ValueError(f"the output record holds {on_bytes} bytes, the input {n_bytes}")
+            est = notch_est(rep, n_bytes // sb, block_log2, len(steps), want_est)
+            rc = self._lib.bds_notch_dev(self._h, C.byref(cs), ptr, n_bytes, optr, C.byref(o), C.byref(rep))
+        else:
+            a, w16 = record_bytes(settings, source)
+            res = None
+            if apply and out is None:
+                res = np.empty(a.size // 2, dtype="<i2") if w16 else np.empty(a.size, dtype=np.asarray(source).dtype if np.asarray(source).dtype == np.uint8 else np.int8)
+            elif apply:
+                res = out
+                if not isinstance(res, np.ndarray) or not res.flags.c_contiguous or res.nbytes != a.size:
+                    raise ValueError(f"out must be a contiguous NumPy array of the record's {a.size} bytes")
+            est = notch_est(rep, a.size // sb, block_log2, len(steps), want_est)
+            rc = self._lib.bds_notch(self._h, C.byref(cs), a.ctypes.data_as(C.c_void_p), a.size, res.ctypes.data_as(C.c_void_p) if apply else None,
+                                     C.byref(o), C.byref(rep))
+        self._check(rc)
+        r = {k: int(getattr(rep, k)) for k in ("n_samples", "n_blocks", "n_saturated", "sum_sq_in", "sum_sq_out")}
+        r["est"] = None if est is None else est[:r["n_blocks"]]
         return res, r
 
     def frame_sync(self, signal, prns, prompt, cap=64):

@@ -152,6 +152,23 @@ def dme_pulses(settings, n_samples, pairs_per_s, peak, f_offset=0.0, seed=0, iq_
     return out
 
 
+def cw_tones(settings, n_samples, tones, first_sample=0, iq_sign=0):
+    """Continuous narrow-band interferers for samples first_sample .. first_sample + n_samples - 1 at settings.samplingFreq:
+    float64[n_samples], or -- iq_sign = +1 / -1 -- complex128 (the analytic signal or its conjugate, as make_if's iq_sign).
+    tones: (f_offset from settings.IF [Hz], amplitude, phase [rad]) each; the sum of amplitude cos(2 pi (IF + f_offset) t + phase),
+    t = n / fs.  NumPy only.  The caller adds it to a record's values and quantises again with clip(rint(.))."""
+    n = int(n_samples)
+    out = np.zeros(n, dtype=np.complex128 if iq_sign else np.float64)
+    t = (np.arange(n, dtype=np.float64) + float(first_sample)) / float(settings.samplingFreq)
+    for f_offset, amp, ph in tones:
+        th = 2.0 * np.pi * (float(settings.IF) + float(f_offset)) * t + float(ph)
+        if iq_sign:
+            out += float(amp) * np.exp((1j if iq_sign > 0 else -1j) * th)
+        else:
+            out += float(amp) * np.cos(th)
+    return out
+
+
 def _device_format(iq_sign, clean, packed):
     if clean:
         if iq_sign or packed:

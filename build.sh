@@ -52,7 +52,7 @@ compile() {  # source, object, extra flags...
     fi
 }
 objs=(); hobjs=(); pids=()
-for f in bds_acq.hip bds_track.hip bds_corrfn.hip bds_codes.cpp bds_nav.cpp bds_pvt.cpp bds_pvt.hip bds_api.hip bds_sync.hip bds_multi.hip bds_synth.hip bds_synth_traj.cpp bds_probedata.hip bds_blank.hip; do
+for f in bds_acq.hip bds_track.hip bds_corrfn.hip bds_codes.cpp bds_nav.cpp bds_pvt.cpp bds_pvt.hip bds_api.hip bds_sync.hip bds_multi.hip bds_synth.hip bds_synth_traj.cpp bds_probedata.hip bds_blank.hip bds_notch.hip; do
     o="$BLD/${f%.*}.o"
     [[ "$f" == *.cpp ]] && o="$BLD/${f%.*}_cpp.o"   # (bds_pvt.cpp and bds_pvt.hip are two objects)
     compile "$f" "$o" & pids+=($!)

@@ -1039,6 +1039,82 @@ BDS_API int bds_blank_file(bds_ctx *ctx, const bds_settings *s, const char *path
 BDS_BLANK_DEV_API int bds_blank_dev(bds_ctx *ctx, const bds_settings *s, const void *d_in, size_t n_bytes, void *d_out,
                                     const bds_blank_opts *opts, bds_blank_out *report);
 
+/* ---- tone excision of an IF record (narrow-band / CW interference in front of acquisition and tracking) -----------------------
+ * The blanker can do nothing against a continuous carrier: a CW line stands above any amplitude threshold all the time or never.
+ * The excisor estimates each interfering carrier's complex amplitude block by block and subtracts it, on the record's own bytes:
+ * int8 real, int8 I/Q pairs, int16 real, int16 I/Q pairs (settings.fileType 1 / 2, dataType 0 / 1).  The packed 2+2-bit format
+ * (fileType 3) has no amplitude to subtract from: BDS_ERR_UNSUPPORTED.  A notched record is an ordinary record of the same format.
+ * The rule, in integers only (csrc/bds_notch_math.h), so every source, every piece size and the NumPy model of the tests give the
+ * same bytes and the same report:
+ *   tones    opts.n_tones of them (1 .. BDS_NOTCH_MAX_TONES), each a uint32 phase step per sample in units of 2^-32 turn,
+ *            step = floor(f / fs 2^32 + 0.5) mod 2^32 (a negative frequency of an I/Q record is the two's complement).  The phase
+ *            of sample n is phi(n) = step (n mod 2^32) mod 2^32; n is the absolute index, opts.first_sample + position in the buffer.
+ *   LO       i = ((phi + 2^(31 - P)) >> (32 - P)) mod 2^P, P = BDS_NOTCH_PHASE_BITS; lo(n) = (C[i], S[i]) with
+ *            S[i] = rint(L sin(2 pi i / 2^P)), L = 2^BDS_NOTCH_LO_LOG2, C[i] = S[(i + 2^(P - 2)) mod 2^P].  The table is defined by
+ *            its first quadrant (f64 on the host) and the exact symmetries of sine; bds_notch_lo hands it out.
+ *   blocks   B = 2^opts.block_log2 samples (BDS_NOTCH_MIN_LOG2 .. BDS_NOTCH_MAX_LOG2) on the absolute grid: first_sample mod B == 0;
+ *            a last block of r < B samples is allowed.  One notch is fs / B wide.
+ *   estimate per block and tone: zr = x C, zi = -x S (real), zr = I C + Q S, zi = Q C - I S (pairs); Sr, Si their int64 sums over
+ *            the block's r samples (at most 2^46); ar = floor((2 256 Sr + r L) / (2 r L)), ai alike: the tone's complex amplitude
+ *            in 1 / 256 LSB (BDS_NOTCH_AMP_FRAC = 8), int32.  For r = B this is (S + 2^(beta + 5)) >> (beta + 6), beta = block_log2.
+ *   subtract er = sum_k (ar_k C_k - ai_k S_k), ei = sum_k (ar_k S_k + ai_k C_k) in int64.  Real: y = x - ((er + 2^20) >> 21) (twice the
+ *            real part: the projection of a real tone carries half its amplitude).  Pairs: yI = I - ((er + 2^21) >> 22),
+ *            yQ = Q - ((ei + 2^21) >> 22).  Arithmetic shifts; y is saturated to the element's range.
+ * The tones are projected independently: two tones D notch widths apart leak about 1 / (pi D) of their amplitude into each other's
+ * estimate; a second call on the output removes the remainder.
+ * Report (bds_notch_out; every value an exact integer):
+ *   n_samples, n_blocks
+ *   n_saturated   samples with any saturated component (each counted once)
+ *   sum_sq_in, sum_sq_out   sums of x^2 (I^2 + Q^2) before and after, modulo 2^64; their ratio is the removed power
+ *   est      (when the caller gives est / est_cap) int32 [n_blocks][n_tones][2]: ar, ai; est_cap counts (ar, ai) pairs
+ * opts.apply = 0 estimates only: the output is not touched and may be NULL; sum_sq_out and n_saturated are 0.
+ * bds_notch       n_bytes raw record bytes in host memory, through the device in pieces (64 MiB of the record each, whole
+ *                 blocks); out == in is allowed, a partial overlap is not.
+ * bds_notch_file  path_in -> path_out.  The window starts behind settings.skipNumberOfBytes (counted in samples as
+ *                 bds_blank_file counts it), is sample opts.first_sample (0 for a record from its start) and runs for n_samples
+ *                 samples (<= 0: to the end of the file); the bytes in front of it and behind it are copied unchanged.  Pieces of
+ *                 piece_samples samples, rounded down to whole blocks (0: 64 MiB of the record; below one block: BDS_ERR_ARG), go
+ *                 through two device buffers and two pinned host buffers on the context's two streams.  Blocks are
+ *                 self-contained, so the pieces' bytes, estimates and sums are the one call's exactly.
+ * bds_notch_dev   the record in DEVICE memory, read and written where it lies; d_out == d_in (in place) or a disjoint buffer; both
+ *                 aligned to the element size.  Every estimate is finished before any byte is written, and the second pass reads
+ *                 only the 16 bytes it writes.  A record whose address is a multiple of 16 moves as 16-byte loads and stores, its
+ *                 ragged end byte by byte; any other address is read (written) byte by byte throughout.  No byte outside the
+ *                 record is read or written.  A caller working in pieces of its own passes first_sample.
+ * bds_notch_lo    the table, C[0 .. 2^P) then S[0 .. 2^P); needs no GPU and no context.
+ * Errors: BDS_ERR_ARG with a message BEFORE ANY DEVICE CALL (with ctx == NULL the message is bds_last_error(NULL)'s) for n_tones or
+ * block_log2 out of range, first_sample negative or off the block grid, two steps closer than 4 2^(32 - beta) in circular
+ * distance, for a real record a step outside (0, 2^31) or closer than 2 2^(32 - beta) to 0 or to 2^31 (there the tone and its image
+ * cannot be told apart), a byte count that is not whole samples, a partial overlap of in and out, est_cap below
+ * n_blocks x n_tones, NULL pointers; BDS_ERR_IO when a file cannot be opened, read or written. */
+#define BDS_NOTCH_MAX_TONES 8
+#define BDS_NOTCH_MIN_LOG2 8
+#define BDS_NOTCH_MAX_LOG2 16
+#define BDS_NOTCH_PHASE_BITS 14
+#define BDS_NOTCH_LO_LOG2 14
+#define BDS_NOTCH_AMP_FRAC 8
+#define BDS_NOTCH_RUN_BYTES 1048576   /* record bytes per workgroup of the device passes: a run of whole blocks (tests cross it) */
+typedef struct bds_notch_opts {
+    int32_t n_tones, block_log2;
+    uint32_t step[BDS_NOTCH_MAX_TONES];
+    int64_t first_sample;
+    int32_t apply, reserved;    /* apply: 0 estimates only */
+} bds_notch_opts;
+typedef struct bds_notch_out {
+    int64_t n_samples, n_blocks, n_saturated;
+    uint64_t sum_sq_in, sum_sq_out;
+    int32_t *est;               /* NULL, or caller-allocated [est_cap][2] */
+    int64_t est_cap;
+} bds_notch_out;
+BDS_API int bds_notch(bds_ctx *ctx, const bds_settings *s, const void *in, size_t n_bytes, void *out, const bds_notch_opts *opts,
+                      bds_notch_out *report);
+BDS_API int bds_notch_file(bds_ctx *ctx, const bds_settings *s, const char *path_in, const char *path_out, int64_t n_samples,
+                           int64_t piece_samples, const bds_notch_opts *opts, bds_notch_out *report);
+BDS_API int bds_notch_lo(int16_t *cos_sin);
+#define BDS_NOTCH_DEV_API __attribute__((visibility("default")))
+BDS_NOTCH_DEV_API int bds_notch_dev(bds_ctx *ctx, const bds_settings *s, const void *d_in, size_t n_bytes, void *d_out,
+                                    const bds_notch_opts *opts, bds_notch_out *report);
+
 #ifdef __cplusplus
 }
 #endif

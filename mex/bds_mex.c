@@ -32,6 +32,13 @@
  *       amplitude above `threshold` (x^2 or I^2 + Q^2 > floor(threshold^2)) is set to 0 in path_out; the bytes in front of
  *       settings.skipNumberOfBytes are copied.  struct with n_samples, n_flagged, n_blanked, n_runs, threshold_sq and duty (column:
  *       blanked samples per duty_samples, empty when duty_samples is 0 or absent).  Not for fileType 3.
+ *   out = bds_mex('notch_tones', path_in, path_out, settings, signal, freqs, block_log2[, piece_samples])
+ *       excision of narrow-band (CW) interference from a record file (mex/notchTones.m; bds_notch_file): per block of 2^block_log2
+ *       samples the complex amplitude of every tone of freqs (Hz on probe_data's axis: 0 .. fs / 2 for fileType 1, signed baseband
+ *       frequencies else; at most 8) is estimated and the tone subtracted in path_out; the bytes in front of
+ *       settings.skipNumberOfBytes are copied.  struct with n_samples, n_blocks, n_saturated, sum_sq_in, sum_sq_out (doubles: exact
+ *       below 2^53), steps (1 x n_tones, the uint32 phase steps applied) and est_re, est_im (n_blocks x n_tones, in LSB).  Not
+ *       for fileType 3.
  *   out = bds_mex('corr_function', path, settings, prn, state6, taps)   % the correlation function of tracked epochs (mex/corrFunction.m
  *       builds prn and state6 from trackResults): prn 1 x n, state6 6 x n = {sample offset; blksize; remCodePhase; codeFreq;
  *       remCarrPhase; carrFreq} per item, taps in chips (at most 128, |tau| <= 16).  struct with I, Q ([numel(taps) * n_comp x n],
@@ -477,6 +484,73 @@ static void do_blank_pulses(int nlhs, mxArray *plhs[], int nrhs, const mxArray *
     plhs[0] = rep;
 }
 
+/* Tone excision of a record file in front of acquisition and tracking (bds_notch_file): file in, file out, report and estimates */
+static void do_notch_tones(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[]) {
+    bds_settings s;
+    bds_notch_opts o;
+    bds_notch_out r;
+    char path_in[4096], path_out[4096];
+    double *pf, *pr, *pi;
+    int64_t piece = 0, file_samples, n_blocks, b;
+    int rc, sb, k, n_tones;
+    FILE *f;
+    mxArray *nr;
+    (void)nlhs;
+    if (nrhs < 7 || nrhs > 8 || !mxIsDouble(prhs[5]))
+        mexErrMsgIdAndTxt("bds:args", "notch_tones: (path_in, path_out, settings, signal, freqs, block_log2[, piece_samples])");
+    if (mxGetString(prhs[1], path_in, sizeof(path_in)) || mxGetString(prhs[2], path_out, sizeof(path_out)))
+        mexErrMsgIdAndTxt("bds:args", "File name must be a string");
+    pack_settings(prhs[3], (int)mxGetScalar(prhs[4]), &s);
+    n_tones = (int)mxGetNumberOfElements(prhs[5]);
+    if (n_tones < 1 || n_tones > BDS_NOTCH_MAX_TONES) mexErrMsgIdAndTxt("bds:args", "notch_tones: freqs holds 1 to %d frequencies", BDS_NOTCH_MAX_TONES);
+    memset(&o, 0, sizeof(o));
+    memset(&r, 0, sizeof(r));
+    pf = mxGetDoubles(prhs[5]);
+    for (k = 0; k < n_tones; ++k) { /* floor(f / fs 2^32 + 0.5) mod 2^32 */
+        double t = fmod(floor(pf[k] / s.samplingFreq * 4294967296.0 + 0.5), 4294967296.0);
+        if (!(t == t)) mexErrMsgIdAndTxt("bds:args", "notch_tones: freqs(%d) is not a frequency", k + 1);
+        if (t < 0) t += 4294967296.0;
+        o.step[k] = (uint32_t)t;
+    }
+    o.n_tones = n_tones;
+    o.block_log2 = (int32_t)mxGetScalar(prhs[6]);
+    o.apply = 1;
+    if (nrhs == 8) piece = (int64_t)mxGetScalar(prhs[7]);
+    if (o.block_log2 < BDS_NOTCH_MIN_LOG2 || o.block_log2 > BDS_NOTCH_MAX_LOG2)
+        mexErrMsgIdAndTxt("bds:args", "notch_tones: block_log2 runs from %d to %d", BDS_NOTCH_MIN_LOG2, BDS_NOTCH_MAX_LOG2);
+    sb = (s.fileType == 2 ? 2 : 1) * (s.dataType == 1 ? 2 : 1); /* the estimates of the window behind skipNumberOfBytes */
+    f = fopen(path_in, "rb");
+    if (!f) mexErrMsgIdAndTxt("bds:notch_tones", "Unable to read file %s", path_in);
+    fseek(f, 0, SEEK_END);
+    file_samples = (int64_t)ftell(f) / sb - s.skipNumberOfBytes;
+    fclose(f);
+    n_blocks = file_samples > 0 ? (file_samples + ((int64_t)1 << o.block_log2) - 1) >> o.block_log2 : 0;
+    r.est = (int32_t *)mxCalloc((size_t)(n_blocks > 0 ? n_blocks : 1) * n_tones * 2, sizeof(int32_t));
+    r.est_cap = n_blocks * n_tones;
+    rc = bds_notch_file(ctx(), &s, path_in, path_out, -1, piece, &o, &r);
+    if (rc) {
+        mxFree(r.est);
+        mexErrMsgIdAndTxt("bds:notch_tones", "%s", bds_last_error(ctx()));
+    }
+    nr = mxCreateStructMatrix(1, 1, 0, NULL);
+    out_field(nr, "n_samples", 1, 1)[0] = (double)r.n_samples;
+    out_field(nr, "n_blocks", 1, 1)[0] = (double)r.n_blocks;
+    out_field(nr, "n_saturated", 1, 1)[0] = (double)r.n_saturated;
+    out_field(nr, "sum_sq_in", 1, 1)[0] = (double)r.sum_sq_in;
+    out_field(nr, "sum_sq_out", 1, 1)[0] = (double)r.sum_sq_out;
+    pf = out_field(nr, "steps", 1, n_tones);
+    for (k = 0; k < n_tones; ++k) pf[k] = (double)o.step[k];
+    pr = out_field(nr, "est_re", (int)r.n_blocks, n_tones);
+    pi = out_field(nr, "est_im", (int)r.n_blocks, n_tones);
+    for (b = 0; b < r.n_blocks; ++b)
+        for (k = 0; k < n_tones; ++k) { /* column-major [n_blocks x n_tones] */
+            pr[(size_t)k * r.n_blocks + b] = (double)r.est[(b * n_tones + k) * 2] / (double)(1 << BDS_NOTCH_AMP_FRAC);
+            pi[(size_t)k * r.n_blocks + b] = (double)r.est[(b * n_tones + k) * 2 + 1] / (double)(1 << BDS_NOTCH_AMP_FRAC);
+        }
+    mxFree(r.est);
+    plhs[0] = nr;
+}
+
 /* postNavigation.m:100-298 of either receiver behind the decoding loop: readiness, measurement grid, pseudoranges, satellite and
  * receiver positions (bds_post_navigation).  mex/B1C/postNavigation.m and mex/B2a/postNavigation.m decode the channels with
  * 'nav_decode' and hand its eph structs back in. */
@@ -660,6 +734,8 @@ void mexFunction(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[]) {
         do_probe_data(nlhs, plhs, nrhs, prhs);
     else if (!strcmp(cmd, "blank_pulses"))
         do_blank_pulses(nlhs, plhs, nrhs, prhs);
+    else if (!strcmp(cmd, "notch_tones"))
+        do_notch_tones(nlhs, plhs, nrhs, prhs);
     else if (!strcmp(cmd, "corr_function"))
         do_corr_function(nlhs, plhs, nrhs, prhs);
     else if (!strcmp(cmd, "post_navigation"))
