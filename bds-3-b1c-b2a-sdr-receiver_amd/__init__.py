@@ -5,6 +5,7 @@ Host-side mirror of the reference's MATLAB call surface
 
     settings   = init_settings_b1c() / init_settings_b2a()      initSettings.m
     acqResults = acquisition(longSignal, settings)              acquisition.m / GPU_acquisition.m
+    acqResults = acquisition_deep(longSignal, settings, K, thr) weak signals: power sums of the search over K code periods (extension)
     channel    = pre_run(acqResults, settings)                  include/preRun.m
     trackResults, channel = tracking(fid, channel, settings)    tracking.m / NB_tracking.m / WB_tracking.m
     TrackSession(source, channel, settings)                     the same run advanced in pieces, or fed by the caller
@@ -19,7 +20,7 @@ All numeric work happens in ``libbds_mi355x.so`` (HIP kernels for gfx950) throug
 the C ABI of ``include/bds_mi355x.h``; there is no CPU fallback.
 """
 from .settings import Settings, init_settings_b1c, init_settings_b2a  # noqa: F401
-from .acquisition import acquisition, GPU_acquisition, AcqResults, get_context, release_context  # noqa: F401
+from .acquisition import acquisition, GPU_acquisition, acquisition_deep, AcqResults, get_context, release_context  # noqa: F401
 from .tracking import tracking, NB_tracking, WB_tracking, pre_run, acquire_track, TrackResults, TrackSession  # noqa: F401
 from .framesync import frame_sync, unpack_cplx  # noqa: F401
 from .distributed import shard_prns, shard_joint, sharded_acquisition, sharded_acquisition_joint  # noqa: F401

@@ -117,6 +117,23 @@ def acquisition(long_signal, settings, device: int = 0, prn_list=None, verbose: 
     return AcqResults(carrFreq=carr, codePhase=cph, peakMetric=pm)
 
 
+def acquisition_deep(long_signal, settings, n_blocks, threshold, compensate=True, keep_surface=False, surface_gib=0.0, device: int = 0,
+                     verbose: bool = False) -> AcqResults:
+    """Weak-signal acquisition (extension; include/bds_mi355x.h "weak-signal acquisition"): the coarse search's squared surfaces of
+    n_blocks blocks one code period apart are added -- aligned per Doppler bin by the code drift unless compensate=False -- and a PRN
+    is detected when deepMetric, (peak - mean) / (largest other value - mean) of its surface, exceeds `threshold` (> 1; the README
+    lists noise-only values).  long_signal: as for acquisition(), int8 real or I/Q, a NumPy array or a torch tensor in HBM, at least
+    N + n_blocks * samplesPerCode samples.  Returns the acqResults fields -- carrFreq and codePhase zero where not detected, so the
+    result feeds pre_run unchanged -- plus deepMetric and fbin (1-based).  keep_surface=True keeps the surfaces for
+    get_context(device).acq_deep_row; acq_deep_fine gives a detected PRN's fine-frequency sums."""
+    ctx = get_context(device)
+    samples, is_complex = _device_block(long_signal, settings) if native.is_device_array(long_signal) else _as_int8(long_signal, settings)
+    carr, cph, pm, dm, fb, det = ctx.acq_deep(settings, samples, is_complex, n_blocks, threshold, compensate, keep_surface, surface_gib)
+    if verbose:
+        sys.stdout.write("(" + "".join(f"{int(p):02d} " if det[int(p) - 1] else ". " for p in np.atleast_1d(settings.acqSatelliteList)) + ")\n")
+    return AcqResults(carrFreq=carr, codePhase=cph, peakMetric=pm, deepMetric=dm, fbin=fb)
+
+
 def GPU_acquisition(long_signal, settings, **kw) -> AcqResults:
     """B1C/GPU_acquisition.m:1 -- same native entry as acquisition()."""
     return acquisition(long_signal, settings, **kw)

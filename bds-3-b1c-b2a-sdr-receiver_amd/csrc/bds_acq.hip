@@ -2086,4 +2086,6 @@ extern "C" int bds_acq_peaks(bds_ctx *ctx, int max_prn, double *peak, double *de
     return BDS_OK;
 }
 
+#include "bds_acq_deep.h"  // bds_acq_deep*: non-coherent power sums over K code periods on the run-time-plan kernels above
+
 BDS_DEBUG_TU_READER(bds_debug_failures_acq)

@@ -213,6 +213,7 @@ extern "C" void bds_destroy(bds_ctx *ctx) {
     if (ctx->stream) (void)hipStreamSynchronize((hipStream_t)ctx->stream);
     if (ctx->stream2) (void)hipStreamSynchronize((hipStream_t)ctx->stream2);
     bds::acq_state_free(ctx->acq);
+    bds::deep_state_free(ctx->deep);
     bds::track_state_free(ctx->trk);
     if (ctx->stream2) (void)hipStreamDestroy((hipStream_t)ctx->stream2);
     if (ctx->stream) (void)hipStreamDestroy((hipStream_t)ctx->stream);

@@ -83,6 +83,8 @@ Tuning tuning_from_env();
 
 struct AcqState;    // bds_acq.hip
 struct TrackState;  // bds_track.hip
+struct DeepState;   // bds_acq_deep.h (bds_acq.hip)
+void deep_state_free(DeepState *);
 void acq_state_free(AcqState *);
 void acq_state_invalidate(AcqState *);  // forget the configuration (plan, storage mode, cached spectra): re-derived by the next prepare
 // The chunk list of the N-point row pass for a launch pair of np PRNs x D cells on `slots` resident workgroups (bds_acq.hip,
@@ -114,6 +116,7 @@ struct bds_ctx {
     std::string devname;
     bds::AcqState *acq = nullptr;
     bds::TrackState *trk = nullptr;
+    bds::DeepState *deep = nullptr;  // weak-signal acquisition (bds_acq_deep*): plan, buffers, the last call's surfaces
     bds_timing timing{};
     bds::Tuning tune;
     std::set<const void *> lds_attr_done;  // kernels whose dynamic-LDS limit has been raised on this device

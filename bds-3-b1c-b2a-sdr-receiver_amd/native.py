@@ -162,6 +162,11 @@ class BlankOut(C.Structure):
                 ("duty", C.POINTER(C.c_int32)), ("duty_cap", C.c_int64), ("n_duty", C.c_int64)]
 
 
+class DeepOpts(C.Structure):
+    _fields_ = [("n_blocks", C.c_int32), ("compensate", C.c_int32), ("keep_surface", C.c_int32), ("threshold", C.c_double),
+                ("surface_gib", C.c_double)]
+
+
 class NotchOpts(C.Structure):
     _fields_ = [("n_tones", C.c_int32), ("block_log2", C.c_int32), ("step", C.c_uint32 * 8), ("first_sample", C.c_int64),
                 ("apply", C.c_int32), ("reserved", C.c_int32)]
@@ -194,6 +199,7 @@ EXPORTS = [
     "bds_create", "bds_destroy", "bds_reload_tuning", "bds_last_error", "bds_device_name", "bds_abi_check", "bds_build_flags", "bds_gen_code", "bds_acquire",
     "bds_acq_load", "bds_acq_prepare", "bds_acq_run", "bds_acq_set_pair_budget_gb", "bds_acq_set_b2a_npoint", "bds_acq_set_b1c_npoint", "bds_resample_plan", "bds_fir1_bandpass", "bds_frame_sync", "bds_sync_pattern", "bds_unpack_cplx", "bds_unpack_cplx_file", "bds_acq_grid", "bds_acq_peaks", "bds_acq_candidates", "bds_acq_coherent_sums", "bds_acq_block", "bds_get_timing",
     "bds_acquire16", "bds_acq_load16", "bds_acquire_track16",
+    "bds_acq_deep", "bds_acq_deep_row", "bds_acq_deep_fine", "bds_acq_deep_release",
     "bds_track", "bds_track_mem", "bds_track_loaded_bytes", "bds_track_set_resident_limit", "bds_track_stream_info", "bds_track_correlate", "bds_track_colon", "bds_track_cno", "bds_track_update",
     "bds_track_open", "bds_track_open_mem", "bds_track_open_feed", "bds_track_feed", "bds_track_advance", "bds_track_session_info", "bds_track_close",
     "bds_calc_loop_coef", "bds_calc_loop_coef_carr",
@@ -218,6 +224,8 @@ PROBE_DEVICE_EXPORTS = ["bds_probe_data_dev"]
 BLANK_DEVICE_EXPORTS = ["bds_blank_dev"]
 # the entry marked BDS_NOTCH_DEV_API: device pointers as well (record in, record out)
 NOTCH_DEVICE_EXPORTS = ["bds_notch_dev"]
+# the entry marked BDS_DEEP_DEV_API: a device pointer as well
+DEEP_DEVICE_EXPORTS = ["bds_acq_deep_dev"]
 # the entry marked BDS_CORR_DEV_API: a device pointer as well
 CORR_DEVICE_EXPORTS = ["bds_corr_function_dev"]
 
@@ -370,6 +378,13 @@ def lib():
         L.bds_notch_file.restype, L.bds_notch_file.argtypes = i32, [vp, SP, C.c_char_p, C.c_char_p, i64, i64, NO, NR]
         L.bds_notch_dev.restype, L.bds_notch_dev.argtypes = i32, [vp, SP, vp, sz, vp, NO, NR]
         L.bds_notch_lo.restype, L.bds_notch_lo.argtypes = i32, [C.POINTER(C.c_int16)]
+    if hasattr(L, "bds_acq_deep"):  # (as above: a build of an older commit has no weak-signal acquisition)
+        tail = [sz, i32, C.POINTER(DeepOpts), i32, _DP, _DP, _DP, _DP, _IP, _IP]
+        L.bds_acq_deep.restype, L.bds_acq_deep.argtypes = i32, [vp, SP, i8p] + tail
+        L.bds_acq_deep_dev.restype, L.bds_acq_deep_dev.argtypes = i32, [vp, SP, vp] + tail
+        L.bds_acq_deep_row.restype, L.bds_acq_deep_row.argtypes = i32, [vp, i32, i32, C.POINTER(C.c_float), C.c_int64]
+        L.bds_acq_deep_fine.restype, L.bds_acq_deep_fine.argtypes = i32, [vp, i32, _DP, i32]
+        L.bds_acq_deep_release.restype, L.bds_acq_deep_release.argtypes = i32, [vp]
     if hasattr(L, "bds_corr_function"):  # (as above: a build of an older commit has no correlation function)
         tail = [i32, _IP, _DP, i32, _DP, _DP, _IP]  # n_items, prn, state6, n_taps, taps, out, n_comp
         L.bds_corr_function.restype, L.bds_corr_function.argtypes = i32, [vp, SP, C.c_char_p] + tail
@@ -1110,6 +1125,46 @@ class Context:
                                           carr.ctypes.data_as(_DP), cph.ctypes.data_as(_DP),
                                           pm.ctypes.data_as(_DP), det.ctypes.data_as(_IP)))
         return carr, cph, pm, det
+
+    # -- weak-signal acquisition (bds_acq_deep*) ----------------------------------------------------
+    def acq_deep(self, settings, samples, is_complex, n_blocks, threshold, compensate=True, keep_surface=False, surface_gib=0.0, n_samples=None):
+        """bds_acq_deep (a host array) / bds_acq_deep_dev (a device array): non-coherent power sums of the coarse search over n_blocks code
+        periods.  The record's bytes go to the library as they are (int16 values as their bytes): what it does not take, it refuses.
+        Returns (carrFreq, codePhase, peakMetric, deepMetric, fbin, detected), each 1 x max(acqSatelliteList)."""
+        cs = pack_settings(settings)
+        max_prn = max(int(p) for p in np.atleast_1d(settings.acqSatelliteList))
+        carr, cph, pm, dm = (np.zeros(max_prn) for _ in range(4))
+        fb, det = np.zeros(max_prn, dtype=np.int32), np.zeros(max_prn, dtype=np.int32)
+        o = DeepOpts(int(n_blocks), 1 if compensate else 0, 1 if keep_surface else 0, float(threshold), float(surface_gib))
+        out = [max_prn] + [a.ctypes.data_as(_DP) for a in (carr, cph, pm, dm)] + [fb.ctypes.data_as(_IP), det.ctypes.data_as(_IP)]
+        if is_device_array(samples):
+            ptr, n_bytes, keep, w16 = device_record(settings, samples, self.device, "the record")
+            n = n_samples_of(n_bytes // 2 if w16 else n_bytes, is_complex, n_samples)
+            rc = self._lib.bds_acq_deep_dev(self._h, C.byref(cs), ptr, n, sample_format(is_complex), C.byref(o), *out)
+        else:
+            a = np.asarray(samples)
+            w16 = record_is_int16(settings, a.dtype.name, "the record")
+            elems = a.size
+            a, p = _i8(np.ascontiguousarray(a).view(np.int8) if w16 else a)
+            n = n_samples_of(elems, is_complex, n_samples)
+            rc = self._lib.bds_acq_deep(self._h, C.byref(cs), p, n, sample_format(is_complex), C.byref(o), *out)
+        self._check(rc)
+        return carr, cph, pm, dm, fb, det
+
+    def acq_deep_row(self, prn, fbin, n):
+        """bds_acq_deep_row: the accumulated surface row of (prn, 1-based bin) of the last acq_deep(keep_surface=True); n = its N lags."""
+        row = np.empty(int(n), dtype=np.float32)
+        got = self._check(self._lib.bds_acq_deep_row(self._h, int(prn), int(fbin), row.ctypes.data_as(C.POINTER(C.c_float)), row.size))
+        return row[:got]
+
+    def acq_deep_fine(self, prn, cap=4096):
+        """bds_acq_deep_fine: F over the fine-frequency grid of a PRN of the last acq_deep (empty when it was not detected)."""
+        f = np.empty(int(cap))
+        return f[:self._check(self._lib.bds_acq_deep_fine(self._h, int(prn), f.ctypes.data_as(_DP), f.size))].copy()
+
+    def acq_deep_release(self):
+        """bds_acq_deep_release: give back everything the deep search holds on the device."""
+        self._check(self._lib.bds_acq_deep_release(self._h))
 
     def acquire(self, settings, samples, is_complex=False, n_samples=None):
         cs = pack_settings(settings)

@@ -1115,6 +1115,63 @@ BDS_API int bds_notch_lo(int16_t *cos_sin);
 BDS_NOTCH_DEV_API int bds_notch_dev(bds_ctx *ctx, const bds_settings *s, const void *d_in, size_t n_bytes, void *d_out,
                                     const bds_notch_opts *opts, bds_notch_out *report);
 
+/* ---- weak-signal acquisition: non-coherent power sums of the coarse search over K code periods ------------------------------------
+ * acquisition() integrates as long as the reference does: one code period (B2a) or acqCohT ms once (B1C).  bds_acq_deep adds the
+ * squared search surfaces of K blocks one code period apart, which acquires satellites 5 - 10 dB below that; beside the
+ * acqResults fields it reports deepMetric, the statistic its decision uses.  Nothing of bds_acquire / bds_acq_* changes.
+ * The rules (0-based bins b and lags l in the formulas; fbin and codePhase are reported 1-based as in the reference):
+ *   sizes    spc = samplesPerCode; N = the reference's block (2 spc for B2a, len10PlusXms for B1C); frq[b] = IF - acqSearchBand +
+ *            acqStep b, D bins; s2c = ceil(fs / codeFreqBasis) 2.
+ *   blocks   block k = x[k spc : k spc + N], k < K = opts.n_blocks.  m_k[b][l] is the reference's results(b, l) on that block with
+ *            the carrier phase counted from the block's first sample: |y_d| + |y_p| (B2a), (sqrt(11) |y_d| + sqrt(29) |y_p|) /
+ *            sqrt(40) (B1C, pilotACQflag 1), |y_d| (B1C, pilotACQflag 0).
+ *   drift    sh(b, k) = rint(k spc (frq[b] - IF) / carrFreqBasis) samples (half to even), 0 with opts.compensate = 0: a positive
+ *            Doppler runs the code fast, so its starts come earlier from block to block.  |sh| must stay below spc.
+ *   surface  S[b][l] = sum_k m_k[b][(l - sh(b, k)) mod N]^2: power sums, fp32 arithmetic on fp32 storage, block 0 first.
+ *   peak     fbin = the first bin whose row maximum is largest, l0 = the first lag whose column maximum is largest (the
+ *            reference's max(max(results, [], 2)) and max(max(results))), S_peak that maximum.
+ *   peakMetric   B2a: sqrt(S_peak / S_second), S_second the maximum of row fbin over the reference's codePhaseRange around l0
+ *            (B2a/acquisition.m:224-249).  B1C: sqrt(S_peak / sum_k sigPower_k^2), sigPower_k = sqrt(var(x[k spc : k spc + X]) X)
+ *            (B1C/acquisition.m:150 on block k).  With K = 1 both are the reference's peakMetric at the reference's cell.
+ *   deepMetric   population: all bins x the lags with min(d, spc - d) >= s2c, d = (l - l0) mod spc (the peak and its images one code
+ *            period away are left out); mu its mean (f64), S_sec its maximum; deepMetric = (S_peak - mu) / (S_sec - mu).
+ *            detected = deepMetric > opts.threshold.  The caller chooses the threshold (> 1; README has noise-only figures).
+ *   fine     for detected PRNs, on the reference's grid around frq[fbin]: -acqStep / 2 + 25 j, j = 0 .. round(acqStep / 25) (B2a),
+ *            -acqStep + 25 j, j = 0 .. 2 round(acqStep / 25) (B1C).  F(f) = sum_k (w_d |sum_{n < spc} x[a_k + n] c_d(n)
+ *            e^{+j 2 pi f n / fs}| + w_p |... c_p ...|)^2 in f64, a_k = l0 + k spc - sh(fbin, k), c the one-period sampling table
+ *            of the coarse search, (w_d, w_p) = (1, 1) (B2a), (11 / 40, 29 / 40) (B1C), (1, 0) (B1C without pilot); a sample
+ *            index outside the record counts as zero.  carrFreq = the first maximum of F (1 if that is 0 Hz).
+ * Results (arrays of max_prn values, index PRN - 1; zero for PRNs that were not searched): peakMetric, deepMetric and fbin for every
+ * searched PRN; detected; carrFreq and codePhase (= l0 + 1) where detected, else 0.  The results feed bds_pre_run unchanged.
+ * Records: int8 real (is_complex 0) or int8 I/Q pairs (1) with at least N + K spc samples, else BDS_ERR_ARG (B1C's move-back
+ * rule therefore never applies); packed records (is_complex 2), settings.dataType 'int16' and settings.resamplingflag 1 are
+ * BDS_ERR_UNSUPPORTED.  opts.n_blocks < 1, opts.threshold <= 1 and NULL pointers are BDS_ERR_ARG.  A refused call writes nothing.
+ * opts.surface_gib (<= 0: 8) bounds the surfaces (D N 4 bytes per PRN): when those of all searched PRNs do not fit, the PRNs are
+ * processed in groups, with the same results bit for bit.  opts.keep_surface keeps the surfaces after the call for
+ * bds_acq_deep_row and needs all of them resident (else BDS_ERR_ARG); without it the surface memory is freed before the call
+ * returns.  Two calls on the same input give the same bits: every surface element has one writer per launch, no atomics.
+ * bds_acq_deep_dev      the same on a record in device memory (the pointer rule of "records in device memory"); it is read, never written.
+ * bds_acq_deep_row      row S[bin - 1][0 .. N) of `prn` from the last call (keep_surface); cap counts floats.  Returns N.
+ * bds_acq_deep_fine     F over the fine grid of `prn` from the last call; returns the number of grid points, 0 if not detected.
+ * bds_acq_deep_release  frees everything the deep search holds on the device (plan, buffers, kept surfaces). */
+typedef struct bds_deep_opts {
+    int32_t n_blocks;       /* K */
+    int32_t compensate;     /* 1: align the blocks by sh(b, k); 0: sh = 0 */
+    int32_t keep_surface;
+    double threshold;       /* on deepMetric; > 1 */
+    double surface_gib;     /* budget of the resident surfaces in GiB; <= 0: 8 */
+} bds_deep_opts;
+BDS_API int bds_acq_deep(bds_ctx *ctx, const bds_settings *s, const int8_t *samples, size_t n_samples, int is_complex,
+                         const bds_deep_opts *opts, int max_prn, double *carrFreq, double *codePhase, double *peakMetric,
+                         double *deepMetric, int32_t *fbin, int32_t *detected);
+BDS_API int bds_acq_deep_row(bds_ctx *ctx, int prn, int bin, float *row, int64_t cap);
+BDS_API int bds_acq_deep_fine(bds_ctx *ctx, int prn, double *F, int cap);
+BDS_API int bds_acq_deep_release(bds_ctx *ctx);
+#define BDS_DEEP_DEV_API __attribute__((visibility("default")))
+BDS_DEEP_DEV_API int bds_acq_deep_dev(bds_ctx *ctx, const bds_settings *s, const void *d_samples, size_t n_samples, int is_complex,
+                                      const bds_deep_opts *opts, int max_prn, double *carrFreq, double *codePhase, double *peakMetric,
+                                      double *deepMetric, int32_t *fbin, int32_t *detected);
+
 #ifdef __cplusplus
 }
 #endif
