@@ -513,13 +513,13 @@ static int rows_uniform_gc(int list_gc, int D, int np, long row_wgs) {
 }
 
 // ---- chunk list of the N-point row pass (bds_acq_pfa.h) ----------------------------------------------------------------------------------
-// A launch of np PRNs x D cells runs MP * K2 workgroups per chunk of cells, every one of them for (cells of the chunk + set-up) cell-times,
+// A launch of np PRNs x D cells runs kRowsWorkWgs working workgroups per chunk of cells, every one of them for (cells of the chunk + set-up) cell-times,
 // on `slots` = 2 per CU resident workgroups: the pass ends when the last slot does.  With one chunk size for the whole launch the last round
 // of workgroups runs on a nearly empty chip (13 PRNs in 67-cell chunks: 24.2 rounds cost 25).  The list therefore tapers: whole PRNs in
 // equal chunks first, then one or a few PRNs in chunks that shrink geometrically, all in non-increasing order, so that what is still
 // running when the slots start to drain is small.  No chunk straddles a PRN (a workgroup holds one PRN's code rows).
 // The model: greedy assignment in block order onto the slots -- what the dispatcher does with workgroups of equal resources.
-static constexpr int kRowsWorkWgs = pfa::kRowsWgs - pfa::K2 / 2;      // per chunk: the odd-k2 workgroups of the last row pair return at once
+static constexpr int kRowsWorkWgs = pfa::kRowsWorkWgs;               // per chunk: the other pfa::kRowsWgs - 318 positions return at once
 static constexpr int kRowsSetup8 = 3;                                 // set-up of a workgroup in eighths of a cell (measured 0.29 of a cell: profiles/r16_rows_chunks.txt)
 
 // makespan in eighths of a cell-time of chunks of these sizes, in this order
@@ -599,6 +599,11 @@ int rows_chunk_list(int np, int D, int slots, int *out, int cap) {
     for (int i = 0; i < (int)plan.size() && i < cap; ++i) out[2 * i] = plan[(size_t)i].x, out[2 * i + 1] = plan[(size_t)i].y;
     return (int)plan.size();
 }
+int rows_place_list(int *out, int cap) {
+    for (int l = 0; l < pfa::kRowsWgs && l < cap; ++l) out[2 * l] = pfa::rows_pos(l), out[2 * l + 1] = pfa::rows_place(pfa::rows_pos(l));
+    return pfa::kRowsWgs;
+}
+int rows_lds_index_of(int e) { return e >= 0 && e < pfa::K3 ? pfa::rows_lds_index(e) : -1; }
 
 // optional per-cell descriptors (device arrays) for a launch whose cells are not "one PRN, consecutive bins"
 struct CellList {

@@ -52,8 +52,37 @@ __host__ __device__ constexpr size_t bw_piece(int mp, int k2, int t3) {  // elem
     return (((size_t)(t3 / kTileLags) * MP + mp) * K2 + k2) * (kTileLags * 4) + (size_t)(t3 % kTileLags) * 4;
 }  // 4-byte (fp16 complex) elements of a cell in the inter-pass buffer
 constexpr int kRowsThreads = 256, kColsThreads = 256;
-constexpr int kRowsWgs = MP * K2;                        // row workgroups per chunk of cells: one row pair of one k2 each
-constexpr size_t kRowsLds = 2 * 3136 * sizeof(float2);   // k_pfa_rows' two row regions of 3125 elements (+ pad)
+// Row workgroups: one row pair of one k2 each.  The last pair has one row only, so its 12 k2 take 6 workgroups (rows 52 of k2 and k2 + 1):
+// kRowsWorkWgs = 318 working workgroups per chunk of cells, numbered w = 12 mp + k2 for mp < 26 and 312 + k2 / 2 for the last pair.
+constexpr int kRowsWorkWgs = MP * K2 - K2 / 2;
+// Placement, for speed only (nothing depends on it for its result): workgroups are dealt round-robin over the 8 XCDs, each with an L2
+// of its own.  With one spectrum bin per Doppler bin, workgroup (mp, k2) reads at its next cell the signal rows that (mp, k2 - 1) and
+// (mp - 1, k2 - 1) read at this one (both k1 and k2 step down by one, the column offset moves by one element: the same cache lines),
+// and all workgroups of a chunk walk their cells at one pace.  A chunk is therefore kRowsXcds x kRowsBand workgroups, a multiple of 8 so
+// that l % 8 of workgroup l = blockIdx.x % kRowsWgs names the same L2 in every chunk, and the workgroups of one label take a band of
+// consecutive w (about 3.3 row pairs with all their k2): 5 of 6 partners sit behind the same L2.  The 318 split as 6 bands of 40 and
+// 2 of 39, the 10 positions left over return at once -- spread so, no L2's CUs carry more than 40 / 39.75 of the mean (all ten idle
+// positions in the last band: 41 / 39.75, and every other XCD ends 3 % after the mean).
+constexpr int kRowsXcds = 8, kRowsBand = (kRowsWorkWgs + kRowsXcds - 1) / kRowsXcds + 1;  // 41
+constexpr int kRowsWgs = kRowsXcds * kRowsBand;                                          // 328 workgroups per chunk of cells
+__host__ __device__ constexpr int rows_pos(int l) { return kRowsBand * (l % kRowsXcds) + l / kRowsXcds; }  // position of workgroup l of a chunk
+// position -> 12 mp + k2 of the workgroup's first row pair member, or -1: nothing to do
+__host__ __device__ constexpr int rows_place(int pos) {
+    constexpr int each = kRowsWorkWgs / kRowsXcds, more = kRowsWorkWgs % kRowsXcds;  // bands 0 .. more - 1 hold each + 1
+    const int band = pos / kRowsBand, i = pos % kRowsBand;
+    if (pos < 0 || pos >= kRowsWgs || i >= each + (band < more ? 1 : 0)) return -1;
+    const int w = each * band + (band < more ? band : more) + i;
+    return w < (MP - 1) * K2 ? w : (MP - 1) * K2 + 2 * (w - (MP - 1) * K2);
+}
+// LDS layout of a row: element e of the 3125 at e + 8 (e / 625).  Stage 3 reads b[p][i][u] at 625 u + 25 i + p over the lanes p + 25 u
+// of a 32-lane half: 625 = 17 (mod 32 eight-byte words) puts lanes 25..31 on the banks of lanes 17..23 in every read; with the five
+// blocks 633 = 25 (mod 32) apart the lanes of a half take 32 different words.  Stages 1 and 2 stay conflict-free (each touches a block
+// through one lane-dependent base: tests/test_pfa_rows_placement.py enumerates all three).
+constexpr int kRowsLdsBlock = 625, kRowsLdsPad = 8;
+__host__ __device__ constexpr int rows_lds_index(int e) { return e + kRowsLdsPad * (e / kRowsLdsBlock); }
+constexpr int kRowRegion = 3168;  // elements of a row's region: a multiple of 32 above rows_lds_index(3124)
+static_assert(rows_lds_index(K3 - 1) < kRowRegion && kRowRegion % 32 == 0 && K3 == 5 * kRowsLdsBlock, "row region");
+constexpr size_t kRowsLds = 2 * kRowRegion * sizeof(float2);  // k_pfa_rows' two row regions: 50 688 bytes, two workgroups per CU
 constexpr size_t kSpecElems = (size_t)K1 * K2 * 2 * K3;  // 4-byte elements of the signal spectrum (rows doubled)
 // stage-1 twiddles W3125^(j (5 p0 + p1)), p0, p1 >= 1, that k_pfa_rows holds in registers of their own, in slot order (the other 16 - kTw1Held
 // slots take two products by the factors W3125^(j p1), W3125^(5 j p0)): 14 is what 256 registers hold without scratch (254 used)
@@ -232,7 +261,7 @@ struct RowsArgs {
     int ncells;          // cells of the launch
     int gc;              // cells a workgroup walks (all of one PRN)
     int shift;           // spectrum bins per Doppler bin (acqStep N / fs)
-    // optional chunk list (k_pfa_rows<2> only; the launch is MP * K2 * nchunks workgroups): chunk i = cells chunks[i].x .. + chunks[i].y
+    // optional chunk list (k_pfa_rows<2> only; the launch is kRowsWgs * nchunks workgroups): chunk i = cells chunks[i].x .. + chunks[i].y
     // of one PRN.  Absent: uniform chunks of gc cells, chunk i = cells i gc .. i gc + gc - 1.
     const int2 *chunks = nullptr;
     int nchunks = 0;
@@ -245,15 +274,15 @@ __global__ __launch_bounds__(kRowsThreads, 2) void k_pfa_rows(RowsArgs A) {
     const int j = wave * 32 + (lane & 31);  // thread of the row: 0..127, 125 of them work
     const bool live = j < 125;
     const int jj = live ? j : 124;
-    const int rp = blockIdx.x % (MP * K2), chunk = blockIdx.x / (MP * K2);
+    const int rp = rows_place(rows_pos(blockIdx.x % kRowsWgs)), chunk = blockIdx.x / kRowsWgs;
+    if (rp < 0) return;  // (10 of the 328 positions of a chunk)
     const int mp = rp / K2, k2 = rp % K2;
     // The two rows of a workgroup, one per half-wave: k1 = 2 mp and 2 mp + 1 of its k2.  The last pair has one row only (k1 = 52; row
-    // 53 is the pad row of the 54 the column pass reads, all zeros): the workgroup of an even k2 takes row 52 of k2 AND of k2 + 1, the one
-    // of the odd k2 has nothing left to do -- no transform runs on a row of zeros.
+    // 53 is the pad row of the 54 the column pass reads, all zeros): a workgroup of it takes row 52 of an even k2 AND of k2 + 1 -- no
+    // transform runs on a row of zeros.
     const bool last = mp == MP - 1;
-    if (last && (k2 & 1)) return;
     const int k1lo = 2 * mp, k1hi = last ? k1lo : k1lo + 1, k2hi = last ? k2 + 1 : k2;  // (half 0: (k1lo, k2), half 1: (k1hi, k2hi))
-    float2 *region = reinterpret_cast<float2 *>(pfa_lds) + (size_t)half * 3136;  // 3125 elements per row (+ pad)
+    float2 *region = reinterpret_cast<float2 *>(pfa_lds) + (size_t)half * kRowRegion;  // 3125 elements per row, rows_lds_index
     int c0, c1;
     if (A.chunks) {
         if (chunk >= A.nchunks) return;
@@ -292,6 +321,12 @@ __global__ __launch_bounds__(kRowsThreads, 2) void k_pfa_rows(RowsArgs A) {
     // first version, was 2-way in every half-wave: SQ_LDS_BANK_CONFLICT 28 % of the LDS cycles, profiles/r06_b1c_pmc_first.txt)
     const int si = jj / 5, spg = jj % 5;
     const unsigned region_b = lds_offset(region);
+    // Every access below stays inside one 625-element block from a block's first element on, so rows_lds_index is taken of that first
+    // element (a lane value formed once, or a compile-time constant) and the offset inside the block added as it was:
+    // stage 1 writes 25 j + p in block j / 25; stage 2 reads and writes 625 r + (25 i + 5 pg + c5); stage 3 reads 625 u + (25 i + p).
+    static_assert(25 * 24 + 24 < kRowsLdsBlock && kRowsLdsBlock % 25 == 0, "25 j + p, p < 25, stays in the block of 25 j");
+    const int s1_base = rows_lds_index(25 * j);
+    constexpr int kBlockStep = rows_lds_index(kRowsLdsBlock);  // 633 elements from block to block
 #pragma unroll
     for (int u = 1; u < 5; ++u) tw2[u] = tw3125(tw_rsrc, 25 * si * u);
 
@@ -331,7 +366,7 @@ __global__ __launch_bounds__(kRowsThreads, 2) void k_pfa_rows(RowsArgs A) {
                         if (sl / 5) v = pk_cmul(v, tw1a[sl / 5]);
                         if (sl % 5) v = pk_cmul(v, tw1b[sl % 5]);
                     }
-                    region[25 * j + p] = to_f2(v);
+                    region[s1_base + p] = to_f2(v);
                 }
             }
             __syncthreads();
@@ -340,19 +375,19 @@ __global__ __launch_bounds__(kRowsThreads, 2) void k_pfa_rows(RowsArgs A) {
 #pragma unroll
                 for (int c5 = 0; c5 < 5; ++c5) {
                     v2f z[5];
-                    // a[i + 25 r][5 pg + c5], r = 0..4: 625 elements apart
-                    lds_read5<0, 625 * 8>(z, region_b + (unsigned)(25 * si + 5 * spg + c5) * 8u);
+                    // a[i + 25 r][5 pg + c5], r = 0..4: one in each block
+                    lds_read5<0, kBlockStep * 8>(z, region_b + (unsigned)(25 * si + 5 * spg + c5) * 8u);
                     pk_radix5(z[0], z[1], z[2], z[3], z[4]);
 #pragma unroll
                     for (int u = 0; u < 5; ++u) {
                         const v2f v = u ? pk_cmul(z[u], tw2[u]) : z[u];
-                        region[25 * (si + 25 * u) + 5 * spg + c5] = to_f2(v);
+                        region[kBlockStep * u + 25 * si + 5 * spg + c5] = to_f2(v);
                     }
                 }
             }
             __syncthreads();
             // stage 3: thread t' = p + 25 u: 25 points over i of b[p][i][u] at 25 (i + 25 u) + p -> t'': X[t' + 125 t'']
-            lds_read25<25 * 8>(x, region_b + (unsigned)(625 * (jj / 25) + jj % 25) * 8u);  // b[p][i][u] at 25 (i + 25 u) + p, i = 0..24
+            lds_read25<25 * 8>(x, region_b + (unsigned)(kBlockStep * (jj / 25) + jj % 25) * 8u);  // b[p][i][u] at block u + 25 i + p, i = 0..24
             pk_radix25(x);
 #pragma unroll
             for (int sl = 0; sl < 25; ++sl) {
@@ -390,14 +425,17 @@ __global__ __launch_bounds__(kRowsThreads, 2) void k_pfa_rows(RowsArgs A) {
                     // cell's 13 stores in front of every cell (the row pass with its stores compiled out ran 17 % faster).  Stores it does not
                     // know of only make its counted waits longer, never shorter: of the k + S operations a wait lets return, at most S are stores.
                     // Nothing in this kernel reads the buffer; the end of the kernel makes the stores visible.
+                    // nt: a cell step streams 2 MB of these stores per XCD through the 4 MB L2 that should hold the signal rows for the neighbour
+                    // workgroups' next cell (kRowsBand above); stored plain they push the rows out (FETCH_SIZE -32 % with the placement alone, -72 %
+                    // with nt; sc1 instead: the call 28 ms slower -- profiles/r17_rows_placement.txt).
                     if constexpr (!kLast) {
-                        asm volatile("buffer_store_dwordx4 %0, %1, %2, 0 offen\n s_nop 0" ::"v"((u4){P[0], Q[0], P[1], Q[1]}), "v"((int)(bw_piece(0, 0, t3s) * 4)), "s"(dst_words)
+                        asm volatile("buffer_store_dwordx4 %0, %1, %2, 0 offen nt\n s_nop 0" ::"v"((u4){P[0], Q[0], P[1], Q[1]}), "v"((int)(bw_piece(0, 0, t3s) * 4)), "s"(dst_words)
                                      : "memory");
                     } else {
                         // the last pair: P is row 52 of k2, Q row 52 of k2 + 1 -- each with the zeros of the pad row into its own piece, the
                         // piece of k2 + 1 one tile row (kTileLags pieces) behind that of k2
                         static_assert(bw_piece(0, 1, 0) * 4 == 256, "piece of the next k2");
-                        asm volatile("buffer_store_dwordx4 %0, %2, %3, 0 offen\n s_nop 0\n buffer_store_dwordx4 %1, %2, %3, 0 offen offset:256\n s_nop 0" ::"v"((u4){P[0], 0u, P[1], 0u}),
+                        asm volatile("buffer_store_dwordx4 %0, %2, %3, 0 offen nt\n s_nop 0\n buffer_store_dwordx4 %1, %2, %3, 0 offen offset:256 nt\n s_nop 0" ::"v"((u4){P[0], 0u, P[1], 0u}),
                                      "v"((u4){Q[0], 0u, Q[1], 0u}), "v"((int)(bw_piece(0, 0, t3s) * 4)), "s"(dst_words)
                                      : "memory");
                     }

@@ -445,6 +445,13 @@ extern "C" __attribute__((visibility("default"))) int bds_test_rows_chunks(int n
     if (np < 1 || D < 1 || slots < 1 || cap < 0 || (cap > 0 && !out)) return BDS_ERR_ARG;
     return bds::rows_chunk_list(np, D, slots, out, cap);
 }
+// (tests/test_pfa_rows_placement.py) the row pass's workgroup placement, (position, 12 mp + k2 or -1) per workgroup of a chunk, and its
+// LDS index of a row's element
+extern "C" __attribute__((visibility("default"))) int bds_test_rows_place(int *out, int cap) {
+    if (cap < 0 || (cap > 0 && !out)) return BDS_ERR_ARG;
+    return bds::rows_place_list(out, cap);
+}
+extern "C" __attribute__((visibility("default"))) int bds_test_rows_lds_index(int e) { return bds::rows_lds_index_of(e); }
 #endif
 
 #ifdef BDS_DEBUG

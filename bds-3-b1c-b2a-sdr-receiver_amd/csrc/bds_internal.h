@@ -90,6 +90,11 @@ void acq_state_invalidate(AcqState *);  // forget the configuration (plan, stora
 // The chunk list of the N-point row pass for a launch pair of np PRNs x D cells on `slots` resident workgroups (bds_acq.hip,
 // rows_chunk_plan) as (first cell, cells) pairs: the number of chunks, of which the first min(n, cap) are written to out.
 int rows_chunk_list(int np, int D, int slots, int *out, int cap);
+// The placement and the LDS layout of the N-point row pass (bds_acq_pfa.h) as the kernel takes them: for each workgroup l of a chunk its
+// position and 12 mp + k2 (-1: it returns at once) as pairs -- the number of workgroups per chunk, the first min(n, cap) written --, and
+// the LDS index of element e of a row (-1 outside 0..3124).
+int rows_place_list(int *out, int cap);
+int rows_lds_index_of(int e);
 void track_state_free(TrackState *);
 // bds_track.hip, for bds_corrfn.hip: what an open-loop replay shares with the trackers
 struct TrkOpenLoop {
