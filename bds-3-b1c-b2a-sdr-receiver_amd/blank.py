@@ -112,28 +112,7 @@ def blank_pulses(source, settings, threshold=None, pre=None, post=None, out=None
     if not (threshold >= 0):
         raise ValueError(f"threshold = {threshold!r}")
     tsq = min(int(math.floor(float(threshold) ** 2)), 2 ** 32 - 1)
-    if is_path:
-        if out is None or out == "inplace":
-            raise ValueError("blanking a file writes another file: give out=path")
-        dst = out
-    elif native.is_device_array(source):
-        if isinstance(out, str) and out != "inplace":
-            raise ValueError(f'out = {out!r}: None, "inplace" or a tensor')
-        if out is None:
-            import torch
-
-            dst = torch.empty_like(source)
-        else:
-            dst = source if isinstance(out, str) else out
-    else:
-        if isinstance(out, str) and out != "inplace":
-            raise ValueError(f'out = {out!r}: None, "inplace" or an array')
-        if isinstance(out, str):
-            if not isinstance(source, np.ndarray) or not source.flags.c_contiguous or not source.flags.writeable:
-                raise ValueError('out="inplace" takes a contiguous writeable NumPy array')
-            dst = source
-        else:
-            dst = out
+    dst = native.conditioner_out(source, out, "blanking a file writes another file: give out=path")
     res, r = ctx.blank(settings, source, tsq, pre, post, out=dst, lead=lead, tail=tail, duty_samples=duty_samples or 0,
                        n_samples=-1 if n_samples is None else int(n_samples), piece_samples=piece_samples)
     return res, BlankReport(threshold_sq=tsq, pre=pre, post=post, **r)

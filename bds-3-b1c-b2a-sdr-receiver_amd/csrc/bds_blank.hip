@@ -479,6 +479,19 @@ static void launch_t(hipStream_t st, const Args &a, int64_t nt, Scratch &sc) {
     hipLaunchKernelGGL(k_blank_sum, dim3((unsigned)((nt + 4095) / 4096)), dim3(1024), 0, st, a.n_blank, a.n_run, nt, sc.totals + 1, sc.totals + 2);
 }
 
+static void fill_report(bds_blank_out *rep, int64_t n_window, const bds_blank_opts &o, const unsigned long long tot[3]) {
+    rep->n_samples = n_window, rep->n_flagged = (int64_t)tot[0], rep->n_blanked = (int64_t)tot[1], rep->n_runs = (int64_t)tot[2];
+    rep->n_duty = duty_bins(n_window, o.duty_samples);
+}
+
+}  // namespace blank
+}  // namespace bds
+
+#include "bds_piece_pipe.h"  // what the entries share with the other conditioners: their checks, the layout switch, the piece loop
+
+using namespace bds;
+using namespace bds::blank;
+
 // One buffer of n samples on the device: [lead, n - tail) is blanked from d_in into d_out (the context copied through when they
 // differ), the three totals are left in sc.totals; asynchronous on `st`.  n = 0 launches nothing (the totals are zeroed).
 static hipError_t run_device(hipStream_t st, int fmt, const uint8_t *d_in, uint8_t *d_out, int64_t n, int64_t lead, int64_t tail, const bds_blank_opts &o,
@@ -495,97 +508,57 @@ static hipError_t run_device(hipStream_t st, int fmt, const uint8_t *d_in, uint8
     a.duty_samples = d_duty ? o.duty_samples : 0, a.duty_origin = duty_origin, a.duty = o.duty_samples > 0 ? d_duty : nullptr;
     a.first = sc.first, a.last = sc.last, a.prev_last = sc.prev, a.next_first = sc.next, a.g_prev = sc.g_prev, a.g_next = sc.g_next;
     a.n_flag = sc.n_flag, a.n_blank = sc.n_blank, a.n_run = sc.n_run;
-    switch (fmt) {
-    case kS8: launch_t<1, 1>(st, a, nt, sc); break;
-    case kS8C: launch_t<2, 1>(st, a, nt, sc); break;
-    case kS16: launch_t<2, 2>(st, a, nt, sc); break;
-    default: launch_t<4, 2>(st, a, nt, sc); break;
-    }
+    with_sample_layout(fmt, [&](auto sb, auto el) { launch_t<decltype(sb)::value, decltype(el)::value>(st, a, nt, sc); });
     return hipGetLastError();
 }
 
-// What every entry checks first: the format, the options against the sample count, the report.  fmt (>= 0) or BDS_ERR_*.
-static int check_entry(bds_ctx *ctx, const char *who, const bds_settings *s, int64_t n_bytes, int64_t n, const bds_blank_opts *o, const bds_blank_out *rep,
-                       int64_t *n_samples) {
-    const char *why;
-    const int fmt = format_of(s, &why);
-    if (fmt < 0) return fail(ctx, fmt, "%s: %s", who, why);
-    char msg[200];
-    if (int rc = check_args(fmt, n_bytes, n, o, rep, n_samples, msg, sizeof msg)) return fail(ctx, rc, "%s: %s", who, msg);
-    return fmt;
-}
-
-static void fill_report(bds_blank_out *rep, int64_t n_window, const bds_blank_opts &o, const unsigned long long tot[3]) {
-    rep->n_samples = n_window, rep->n_flagged = (int64_t)tot[0], rep->n_blanked = (int64_t)tot[1], rep->n_runs = (int64_t)tot[2];
-    rep->n_duty = duty_bins(n_window, o.duty_samples);
-}
-
-// bds_blank and bds_blank_file: the window [w0, w1) of a buffer of n samples in pieces.  read(first_byte, n_bytes, dst) delivers
-// bytes of the buffer into pinned memory, write(first_byte, n_bytes, src) takes the blanked bytes of a piece's own samples.
-// Piece k is read by this thread and uploaded, worked on in place and brought back on stream k & 1 while piece k - 1 runs on the other.
+// bds_blank and bds_blank_file: the window [w0, w1) of a buffer of n samples in pieces (pipe::run, bds_piece_pipe.h).
+// read(first_byte, n_bytes, dst) delivers bytes of the buffer into pinned memory, write(first_byte, n_bytes, src) takes the blanked
+// bytes of a piece's own samples.  A piece is uploaded with its context and worked on in place; only its own samples come back.
 template <class Read, class Write>
 static int run_pieces(bds_ctx *ctx, const char *who, int fmt, int64_t n, const bds_blank_opts &o, int64_t piece_samples, bds_blank_out *rep, Read read, Write write) {
     const int SB = sample_bytes(fmt);
     const int64_t w0 = o.lead, w1 = n - o.tail, piece = default_piece(fmt, piece_samples), np = piece_count(w0, w1, piece);
     const int64_t bins = duty_bins(w1 - w0, o.duty_samples);
-    unsigned long long tot[3] = {0, 0, 0};
-    int rc = BDS_OK;
-    hipError_t e = hipSetDevice(ctx->device);
-    hipStream_t st[2] = {(hipStream_t)ctx->stream, (hipStream_t)ctx->stream2};
-    uint8_t *d_buf[2] = {nullptr, nullptr}, *h_buf[2] = {nullptr, nullptr};
-    unsigned long long *h_tot[2] = {nullptr, nullptr};
-    hipEvent_t done[2] = {nullptr, nullptr};
-    int32_t *d_duty = nullptr;
-    Scratch sc[2];
     const size_t cap = (size_t)(std::min(piece, std::max<int64_t>(w1 - w0, 1)) + o.pre + o.post + 1) * SB + 16;
-    for (int i = 0; i < 2 && e == hipSuccess && np; ++i) {
-        e = hipMalloc(&d_buf[i], cap);
-        if (e == hipSuccess) e = hipHostMalloc(&h_buf[i], cap, hipHostMallocDefault);
-        if (e == hipSuccess) e = hipHostMalloc(&h_tot[i], 3 * 8, hipHostMallocDefault);
-        if (e == hipSuccess) e = hipEventCreate(&done[i]);
-        if (e == hipSuccess) e = sc[i].alloc(tiles((int64_t)(cap / SB)));
-    }
-    if (e == hipSuccess && bins && np) {
-        e = hipMalloc(&d_duty, (size_t)bins * 4);
-        if (e == hipSuccess) e = hipMemsetAsync(d_duty, 0, (size_t)bins * 4, st[0]);
-        if (e == hipSuccess) e = hipStreamSynchronize(st[0]);  // (the other stream adds to it as well)
-    }
-    auto finish = [&](int64_t k) {  // wait for piece k, hand its own samples on, add its counts
-        const int b = (int)(k & 1);
-        const Piece pc = piece_of(n, w0, w1, piece, o.pre, o.post, k);
-        e = hipEventSynchronize(done[b]);
-        if (e != hipSuccess) return;
-        rc = write(pc.core0 * SB, (size_t)((pc.core1 - pc.core0) * SB), h_buf[b] + (pc.core0 - pc.load0) * SB);
-        for (int i = 0; i < 3; ++i) tot[i] += h_tot[b][i];
-    };
-    for (int64_t k = 0; k < np && !rc && e == hipSuccess; ++k) {
-        const int b = (int)(k & 1);
-        const Piece pc = piece_of(n, w0, w1, piece, o.pre, o.post, k);
-        const size_t nb = (size_t)((pc.load1 - pc.load0) * SB);
-        rc = read(pc.load0 * SB, nb, h_buf[b]);  // (piece k - 2, the last user of these buffers, is finished)
-        if (rc) break;
-        e = hipMemcpyAsync(d_buf[b], h_buf[b], nb, hipMemcpyHostToDevice, st[b]);
-        if (e == hipSuccess)
-            e = run_device(st[b], fmt, d_buf[b], d_buf[b], pc.load1 - pc.load0, pc.core0 - pc.load0, pc.load1 - pc.core1, o, d_duty, pc.core0 - w0, sc[b]);
-        const size_t core_off = (size_t)((pc.core0 - pc.load0) * SB);  // only the piece's own samples come back
-        if (e == hipSuccess) e = hipMemcpyAsync(h_buf[b] + core_off, d_buf[b] + core_off, (size_t)((pc.core1 - pc.core0) * SB), hipMemcpyDeviceToHost, st[b]);
-        if (e == hipSuccess) e = hipMemcpyAsync(h_tot[b], sc[b].totals, 3 * 8, hipMemcpyDeviceToHost, st[b]);
-        if (e == hipSuccess) e = hipEventRecord(done[b], st[b]);
-        if (e == hipSuccess && k >= 1) finish(k - 1);
-    }
-    if (!rc && e == hipSuccess && np) finish(np - 1);
-    (void)hipStreamSynchronize(st[0]);  // nothing of this call may still run when its buffers go
-    (void)hipStreamSynchronize(st[1]);
-    if (!rc && e == hipSuccess && bins && np) e = hipMemcpy(rep->duty, d_duty, (size_t)bins * 4, hipMemcpyDeviceToHost);
-    for (int i = 0; i < 2; ++i) {
-        if (d_buf[i]) (void)hipFree(d_buf[i]);
-        if (h_buf[i]) (void)hipHostFree(h_buf[i]);
-        if (h_tot[i]) (void)hipHostFree(h_tot[i]);
-        if (done[i]) (void)hipEventDestroy(done[i]);
-    }
-    if (d_duty) (void)hipFree(d_duty);
+    unsigned long long tot[3] = {0, 0, 0};
+    Scratch sc[2];
+    DevScope scope;
+    int32_t *d_duty = nullptr;  // one for both streams
+    auto piece_k = [&](int64_t k) { return piece_of(n, w0, w1, piece, o.pre, o.post, k); };
+    const int rc = pipe::run(
+        ctx, who, np, cap, 3 * 8,
+        [&] {
+            hipError_t e = sc[0].alloc(tiles((int64_t)(cap / SB)));
+            if (e == hipSuccess) e = sc[1].alloc(tiles((int64_t)(cap / SB)));
+            if (e != hipSuccess || !bins) return e;
+            e = scope.alloc(&d_duty, (size_t)bins * 4);
+            if (e == hipSuccess) e = hipMemsetAsync(d_duty, 0, (size_t)bins * 4, (hipStream_t)ctx->stream);
+            return e == hipSuccess ? hipStreamSynchronize((hipStream_t)ctx->stream) : e;  // (the other stream adds to it as well)
+        },
+        [&](int64_t k) {
+            const Piece pc = piece_k(k);
+            return pipe::Span{pc.load0 * SB, (size_t)((pc.load1 - pc.load0) * SB)};
+        },
+        read,
+        [&](int64_t k, pipe::Slot &s) {
+            const Piece pc = piece_k(k);
+            hipError_t e = run_device(s.stream, fmt, s.d_buf, s.d_buf, pc.load1 - pc.load0, pc.core0 - pc.load0, pc.load1 - pc.core1, o, d_duty, pc.core0 - w0, sc[k & 1]);
+            const size_t core_off = (size_t)((pc.core0 - pc.load0) * SB);  // only the piece's own samples come back
+            if (e == hipSuccess) e = hipMemcpyAsync(s.h_buf + core_off, s.d_buf + core_off, (size_t)((pc.core1 - pc.core0) * SB), hipMemcpyDeviceToHost, s.stream);
+            if (e == hipSuccess) e = hipMemcpyAsync(s.h_res, sc[k & 1].totals, 3 * 8, hipMemcpyDeviceToHost, s.stream);
+            return e;
+        },
+        [&](int64_t k, pipe::Slot &s) {
+            const Piece pc = piece_k(k);
+            for (int i = 0; i < 3; ++i) tot[i] += reinterpret_cast<const unsigned long long *>(s.h_res)[i];
+            return write(pc.core0 * SB, (size_t)((pc.core1 - pc.core0) * SB), s.h_buf + (pc.core0 - pc.load0) * SB);
+        });
     if (rc) return rc;
-    if (e != hipSuccess) return fail(ctx, e == hipErrorOutOfMemory ? BDS_ERR_NOMEM : BDS_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
+    if (bins && np) {
+        const hipError_t e = hipMemcpy(rep->duty, d_duty, (size_t)bins * 4, hipMemcpyDeviceToHost);
+        if (e != hipSuccess) return hip_fail(ctx, who, e);
+    }
     if (!np)
         for (int64_t i = 0; i < bins; ++i) rep->duty[i] = 0;
     fill_report(rep, w1 - w0, o, tot);
@@ -599,20 +572,12 @@ static int check_piece(bds_ctx *ctx, const char *who, int64_t piece_samples, con
     return BDS_OK;
 }
 
-}  // namespace blank
-}  // namespace bds
-
-using namespace bds;
-using namespace bds::blank;
-
 extern "C" int bds_blank(bds_ctx *ctx, const bds_settings *s, const void *in, size_t n_bytes, void *out, const bds_blank_opts *opts, bds_blank_out *report) {
     const char *who = "bds_blank";
     int64_t n = 0;
-    const int fmt = check_entry(ctx, who, s, (int64_t)n_bytes, 0, opts, report, &n);
+    const int fmt = check_entry(ctx, who, format_of, check_args, s, (int64_t)n_bytes, 0, opts, report, &n);
     if (fmt < 0) return fmt;
-    if (n_bytes && (!in || !out)) return fail(ctx, BDS_ERR_ARG, "%s: in or out is NULL", who);
-    if (partial_overlap(in, out, n_bytes)) return fail(ctx, BDS_ERR_ARG, "%s: in and out overlap in part (they must be the same buffer or disjoint)", who);
-    if (!ctx) return fail(ctx, BDS_ERR_ARG, "%s: ctx is NULL", who);
+    if (int rc = check_host_pair(ctx, who, in, out, n_bytes, true)) return rc;
     const uint8_t *src = static_cast<const uint8_t *>(in);
     uint8_t *dst = static_cast<uint8_t *>(out);
     const int SB = sample_bytes(fmt);
@@ -622,16 +587,7 @@ extern "C" int bds_blank(bds_ctx *ctx, const bds_settings *s, const void *in, si
     }
     // In place the pieces still see raw context: piece k + 1 is read before piece k is written back, a piece's context in front
     // lies in the one piece before it (a piece is longer than post + 1 samples) and its context behind in pieces not yet written.
-    return run_pieces(
-        ctx, who, fmt, n, *opts, 0, report,
-        [&](int64_t b0, size_t nb, uint8_t *to) {
-            std::memcpy(to, src + b0, nb);
-            return (int)BDS_OK;
-        },
-        [&](int64_t b0, size_t nb, const uint8_t *from) {
-            std::memcpy(dst + b0, from, nb);
-            return (int)BDS_OK;
-        });
+    return run_pieces(ctx, who, fmt, n, *opts, 0, report, pipe::from_memory(in), pipe::to_memory(out));
 }
 
 extern "C" int bds_blank_file(bds_ctx *ctx, const bds_settings *s, const char *path_in, const char *path_out, int64_t n_samples, int64_t piece_samples,
@@ -640,55 +596,28 @@ extern "C" int bds_blank_file(bds_ctx *ctx, const bds_settings *s, const char *p
     const char *why;
     const int fmt = format_of(s, &why);
     if (fmt < 0) return fail(ctx, fmt, "%s: %s", who, why);
-    if (!path_in || !path_out) return fail(ctx, BDS_ERR_ARG, "%s: path_in or path_out is NULL", who);
-    if (!std::strcmp(path_in, path_out)) return fail(ctx, BDS_ERR_ARG, "%s: path_in and path_out are the same file", who);
-    if (s->skipNumberOfBytes < 0) return fail(ctx, BDS_ERR_ARG, "%s: skipNumberOfBytes < 0", who);
+    char msg[1024];
+    if (int rc = RecordWindow::check_names(path_in, path_out, true, s->skipNumberOfBytes, msg, sizeof msg)) return fail(ctx, rc, "%s: %s", who, msg);
     if (!opts || !report) return fail(ctx, BDS_ERR_ARG, "%s: opts or report is NULL", who);
     if (int rc = check_piece(ctx, who, piece_samples, *opts)) return rc;
-    FILE *fi = std::fopen(path_in, "rb");
-    if (!fi) return fail(ctx, BDS_ERR_IO, "Unable to read file %s", path_in);
-    std::fseek(fi, 0, SEEK_END);
-    const int64_t file_bytes = (int64_t)ftello(fi);
-    const int SB = sample_bytes(fmt);
-    const int64_t skip = s->skipNumberOfBytes, have = file_bytes / SB - skip;  // (counted in samples, as bds_probe_data_file counts)
-    const int64_t n = n_samples > 0 ? n_samples : have;
+    RecordWindow w;
+    if (int rc = w.open(path_in, fmt, s->skipNumberOfBytes, msg, sizeof msg)) return fail(ctx, rc, "%s", msg);
+    const int64_t n = n_samples > 0 ? n_samples : w.have;
     int64_t n_chk = 0;
-    char msg[200];
-    int rc = BDS_OK;
-    if (have < 0 || n > have)
-        rc = fail(ctx, BDS_ERR_ARG, "%s: Could not read enough data from the data file (%lld samples behind skipNumberOfBytes, %lld wanted)", who,
-                  (long long)std::max<int64_t>(have, 0), (long long)n);
-    else if ((rc = check_args(fmt, -1, n, opts, report, &n_chk, msg, sizeof msg)) != 0)
-        rc = fail(ctx, rc, "%s: %s", who, msg);
-    else if (!ctx)
-        rc = fail(ctx, BDS_ERR_ARG, "%s: ctx is NULL", who);
-    FILE *fo = rc ? nullptr : std::fopen(path_out, "wb");
-    if (!rc && !fo) rc = fail(ctx, BDS_ERR_IO, "Unable to write file %s", path_out);
-    const int64_t b0 = skip * SB, b1 = b0 + n * SB;
+    if (int rc = w.select(n, msg, sizeof msg)) return fail(ctx, rc, "%s: %s", who, msg);
+    if (int rc = check_args(fmt, -1, n, opts, report, &n_chk, msg, sizeof msg)) return fail(ctx, rc, "%s: %s", who, msg);
+    if (!ctx) return fail(ctx, BDS_ERR_ARG, "%s: ctx is NULL", who);
+    if (int rc = w.open_out(path_out, msg, sizeof msg)) return fail(ctx, rc, "%s", msg);
+    auto told = [&](int rc) { return rc ? fail(ctx, rc, "%s: %s", who, msg) : rc; };
+    const int SB = sample_bytes(fmt);
     // the bytes in front of the window and behind it, and the window's context samples, go through as they are
-    auto copy_through = [&](int64_t from, int64_t to) {
-        std::vector<uint8_t> buf((size_t)std::min<int64_t>(std::max<int64_t>(to - from, 1), 1 << 22));
-        for (int64_t o = from; o < to && !rc; o += (int64_t)buf.size()) {
-            const size_t nb = (size_t)std::min<int64_t>((int64_t)buf.size(), to - o);
-            if (fseeko(fi, (off_t)o, SEEK_SET) != 0 || std::fread(buf.data(), 1, nb, fi) != nb) rc = fail(ctx, BDS_ERR_IO, "%s: short read of %s", who, path_in);
-            else if (fseeko(fo, (off_t)o, SEEK_SET) != 0 || std::fwrite(buf.data(), 1, nb, fo) != nb) rc = fail(ctx, BDS_ERR_IO, "%s: short write on %s", who, path_out);
-        }
-    };
-    if (!rc) copy_through(0, b0 + opts->lead * SB);
+    int rc = told(w.copy_front(opts->lead * SB, msg, sizeof msg));
     if (!rc)
         rc = run_pieces(
-            ctx, who, fmt, n, *opts, piece_samples, report,
-            [&](int64_t o, size_t nb, uint8_t *to) {
-                if (fseeko(fi, (off_t)(b0 + o), SEEK_SET) != 0 || std::fread(to, 1, nb, fi) != nb) return fail(ctx, BDS_ERR_IO, "%s: short read of %s", who, path_in);
-                return (int)BDS_OK;
-            },
-            [&](int64_t o, size_t nb, const uint8_t *from) {
-                if (fseeko(fo, (off_t)(b0 + o), SEEK_SET) != 0 || std::fwrite(from, 1, nb, fo) != nb) return fail(ctx, BDS_ERR_IO, "%s: short write on %s", who, path_out);
-                return (int)BDS_OK;
-            });
-    if (!rc) copy_through(b1 - opts->tail * SB, file_bytes);
-    std::fclose(fi);
-    if (fo && std::fclose(fo) != 0 && !rc) rc = fail(ctx, BDS_ERR_IO, "%s: short write on %s", who, path_out);
+            ctx, who, fmt, n, *opts, piece_samples, report, [&](int64_t o, size_t nb, uint8_t *to) { return told(w.read(o, nb, to, msg, sizeof msg)); },
+            [&](int64_t o, size_t nb, const uint8_t *from) { return told(w.write(o, nb, from, msg, sizeof msg)); });
+    if (!rc) rc = told(w.copy_back(opts->tail * SB, msg, sizeof msg));
+    if (!rc) rc = told(w.close(msg, sizeof msg));
     return rc;
 }
 
@@ -696,14 +625,9 @@ extern "C" int bds_blank_dev(bds_ctx *ctx, const bds_settings *s, const void *d_
                              bds_blank_out *report) {
     const char *who = "bds_blank_dev";
     int64_t n = 0;
-    const int fmt = check_entry(ctx, who, s, (int64_t)n_bytes, 0, opts, report, &n);
+    const int fmt = check_entry(ctx, who, format_of, check_args, s, (int64_t)n_bytes, 0, opts, report, &n);
     if (fmt < 0) return fmt;
-    const int el = probe::elem_bytes(fmt);
-    if (reinterpret_cast<uintptr_t>(d_in) % (uintptr_t)el || reinterpret_cast<uintptr_t>(d_out) % (uintptr_t)el)
-        return fail(ctx, BDS_ERR_ARG, "%s: d_in or d_out is not aligned to the %d-byte samples of the record", who, el);
-    if (partial_overlap(d_in, d_out, n_bytes)) return fail(ctx, BDS_ERR_ARG, "%s: d_in and d_out overlap in part (they must be the same buffer or disjoint)", who);
-    if (int rc = check_device_span(ctx, who, "d_in", d_in, n_bytes)) return rc;
-    if (int rc = check_device_span(ctx, who, "d_out", d_out, n_bytes)) return rc;
+    if (int rc = check_device_pair(ctx, who, fmt, d_in, d_out, n_bytes, true)) return rc;
     BDS_HIP(ctx, hipSetDevice(ctx->device));
     hipStream_t st = (hipStream_t)ctx->stream;
     const int64_t n_window = n - opts->lead - opts->tail, bins = duty_bins(n_window, opts->duty_samples);
@@ -712,7 +636,7 @@ extern "C" int bds_blank_dev(bds_ctx *ctx, const bds_settings *s, const void *d_
     int32_t *d_duty = nullptr;
     hipError_t e = sc.alloc(tiles(n));
     if (e == hipSuccess && bins) e = scope.alloc(&d_duty, (size_t)bins * 4);
-    if (e != hipSuccess) return fail(ctx, e == hipErrorOutOfMemory ? BDS_ERR_NOMEM : BDS_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
+    if (e != hipSuccess) return hip_fail(ctx, who, e);
     if (bins) BDS_HIP(ctx, hipMemsetAsync(d_duty, 0, (size_t)bins * 4, st));
     unsigned long long tot[3] = {0, 0, 0};
     e = run_device(st, fmt, static_cast<const uint8_t *>(d_in), static_cast<uint8_t *>(d_out), n, opts->lead, opts->tail, *opts, d_duty, 0, sc);
@@ -724,3 +648,4 @@ extern "C" int bds_blank_dev(bds_ctx *ctx, const bds_settings *s, const void *d_
     fill_report(report, n_window, *opts, tot);
     return BDS_OK;
 }
+

@@ -8,6 +8,7 @@
 
 #include "bds_mi355x.h"
 #include "bds_probe_math.h"
+#include "bds_record_window.h"
 
 #ifdef __HIPCC__
 #define BDS_BLANK_HD __host__ __device__ __forceinline__
@@ -52,8 +53,6 @@ inline Fast8 fast8(uint32_t threshold_sq) {
     return f;
 }
 
-inline int sample_bytes(int fmt) { return probe::bits_per_sample(fmt) / 8; }  // 1, 2, 2, 4
-
 // ---- arguments --------------------------------------------------------------------------------------------------------------------
 // fileType / dataType -> format; the packed 2+2-bit format has no amplitude to threshold
 inline int format_of(const bds_settings *s, const char **why) {
@@ -92,12 +91,6 @@ inline int check_args(int fmt, int64_t n_bytes, int64_t n, const bds_blank_opts 
         return snprintf(msg, len, "report->duty holds %lld bins, the window takes %lld", (long long)(rep->duty ? rep->duty_cap : 0), (long long)bins), BDS_ERR_ARG;
     *n_samples = n;
     return BDS_OK;
-}
-
-// in and out must be the same buffer or disjoint ones
-inline bool partial_overlap(const void *in, const void *out, size_t n_bytes) {
-    const uintptr_t a = (uintptr_t)in, b = (uintptr_t)out;
-    return a != b && a < b + n_bytes && b < a + n_bytes;
 }
 
 // ---- pieces ------------------------------------------------------------------------------------------------------------------------

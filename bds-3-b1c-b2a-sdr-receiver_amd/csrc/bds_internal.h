@@ -163,9 +163,14 @@ int check_device_span(bds_ctx *ctx, const char *who, const char *arg, const void
 
 #ifdef __HIPCC__  // (bds_codes.cpp is plain C++ and sees no HIP runtime)
 namespace bds {
-// Device allocations and events of one call, released on every exit path (or earlier, by release()).
+// a failed HIP call of entry `who` as its return code: BDS_ERR_NOMEM for an allocation that did not fit, else BDS_ERR_HIP
+inline int hip_fail(bds_ctx *ctx, const char *who, hipError_t e) {
+    return fail(ctx, e == hipErrorOutOfMemory ? BDS_ERR_NOMEM : BDS_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
+}
+
+// Device allocations, pinned host allocations and events of one call, released on every exit path (or earlier, by release()).
 struct DevScope {
-    std::vector<void *> mem;
+    std::vector<void *> mem, host;
     std::vector<hipEvent_t> ev;
     DevScope() = default;
     DevScope(const DevScope &) = delete;
@@ -177,6 +182,13 @@ struct DevScope {
         if (e == hipSuccess) mem.push_back(*q);
         return e;
     }
+    template <class T>
+    hipError_t pinned(T **q, size_t bytes) {  // page-locked host memory, at least 8 bytes as well
+        *q = nullptr;
+        const hipError_t e = hipHostMalloc((void **)q, bytes < 8 ? 8 : bytes, hipHostMallocDefault);
+        if (e == hipSuccess) host.push_back(*q);
+        return e;
+    }
     hipError_t event(hipEvent_t *e) {
         const hipError_t r = hipEventCreate(e);
         if (r == hipSuccess) ev.push_back(*e);
@@ -184,8 +196,10 @@ struct DevScope {
     }
     void release() {
         for (void *q : mem) (void)hipFree(q);
+        for (void *q : host) (void)hipHostFree(q);
         for (hipEvent_t e : ev) (void)hipEventDestroy(e);
         mem.clear();
+        host.clear();
         ev.clear();
     }
     ~DevScope() { release(); }

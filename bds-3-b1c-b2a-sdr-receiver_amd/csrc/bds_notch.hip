@@ -233,6 +233,19 @@ static void launch_t(hipStream_t st, const Args &a, bool apply) {
     if (apply) hipLaunchKernelGGL((k_notch_apply<SB, E>), dim3(nwg), dim3(kThreads), 0, st, a);
 }
 
+static void fill_report(bds_notch_out *rep, int64_t n, const bds_notch_opts &o, const unsigned long long tot[3]) {
+    rep->n_samples = n, rep->n_blocks = block_count(n, o.block_log2);
+    rep->sum_sq_in = tot[0], rep->sum_sq_out = o.apply ? tot[1] : 0, rep->n_saturated = o.apply ? (int64_t)tot[2] : 0;
+}
+
+}  // namespace notch
+}  // namespace bds
+
+#include "bds_piece_pipe.h"  // what the entries share with the other conditioners: their checks, the layout switch, the piece loop
+
+using namespace bds;
+using namespace bds::notch;
+
 // One buffer of n samples on the device, sample 0 of it the absolute sample `first`: estimates into d_est, the three sums into
 // d_tot, the notched bytes into d_out when o.apply; asynchronous on `st`.  n = 0 launches nothing (the sums are zeroed).
 static hipError_t run_device(hipStream_t st, int fmt, const uint8_t *d_in, uint8_t *d_out, int64_t n, int64_t first, const bds_notch_opts &o,
@@ -248,13 +261,7 @@ static hipError_t run_device(hipStream_t st, int fmt, const uint8_t *d_in, uint8
     a.vec_out = o.apply && (reinterpret_cast<uintptr_t>(d_out) & 15u) == 0;
     for (int k = 0; k < kMaxTones; ++k) a.step[k] = k < o.n_tones ? o.step[k] : 0u;
     a.tab = d_tab, a.est = d_est, a.tot = d_tot;
-    const bool apply = o.apply != 0;
-    switch (fmt) {
-    case kS8: launch_t<1, 1>(st, a, apply); break;
-    case kS8C: launch_t<2, 1>(st, a, apply); break;
-    case kS16: launch_t<2, 2>(st, a, apply); break;
-    default: launch_t<4, 2>(st, a, apply); break;
-    }
+    with_sample_layout(fmt, [&](auto sb, auto el) { launch_t<decltype(sb)::value, decltype(el)::value>(st, a, o.apply != 0); });
     return hipGetLastError();
 }
 
@@ -269,21 +276,6 @@ static hipError_t upload_table(DevScope &scope, uint32_t **d_tab) {
     return e;
 }
 
-static int check_entry(bds_ctx *ctx, const char *who, const bds_settings *s, int64_t n_bytes, int64_t n, const bds_notch_opts *o, const bds_notch_out *rep,
-                       int64_t *n_samples) {
-    const char *why;
-    const int fmt = format_of(s, &why);
-    if (fmt < 0) return fail(ctx, fmt, "%s: %s", who, why);
-    char msg[256];
-    if (int rc = check_args(fmt, n_bytes, n, o, rep, n_samples, msg, sizeof msg)) return fail(ctx, rc, "%s: %s", who, msg);
-    return fmt;
-}
-
-static void fill_report(bds_notch_out *rep, int64_t n, const bds_notch_opts &o, const unsigned long long tot[3]) {
-    rep->n_samples = n, rep->n_blocks = block_count(n, o.block_log2);
-    rep->sum_sq_in = tot[0], rep->sum_sq_out = o.apply ? tot[1] : 0, rep->n_saturated = o.apply ? (int64_t)tot[2] : 0;
-}
-
 static int check_piece(bds_ctx *ctx, const char *who, int fmt, int64_t piece_samples, const bds_notch_opts &o) {
     if (piece_samples < 0) return fail(ctx, BDS_ERR_ARG, "%s: piece_samples = %lld", who, (long long)piece_samples);
     if (piece_samples > 0 && piece_of(fmt, piece_samples, o.block_log2) == 0)
@@ -291,82 +283,60 @@ static int check_piece(bds_ctx *ctx, const char *who, int fmt, int64_t piece_sam
     return BDS_OK;
 }
 
-// bds_notch and bds_notch_file: a window of n samples in pieces of whole blocks.  read(first_byte, n_bytes, dst) delivers bytes of
-// the window into pinned memory, write(first_byte, n_bytes, src) takes a piece's notched bytes.  Piece k is read by this thread
-// and uploaded, worked on in place and brought back on stream k & 1 while piece k - 1 runs on the other.
+// bds_notch and bds_notch_file: a window of n samples in pieces of whole blocks (pipe::run, bds_piece_pipe.h).
+// read(first_byte, n_bytes, dst) delivers bytes of the window into pinned memory, write(first_byte, n_bytes, src) takes a piece's
+// notched bytes.  A slot's result block holds the three sums, then the piece's estimates.
 template <class Read, class Write>
 static int run_pieces(bds_ctx *ctx, const char *who, int fmt, int64_t n, const bds_notch_opts &o, int64_t piece_samples, bds_notch_out *rep, Read read, Write write) {
     const int SB = sample_bytes(fmt);
     const int64_t piece = piece_of(fmt, piece_samples, o.block_log2), np = n > 0 ? (n + piece - 1) / piece : 0;
     const int64_t per_block = (int64_t)o.n_tones * 2;
-    unsigned long long tot[3] = {0, 0, 0};
-    int rc = BDS_OK;
-    hipError_t e = hipSetDevice(ctx->device);
-    hipStream_t st[2] = {(hipStream_t)ctx->stream, (hipStream_t)ctx->stream2};
-    uint8_t *d_buf[2] = {nullptr, nullptr}, *h_buf[2] = {nullptr, nullptr};
-    int32_t *d_est[2] = {nullptr, nullptr}, *h_est[2] = {nullptr, nullptr};
-    unsigned long long *d_tot[2] = {nullptr, nullptr}, *h_tot[2] = {nullptr, nullptr};
-    hipEvent_t done[2] = {nullptr, nullptr};
-    uint32_t *d_tab = nullptr;
-    DevScope scope;
     const int64_t cap_samples = std::min(piece, std::max<int64_t>(n, 1));
-    const size_t cap = (size_t)cap_samples * SB + 16, est_bytes = (size_t)(block_count(cap_samples, o.block_log2) * per_block) * 4;
-    if (e == hipSuccess && np) e = upload_table(scope, &d_tab);
-    for (int i = 0; i < 2 && e == hipSuccess && np; ++i) {
-        e = scope.alloc(&d_buf[i], cap);
-        if (e == hipSuccess) e = scope.alloc(&d_est[i], est_bytes);
-        if (e == hipSuccess) e = scope.alloc(&d_tot[i], 3 * 8);
-        if (e == hipSuccess) e = hipHostMalloc(&h_buf[i], cap, hipHostMallocDefault);
-        if (e == hipSuccess) e = hipHostMalloc(&h_est[i], std::max<size_t>(est_bytes, 8), hipHostMallocDefault);
-        if (e == hipSuccess) e = hipHostMalloc(&h_tot[i], 3 * 8, hipHostMallocDefault);
-        if (e == hipSuccess) e = scope.event(&done[i]);
-    }
-    auto span = [&](int64_t k, int64_t *s0, int64_t *s1) { *s0 = k * piece, *s1 = std::min(n, *s0 + piece); };
-    auto finish = [&](int64_t k) {  // wait for piece k, hand its bytes and estimates on, add its sums
-        const int b = (int)(k & 1);
-        int64_t s0, s1;
-        span(k, &s0, &s1);
-        e = hipEventSynchronize(done[b]);
-        if (e != hipSuccess) return;
-        if (o.apply) rc = write(s0 * SB, (size_t)((s1 - s0) * SB), h_buf[b]);
-        if (rep->est) std::memcpy(rep->est + (s0 >> o.block_log2) * per_block, h_est[b], (size_t)(block_count(s1 - s0, o.block_log2) * per_block) * 4);
-        for (int i = 0; i < 3; ++i) tot[i] += h_tot[b][i];
-    };
-    for (int64_t k = 0; k < np && !rc && e == hipSuccess; ++k) {
-        const int b = (int)(k & 1);
-        int64_t s0, s1;
-        span(k, &s0, &s1);
-        const size_t nb = (size_t)((s1 - s0) * SB);
-        rc = read(s0 * SB, nb, h_buf[b]);  // (piece k - 2, the last user of these buffers, is finished)
-        if (rc) break;
-        e = hipMemcpyAsync(d_buf[b], h_buf[b], nb, hipMemcpyHostToDevice, st[b]);
-        if (e == hipSuccess) e = run_device(st[b], fmt, d_buf[b], d_buf[b], s1 - s0, o.first_sample + s0, o, d_tab, d_est[b], d_tot[b]);
-        if (e == hipSuccess && o.apply) e = hipMemcpyAsync(h_buf[b], d_buf[b], nb, hipMemcpyDeviceToHost, st[b]);
-        if (e == hipSuccess && rep->est)
-            e = hipMemcpyAsync(h_est[b], d_est[b], (size_t)(block_count(s1 - s0, o.block_log2) * per_block) * 4, hipMemcpyDeviceToHost, st[b]);
-        if (e == hipSuccess) e = hipMemcpyAsync(h_tot[b], d_tot[b], 3 * 8, hipMemcpyDeviceToHost, st[b]);
-        if (e == hipSuccess) e = hipEventRecord(done[b], st[b]);
-        if (e == hipSuccess && k >= 1) finish(k - 1);
-    }
-    if (!rc && e == hipSuccess && np) finish(np - 1);
-    (void)hipStreamSynchronize(st[0]);  // nothing of this call may still run when its buffers go
-    (void)hipStreamSynchronize(st[1]);
-    for (int i = 0; i < 2; ++i) {
-        if (h_buf[i]) (void)hipHostFree(h_buf[i]);
-        if (h_est[i]) (void)hipHostFree(h_est[i]);
-        if (h_tot[i]) (void)hipHostFree(h_tot[i]);
-    }
+    const size_t est_bytes = (size_t)(block_count(cap_samples, o.block_log2) * per_block) * 4;
+    unsigned long long tot[3] = {0, 0, 0};
+    DevScope scope;
+    uint32_t *d_tab = nullptr;
+    int32_t *d_est[2] = {nullptr, nullptr};
+    unsigned long long *d_tot[2] = {nullptr, nullptr};
+    auto samples_of = [&](int64_t k, int64_t *s0) { return *s0 = k * piece, std::min(n, *s0 + piece) - *s0; };
+    auto est_bytes_of = [&](int64_t n_piece) { return (size_t)(block_count(n_piece, o.block_log2) * per_block) * 4; };
+    const int rc = pipe::run(
+        ctx, who, np, (size_t)cap_samples * SB + 16, 3 * 8 + est_bytes,
+        [&] {
+            hipError_t e = upload_table(scope, &d_tab);
+            for (int i = 0; i < 2 && e == hipSuccess; ++i) {
+                e = scope.alloc(&d_est[i], est_bytes);
+                if (e == hipSuccess) e = scope.alloc(&d_tot[i], 3 * 8);
+            }
+            return e;
+        },
+        [&](int64_t k) {
+            int64_t s0;
+            const int64_t ns = samples_of(k, &s0);
+            return pipe::Span{s0 * SB, (size_t)(ns * SB)};
+        },
+        read,
+        [&](int64_t k, pipe::Slot &s) {
+            int64_t s0;
+            const int64_t ns = samples_of(k, &s0);
+            const int b = (int)(k & 1);
+            hipError_t e = run_device(s.stream, fmt, s.d_buf, s.d_buf, ns, o.first_sample + s0, o, d_tab, d_est[b], d_tot[b]);
+            if (e == hipSuccess && o.apply) e = hipMemcpyAsync(s.h_buf, s.d_buf, (size_t)(ns * SB), hipMemcpyDeviceToHost, s.stream);
+            if (e == hipSuccess && rep->est) e = hipMemcpyAsync(s.h_res + 3 * 8, d_est[b], est_bytes_of(ns), hipMemcpyDeviceToHost, s.stream);
+            if (e == hipSuccess) e = hipMemcpyAsync(s.h_res, d_tot[b], 3 * 8, hipMemcpyDeviceToHost, s.stream);
+            return e;
+        },
+        [&](int64_t k, pipe::Slot &s) {
+            int64_t s0;
+            const int64_t ns = samples_of(k, &s0);
+            if (rep->est) std::memcpy(rep->est + (s0 >> o.block_log2) * per_block, s.h_res + 3 * 8, est_bytes_of(ns));
+            for (int i = 0; i < 3; ++i) tot[i] += reinterpret_cast<const unsigned long long *>(s.h_res)[i];
+            return o.apply ? write(s0 * SB, (size_t)(ns * SB), s.h_buf) : (int)BDS_OK;
+        });
     if (rc) return rc;
-    if (e != hipSuccess) return fail(ctx, e == hipErrorOutOfMemory ? BDS_ERR_NOMEM : BDS_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
     fill_report(rep, n, o, tot);
     return BDS_OK;
 }
-
-}  // namespace notch
-}  // namespace bds
-
-using namespace bds;
-using namespace bds::notch;
 
 extern "C" int bds_notch_lo(int16_t *cos_sin) {
     if (!cos_sin) return fail(nullptr, BDS_ERR_ARG, "bds_notch_lo: cos_sin is NULL");
@@ -377,23 +347,10 @@ extern "C" int bds_notch_lo(int16_t *cos_sin) {
 extern "C" int bds_notch(bds_ctx *ctx, const bds_settings *s, const void *in, size_t n_bytes, void *out, const bds_notch_opts *opts, bds_notch_out *report) {
     const char *who = "bds_notch";
     int64_t n = 0;
-    const int fmt = check_entry(ctx, who, s, (int64_t)n_bytes, 0, opts, report, &n);
+    const int fmt = check_entry(ctx, who, format_of, check_args, s, (int64_t)n_bytes, 0, opts, report, &n);
     if (fmt < 0) return fmt;
-    if (n_bytes && (!in || (opts->apply && !out))) return fail(ctx, BDS_ERR_ARG, "%s: in or out is NULL", who);
-    if (opts->apply && partial_overlap(in, out, n_bytes)) return fail(ctx, BDS_ERR_ARG, "%s: in and out overlap in part (they must be the same buffer or disjoint)", who);
-    if (!ctx) return fail(ctx, BDS_ERR_ARG, "%s: ctx is NULL", who);
-    const uint8_t *src = static_cast<const uint8_t *>(in);
-    uint8_t *dst = static_cast<uint8_t *>(out);
-    return run_pieces(
-        ctx, who, fmt, n, *opts, 0, report,
-        [&](int64_t b0, size_t nb, uint8_t *to) {
-            std::memcpy(to, src + b0, nb);
-            return (int)BDS_OK;
-        },
-        [&](int64_t b0, size_t nb, const uint8_t *from) {
-            std::memcpy(dst + b0, from, nb);
-            return (int)BDS_OK;
-        });
+    if (int rc = check_host_pair(ctx, who, in, out, n_bytes, opts->apply != 0)) return rc;
+    return run_pieces(ctx, who, fmt, n, *opts, 0, report, pipe::from_memory(in), pipe::to_memory(out));
 }
 
 extern "C" int bds_notch_file(bds_ctx *ctx, const bds_settings *s, const char *path_in, const char *path_out, int64_t n_samples, int64_t piece_samples,
@@ -403,56 +360,28 @@ extern "C" int bds_notch_file(bds_ctx *ctx, const bds_settings *s, const char *p
     const int fmt = format_of(s, &why);
     if (fmt < 0) return fail(ctx, fmt, "%s: %s", who, why);
     if (!opts || !report) return fail(ctx, BDS_ERR_ARG, "%s: opts or report is NULL", who);
-    if (!path_in || (opts->apply && !path_out)) return fail(ctx, BDS_ERR_ARG, "%s: path_in or path_out is NULL", who);
-    if (opts->apply && !std::strcmp(path_in, path_out)) return fail(ctx, BDS_ERR_ARG, "%s: path_in and path_out are the same file", who);
-    if (s->skipNumberOfBytes < 0) return fail(ctx, BDS_ERR_ARG, "%s: skipNumberOfBytes < 0", who);
-    FILE *fi = std::fopen(path_in, "rb");
-    if (!fi) return fail(ctx, BDS_ERR_IO, "Unable to read file %s", path_in);
-    std::fseek(fi, 0, SEEK_END);
-    const int64_t file_bytes = (int64_t)ftello(fi);
-    const int SB = sample_bytes(fmt);
-    const int64_t skip = s->skipNumberOfBytes, have = file_bytes / SB - skip;  // (counted in samples, as bds_blank_file counts)
-    const int64_t n = n_samples > 0 ? n_samples : have;
-    int64_t n_chk = 0;
-    char msg[256];
-    int rc = BDS_OK;
-    if (have < 0 || n > have)
-        rc = fail(ctx, BDS_ERR_ARG, "%s: Could not read enough data from the data file (%lld samples behind skipNumberOfBytes, %lld wanted)", who,
-                  (long long)std::max<int64_t>(have, 0), (long long)n);
-    else if ((rc = check_args(fmt, -1, n, opts, report, &n_chk, msg, sizeof msg)) != 0)
-        rc = fail(ctx, rc, "%s: %s", who, msg);
-    else if ((rc = check_piece(ctx, who, fmt, piece_samples, *opts)) != 0)
-        ;
-    else if (!ctx)
-        rc = fail(ctx, BDS_ERR_ARG, "%s: ctx is NULL", who);
     const bool writes = opts->apply != 0;
-    FILE *fo = (rc || !writes) ? nullptr : std::fopen(path_out, "wb");
-    if (!rc && writes && !fo) rc = fail(ctx, BDS_ERR_IO, "Unable to write file %s", path_out);
-    const int64_t b0 = skip * SB, b1 = b0 + n * SB;
+    char msg[1024];
+    if (int rc = RecordWindow::check_names(path_in, path_out, writes, s->skipNumberOfBytes, msg, sizeof msg)) return fail(ctx, rc, "%s: %s", who, msg);
+    RecordWindow w;
+    if (int rc = w.open(path_in, fmt, s->skipNumberOfBytes, msg, sizeof msg)) return fail(ctx, rc, "%s", msg);
+    const int64_t n = n_samples > 0 ? n_samples : w.have;
+    int64_t n_chk = 0;
+    if (int rc = w.select(n, msg, sizeof msg)) return fail(ctx, rc, "%s: %s", who, msg);
+    if (int rc = check_args(fmt, -1, n, opts, report, &n_chk, msg, sizeof msg)) return fail(ctx, rc, "%s: %s", who, msg);
+    if (int rc = check_piece(ctx, who, fmt, piece_samples, *opts)) return rc;
+    if (!ctx) return fail(ctx, BDS_ERR_ARG, "%s: ctx is NULL", who);
+    if (writes)
+        if (int rc = w.open_out(path_out, msg, sizeof msg)) return fail(ctx, rc, "%s", msg);
+    auto told = [&](int rc) { return rc ? fail(ctx, rc, "%s: %s", who, msg) : rc; };
     // the bytes in front of the window and behind it go through as they are
-    auto copy_through = [&](int64_t from, int64_t to) {
-        std::vector<uint8_t> buf((size_t)std::min<int64_t>(std::max<int64_t>(to - from, 1), 1 << 22));
-        for (int64_t o = from; o < to && !rc; o += (int64_t)buf.size()) {
-            const size_t nb = (size_t)std::min<int64_t>((int64_t)buf.size(), to - o);
-            if (fseeko(fi, (off_t)o, SEEK_SET) != 0 || std::fread(buf.data(), 1, nb, fi) != nb) rc = fail(ctx, BDS_ERR_IO, "%s: short read of %s", who, path_in);
-            else if (fseeko(fo, (off_t)o, SEEK_SET) != 0 || std::fwrite(buf.data(), 1, nb, fo) != nb) rc = fail(ctx, BDS_ERR_IO, "%s: short write on %s", who, path_out);
-        }
-    };
-    if (!rc && writes) copy_through(0, b0);
+    int rc = writes ? told(w.copy_front(0, msg, sizeof msg)) : (int)BDS_OK;
     if (!rc)
         rc = run_pieces(
-            ctx, who, fmt, n, *opts, piece_samples, report,
-            [&](int64_t o, size_t nb, uint8_t *to) {
-                if (fseeko(fi, (off_t)(b0 + o), SEEK_SET) != 0 || std::fread(to, 1, nb, fi) != nb) return fail(ctx, BDS_ERR_IO, "%s: short read of %s", who, path_in);
-                return (int)BDS_OK;
-            },
-            [&](int64_t o, size_t nb, const uint8_t *from) {
-                if (fseeko(fo, (off_t)(b0 + o), SEEK_SET) != 0 || std::fwrite(from, 1, nb, fo) != nb) return fail(ctx, BDS_ERR_IO, "%s: short write on %s", who, path_out);
-                return (int)BDS_OK;
-            });
-    if (!rc && writes) copy_through(b1, file_bytes);
-    std::fclose(fi);
-    if (fo && std::fclose(fo) != 0 && !rc) rc = fail(ctx, BDS_ERR_IO, "%s: short write on %s", who, path_out);
+            ctx, who, fmt, n, *opts, piece_samples, report, [&](int64_t o, size_t nb, uint8_t *to) { return told(w.read(o, nb, to, msg, sizeof msg)); },
+            [&](int64_t o, size_t nb, const uint8_t *from) { return told(w.write(o, nb, from, msg, sizeof msg)); });
+    if (!rc && writes) rc = told(w.copy_back(0, msg, sizeof msg));
+    if (!rc) rc = told(w.close(msg, sizeof msg));
     return rc;
 }
 
@@ -460,17 +389,9 @@ extern "C" int bds_notch_dev(bds_ctx *ctx, const bds_settings *s, const void *d_
                              bds_notch_out *report) {
     const char *who = "bds_notch_dev";
     int64_t n = 0;
-    const int fmt = check_entry(ctx, who, s, (int64_t)n_bytes, 0, opts, report, &n);
+    const int fmt = check_entry(ctx, who, format_of, check_args, s, (int64_t)n_bytes, 0, opts, report, &n);
     if (fmt < 0) return fmt;
-    const bool writes = opts->apply != 0;
-    const int el = probe::elem_bytes(fmt);
-    if (reinterpret_cast<uintptr_t>(d_in) % (uintptr_t)el || (writes && reinterpret_cast<uintptr_t>(d_out) % (uintptr_t)el))
-        return fail(ctx, BDS_ERR_ARG, "%s: d_in or d_out is not aligned to the %d-byte samples of the record", who, el);
-    if (writes && partial_overlap(d_in, d_out, n_bytes))
-        return fail(ctx, BDS_ERR_ARG, "%s: d_in and d_out overlap in part (they must be the same buffer or disjoint)", who);
-    if (int rc = check_device_span(ctx, who, "d_in", d_in, n_bytes)) return rc;
-    if (writes)
-        if (int rc = check_device_span(ctx, who, "d_out", d_out, n_bytes)) return rc;
+    if (int rc = check_device_pair(ctx, who, fmt, d_in, d_out, n_bytes, opts->apply != 0)) return rc;
     BDS_HIP(ctx, hipSetDevice(ctx->device));
     hipStream_t st = (hipStream_t)ctx->stream;
     DevScope scope;
@@ -481,7 +402,7 @@ extern "C" int bds_notch_dev(bds_ctx *ctx, const bds_settings *s, const void *d_
     hipError_t e = upload_table(scope, &d_tab);
     if (e == hipSuccess) e = scope.alloc(&d_est, est_bytes);
     if (e == hipSuccess) e = scope.alloc(&d_tot, 3 * 8);
-    if (e != hipSuccess) return fail(ctx, e == hipErrorOutOfMemory ? BDS_ERR_NOMEM : BDS_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
+    if (e != hipSuccess) return hip_fail(ctx, who, e);
     unsigned long long tot[3] = {0, 0, 0};
     e = run_device(st, fmt, static_cast<const uint8_t *>(d_in), static_cast<uint8_t *>(d_out), n, opts->first_sample, *opts, d_tab, d_est, d_tot);
     if (e == hipSuccess) e = hipMemcpyAsync(tot, d_tot, sizeof tot, hipMemcpyDeviceToHost, st);
@@ -492,3 +413,4 @@ extern "C" int bds_notch_dev(bds_ctx *ctx, const bds_settings *s, const void *d_
     fill_report(report, n, *opts, tot);
     return BDS_OK;
 }
+

@@ -9,9 +9,9 @@
 #include <cstdint>
 #include <cstdio>
 
-#include "bds_blank_math.h"
 #include "bds_mi355x.h"
 #include "bds_probe_math.h"
+#include "bds_record_window.h"
 
 #ifdef __HIPCC__
 #define BDS_NOTCH_HD __host__ __device__ __forceinline__
@@ -54,8 +54,6 @@ BDS_NOTCH_HD int32_t estimate_full(int64_t sum, int block_log2) { return (int32_
 // each component of a pair; er, ei = sum over the tones of a x lo, at most 2^42
 BDS_NOTCH_HD int32_t sub_real(int64_t er) { return (int32_t)((er + ((int64_t)1 << 20)) >> 21); }
 BDS_NOTCH_HD int32_t sub_cplx(int64_t e) { return (int32_t)((e + ((int64_t)1 << 21)) >> 22); }
-
-inline int sample_bytes(int fmt) { return probe::bits_per_sample(fmt) / 8; }  // 1, 2, 2, 4
 
 // ---- the table --------------------------------------------------------------------------------------------------------------------
 // S[i] = rint(L sin(2 pi i / 2^P)) from the first quadrant j = 0 .. 2^(P - 2) and the exact symmetries of sine;
@@ -122,8 +120,6 @@ inline int check_args(int fmt, int64_t n_bytes, int64_t n, const bds_notch_opts 
     *n_samples = n;
     return BDS_OK;
 }
-
-using blank::partial_overlap;
 
 // ---- pieces ------------------------------------------------------------------------------------------------------------------------
 // Blocks are self-contained: a piece is a whole number of blocks and needs no context.  Samples per piece: the caller's rounded

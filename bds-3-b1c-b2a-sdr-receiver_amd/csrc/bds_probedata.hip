@@ -339,7 +339,7 @@ static int run_pieces(bds_ctx *ctx, const char *who, const bds_settings *s, int 
     uint8_t *d_rec = nullptr;
     std::vector<uint8_t> host(cap);
     hipError_t e = hipMalloc(&d_rec, cap);
-    if (e != hipSuccess) return fail(ctx, e == hipErrorOutOfMemory ? BDS_ERR_NOMEM : BDS_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
+    if (e != hipSuccess) return hip_fail(ctx, who, e);
     int rc = BDS_OK;
     for (int64_t j = 0; j < np && !rc; ++j) {
         const Piece pc = piece(n, spp, j);
@@ -372,6 +372,8 @@ static int settings_format(bds_ctx *ctx, const char *who, const bds_settings *s)
 }  // namespace probe
 }  // namespace bds
 
+#include "bds_record_window.h"  // the file entry's window, as the conditioners take theirs
+
 using namespace bds;
 using namespace bds::probe;
 
@@ -401,29 +403,17 @@ extern "C" int bds_probe_data_file(bds_ctx *ctx, const bds_settings *s, const ch
     if (fmt < 0) return fmt;
     if (!path) return fail(ctx, BDS_ERR_ARG, "%s: path is NULL", who);
     if (s->skipNumberOfBytes < 0 || n_samples < -1) return fail(ctx, BDS_ERR_ARG, "%s: skipNumberOfBytes < 0 or n_samples < -1", who);
-    FILE *f = std::fopen(path, "rb");
-    if (!f) return fail(ctx, BDS_ERR_IO, "Unable to read file %s", path);  // probeData.m:173
-    std::fseek(f, 0, SEEK_END);
-    const int64_t file_bytes = (int64_t)ftello(f);
-    const int64_t skip = s->skipNumberOfBytes, have = samples_in_bytes(fmt, (uint64_t)file_bytes) - skip;  // (counted in samples: include/bds_mi355x.h)
-    const int64_t n = n_samples == 0 ? reference_window(*s) : n_samples < 0 ? have : n_samples;
-    int64_t b0, b1;
-    byte_span(fmt, skip, skip + std::max<int64_t>(n, 0), &b0, &b1);
-    const int sub = fmt == kPacked ? (int)(skip & 1) : 0;
-    char msg[200];
+    RecordWindow w;
+    char msg[1024];
+    if (int rc = w.open(path, fmt, s->skipNumberOfBytes, msg, sizeof msg)) return fail(ctx, rc, "%s", msg);  // probeData.m:173
+    const int64_t n = n_samples == 0 ? reference_window(*s) : n_samples < 0 ? w.have : n_samples;
     int64_t n_chk = 0;
-    int rc = BDS_OK;
-    if (have < 0 || n > have)  // probeData.m:81-84
-        rc = fail(ctx, BDS_ERR_ARG, "%s: Could not read enough data from the data file (%lld samples behind skipNumberOfBytes, %lld wanted)", who, (long long)std::max<int64_t>(have, 0), (long long)n);
-    else if ((rc = check_args(s, fmt, -1, n, n_time, out, &n_chk, msg, sizeof msg)) != 0)
-        rc = fail(ctx, rc, "%s: %s", who, msg);
-    if (!rc)
-        rc = run_pieces(ctx, who, s, fmt, sub, n, n_time, out, [&](int64_t o, size_t nb, uint8_t *dst) {
-            if (fseeko(f, (off_t)(b0 + o), SEEK_SET) != 0 || std::fread(dst, 1, nb, f) != nb) return fail(ctx, BDS_ERR_IO, "%s: short read of %s", who, path);
-            return (int)BDS_OK;
-        });
-    std::fclose(f);
-    return rc;
+    if (int rc = w.select(n, msg, sizeof msg)) return fail(ctx, rc, "%s: %s", who, msg);  // probeData.m:81-84
+    if (int rc = check_args(s, fmt, -1, n, n_time, out, &n_chk, msg, sizeof msg)) return fail(ctx, rc, "%s: %s", who, msg);
+    return run_pieces(ctx, who, s, fmt, w.sub, n, n_time, out, [&](int64_t o, size_t nb, uint8_t *dst) {
+        const int rc = w.read(o, nb, dst, msg, sizeof msg);
+        return rc ? fail(ctx, rc, "%s: %s", who, msg) : rc;
+    });
 }
 
 extern "C" int bds_probe_data_dev(bds_ctx *ctx, const bds_settings *s, const void *d_bytes, size_t n_bytes, int64_t n_time, bds_probe_out *out) {

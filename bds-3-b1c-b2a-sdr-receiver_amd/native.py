@@ -764,6 +764,55 @@ def notch_est(rep, n, block_log2, n_tones, want=True):
     return est
 
 
+def conditioner_out(source, out, file_message):
+    """What blank_pulses / notch_tones hand Context.blank / .notch as `out`: the path for a path (file_message is raised when
+    none is given), else `source` itself for "inplace", a new tensor for a tensor without one, and `out` as it is otherwise."""
+    if isinstance(source, (str, bytes, os.PathLike)):
+        if out is None or (isinstance(out, str) and out == "inplace"):
+            raise ValueError(file_message)
+        return out
+    on_device = is_device_array(source)
+    if isinstance(out, str) and out != "inplace":
+        raise ValueError(f'out = {out!r}: None, "inplace" or {"a tensor" if on_device else "an array"}')
+    if on_device and out is None:
+        import torch
+
+        return torch.empty_like(source)
+    if isinstance(out, str) and not on_device:
+        if not isinstance(source, np.ndarray) or not source.flags.c_contiguous or not source.flags.writeable:
+            raise ValueError('out="inplace" takes a contiguous writeable NumPy array')
+    return source if isinstance(out, str) else out
+
+
+def conditioner_io(settings, source, out, writes, ctx_device, verb):
+    """The record of one bds_blank* / bds_notch* call and where its output goes, for the three places a record can lie in:
+    (kind, in, out, n_bytes, result, keepalive) with kind "file" (in / out: encoded paths, n_bytes None), "dev" or "host"
+    (in / out: pointers).  out and result are None for a call that writes nothing; `verb` words the file refusal."""
+    if isinstance(source, (str, bytes, os.PathLike)):
+        if writes and not isinstance(out, (str, bytes, os.PathLike)):
+            raise ValueError(f"{verb} a file writes a file: out must be a path")
+        return "file", os.fsencode(source), os.fsencode(out) if writes else None, None, out if writes else None, ()
+    if is_device_array(source):
+        ptr, n_bytes, keep, _ = device_record(settings, source, ctx_device)
+        if not writes:
+            return "dev", ptr, None, n_bytes, None, (keep,)
+        res = source if out is None else out
+        optr, on_bytes, okeep, _ = device_record(settings, res, ctx_device, "the output record")
+        if on_bytes != n_bytes:
+            raise ValueError(f"the output record holds {on_bytes} bytes, the input {n_bytes}")
+        return "dev", ptr, optr, n_bytes, res, (keep, okeep)
+    a, w16 = record_bytes(settings, source)
+    if not writes:
+        return "host", a.ctypes.data_as(C.c_void_p), None, a.size, None, (a,)
+    if out is None:
+        res = np.empty(a.size // 2, dtype="<i2") if w16 else np.empty(a.size, dtype=np.asarray(source).dtype if np.asarray(source).dtype == np.uint8 else np.int8)
+    else:
+        res = out
+        if not isinstance(res, np.ndarray) or not res.flags.c_contiguous or res.nbytes != a.size:
+            raise ValueError(f"out must be a contiguous NumPy array of the record's {a.size} bytes")
+    return "host", a.ctypes.data_as(C.c_void_p), res.ctypes.data_as(C.c_void_p), a.size, res, (a, res)
+
+
 def notch_lo() -> np.ndarray:
     """bds_notch_lo (no GPU): the excisor's local-oscillator table, int16 [2, 2^14]: cosines, then sines."""
     t = np.zeros((2, 1 << NOTCH_PHASE_BITS), dtype=np.int16)
@@ -1283,35 +1332,16 @@ class Context:
         Returns (the record written, a dict of n_samples, n_flagged, n_blanked, n_runs and duty: int32 array or None)."""
         cs = pack_settings(settings)
         o, rep, duty = pack_blank(threshold_sq, pre, post, lead, tail, duty_samples)
-        if isinstance(source, (str, bytes, os.PathLike)):
-            if not isinstance(out, (str, bytes, os.PathLike)):
-                raise ValueError("blanking a file writes a file: out must be a path")
-            ds = int(duty_samples)
-            if ds > 0:  # the window's length is the file's to tell
-                size, sb = os.path.getsize(source), blank_sample_bytes(settings)
-                n = int(n_samples) if int(n_samples) > 0 else size // sb - int(settings.skipNumberOfBytes)
-                duty = np.zeros(max(-(-max(n - int(lead) - int(tail), 0) // ds), 1), dtype=np.int32)
-                rep.duty, rep.duty_cap = duty.ctypes.data_as(_IP), duty.size
-            rc = self._lib.bds_blank_file(self._h, C.byref(cs), os.fsencode(source), os.fsencode(out), int(n_samples), int(piece_samples), C.byref(o), C.byref(rep))
-            res = out
-        elif is_device_array(source):
-            ptr, n_bytes, keep, _ = device_record(settings, source, self.device)
-            res = source if out is None else out
-            optr, on_bytes, okeep, _ = device_record(settings, res, self.device, "the output record")
-            if on_bytes != n_bytes:
-                raise ValueError(f"the output record holds {on_bytes} bytes, the input {n_bytes}")
-            duty = blank_duty(rep, n_bytes // blank_sample_bytes(settings), lead, tail, duty_samples)
-            rc = self._lib.bds_blank_dev(self._h, C.byref(cs), ptr, n_bytes, optr, C.byref(o), C.byref(rep))
+        sb = blank_sample_bytes(settings)
+        kind, src, dst, n_bytes, res, keep = conditioner_io(settings, source, out, True, self.device, "blanking")
+        if kind == "file":
+            if int(duty_samples) > 0:  # the window's length is the file's to tell
+                n = int(n_samples) if int(n_samples) > 0 else os.path.getsize(source) // sb - int(settings.skipNumberOfBytes)
+                duty = blank_duty(rep, n, lead, tail, duty_samples)
+            rc = self._lib.bds_blank_file(self._h, C.byref(cs), src, dst, int(n_samples), int(piece_samples), C.byref(o), C.byref(rep))
         else:
-            a, w16 = record_bytes(settings, source)
-            if out is None:
-                res = np.empty(a.size // 2, dtype="<i2") if w16 else np.empty(a.size, dtype=np.asarray(source).dtype if np.asarray(source).dtype == np.uint8 else np.int8)
-            else:
-                res = out
-                if not isinstance(res, np.ndarray) or not res.flags.c_contiguous or res.nbytes != a.size:
-                    raise ValueError(f"out must be a contiguous NumPy array of the record's {a.size} bytes")
-            duty = blank_duty(rep, a.size // blank_sample_bytes(settings), lead, tail, duty_samples)
-            rc = self._lib.bds_blank(self._h, C.byref(cs), a.ctypes.data_as(C.c_void_p), a.size, res.ctypes.data_as(C.c_void_p), C.byref(o), C.byref(rep))
+            duty = blank_duty(rep, n_bytes // sb, lead, tail, duty_samples)
+            rc = (self._lib.bds_blank_dev if kind == "dev" else self._lib.bds_blank)(self._h, C.byref(cs), src, n_bytes, dst, C.byref(o), C.byref(rep))
         self._check(rc)
         r = {k: int(getattr(rep, k)) for k in ("n_samples", "n_flagged", "n_blanked", "n_runs")}
         r["duty"] = None if duty is None else duty[:int(rep.n_duty)]
@@ -1327,36 +1357,14 @@ class Context:
         cs = pack_settings(settings)
         o, rep = pack_notch(steps, block_log2, first_sample, apply)
         sb = blank_sample_bytes(settings)
-        if isinstance(source, (str, bytes, os.PathLike)):
-            if apply and not isinstance(out, (str, bytes, os.PathLike)):
-                raise ValueError("notching a file writes a file: out must be a path")
+        kind, src, dst, n_bytes, res, keep = conditioner_io(settings, source, out, bool(apply), self.device, "notching")
+        if kind == "file":
             n = int(n_samples) if int(n_samples) > 0 else os.path.getsize(source) // sb - int(settings.skipNumberOfBytes)
             est = notch_est(rep, n, block_log2, len(steps), want_est)
-            rc = self._lib.bds_notch_file(self._h, C.byref(cs), os.fsencode(source), os.fsencode(out) if apply else None, int(n_samples),
-                                          int(piece_samples), C.byref(o), C.byref(rep))
-            res = out if apply else None
-        elif is_device_array(source):
-            ptr, n_bytes, keep, _ = device_record(settings, source, self.device)
-            res, optr = None, None
-            if apply:
-                res = source if out is None else out
-                optr, on_bytes, okeep, _ = device_record(settings, res, self.device, "the output record")
-                if on_bytes != n_bytes:
-                    raise ValueError(f"the output record holds {on_bytes} bytes, the input {n_bytes}")
-            est = notch_est(rep, n_bytes // sb, block_log2, len(steps), want_est)
-            rc = self._lib.bds_notch_dev(self._h, C.byref(cs), ptr, n_bytes, optr, C.byref(o), C.byref(rep))
+            rc = self._lib.bds_notch_file(self._h, C.byref(cs), src, dst, int(n_samples), int(piece_samples), C.byref(o), C.byref(rep))
         else:
-            a, w16 = record_bytes(settings, source)
-            res = None
-            if apply and out is None:
-                res = np.empty(a.size // 2, dtype="<i2") if w16 else np.empty(a.size, dtype=np.asarray(source).dtype if np.asarray(source).dtype == np.uint8 else np.int8)
-            elif apply:
-                res = out
-                if not isinstance(res, np.ndarray) or not res.flags.c_contiguous or res.nbytes != a.size:
-                    raise ValueError(f"out must be a contiguous NumPy array of the record's {a.size} bytes")
-            est = notch_est(rep, a.size // sb, block_log2, len(steps), want_est)
-            rc = self._lib.bds_notch(self._h, C.byref(cs), a.ctypes.data_as(C.c_void_p), a.size, res.ctypes.data_as(C.c_void_p) if apply else None,
-                                     C.byref(o), C.byref(rep))
+            est = notch_est(rep, n_bytes // sb, block_log2, len(steps), want_est)
+            rc = (self._lib.bds_notch_dev if kind == "dev" else self._lib.bds_notch)(self._h, C.byref(cs), src, n_bytes, dst, C.byref(o), C.byref(rep))
         self._check(rc)
         r = {k: int(getattr(rep, k)) for k in ("n_samples", "n_blocks", "n_saturated", "sum_sq_in", "sum_sq_out")}
         r["est"] = None if est is None else est[:r["n_blocks"]]

@@ -7,7 +7,6 @@ the block estimates of an estimate-only call: detect, notch_tones(estimate_only=
 from __future__ import annotations
 
 import math
-import os
 from dataclasses import dataclass
 
 import numpy as np
@@ -68,31 +67,7 @@ def notch_tones(source, settings, tones, block=1024, out=None, estimate_only=Fal
     steps = [notch_step(f, fs) for f in tones]
     beta = _block_log2(block)
     apply = not estimate_only
-    is_path = isinstance(source, (str, bytes, os.PathLike))
-    dst = None
-    if apply:
-        if is_path:
-            if out is None or (isinstance(out, str) and out == "inplace"):
-                raise ValueError("notching a file writes another file: give out=path")
-            dst = out
-        elif native.is_device_array(source):
-            if isinstance(out, str) and out != "inplace":
-                raise ValueError(f'out = {out!r}: None, "inplace" or a tensor')
-            if out is None:
-                import torch
-
-                dst = torch.empty_like(source)
-            else:
-                dst = source if isinstance(out, str) else out
-        else:
-            if isinstance(out, str) and out != "inplace":
-                raise ValueError(f'out = {out!r}: None, "inplace" or an array')
-            if isinstance(out, str):
-                if not isinstance(source, np.ndarray) or not source.flags.c_contiguous or not source.flags.writeable:
-                    raise ValueError('out="inplace" takes a contiguous writeable NumPy array')
-                dst = source
-            else:
-                dst = out
+    dst = native.conditioner_out(source, out, "notching a file writes another file: give out=path") if apply else None
     res, r = get_context(device).notch(settings, source, steps, beta, out=dst, first_sample=first_sample, apply=apply,
                        n_samples=-1 if n_samples is None else int(n_samples), piece_samples=piece_samples)
     est = (r["est"][..., 0].astype(np.float64) + 1j * r["est"][..., 1].astype(np.float64)) / float(1 << native.NOTCH_AMP_FRAC)

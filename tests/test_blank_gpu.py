@@ -183,6 +183,21 @@ def test_sources_file_host_and_tensor_agree(ctx, fmt, tmp_path):
     np.testing.assert_array_equal(inplace, bc.model(rec, fmt, 2500, pre, post)[0])
 
 
+def test_an_empty_window_changes_nothing(ctx, tmp_path):
+    """No sample in the window: nothing is uploaded or launched, every byte goes through and every count is 0 -- a host array that
+    is all context, and a file that is only its header."""
+    s = bc.settings_of("s8")
+    rec = np.full(64, 100, dtype=np.int8)  # every sample above the threshold, none owned
+    got, rep = ctx.blank(s, rec, 2500, 3, 3, lead=40, tail=24, duty_samples=8)
+    np.testing.assert_array_equal(got, rec)
+    assert (rep["n_samples"], rep["n_flagged"], rep["n_blanked"], rep["n_runs"]) == (0, 0, 0, 0) and rep["duty"].size == 0  # (n_duty bins)
+    src, dst = tmp_path / "header.bin", tmp_path / "out.bin"
+    np.array([100, -100, 100], dtype=np.int8).tofile(src)
+    _, rep = ctx.blank(bc.settings_of("s8", skipNumberOfBytes=3), str(src), 2500, 3, 3, out=str(dst), duty_samples=8)
+    assert dst.read_bytes() == src.read_bytes()
+    assert (rep["n_samples"], rep["n_flagged"], rep["n_blanked"], rep["n_runs"]) == (0, 0, 0, 0) and rep["duty"].size == 0
+
+
 def test_windows_across_the_groups_of_the_tile_scan(ctx):
     """The scan over the tile summaries has two levels, groups of 1024 tiles: a record of three groups with hits at the group seams
     and windows that reach across them (the smallest size at which the second level does anything)."""

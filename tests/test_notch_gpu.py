@@ -212,6 +212,21 @@ def test_sources_and_pieces_agree_with_one_call(ctx, fmt, tmp_path):
     assert tuple(int(v) for v in tot) == (wrep["n_blocks"], wrep["n_saturated"], wrep["sum_sq_in"], wrep["sum_sq_out"])
 
 
+def test_an_empty_window_changes_nothing(ctx, tmp_path):
+    """No sample in the window: nothing is uploaded or launched, no block and no sum -- a host record of 0 bytes, and a file that
+    is only its header, which goes through as it is."""
+    s = nc.settings_of("s8")
+    steps = nc.steps_for("s8", 8, 2)
+    got, rep = ctx.notch(s, np.zeros(0, dtype=np.int8), steps, 8)
+    assert got.size == 0 and rep["est"].shape == (0, 2, 2)
+    assert (rep["n_samples"], rep["n_blocks"], rep["n_saturated"], rep["sum_sq_in"], rep["sum_sq_out"]) == (0, 0, 0, 0, 0)
+    src, dst = tmp_path / "header.bin", tmp_path / "out.bin"
+    np.array([100, -100, 100], dtype=np.int8).tofile(src)
+    _, rep = ctx.notch(nc.settings_of("s8", skipNumberOfBytes=3), str(src), steps, 8, out=str(dst))
+    assert dst.read_bytes() == src.read_bytes() and rep["est"].shape == (0, 2, 2)
+    assert (rep["n_samples"], rep["n_blocks"], rep["n_saturated"], rep["sum_sq_in"], rep["sum_sq_out"]) == (0, 0, 0, 0, 0)
+
+
 def test_the_same_call_twice_gives_the_same_bytes_and_sums(ctx):
     steps = nc.steps_for("s8c", 10, 8)
     rec = nc.with_tones("s8c", 70 * 1024 + 5, steps[:3], seed=11)
