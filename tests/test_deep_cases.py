@@ -1,11 +1,12 @@
 """The NumPy model of the weak-signal acquisition rule (tests/deep_cases.py) on its own, no GPU: it is the reference's search at
-K = 1, it finds what the reference misses, the block alignment matters, four deliberate changes of the rule are told apart by the
+K = 1, it finds what the reference misses, the block alignment matters, five deliberate changes of the rule are told apart by the
 tolerances the GPU tests use, and no GPU scene turns on a near-tie.  Figures of the scenes (model, float64):
 
   B2a 25 MS/s, K = 16   PRN 9 (46 dB-Hz)  reference peakMetric 2.31, deepMetric 33.8
                         PRN 14 (36 dB-Hz) reference 1.17 (missed), bin 8, codePhase 20323, deepMetric 3.73 (K = 1: 1.05)
                         PRN 21 (absent)   reference 1.11, deepMetric 1.03
   B1C 12.5 MS/s, K = 8  PRN 12 (35 dB-Hz) reference 6.39 < 7.5 (missed), deepMetric 7.64; PRN 7 (absent) 1.07
+The 12 MS/s and 5 MS/s scenes (plan matrix, shifts, peaks at the ends of the surface, bin chunks) carry theirs in their docstrings.
 """
 import os
 
@@ -76,6 +77,18 @@ def test_changed_rules_are_told_apart():
     r = dc.scene_model("wrap_b2a")[9]
     wrong, _, _ = dc.surface(dc.as_samples(x, s), s, 9, k, sign=-1)
     assert np.max(np.abs(wrong - r.surface)) > 100 * r.tol
+    # one tile of the column pass skipped (the surface keeps what it held) or run twice in one block: the values of that block at
+    # the tile's lags n1 L2 + col are missing or doubled.  The smallest tile of the plan matrix (tests/test_deep_plans_gpu.py): the
+    # last one of 8 x 4500, 4 columns x 5 rows inside N -- in every bin and every block
+    s, x, k = dc.plans_b2a()
+    r = dc.scene_model("plans_b2a")[9]
+    (t, tiles, last), l2, n = dc.PLANS_B2A["8x4500"], 4500, dc.sizes(s)[2]
+    lags = np.array([n1 * l2 + (tiles - 1) * t + j for n1 in range(8) for j in range(last)])
+    lags = lags[lags < n]
+    assert lags.size == 20
+    for kk in range(k):
+        rows = dc.block_rows(dc.as_samples(x, s), s, 9, kk)
+        assert min(float(np.max(row[lags] ** 2)) for row in rows.values()) > 100 * r.tol
     # amplitude sums instead of power sums: another surface, and a worse statistic for the weak satellite
     s, x, k = dc.mixed_b2a()
     r = dc.scene_model("mixed_b2a")[14]
